@@ -12,11 +12,16 @@ and the per-call overflow check), inputs resident in HBM.
            queries (RCCL), recall on the local shard for all N*2048 of them, all-gather the per-shard
            top-k, merge (``sharded.ShardedHippocampus``).  value = N*2048*steps / time.
 
-Also on the same JSON line: `roofline` of the dominant kernel (the bf16 prefilter over the list-sorted
-shadow, timed with HIP events on its launch stream via aura_profile_*), `cpu_baseline` (the oracle's
-reference-cost recall on the same bank, a handful of queries, with the parity of the GPU result on
-those queries) and `secondary` (exact recall at 1M, recall@k of the index, config 2, rebuild /
-interleaved-write timings, config 5 seeding, neuron-timestep throughput).
+A plain run sets up, warms up, times ``--steps`` steps and prints one JSON line (``ms_per_step`` = wall
+milliseconds of one timed step).  ``--dump-outputs DIR`` writes what the last timed step returned
+(``scores.npy`` float32, ``rows.npy`` as float64) for output-for-output comparisons between builds; the bank,
+its timestamps and the queries are seeded, so the inputs are the same from run to run.
+
+``--full`` adds, on the same JSON line: `roofline` of the dominant kernel (the bf16 prefilter over the
+list-sorted shadow, timed with HIP events on its launch stream via aura_profile_* in a pass of its own after
+the timed steps), `cpu_baseline` (the oracle's reference-cost recall on the same bank, a handful of queries,
+with the parity of the GPU result on those queries) and `secondary` (exact recall at 1M, recall@k of the
+index, config 2, rebuild / interleaved-write timings, config 5 seeding, neuron-timestep throughput).
 """
 from __future__ import annotations
 
@@ -36,6 +41,9 @@ import torch.distributed as dist
 
 HBM_PEAK_GBS = 8000.0       # MI355X_MICROARCH.md: HBM3E 8 TB/s spec (6.3 TB/s achievable)
 MFMA_F32_PEAK_TF = 157.3    # fp32 matrix peak (v_mfma_f32_32x32x2_f32), dense
+# every bank row gets this write time (fp32-exact; the write path stamps wall-clock time, whose fp32 value
+# moves in 128 s steps and could land two chunks of one fill in different steps)
+BENCH_WRITE_TIME = 1.7e9
 PMC_FILE = os.path.join(ROOT, "profiles", "r03_pmc_per_dispatch.json")
 KERNEL_OF_KIND = {0: "knn_scan_filter_v2<true, true>",
                   1: "coarse_scan_kernel<24, 1, false, false, false, 4>",
@@ -46,7 +54,7 @@ KERNEL_OF_KIND = {0: "knn_scan_filter_v2<true, true>",
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--steps", type=int, default=200, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--bank-rows", type=int, default=1_000_000)
     ap.add_argument("--dim", type=int, default=768)
@@ -57,7 +65,15 @@ def parse():
     ap.add_argument("--no-secondary", action="store_true")
     ap.add_argument("--cpu-queries", type=int, default=64)
     ap.add_argument("--c5-rows", type=int, default=10_000_000, help="rows of the config-5 seeding secondary (0: skip)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also the roofline pass, the CPU baseline and the secondaries (--no-cpu-baseline / "
+                         "--no-secondary deselect the last two)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's scores and rows as DIR/<name>.npy")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def new_bank(rows, dim, dev, use_index=True):
@@ -449,6 +465,7 @@ def main():
     hf = new_bank(rows, D, dev)
     sh = ShardedHippocampus(hf, total, force_collectives=use_dist and world == 1)
     fill_bank(hf, rows, D, 1234 + rank, dev)
+    hf.memory_metadata[:hf.memory_count, 1] = BENCH_WRITE_TIME
     sh.memory_count = total
     sh.rebuild_centroids(perm=torch.randperm(total, generator=torch.Generator().manual_seed(7)))
     now = float(hf.memory_metadata[0, 1].item())
@@ -465,7 +482,8 @@ def main():
     def step():
         return sh.recall_batch(q, k=k, now=now, all_gather_queries=use_dist, use_candidates=cand)
 
-    # correctness guard before timing: planted neighbours found (query = stored row + 5 % noise)
+    # the first call builds the inverted lists (setup); guard on its output: planted neighbours found
+    # (query = stored row + 5 % noise)
     s, i = step()
     torch.cuda.synchronize()
     planted_ok = bool((i[: nq // 2, 0] == (pick + sh.row_base).to(torch.int32)).float().mean() > 0.98)
@@ -475,35 +493,47 @@ def main():
     torch.cuda.synchronize()
     if use_dist:
         dist.barrier()
-    lib.aura_profile_begin(max(1, args.steps * 16))
-    torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        last = step()
     torch.cuda.synchronize()
     if use_dist:
         dist.barrier()
     elapsed = time.perf_counter() - t0
-    buf = (ctypes.c_float * (args.steps * 16))()
-    nprof = lib.aura_profile_end(buf, args.steps * 16)
     if use_dist:
         t = torch.tensor([elapsed], device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "scores.npy"), last[0].cpu().numpy().astype(np.float32))
+        np.save(os.path.join(args.dump_outputs, "rows.npy"), last[1].cpu().numpy().astype(np.float64))
+    del last
 
     value = nq * world * args.steps / elapsed
-    kms = sum(buf[j] for j in range(nprof)) / max(nprof, 1)
-    rows_c, nq_c = ctypes.c_int64(0), ctypes.c_int64(0)
-    lib.aura_profile_last_scan(ctypes.byref(rows_c), ctypes.byref(nq_c))
-    kind = lib.aura_profile_last_scan_kind()
-    cfg_key = f"headline_{args.bank_rows}x{D}_n{world}_{'index' if cand else 'exact'}"
-    # kind 3 reports the allocated sorted rows (slack and padding included); the algorithmic unit is one
-    # read of every bank row
-    issued = useful = None
-    if kind == 3 and world == 1:
-        issued, useful = ivf_issued_flop(hf, q, D)
-    roof = hbm_roofline(kind, kms, nprof / max(args.steps, 1), hf.memory_count if kind == 3 else rows_c.value, D,
-                        nq_c.value, cfg_key, issued, useful) if nprof else None
+    roof = None
+    if args.full:
+        # the dominant launch timed with HIP events, in a pass of its own over as many steps
+        lib.aura_profile_begin(max(1, args.steps * 16))
+        torch.cuda.synchronize()
+        for _ in range(args.steps):
+            step()
+        torch.cuda.synchronize()
+        buf = (ctypes.c_float * (args.steps * 16))()
+        nprof = lib.aura_profile_end(buf, args.steps * 16)
+        kms = sum(buf[j] for j in range(nprof)) / max(nprof, 1)
+        rows_c, nq_c = ctypes.c_int64(0), ctypes.c_int64(0)
+        lib.aura_profile_last_scan(ctypes.byref(rows_c), ctypes.byref(nq_c))
+        kind = lib.aura_profile_last_scan_kind()
+        cfg_key = f"headline_{args.bank_rows}x{D}_n{world}_{'index' if cand else 'exact'}"
+        # kind 3 reports the allocated sorted rows (slack and padding included); the algorithmic unit is one
+        # read of every bank row
+        issued = useful = None
+        if kind == 3 and world == 1:
+            issued, useful = ivf_issued_flop(hf, q, D)
+        roof = hbm_roofline(kind, kms, nprof / max(args.steps, 1), hf.memory_count if kind == 3 else rows_c.value,
+                            D, nq_c.value, cfg_key, issued, useful) if nprof else None
 
     mode = ("centroid-index recall (8 nearest of 256 centroids, hippocampal.py:259-270) through inverted lists on "
             "the two-stage scan" if cand else "exact recall (two-stage scan)")
@@ -522,9 +552,10 @@ def main():
                    "bank_rows": total, "dim": D, "queries_per_rank": nq, "k": k, "nprobe": 8, "lists": 256,
                    "parallelism": f"bank-sharded x{world}" if world > 1 else "single"},
         "planted_neighbours_found": planted_ok,
-        "roofline": roof,
     }
-    if rank == 0 and world == 1:
+    if args.full:
+        out["roofline"] = roof
+    if args.full and rank == 0 and world == 1:
         s_c, r_c = s, i
         # CPU baseline and the GPU's parity on its sample FIRST, on the bank the headline ran on: the write
         # benchmarks of the secondary section store the same random batch several times over (exact duplicate

@@ -1,5 +1,7 @@
 #!/bin/bash
-mkdir -p gpurun_out/r03
-timeout -k 10 1000 python bench.py > gpurun_out/r03/bench_full.json 2> gpurun_out/r03/bench_full.err; echo "bench rc $?"
-tail -3 gpurun_out/r03/bench_full.err
-python tools/bench_summary.py gpurun_out/r03/bench_full.json
+# the whole bench (headline, roofline, CPU baseline, secondaries): bash tools/gpu_bench_full.sh <output dir>
+O=${1:?usage: $0 <output dir>}
+mkdir -p "$O"
+timeout -k 10 1000 python bench.py --full > "$O/bench_full.json" 2> "$O/bench_full.err"; echo "bench rc $?"
+tail -3 "$O/bench_full.err"
+python tools/bench_summary.py "$O/bench_full.json"
