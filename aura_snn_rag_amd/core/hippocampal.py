@@ -28,7 +28,6 @@ Reference defects on this path (SURVEY.md 8a "hazards") and what this class does
 """
 from __future__ import annotations
 
-import os
 import time
 from dataclasses import dataclass, field
 from collections.abc import Mapping
@@ -77,12 +76,6 @@ class _EpisodicView(Mapping):
         return mid in self._o.id_to_idx
 
 
-# AURA_NO_HOST_WORD=1: read the recall's flag with a device-to-host copy instead of polling the completion word (A/B runs)
-_NO_HOST_WORD = os.environ.get("AURA_NO_HOST_WORD") is not None
-# AURA_EXCHANGE_ONCE=1: a sharded recall combines only the sampled bounds (stage 1), not the candidates' (A/B runs)
-_EXCHANGE_TWICE = os.environ.get("AURA_EXCHANGE_ONCE") is None
-
-
 class _IvfState:
     """Inverted lists of the centroid index in the layout ``aura_knn_search_ivf2`` streams: a
     list-sorted bf16 shadow with ``slack`` free entries behind every list, so that writes are
@@ -101,9 +94,10 @@ class _IvfState:
         self.n_sorted = 16            # sorted rows in use (host-side bound, a multiple of 16; fixed between re-packs)
         self.appended = 0             # rows appended since the last re-pack
         self.valid = False
+        self.lists: Optional[ops.Ivf2Lists] = None     # validated handle of this layout (HippocampalFormation._ivf_lists)
+        self.word = ops.CompletionWord(device)         # the recall's flag, polled on the host
         # cached score constants of the sorted rows (aura_ivf2_row_constants): valid for ONE fp32 `now` (the
         # reference's fp32 timestamps give time a 128-second grain) while metadata, rho and layout are unchanged
-        self.plan = None              # ops.Ivf2Plan of this layout (validated once, see recall_batch)
         self.rowc: Optional[torch.Tensor] = None
         self.rowc_live = False
         self.rowc_now = 0.0           # the fp32 `now` the table was built for
@@ -593,94 +587,42 @@ class HippocampalFormation(nn.Module):
         on another shard, so the fallback is the caller's decision after the merge).  ``probe_ids``:
         ``probe(queries)`` computed earlier for these queries against the current centroid table (the
         inverted-list path then skips its own probe; other paths ignore it).  ``bound_exchange``
-        (``sharded.ShardedHippocampus``): ``(fn, parts)`` -- the inverted-list recall runs in two stages per pass of
-        at most 8192 queries and ``fn(bounds [n, 2]) -> bound [n]`` combines every shard's sampled bounds in
-        between (a collective: it is called exactly ``2 ceil(nq / 8192)`` times -- sampled bounds, then the filtered
-        candidates' bounds; once per pass with ``AURA_EXCHANGE_ONCE`` -- whatever path this bank takes)."""
+        (``sharded.ShardedHippocampus``): ``(fn, parts)`` -- the inverted-list recall runs in stages per pass of
+        at most 8192 queries and ``fn(bounds [n, 2]) -> bound [n]`` combines every shard's bounds in between (a
+        collective: it is called exactly ``2 ceil(nq / 8192)`` times -- sampled bounds, then the filtered
+        candidates' bounds -- whatever path this bank takes)."""
         self._last_flag = None                        # set only by a candidate-mode recall that read its flag
-
-        def drain_exchanges(nq_: int) -> None:
-            # this bank does not take the staged path: keep the shards' collectives matched with neutral bounds
-            if bound_exchange is not None:
-                step = ops.Ivf2Staged.MAX_QUERIES
-                for lo_ in range(0, nq_, step):
-                    for _ in range(2 if _EXCHANGE_TWICE else 1):     # (sampled bounds, then the candidates' bounds)
-                        bound_exchange[0](torch.full((min(step, nq_ - lo_), 2), -3.0e38, dtype=torch.float32,
-                                                     device=self.device))
         if self.memory_count == 0:
-            drain_exchanges(queries.shape[0])
+            self._drain_exchanges(queries.shape[0], bound_exchange)
             z = torch.empty(queries.shape[0], 0, device=self.device)
             return z, z.to(torch.int32)
         q = self._features_to_device(queries)
         self._ensure_norms()
         kk = min(int(k), self.memory_count)
         now = time.time() if now is None else now
-        q_loc = None
-        if locations is not None:
-            if isinstance(locations, np.ndarray):
-                locations = torch.from_numpy(locations)
-            q_loc = locations.to(device=self.device, dtype=torch.float32).reshape(-1, self.spatial_dims)
-            if q_loc.shape[0] == 1 and q.shape[0] > 1:
-                q_loc = q_loc.expand(q.shape[0], -1)
-            q_loc = q_loc.contiguous()
+        q_loc = self._query_locations(locations, q.shape[0])
         cand = self._candidate_mode() if use_candidates is None else (use_candidates and self._candidate_mode())
         kw = dict(count=self.memory_count, loc=self.memory_locations if q_loc is not None else None,
                   q_loc=q_loc, check_overflow=check_overflow)
         if not cand:
-            drain_exchanges(q.shape[0])
+            self._drain_exchanges(q.shape[0], bound_exchange)
             shadow = self._ensure_shadow() if q_loc is None else None
             return ops.knn_search(self.memory_features, self._inv_norm, self.memory_metadata, q, kk, now,
                                   shadow=shadow, rho=self._rho if shadow is not None else None, **kw)
         nprobe = min(8, self.centroids_k)
-        scores = rows = ovf = flag_of = None
         full_index = self.centroids.shape[0] == 256
-        masked_ok = (q_loc is None and full_index and self.memory_count <= self.MASKED_SCAN_MAX_ROWS and
-                     q.shape[0] <= self.MASKED_SCAN_MAX_QUERIES and bound_exchange is None)
-        exchanged = False
-        shadow = self._ensure_shadow() if masked_ok else None
-        if shadow is not None:
-            # up to a few hundred thousand rows the candidate restriction is cheapest as probe masks
-            # inside the two-stage scan (one pass over the bf16 shadow; 0.15 vs 0.20 ms at 100k x 768,
-            # 256 queries); same rows and score bits as the inverted lists
-            scores, rows, ovf = ops.knn_search(self.memory_features, self._inv_norm, self.memory_metadata,
-                                               q, kk, now, centroids=self.centroids, nprobe=nprobe,
-                                               shadow=shadow, rho=self._rho, count=self.memory_count,
-                                               check_overflow=False, return_flag=True)
-        elif q_loc is None and full_index and kk <= 256:
-            ivf = self._ensure_ivf()
-            if ivf is not None and not check_overflow and ivf.appended > ivf.slack:
-                ivf.valid = False                     # nobody will read the lists' flag: stay within the proven slack
-                ivf = self._ensure_ivf()
-            if ivf is not None and bound_exchange is not None:
-                scores, rows, ovf = self._recall_ivf2_exchanged(q, kk, now, nprobe, ivf, probe_ids, bound_exchange)
-                exchanged = True
-                if check_overflow and not _NO_HOST_WORD:
-                    # the flag through a host-mapped word behind the last stage (as the plan's path below): polled,
-                    # not synchronised for
-                    hw = getattr(ivf, "_host_flag", None)
-                    if hw is None:
-                        hw = ivf._host_flag = ops.HostFlag(q.device)
-                    hw.signal(ovf)
-                    flag_of = hw.wait
-            elif ivf is not None:
-                # large banks / large batches: inverted lists on the two-stage scan (every probed list is
-                # streamed once per 2048 queries from the list-sorted bf16 shadow); same rows and score bits
-                rowc = self._ivf_row_constants(ivf, now)
-                plan = ivf.plan
-                if plan is None or not plan.matches(self.memory_features, self.memory_metadata, self.centroids,
-                                                    ivf.sorted_bf16, ivf.n_sorted, rowc) or plan.nprobe != nprobe:
-                    plan = ivf.plan = ops.Ivf2Plan(self.memory_features, self._inv_norm, self.memory_metadata, self.centroids,
-                                                   nprobe, ivf.sorted_bf16, self._rho, ivf.sorted_rows, ivf.pad_off,
-                                                   ivf.list_len, ivf.n_sorted, ivf.flag, rowc)
-                scores, rows, ovf = plan.run(q, kk, now, probe_ids=probe_ids)
-                if not _NO_HOST_WORD:
-                    flag_of = plan.wait_flag                # (the flag arrives through the plan's completion word)
-        if not exchanged:
-            drain_exchanges(q.shape[0])
+        scores = rows = None
+        first = None
+        if q_loc is None and full_index:
+            first = self._recall_two_stage(q, kk, now, nprobe, probe_ids, check_overflow, bound_exchange)
+        if first is None:                             # (with an exchange, a two-stage recall is the staged one)
+            self._drain_exchanges(q.shape[0], bound_exchange)
+        else:
+            scores, rows, read_flag = first
         if check_overflow and scores is not None:
             # ONE host read for both conditions: the library's flag carries the overflow bits of the
             # two-stage lists and the "a query has no candidate at all" bit
-            f = flag_of() if flag_of is not None else int(ovf.item())
+            f = read_flag()
             if f & ops.KNN_FLAG_LISTS_STALE:          # a write outgrew a list's slack: re-pack, then once more
                 self._ivf.valid = False
                 if _retry < 2 and bound_exchange is None:   # (an exchanged recall is never repeated: collectives)
@@ -693,8 +635,108 @@ class HippocampalFormation(nn.Module):
             elif not (f & ops.KNN_FLAG_NO_CANDIDATES) or not fallback_empty:
                 self._last_flag = f                   # (sharded.ShardedHippocampus: was any query left without candidates?)
                 return scores, rows
-        if scores is None and q_loc is None and full_index:
-            # fp32 inverted lists: every probed list is streamed once per batch
+        if scores is None:
+            scores, rows = self._recall_fp32(q, kk, now, nprobe, q_loc is None and full_index, kw)
+        if check_overflow and fallback_empty:
+            self._fill_empty_queries(q, q_loc, kk, now, scores, rows, kw)
+        return scores, rows
+
+    def _query_locations(self, locations, nq: int) -> Optional[torch.Tensor]:
+        if locations is None:
+            return None
+        if isinstance(locations, np.ndarray):
+            locations = torch.from_numpy(locations)
+        q_loc = locations.to(device=self.device, dtype=torch.float32).reshape(-1, self.spatial_dims)
+        if q_loc.shape[0] == 1 and nq > 1:
+            q_loc = q_loc.expand(nq, -1)
+        return q_loc.contiguous()
+
+    def _drain_exchanges(self, nq: int, bound_exchange) -> None:
+        """This bank does not take the staged path: keep the shards' collectives matched with neutral bounds."""
+        if bound_exchange is None:
+            return
+        step = ops.STAGED_MAX_QUERIES
+        for lo in range(0, nq, step):
+            for _ in range(2):                        # (sampled bounds, then the candidates' bounds)
+                bound_exchange[0](torch.full((min(step, nq - lo), 2), -3.0e38, dtype=torch.float32, device=self.device))
+
+    def _recall_two_stage(self, q, kk: int, now: float, nprobe: int, probe_ids, check_overflow: bool, bound_exchange):
+        """Candidate mode on the bf16 two-stage scan: ``(scores, rows, read_flag)`` -- ``read_flag()`` returns the
+        call's flag -- or None when neither the probe masks nor the inverted lists apply."""
+        masked_ok = (self.memory_count <= self.MASKED_SCAN_MAX_ROWS and q.shape[0] <= self.MASKED_SCAN_MAX_QUERIES and
+                     bound_exchange is None)
+        shadow = self._ensure_shadow() if masked_ok else None
+        if shadow is not None:
+            # up to a few hundred thousand rows the candidate restriction is cheapest as probe masks
+            # inside the two-stage scan (one pass over the bf16 shadow; 0.15 vs 0.20 ms at 100k x 768,
+            # 256 queries); same rows and score bits as the inverted lists
+            scores, rows, ovf = ops.knn_search(self.memory_features, self._inv_norm, self.memory_metadata,
+                                               q, kk, now, centroids=self.centroids, nprobe=nprobe,
+                                               shadow=shadow, rho=self._rho, count=self.memory_count,
+                                               check_overflow=False, return_flag=True)
+            return scores, rows, ovf.item
+        if kk > 256:
+            return None
+        ivf = self._ensure_ivf()
+        if ivf is not None and not check_overflow and ivf.appended > ivf.slack:
+            ivf.valid = False                         # nobody will read the lists' flag: stay within the proven slack
+            ivf = self._ensure_ivf()
+        if ivf is None:
+            return None
+        # large banks / large batches: inverted lists on the two-stage scan (every probed list is streamed once
+        # per 2048 queries from the list-sorted bf16 shadow); same rows and score bits.  The flag arrives through
+        # the completion word: polled, not synchronised for.
+        lists = self._ivf_lists(ivf, now, nprobe)
+        if bound_exchange is None:
+            scores, rows, _ = lists.search(q, kk, now, probe_ids=probe_ids, word=ivf.word)
+            return scores, rows, ivf.word.wait
+        scores, rows, ovf = self._recall_staged(lists, q, kk, now, probe_ids, bound_exchange)
+        if check_overflow:
+            ivf.word.signal(ovf)                      # (the staged chain ends in an entry point without a word)
+        return scores, rows, ivf.word.wait
+
+    def _ivf_lists(self, ivf: _IvfState, now: float, nprobe: int) -> "ops.Ivf2Lists":
+        """The validated handle of the current lists (rebuilt only when one of its tensors was replaced)."""
+        args = (self.memory_features, self._inv_norm, self.memory_metadata, self.centroids, nprobe, ivf.sorted_bf16,
+                self._rho, ivf.sorted_rows, ivf.pad_off, ivf.list_len, ivf.n_sorted, ivf.flag,
+                self._ivf_row_constants(ivf, now))
+        if ivf.lists is None or not ivf.lists.holds(*args):
+            ivf.lists = ops.Ivf2Lists(*args)
+        return ivf.lists
+
+    def _recall_staged(self, lists: "ops.Ivf2Lists", q, kk: int, now: float, probe_ids, bound_exchange):
+        """Inverted-list recall in passes of at most 8192 queries, each in stages with the shards' bounds combined
+        in between (``aura_knn_search_ivf2_staged``): ``(scores, rows, overflow flag)``."""
+        fn, parts = bound_exchange
+        k2 = max(1, -(-kk // max(int(parts), 1)))
+        step = ops.STAGED_MAX_QUERIES
+        nq = q.shape[0]
+        # results land in ONE pair of tensors (each pass writes its slice); the layout is checked once per handle, not
+        # once per pass and call: the staged recall of a sharded bank is host-bound otherwise (eight ranks: 2 passes x
+        # 5 Python-level steps per call against ~1.1 ms of kernels)
+        out_s = torch.empty(nq, kk, dtype=torch.float32, device=q.device)
+        out_i = torch.empty(nq, kk, dtype=torch.int32, device=q.device)
+        flag = torch.zeros(1, dtype=torch.int32, device=q.device) if nq == 0 else None
+        for lo in range(0, nq, step):
+            hi = min(nq, lo + step)
+            p = lists.staged(q[lo:hi], kk, now, None if probe_ids is None else probe_ids[lo:hi],
+                             out=(out_s[lo:hi], out_i[lo:hi]))
+            bound = fn(p.stage1(k2))
+            # second exchange, on the FILTERED candidates' bounds: the k-th largest lower bound over the shards'
+            # candidates (max over shards of each one's k-th, min over shards of each one's ceil(k / S)-th) is close
+            # to the global k-th best score itself, so a shard re-scores ~k / S + gap rows per query instead of
+            # k + gap -- the refine is half of a shard's share at 8 shards
+            bound2 = fn(p.stage2_bounds(bound, k2))
+            _, _, f_ = p.stage3(torch.maximum(bound2, bound))
+            if hi - lo == nq:
+                return out_s, out_i, f_
+            flag = f_.clone() if flag is None else flag.bitwise_or_(f_)   # stage 1 of the next pass resets the flag
+        return out_s, out_i, flag
+
+    def _recall_fp32(self, q, kk: int, now: float, nprobe: int, use_lists: bool, kw) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Candidate mode on the fp32 paths: the fp32 inverted lists (every probed list is streamed once per batch),
+        else the fp32 scan with probe masks."""
+        if use_lists:
             list_rows, list_off, list_len, longest = self._ensure_lists()
             cap = ops.ivf_capacity(longest, kk)
             if cap is not None:               # else: lists too long for the two-level select
@@ -702,12 +744,12 @@ class HippocampalFormation(nn.Module):
                                                      self.memory_metadata, q, kk, now, self.memory_count,
                                                      self.centroids, nprobe, list_rows, list_off,
                                                      list_len, cap)
-        if scores is None:
-            scores, rows = ops.knn_search(self.memory_features, self._inv_norm, self.memory_metadata,
-                                          q, kk, now, centroids=self.centroids, nprobe=nprobe, **kw)
-        if not check_overflow or not fallback_empty:
-            return scores, rows
-        # a query whose probed centroids own no rows falls back to the full scan (ref :269-270)
+                return scores, rows
+        return ops.knn_search(self.memory_features, self._inv_norm, self.memory_metadata,
+                              q, kk, now, centroids=self.centroids, nprobe=nprobe, **kw)
+
+    def _fill_empty_queries(self, q, q_loc, kk: int, now: float, scores, rows, kw) -> None:
+        """A query whose probed centroids own no rows falls back to the full scan (ref :269-270), in place."""
         empty = (rows[:, 0] < 0)
         if bool(empty.any()):
             sel = torch.nonzero(empty).squeeze(-1)
@@ -717,48 +759,6 @@ class HippocampalFormation(nn.Module):
             s2, r2 = ops.knn_search(self.memory_features, self._inv_norm, self.memory_metadata,
                                     q[sel].contiguous(), kk, now, **kw2)
             scores[sel], rows[sel] = s2, r2
-        return scores, rows
-
-    def _recall_ivf2_exchanged(self, q, kk: int, now: float, nprobe: int, ivf: "_IvfState", probe_ids, bound_exchange):
-        """Inverted-list recall in passes of at most 8192 queries, each in two stages with the shards' bounds
-        combined in between (``aura_knn_search_ivf2_staged``)."""
-        fn, parts = bound_exchange
-        k2 = max(1, -(-kk // max(int(parts), 1)))
-        rowc = self._ivf_row_constants(ivf, now)
-        step = ops.Ivf2Staged.MAX_QUERIES
-        nq = q.shape[0]
-        # results land in ONE pair of tensors (each pass writes its slice); the constructor's tensor checks run once
-        # per bank layout, not once per pass and call: the staged recall of a sharded bank is host-bound otherwise
-        # (eight ranks: 2 passes x 5 Python-level steps per call against ~1.1 ms of kernels)
-        out_s = torch.empty(nq, kk, dtype=torch.float32, device=q.device)
-        out_i = torch.empty(nq, kk, dtype=torch.int32, device=q.device)
-        sig = (id(self.memory_features), id(self.memory_metadata), id(self.centroids), id(ivf.sorted_bf16), id(rowc),
-               ivf.n_sorted, int(kk), int(nprobe))
-        validated = getattr(ivf, "_staged_sig", None) == sig
-        flag = None
-        for lo in range(0, nq, step):
-            hi = min(nq, lo + step)
-            st = ops.Ivf2Staged(self.memory_features, self._inv_norm, self.memory_metadata, q[lo:hi], kk, now,
-                                self.centroids, nprobe, ivf.sorted_bf16, self._rho, ivf.sorted_rows, ivf.pad_off,
-                                ivf.list_len, n_sorted=ivf.n_sorted, lists_flag=ivf.flag,
-                                probe_ids=None if probe_ids is None else probe_ids[lo:hi],
-                                row_constants=rowc, out=(out_s[lo:hi], out_i[lo:hi]), validated=validated)
-            ivf._staged_sig = sig
-            validated = True
-            bound = fn(st.stage1(k2))
-            if _EXCHANGE_TWICE:
-                # second exchange, on the FILTERED candidates' bounds: the k-th largest lower bound over the shards'
-                # candidates (max over shards of each one's k-th, min over shards of each one's ceil(k / S)-th) is
-                # close to the global k-th best score itself, so a shard re-scores ~k / S + gap rows per query
-                # instead of k + gap -- the refine is half of a shard's share at 8 shards
-                bound2 = fn(st.stage2_bounds(bound, k2))
-                _, _, f_ = st.stage3(torch.maximum(bound2, bound))
-            else:
-                _, _, f_ = st.stage2(bound)
-            if hi - lo == nq:
-                return out_s, out_i, f_
-            flag = f_.clone() if flag is None else flag.bitwise_or_(f_)   # stage 1 of the next pass resets the flag
-        return out_s, out_i, flag
 
     def probe(self, queries: torch.Tensor) -> Optional[torch.Tensor]:
         """The centroid probes of ``queries`` ([nq, 8] int32, the 8 nearest of the 256 centroid rows in

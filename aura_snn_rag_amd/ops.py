@@ -7,6 +7,8 @@ stream.  There is no fallback: CPU tensors raise ``AuraDeviceError``.
 from __future__ import annotations
 
 import ctypes
+import time
+import warnings
 from typing import Optional, Sequence, Tuple
 
 import torch
@@ -339,8 +341,7 @@ def bank_write(bank, loc, meta, inv_norm, feats, slots, cur_loc, now: float,
     if centroids is not None and distinct_slots and not serial and n > 0:
         L = lib()
         nbytes = L.aura_bank_write_online_workspace_bytes(n)
-        ws = _workspace(bank.device, nbytes)
-        base = (ws.data_ptr() + 255) // 256 * 256
+        base = _workspace(bank.device, nbytes)
         check(L.aura_bank_write_online(_p(bank), _p(loc), _p(meta), _p(inv_norm), _p(centroids),
                                        _p(centroid_counts), eff_k, _p(feats), _p(slots), _p(cur_loc), sd,
                                        now, n, D, base, nbytes, _stream()), "aura_bank_write_online")
@@ -369,13 +370,14 @@ def _wkey(device):
     return (device, torch.cuda.current_stream(device).cuda_stream)
 
 
-def _workspace(device, nbytes: int) -> torch.Tensor:
+def _workspace(device, nbytes: int) -> int:
+    """Base address (256-byte aligned) of this (device, stream)'s scratch of at least ``nbytes``."""
     key = _wkey(device)
     ws = _workspaces.get(key)
-    if ws is None or ws.numel() < nbytes:
-        ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=device)
-        _workspaces[key] = ws
-    return ws
+    if ws is None or ws[0] < nbytes:
+        buf = torch.empty(nbytes + 256, dtype=torch.uint8, device=device)
+        ws = _workspaces[key] = (nbytes, (buf.data_ptr() + 255) // 256 * 256, buf)   # (usable bytes, base, buffer)
+    return ws[1]
 
 
 def _overflow_flag(device) -> torch.Tensor:
@@ -429,8 +431,7 @@ def knn_search(bank, inv_norm, meta, queries, k: int, now: float, count: Optiona
     nbytes = L.aura_knn_workspace_bytes(N, nq, k)
     if nbytes < 0:
         raise _lib.AuraHipError("aura_knn_workspace_bytes failed")
-    ws = _workspace(dev, nbytes)
-    base = (ws.data_ptr() + 255) // 256 * 256
+    base = _workspace(dev, nbytes)
     ovf = _overflow_flag(dev)
 
     use_shadow = shadow is not None and q_loc is None
@@ -495,8 +496,7 @@ def knn_search_ivf(bank, inv_norm, meta, queries, k: int, now: float, count: int
     nbytes = L.aura_knn_ivf_workspace_bytes(nq, k, cap)
     if nbytes < 0:
         raise ValueError(f"knn_search_ivf: capacity {cap} is not usable with k={k}")
-    ws = _workspace(dev, nbytes)
-    base = (ws.data_ptr() + 255) // 256 * 256
+    base = _workspace(dev, nbytes)
     check(L.aura_knn_search_ivf(_p(bank), _p(inv_norm), _p(meta), _p(queries), now, count, D, nq, k,
                                 _p(centroids), nprobe, _p(list_rows), _p(list_off), _p(list_len), cap,
                                 idx_base, _p(out_s), _p(out_i), base, nbytes, _p(ovf), _stream()),
@@ -631,11 +631,13 @@ def centroid_probe(queries, centroids, nprobe: int = 8) -> torch.Tensor:
         return ids
     L = lib()
     nbytes = L.aura_centroid_probe_workspace_bytes(nq)
-    ws = _workspace(queries.device, nbytes)
-    base = (ws.data_ptr() + 255) // 256 * 256
+    base = _workspace(queries.device, nbytes)
     check(L.aura_centroid_probe(_p(centroids), _p(queries), D, nq, nprobe, _p(ids), base, nbytes, _stream()),
           "aura_centroid_probe")
     return ids
+
+
+STAGED_MAX_QUERIES = 8192            # queries per staged pass (aura_knn_search_ivf2_staged)
 
 
 def knn_search_ivf2(bank, inv_norm, meta, queries, k: int, now: float, centroids, nprobe: int,
@@ -643,346 +645,248 @@ def knn_search_ivf2(bank, inv_norm, meta, queries, k: int, now: float, centroids
                     n_sorted: Optional[int] = None, lists_flag=None, probe_ids=None, row_constants=None
                     ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """Inverted-list recall through the two-stage scan: (scores [nq, k], idx [nq, k], overflow flag [1]).
-    Same results as ``knn_search_ivf``; layout arrays from ``ivf2_layout`` + ``bank_shadow_sorted``
-    (kept current by ``ivf2_append``).  ``n_sorted``: sorted rows in use (a multiple of 16 that covers
-    pad_off[256]; default: all of ``sorted_rows``).  ``lists_flag``: ``ivf2_append``'s flag; if it is
-    set the returned overflow flag carries ``KNN_FLAG_LISTS_STALE``.  ``probe_ids``: ``centroid_probe``'s
-    output for these queries and this centroid table (the probes are then not recomputed).
-    ``row_constants``: ``ivf2_row_constants`` of the current lists for exactly this ``now`` (as fp32)."""
-    _need(bank, "bank", torch.float32); _need(inv_norm, "inv_norm", torch.float32)
-    _need(meta, "meta", torch.float32); _need(queries, "queries", torch.float32)
-    _need(centroids, "centroids", torch.float32); _need(sorted_shadow, "sorted_shadow", torch.bfloat16)
-    _need(rho, "rho", torch.float32)
-    for t, n in ((sorted_rows, "sorted_rows"), (pad_off, "pad_off"), (list_len, "list_len")):
-        _need(t, n, torch.int32)
-    M, D = bank.shape
-    nq = queries.shape[0]
-    ns = sorted_rows.numel() if n_sorted is None else int(n_sorted)
-    if queries.dim() != 2 or queries.shape[1] != D or meta.shape != (M, 4) or rho.numel() != M:
-        raise ValueError("knn_search_ivf2: shape mismatch")
-    if centroids.shape != (256, D) or not (0 < nprobe <= 8):
-        raise ValueError("knn_search_ivf2: centroids must be [256, D], nprobe in [1, 8]")
-    if sorted_shadow.shape[1] != D or not (0 < ns <= min(sorted_rows.numel(), sorted_shadow.shape[0])) or \
-            pad_off.numel() != 257 or list_len.numel() != 256 or ns % 16:
-        raise ValueError("knn_search_ivf2: layout arrays do not match")
-    if not (0 < k <= 256) or D % 8 or D > 768:
-        raise ValueError("knn_search_ivf2: k <= 256, D % 8 == 0, D <= 768")
-    dev = bank.device
-    out_s = torch.empty(nq, k, dtype=torch.float32, device=dev)
-    out_i = torch.empty(nq, k, dtype=torch.int32, device=dev)
-    ovf = torch.zeros(1, dtype=torch.int32, device=dev) if nq == 0 else _overflow_flag(dev)
-    if nq == 0:
-        return out_s, out_i, ovf
-    L = lib()
-    nbytes = L.aura_knn_ivf2_workspace_bytes(ns, nq, k)
-    ws = _workspace(dev, nbytes)
-    base = (ws.data_ptr() + 255) // 256 * 256
-    if lists_flag is not None:
-        _need(lists_flag, "lists_flag", torch.int32)
-    if row_constants is not None:
-        _need(row_constants, "row_constants", torch.float32)
-        if row_constants.dim() != 2 or row_constants.shape[1] != 4 or row_constants.shape[0] < ns:
-            raise ValueError("knn_search_ivf2: row_constants must be [>= n_sorted, 4]")
-    if probe_ids is not None:
-        _need(probe_ids, "probe_ids", torch.int32)
-        if tuple(probe_ids.shape) != (nq, 8):
-            raise ValueError("knn_search_ivf2: probe_ids must be [nq, 8] (centroid_probe)")
-        check(L.aura_knn_search_ivf2_probed(_p(bank), _p(inv_norm), _p(meta), _p(sorted_shadow), _p(rho),
-                                            _p(sorted_rows), _p(pad_off), _p(list_len), _p(lists_flag),
-                                            _p(row_constants), ns, M,
-                                            _p(queries), now, D, nq, k, _p(centroids), nprobe, _p(probe_ids),
-                                            idx_base, _p(out_s), _p(out_i), base, nbytes, _p(ovf), _stream()),
-              "aura_knn_search_ivf2_probed")
-        return out_s, out_i, ovf
-    check(L.aura_knn_search_ivf2(_p(bank), _p(inv_norm), _p(meta), _p(sorted_shadow), _p(rho), _p(sorted_rows),
-                                 _p(pad_off), _p(list_len), _p(lists_flag), _p(row_constants), ns, M, _p(queries), now, D,
-                                 nq, k,
-                                 _p(centroids), nprobe, idx_base, _p(out_s), _p(out_i), base, nbytes,
-                                 _p(ovf), _stream()), "aura_knn_search_ivf2")
-    return out_s, out_i, ovf
+    Same results as ``knn_search_ivf``; the arguments are those of ``Ivf2Lists`` and ``Ivf2Lists.search``."""
+    lists = Ivf2Lists(bank, inv_norm, meta, centroids, nprobe, sorted_shadow, rho, sorted_rows, pad_off, list_len,
+                      n_sorted, lists_flag, row_constants)
+    return lists.search(queries, k, now, probe_ids=probe_ids, idx_base=idx_base)
 
 
-class Ivf2Plan:
-    """``knn_search_ivf2`` for ONE list layout, validated once: the per-call path is a shape check of the queries,
-    two output allocations and the C call.  (Between a recall's flag read and the next recall's first launch the
-    GPU idles; the generic wrapper spends ~30 us of Python there -- a dozen tensor checks, ~25 ``data_ptr()`` calls,
-    a workspace-size query -- against a 0.7 ms step.)  Built by ``HippocampalFormation`` after every re-pack of its
-    lists; any tensor of the layout being replaced invalidates the plan (the owner drops it)."""
+class Ivf2Lists:
+    """One layout of the inverted lists that ``knn_search_ivf2`` streams, validated once: the per-call path checks
+    only the queries, ``k`` and the probes, allocates the outputs and makes the C call.  (Between a recall's flag
+    read and the next recall's first launch the GPU idles; checking the layout on every call cost ~30 us of Python
+    -- a dozen tensor checks, ~25 ``data_ptr()`` calls, a workspace-size query -- against a 0.7 ms step.)
+
+    Layout arrays from ``ivf2_layout`` + ``bank_shadow_sorted`` (kept current by ``ivf2_append``).  ``n_sorted``:
+    sorted rows in use (a multiple of 16 that covers pad_off[256]; default: all of ``sorted_rows``).
+    ``lists_flag``: ``ivf2_append``'s flag; if it is set the returned overflow flag carries ``KNN_FLAG_LISTS_STALE``.
+    ``row_constants``: ``ivf2_row_constants`` of the current lists for exactly the ``now`` of every call (fp32).
+    The handle keeps its tensors alive and caches their pointers: an owner rebuilds it when ``holds`` fails."""
 
     def __init__(self, bank, inv_norm, meta, centroids, nprobe: int, sorted_shadow, rho, sorted_rows, pad_off, list_len,
-                 n_sorted: int, lists_flag, row_constants):
+                 n_sorted: Optional[int] = None, lists_flag=None, row_constants=None):
         _need(bank, "bank", torch.float32); _need(inv_norm, "inv_norm", torch.float32)
         _need(meta, "meta", torch.float32); _need(centroids, "centroids", torch.float32)
         _need(sorted_shadow, "sorted_shadow", torch.bfloat16); _need(rho, "rho", torch.float32)
-        for t, n in ((sorted_rows, "sorted_rows"), (pad_off, "pad_off"), (list_len, "list_len"), (lists_flag, "lists_flag")):
-            _need(t, n, torch.int32)
-        _need(row_constants, "row_constants", torch.float32)
-        M, D = bank.shape
-        ns = int(n_sorted)
-        if meta.shape != (M, 4) or rho.numel() != M or centroids.shape != (256, D) or not (0 < nprobe <= 8):
-            raise ValueError("Ivf2Plan: shape mismatch")
-        if sorted_shadow.shape[1] != D or not (0 < ns <= min(sorted_rows.numel(), sorted_shadow.shape[0])) or \
-                pad_off.numel() != 257 or list_len.numel() != 256 or ns % 16 or D % 8 or D > 768:
-            raise ValueError("Ivf2Plan: layout arrays do not match")
-        if row_constants.dim() != 2 or row_constants.shape[1] != 4 or row_constants.shape[0] < ns:
-            raise ValueError("Ivf2Plan: row_constants must be [>= n_sorted, 4]")
-        self._keep = (bank, inv_norm, meta, centroids, sorted_shadow, rho, sorted_rows, pad_off, list_len, lists_flag,
-                      row_constants)
-        self.M, self.D, self.ns, self.nprobe, self.device = M, D, ns, int(nprobe), bank.device
-        self._head = tuple(t.data_ptr() for t in (bank, inv_norm, meta, sorted_shadow, rho, sorted_rows, pad_off, list_len,
-                                                  lists_flag, row_constants))
-        self._cent = centroids.data_ptr()
-        self._bytes = {}
-        self._fn = lib().aura_knn_search_ivf2_signal
-        # completion word: the call's last workgroup stores the flag and a sequence number into host-mapped memory;
-        # wait_flag polls it -- no device-to-host copy, no stream synchronisation (aura_knn_search_ivf2_signal)
-        hw = ctypes.c_void_p()
-        check(lib().aura_host_word_alloc(ctypes.byref(hw)), "aura_host_word_alloc")
-        self._hw_ptr = hw.value
-        self._hw = (ctypes.c_uint32 * 2).from_address(hw.value)
-        self._seq = 0
-        self._last_ovf = None
-
-    def __del__(self):
-        try:
-            if getattr(self, "_hw_ptr", None):
-                torch.cuda.synchronize(self.device)          # no launch may still hold the word
-                lib().aura_host_word_free(self._hw_ptr)
-                self._hw_ptr = None
-        except Exception:
-            pass
-
-    def wait_flag(self, timeout_s: float = 5.0) -> int:
-        """The flag of the last ``run`` (blocks until that call's last launch has finished)."""
-        import time as _t
-        hw, seq = self._hw, self._seq
-        if hw[1] != seq:
-            t_end = None
-            n = 0
-            while hw[1] != seq:
-                n += 1
-                if (n & 0xfff) == 0:                         # every ~4000 polls: give up after timeout_s
-                    now = _t.perf_counter()
-                    if t_end is None:
-                        t_end = now + timeout_s
-                    elif now > t_end:
-                        return int(self._last_ovf.item())     # (never seen: the ordinary read still works)
-        return int(hw[0])
-
-    def matches(self, bank, meta, centroids, sorted_shadow, n_sorted: int, row_constants) -> bool:
-        k = self._keep
-        return (k[0] is bank and k[2] is meta and k[3] is centroids and k[4] is sorted_shadow and k[10] is row_constants
-                and self.ns == int(n_sorted))
-
-    def run(self, queries, k: int, now: float, probe_ids=None, idx_base: int = 0):
-        if not (queries.is_cuda and queries.dtype == torch.float32 and queries.dim() == 2 and queries.shape[1] == self.D
-                and queries.is_contiguous()):
-            raise ValueError("Ivf2Plan.run: queries must be a contiguous fp32 [nq, D] tensor on the bank's device")
-        nq = queries.shape[0]
-        if not (0 < k <= 256):
-            raise ValueError("Ivf2Plan.run: k <= 256")
-        dev = self.device
-        out_s = torch.empty(nq, k, dtype=torch.float32, device=dev)
-        out_i = torch.empty(nq, k, dtype=torch.int32, device=dev)
-        if nq == 0:
-            return out_s, out_i, torch.zeros(1, dtype=torch.int32, device=dev)
-        nbytes = self._bytes.get((nq, k))
-        if nbytes is None:
-            nbytes = self._bytes[(nq, k)] = lib().aura_knn_ivf2_workspace_bytes(self.ns, nq, k)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        key = (dev, stream)
-        ws = _workspaces.get(key)
-        if ws is None or ws.numel() < nbytes:
-            ws = _workspace(dev, nbytes)
-        ovf = _ovf_flags.get(key)
-        if ovf is None:
-            ovf = _overflow_flag(dev)
-        base = (ws.data_ptr() + 255) // 256 * 256
-        h = self._head
-        pid = None
-        if probe_ids is not None:
-            _need(probe_ids, "probe_ids", torch.int32)
-            if tuple(probe_ids.shape) != (nq, 8):
-                raise ValueError("Ivf2Plan.run: probe_ids must be [nq, 8] (centroid_probe)")
-            pid = probe_ids.data_ptr()
-        self._seq = (self._seq + 1) & 0x7fffffff or 1
-        self._last_ovf = ovf
-        check(self._fn(h[0], h[1], h[2], h[3], h[4], h[5], h[6], h[7], h[8], h[9], self.ns, self.M, queries.data_ptr(),
-                       now, self.D, nq, k, self._cent, self.nprobe, pid, idx_base, out_s.data_ptr(), out_i.data_ptr(), base,
-                       nbytes, ovf.data_ptr(), self._hw_ptr, self._seq, stream), "aura_knn_search_ivf2_signal")
-        return out_s, out_i, ovf
-
-
-class HostFlag:
-    """A host-mapped completion word for call chains that end in an entry point without one (the staged recall):
-    ``signal(flag_tensor)`` enqueues a one-thread launch that stores the flag and a sequence number;
-    ``wait()`` polls it and returns the flag -- no device-to-host copy, no stream synchronisation (a blocking wait
-    on a ~1 ms stream costs the host 1-2 ms on this runtime)."""
-
-    def __init__(self, device):
-        self.device = torch.device(device)
-        hw = ctypes.c_void_p()
-        with torch.cuda.device(self.device):
-            check(lib().aura_host_word_alloc(ctypes.byref(hw)), "aura_host_word_alloc")
-        self._hw_ptr = hw.value
-        self._hw = (ctypes.c_uint32 * 2).from_address(hw.value)
-        self._seq = 0
-        self._flag = None
-
-    def __del__(self):
-        try:
-            if getattr(self, "_hw_ptr", None):
-                torch.cuda.synchronize(self.device)          # no launch may still hold the word
-                lib().aura_host_word_free(self._hw_ptr)
-                self._hw_ptr = None
-        except Exception:
-            pass
-
-    def signal(self, flag: torch.Tensor) -> None:
-        _need(flag, "flag", torch.int32)
-        self._seq = (self._seq + 1) & 0x7fffffff or 1
-        self._flag = flag
-        check(lib().aura_signal_flag(_p(flag), self._hw_ptr, self._seq, _stream()), "aura_signal_flag")
-
-    def wait(self, timeout_s: float = 5.0) -> int:
-        import time as _t
-        hw, seq = self._hw, self._seq
-        t_end, n = None, 0
-        while hw[1] != seq:
-            n += 1
-            if (n & 0xfff) == 0:                             # every ~4000 polls: give up after timeout_s
-                now = _t.perf_counter()
-                if t_end is None:
-                    t_end = now + timeout_s
-                elif now > t_end:
-                    return int(self._flag.item())             # (never seen: the ordinary read still works)
-        return int(hw[0])
-
-
-class Ivf2Staged:
-    """``knn_search_ivf2`` in stages (``aura_knn_search_ivf2_staged``) for one pass of at most 8192 queries:
-    ``stage1(k2)`` -> bounds [nq, 2] (the k-th and the k2-th largest sampled lower bound of every query on this
-    bank), ``stage2(bound [nq])`` -> (scores, idx, overflow flag) with every threshold raised to ``bound`` first --
-    or ``stage2_bounds(bound, k2)`` -> the filtered candidates' own bounds [nq, 2] and ``stage3(bound2 [nq])`` -> the
-    result re-scored only where a candidate can still reach ``bound2``.  Between the calls the caller combines the
-    bounds of all shards of a row-sharded bank; nothing else may use this stream's kNN workspace in between."""
-
-    MAX_QUERIES = 8192
-
-    def __init__(self, bank, inv_norm, meta, queries, k: int, now: float, centroids, nprobe: int,
-                 sorted_shadow, rho, sorted_rows, pad_off, list_len, idx_base: int = 0,
-                 n_sorted: Optional[int] = None, lists_flag=None, probe_ids=None, row_constants=None,
-                 out=None, validated: bool = False):
-        """``out``: (scores [nq, k] fp32, idx [nq, k] int32) to write into (contiguous; e.g. slices of the caller's
-        result); ``validated``: the caller has run this constructor's checks on the same tensors before (a pass of a
-        multi-pass recall, or the next call on an unchanged bank) -- only the per-call shapes are checked."""
-        if validated:
-            self._init_fast(bank, inv_norm, meta, queries, k, now, centroids, nprobe, sorted_shadow, rho, sorted_rows,
-                            pad_off, list_len, idx_base, n_sorted, lists_flag, probe_ids, row_constants, out)
-            return
-        _need(bank, "bank", torch.float32); _need(inv_norm, "inv_norm", torch.float32)
-        _need(meta, "meta", torch.float32); _need(queries, "queries", torch.float32)
-        _need(centroids, "centroids", torch.float32); _need(sorted_shadow, "sorted_shadow", torch.bfloat16)
-        _need(rho, "rho", torch.float32)
         for t, n in ((sorted_rows, "sorted_rows"), (pad_off, "pad_off"), (list_len, "list_len")):
             _need(t, n, torch.int32)
         M, D = bank.shape
-        nq = queries.shape[0]
         ns = sorted_rows.numel() if n_sorted is None else int(n_sorted)
-        if queries.dim() != 2 or queries.shape[1] != D or meta.shape != (M, 4) or rho.numel() != M or \
-                not (0 < nq <= self.MAX_QUERIES):
-            raise ValueError("Ivf2Staged: shape mismatch (1..8192 queries per staged pass)")
-        if centroids.shape != (256, D) or not (0 < nprobe <= 8) or not (0 < k <= 256) or D % 8 or D > 768:
-            raise ValueError("Ivf2Staged: centroids [256, D], nprobe <= 8, k <= 256, D % 8 == 0, D <= 768")
+        if meta.shape != (M, 4) or rho.numel() != M:
+            raise ValueError("Ivf2Lists: shape mismatch")
+        if centroids.shape != (256, D) or not (0 < nprobe <= 8):
+            raise ValueError("Ivf2Lists: centroids must be [256, D], nprobe in [1, 8]")
         if sorted_shadow.shape[1] != D or not (0 < ns <= min(sorted_rows.numel(), sorted_shadow.shape[0])) or \
                 pad_off.numel() != 257 or list_len.numel() != 256 or ns % 16:
-            raise ValueError("Ivf2Staged: layout arrays do not match")
+            raise ValueError("Ivf2Lists: layout arrays do not match")
+        if D % 8 or D > 768:
+            raise ValueError("Ivf2Lists: D % 8 == 0, D <= 768")
         if lists_flag is not None:
             _need(lists_flag, "lists_flag", torch.int32)
         if row_constants is not None:
             _need(row_constants, "row_constants", torch.float32)
             if row_constants.dim() != 2 or row_constants.shape[1] != 4 or row_constants.shape[0] < ns:
-                raise ValueError("Ivf2Staged: row_constants must be [>= n_sorted, 4]")
-        if probe_ids is not None:
-            _need(probe_ids, "probe_ids", torch.int32)
-            if tuple(probe_ids.shape) != (nq, 8):
-                raise ValueError("Ivf2Staged: probe_ids must be [nq, 8]")
-        self._init_fast(bank, inv_norm, meta, queries, k, now, centroids, nprobe, sorted_shadow, rho, sorted_rows, pad_off,
-                        list_len, idx_base, ns, lists_flag, probe_ids, row_constants, out)
+                raise ValueError("Ivf2Lists: row_constants must be [>= n_sorted, 4]")
+        # (the first ten in the order of the C entry points' leading arguments)
+        self._keep = (bank, inv_norm, meta, sorted_shadow, rho, sorted_rows, pad_off, list_len, lists_flag, row_constants,
+                      centroids)
+        self._ptrs = tuple(_p(t) for t in self._keep[:10])
+        self._cent = centroids.data_ptr()
+        self.M, self.D, self.ns, self.nprobe, self.device = M, D, ns, int(nprobe), bank.device
+        self._bytes = {}
+        self._lib = lib()
 
-    def _init_fast(self, bank, inv_norm, meta, queries, k, now, centroids, nprobe, sorted_shadow, rho, sorted_rows,
-                   pad_off, list_len, idx_base, n_sorted, lists_flag, probe_ids, row_constants, out):
-        M, D = bank.shape
-        nq = queries.shape[0]
+    def holds(self, bank, inv_norm, meta, centroids, nprobe: int, sorted_shadow, rho, sorted_rows, pad_off, list_len,
+              n_sorted: Optional[int] = None, lists_flag=None, row_constants=None) -> bool:
+        """Whether this handle was built from exactly these tensors (the constructor's arguments)."""
+        k = self._keep
         ns = sorted_rows.numel() if n_sorted is None else int(n_sorted)
-        if not (queries.is_cuda and queries.dtype == torch.float32 and queries.dim() == 2 and queries.shape[1] == D
-                and queries.is_contiguous() and 0 < nq <= self.MAX_QUERIES):
-            raise ValueError("Ivf2Staged: queries must be a contiguous fp32 [1..8192, D] tensor on the bank's device")
-        if probe_ids is not None and not (probe_ids.is_cuda and probe_ids.dtype == torch.int32 and
-                                          tuple(probe_ids.shape) == (nq, 8) and probe_ids.is_contiguous()):
-            raise ValueError("Ivf2Staged: probe_ids must be a contiguous int32 [nq, 8] tensor")
-        dev = bank.device
-        self._keep = (bank, inv_norm, meta, queries, centroids, sorted_shadow, rho, sorted_rows, pad_off, list_len,
-                      lists_flag, probe_ids, row_constants)
-        self.nq, self.k = nq, int(k)
-        if out is None:
-            self.out_s = torch.empty(nq, k, dtype=torch.float32, device=dev)
-            self.out_i = torch.empty(nq, k, dtype=torch.int32, device=dev)
+        return (k[0] is bank and k[1] is inv_norm and k[2] is meta and k[3] is sorted_shadow and k[4] is rho
+                and k[5] is sorted_rows and k[6] is pad_off and k[7] is list_len and k[8] is lists_flag
+                and k[9] is row_constants and k[10] is centroids and self.ns == ns and self.nprobe == int(nprobe))
+
+    def _call_args(self, queries, k: int, probe_ids):
+        """Checks of one call's queries, ``k`` and probes: (nq, probe pointer or None)."""
+        if not (isinstance(queries, torch.Tensor) and queries.is_cuda and queries.dtype == torch.float32
+                and queries.dim() == 2 and queries.shape[1] == self.D and queries.is_contiguous()):
+            _need(queries, "queries", torch.float32)
+            raise ValueError(f"Ivf2Lists: queries must be [nq, {self.D}]")
+        nq = queries.shape[0]
+        if not (0 < k <= 256):
+            raise ValueError("Ivf2Lists: k <= 256")
+        if probe_ids is None:
+            return nq, None
+        _need(probe_ids, "probe_ids", torch.int32)
+        if tuple(probe_ids.shape) != (nq, 8):
+            raise ValueError("Ivf2Lists: probe_ids must be [nq, 8] (centroid_probe)")
+        return nq, probe_ids.data_ptr()
+
+    def _scratch(self, nq: int, k: int):
+        """(workspace bytes, aligned workspace base, overflow flag, stream) of a call on the current stream."""
+        nbytes = self._bytes.get((nq, k))
+        if nbytes is None:
+            nbytes = self._bytes[(nq, k)] = self._lib.aura_knn_ivf2_workspace_bytes(self.ns, nq, k)
+        dev = self.device
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        key = (dev, stream)
+        ws = _workspaces.get(key)
+        base = ws[1] if ws is not None and ws[0] >= nbytes else _workspace(dev, nbytes)
+        ovf = _ovf_flags.get(key)
+        if ovf is None:
+            ovf = _overflow_flag(dev)
+        return nbytes, base, ovf, stream
+
+    def search(self, queries, k: int, now: float, probe_ids=None, idx_base: int = 0, word=None):
+        """(scores [nq, k], idx [nq, k], overflow flag [1]) of ``queries`` fp32 [nq, D].  ``probe_ids``:
+        ``centroid_probe``'s output for these queries and this centroid table (the probes are then not recomputed).
+        ``word`` (``CompletionWord``): the call's last workgroup also stores the flag there."""
+        nq, pid = self._call_args(queries, k, probe_ids)
+        dev = self.device
+        out_s = torch.empty(nq, k, dtype=torch.float32, device=dev)
+        out_i = torch.empty(nq, k, dtype=torch.int32, device=dev)
+        if nq == 0:
+            if word is not None:
+                word.arm(None)
+            return out_s, out_i, torch.zeros(1, dtype=torch.int32, device=dev)
+        nbytes, base, ovf, stream = self._scratch(nq, k)
+        h, L = self._ptrs, self._lib
+        if word is not None:
+            check(L.aura_knn_search_ivf2_signal(*h, self.ns, self.M, queries.data_ptr(), now, self.D, nq, k, self._cent,
+                                                self.nprobe, pid, idx_base, out_s.data_ptr(), out_i.data_ptr(), base,
+                                                nbytes, ovf.data_ptr(), word.ptr, word.arm(ovf), stream),
+                  "aura_knn_search_ivf2_signal")
+        elif pid is not None:
+            check(L.aura_knn_search_ivf2_probed(*h, self.ns, self.M, queries.data_ptr(), now, self.D, nq, k, self._cent,
+                                                self.nprobe, pid, idx_base, out_s.data_ptr(), out_i.data_ptr(), base,
+                                                nbytes, ovf.data_ptr(), stream), "aura_knn_search_ivf2_probed")
         else:
-            self.out_s, self.out_i = out
-            if not (self.out_s.is_contiguous() and self.out_i.is_contiguous() and tuple(self.out_s.shape) == (nq, k)
-                    and tuple(self.out_i.shape) == (nq, k) and self.out_s.dtype == torch.float32
-                    and self.out_i.dtype == torch.int32 and self.out_s.device == dev and self.out_i.device == dev):
-                raise ValueError("Ivf2Staged: out must be contiguous (fp32 [nq, k], int32 [nq, k]) on the bank's device")
-        self.ovf = _overflow_flag(dev)
-        L = lib()
-        self._nbytes = L.aura_knn_ivf2_workspace_bytes(ns, nq, k)
-        self._ws = _workspace(dev, self._nbytes)
-        base = (self._ws.data_ptr() + 255) // 256 * 256
+            check(L.aura_knn_search_ivf2(*h, self.ns, self.M, queries.data_ptr(), now, self.D, nq, k, self._cent,
+                                         self.nprobe, idx_base, out_s.data_ptr(), out_i.data_ptr(), base, nbytes,
+                                         ovf.data_ptr(), stream), "aura_knn_search_ivf2")
+        return out_s, out_i, ovf
+
+    def staged(self, queries, k: int, now: float, probe_ids=None, out=None, idx_base: int = 0) -> "Ivf2Pass":
+        """``search`` in stages for one pass of 1..``STAGED_MAX_QUERIES`` queries (see ``Ivf2Pass``).  ``out``:
+        (scores [nq, k] fp32, idx [nq, k] int32) to write into (contiguous; e.g. slices of the caller's result)."""
+        nq, pid = self._call_args(queries, k, probe_ids)
+        if not (0 < nq <= STAGED_MAX_QUERIES):
+            raise ValueError("Ivf2Lists.staged: 1..8192 queries per staged pass")
+        dev = self.device
+        if out is None:
+            out = (torch.empty(nq, k, dtype=torch.float32, device=dev), torch.empty(nq, k, dtype=torch.int32, device=dev))
+        out_s, out_i = out
+        if not (out_s.is_contiguous() and out_i.is_contiguous() and tuple(out_s.shape) == (nq, k)
+                and tuple(out_i.shape) == (nq, k) and out_s.dtype == torch.float32
+                and out_i.dtype == torch.int32 and out_s.device == dev and out_i.device == dev):
+            raise ValueError("Ivf2Lists.staged: out must be contiguous (fp32 [nq, k], int32 [nq, k]) on the bank's device")
+        nbytes, base, ovf, _ = self._scratch(nq, k)
+        args = self._ptrs + (self.ns, self.M, queries.data_ptr(), now, self.D, nq, k, self._cent, self.nprobe, pid,
+                             idx_base, out_s.data_ptr(), out_i.data_ptr(), base, nbytes, ovf.data_ptr())
+        return Ivf2Pass(self, queries, probe_ids, out_s, out_i, ovf, args)
+
+
+class Ivf2Pass:
+    """One staged pass of ``Ivf2Lists.staged`` (``aura_knn_search_ivf2_staged``): ``stage1(k2)`` -> bounds [nq, 2]
+    (the k-th and the k2-th largest sampled lower bound of every query on this bank), ``stage2_bounds(bound [nq], k2)``
+    -> the filtered candidates' own bounds [nq, 2], ``stage3(bound2 [nq])`` -> the result re-scored only where a
+    candidate can still reach ``bound2``.  Between the calls the caller combines the bounds of all shards of a
+    row-sharded bank; nothing else may use this stream's kNN workspace in between."""
+
+    def __init__(self, lists: Ivf2Lists, queries, probe_ids, out_s, out_i, ovf, args: tuple):
+        self._keep = (lists, queries, probe_ids)
+        self.nq = queries.shape[0]
+        self.out_s, self.out_i, self.ovf = out_s, out_i, ovf
         # (a plain tuple, not a closure over self: a self-referencing lambda made every staged pass a reference cycle
         #  that only the cyclic collector freed -- with its 2-MB result views -- and the allocator answered the pile-up
         #  with fresh hipMallocs: recalls of 1.2 ms read 1.6-3.4 ms at random)
-        self._args = (_p(bank), _p(inv_norm), _p(meta), _p(sorted_shadow), _p(rho), _p(sorted_rows), _p(pad_off),
-                      _p(list_len), _p(lists_flag), _p(row_constants), ns, M, _p(queries), now, D, nq, k, _p(centroids),
-                      nprobe, _p(probe_ids), idx_base, _p(self.out_s), _p(self.out_i), base, self._nbytes, _p(self.ovf))
+        self._args = args
 
     def _call(self, stage: int, k2: int, bounds) -> None:
         check(lib().aura_knn_search_ivf2_staged(*self._args, stage, k2, _p(bounds), _stream()),
               "aura_knn_search_ivf2_staged")
+
+    def _bound(self, bound: torch.Tensor) -> torch.Tensor:
+        _need(bound, "bound", torch.float32)
+        if bound.numel() != self.nq:
+            raise ValueError("Ivf2Pass: one bound per query")
+        return bound
 
     def stage1(self, k2: int = 0) -> torch.Tensor:
         b = torch.empty(self.nq, 2, dtype=torch.float32, device=self.out_s.device)
         self._call(1, int(k2), b)
         return b
 
-    def stage2(self, bound: torch.Tensor):
-        _need(bound, "bound", torch.float32)
-        if bound.numel() != self.nq:
-            raise ValueError("Ivf2Staged.stage2: one bound per query")
-        self._call(2, 0, bound)
-        return self.out_s, self.out_i, self.ovf
-
     def stage2_bounds(self, bound: torch.Tensor, k2: int) -> torch.Tensor:
-        """Stage 2 up to the filter scan, then the CANDIDATES' bounds [nq, 2] (the k-th and the k2-th largest lower
-        bound among this bank's candidates, -inf where there are fewer) instead of the refine: for a second, much
-        tighter combination over the shards, consumed by ``stage3``."""
-        _need(bound, "bound", torch.float32)
-        if bound.numel() != self.nq:
-            raise ValueError("Ivf2Staged.stage2_bounds: one bound per query")
+        """Stage 2 up to the filter scan with every threshold raised to ``bound`` first, then the CANDIDATES' bounds
+        [nq, 2] (the k-th and the k2-th largest lower bound among this bank's candidates, -inf where there are
+        fewer) instead of the refine: for a second, much tighter combination over the shards, consumed by ``stage3``."""
         b = torch.empty(self.nq, 2, dtype=torch.float32, device=self.out_s.device)
-        b.view(-1)[: self.nq].copy_(bound.reshape(-1))     # in: one bound per query; out: [nq, 2]
+        b.view(-1)[: self.nq].copy_(self._bound(bound).reshape(-1))     # in: one bound per query; out: [nq, 2]
         self._call(4, int(k2), b)
         return b
 
     def stage3(self, bound: torch.Tensor):
         """The refine against a lower bound of every query's k-th best score over ALL shards: candidates whose
         upper bound stays below it are not re-scored (rows of this bank's top k that cannot be in the global top k
-        come back as -1)."""
-        _need(bound, "bound", torch.float32)
-        if bound.numel() != self.nq:
-            raise ValueError("Ivf2Staged.stage3: one bound per query")
-        self._call(3, 0, bound)
+        come back as -1).  (scores, idx, overflow flag) as ``search``."""
+        self._call(3, 0, self._bound(bound))
         return self.out_s, self.out_i, self.ovf
+
+
+class CompletionWord:
+    """A host-mapped word that receives a recall's flag and a sequence number behind the recall's last launch:
+    ``wait()`` polls it -- no device-to-host copy, no stream synchronisation (a blocking wait on a ~1 ms stream costs
+    the host 1-2 ms on this runtime).  ``Ivf2Lists.search(word=...)`` fills it from the call's last workgroup
+    (``aura_knn_search_ivf2_signal``); ``signal(flag)`` enqueues a one-thread launch that copies a flag tensor into
+    it (a chain that ends in an entry point without one: the staged recall)."""
+
+    def __init__(self, device):
+        self.device = torch.device(device)
+        hw = ctypes.c_void_p()
+        with torch.cuda.device(self.device):
+            check(lib().aura_host_word_alloc(ctypes.byref(hw)), "aura_host_word_alloc")
+        self.ptr = hw.value
+        self._hw = (ctypes.c_uint32 * 2).from_address(hw.value)
+        self._seq = 0
+        self._flag = None             # the device flag behind the last launch; None: nothing was launched
+
+    def __del__(self):
+        try:
+            if getattr(self, "ptr", None):
+                torch.cuda.synchronize(self.device)          # no launch may still hold the word
+                lib().aura_host_word_free(self.ptr)
+                self.ptr = None
+        except Exception:
+            pass
+
+    def arm(self, flag: Optional[torch.Tensor]) -> int:
+        """Record a launch that will fill the word from the device tensor ``flag`` (None: the call launched
+        nothing, ``wait`` then reports 0); returns the sequence number that launch has to store."""
+        self._flag = flag
+        if flag is not None:
+            self._seq = (self._seq + 1) & 0x7fffffff or 1
+        return self._seq
+
+    def signal(self, flag: torch.Tensor) -> None:
+        _need(flag, "flag", torch.int32)
+        check(lib().aura_signal_flag(_p(flag), self.ptr, self.arm(flag), _stream()), "aura_signal_flag")
+
+    def wait(self, timeout_s: float = 5.0) -> int:
+        """The flag of the last launch (blocks until it has finished)."""
+        if self._flag is None:
+            return 0
+        hw, seq = self._hw, self._seq
+        t_end, n = None, 0
+        while hw[1] != seq:
+            n += 1
+            if (n & 0xfff) == 0:                             # every ~4000 polls: give up after timeout_s
+                now = time.perf_counter()
+                if t_end is None:
+                    t_end = now + timeout_s
+                elif now > t_end:
+                    warnings.warn(f"CompletionWord: no signal after {timeout_s} s; reading the flag from the device")
+                    return int(self._flag.item())
+        return int(hw[0])
 
 
 def topk_merge(scores, idx, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -1045,8 +949,7 @@ def kmeans_segment_means(bank, order, seg_off, centroids, k: int, sums_only: boo
         raise ValueError("kmeans_segment_means: shape mismatch")
     L = lib()
     nbytes = L.aura_kmeans_means_workspace_bytes(N, D, k)
-    ws = _workspace(bank.device, nbytes)
-    base = (ws.data_ptr() + 255) // 256 * 256
+    base = _workspace(bank.device, nbytes)
     check(L.aura_kmeans_segment_means(_p(bank), _p(order), _p(seg_off), _p(centroids), base, nbytes, N, D, k,
                                       1 if sums_only else 0, _stream()), "aura_kmeans_segment_means")
 

@@ -387,7 +387,7 @@ class ShardedHippocampus:
         # nq x 2 floats per pass of 8192 queries; every shard then keeps ~1/S of the candidates and survivors
         # it would keep against its own bound.  Whether the staged path is taken is agreed collectively once
         # per mutation epoch (every shard must be able to run it), never per call.
-        if cand and self.exchange_bounds and self._collective() and int(k) <= 256 and hasattr(self.ops, "Ivf2Staged") \
+        if cand and self.exchange_bounds and self._collective() and int(k) <= 256 and hasattr(self.ops, "Ivf2Lists") \
                 and self._exchange_agreed():
             self._recall_kw["bound_exchange"] = (self._exchange, self.world)
         if all_gather_queries and self._collective():

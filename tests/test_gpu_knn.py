@@ -623,6 +623,16 @@ def test_product_centroid_recall_paths_agree(dev):
     a.create_episodic_memories([f"n{i}" for i in range(64)], feats[:64] * 1.01)   # lists change
     b.create_episodic_memories([f"n{i}" for i in range(64)], feats[:64] * 1.01)
     b.memory_metadata.copy_(a.memory_metadata)
+    # zero queries on the inverted lists (the masked scan switched off for this bank): an empty result that
+    # launches nothing and reports no flag, and the next call's flag is its own
+    a.MASKED_SCAN_MAX_ROWS = 0
+    s0, r0 = a.recall_batch(q2[:0], k=9, now=now)
+    assert tuple(s0.shape) == (0, 9) and tuple(r0.shape) == (0, 9) and r0.dtype == torch.int32
+    assert a._ivf.lists is not None and a._last_flag == 0
+    sa, ra = a.recall_batch(q[:7], k=9, now=now)
+    sb, rb = b.recall_batch(q[:7], k=9, now=now)
+    assert torch.equal(ra, rb) and torch.equal(sa, sb)
+    del a.MASKED_SCAN_MAX_ROWS
     sa, ra = a.recall_batch(q2, k=9, now=now)
     sb, rb = b.recall_batch(q2, k=9, now=now)
     assert torch.equal(ra, rb) and torch.equal(sa, sb)
