@@ -20,7 +20,9 @@ Batch entry points that the reference lacks (its callers loop in Python,
 
 Reference defects on this path (SURVEY.md 8a "hazards") and what this class does:
   * full bank -> always slot 0 (``:200-202``): REPRODUCED by default (``overflow='reference'``);
-    ``overflow='fifo'`` opts into a real ring buffer.
+    ``overflow='fifo'`` opts into a real ring buffer, ``overflow='weakest'`` into retention: a full bank
+    gives up the rows with the smallest ``strength * exp(-age / 3600)`` (``aura_bank_select_weakest``), and
+    ``reinforce`` / ``recall_batch(reinforce=...)`` raise the strength of rows that are used.
   * centroid candidates: ``topk`` positions are looked up as bank rows (``:307-317``) -> right
     scores, wrong ids: FIXED (rows are reported); ``k`` is clamped to the number of candidates
     instead of raising; ``location=`` works with candidates.
@@ -104,6 +106,9 @@ class _IvfState:
         self.rowc_version = -1        # memory_metadata._version it was built from (catches in-place edits by the user)
 
 
+OVERFLOW_POLICIES = ('reference', 'fifo', 'weakest')
+
+
 class HippocampalFormation(nn.Module):
     # above this many rows the inverted lists (each probed list read once per batch) beat a masked
     # pass over every row
@@ -181,8 +186,8 @@ class HippocampalFormation(nn.Module):
         self._lists = None                        # fp32 fallback lists (list_rows, list_off, list_len, longest)
         self._lists_dirty = True
 
-        if overflow not in ('reference', 'fifo'):
-            raise ValueError("overflow must be 'reference' or 'fifo'")
+        if overflow not in OVERFLOW_POLICIES:
+            raise ValueError(f"overflow must be 'reference', 'fifo' or 'weakest', got {overflow!r}")
         self._overflow = overflow
         self._write_cursor = 0
         self.register_load_state_dict_post_hook(lambda module, incompatible: module._invalidate_norms())
@@ -387,9 +392,18 @@ class HippocampalFormation(nn.Module):
         return {"time_cells": time_rates.flatten(), "elapsed": elapsed}
 
     # ------------------------------------------------------------------ write
-    def _plan_slots(self, n: int):
+    def _plan_slots(self, n: int, now: Optional[float] = None):
         """Slots (int64 ndarray) for the next n writes, how many of them append, and the counters they
-        leave behind (nothing is mutated until the kernel launch has been accepted)."""
+        leave behind (nothing is mutated until the kernel launch has been accepted).
+
+        ``overflow='weakest'``: the ``rest`` rows that do not fit overwrite the first ``rest`` rows of the
+        eviction order -- ascending ``(strength * exp(-(now - timestamp) / 3600), (row - cursor) mod count)``
+        over the rows held BEFORE this write, ``now`` the write's own timestamp.  The batch is the unit: all
+        its victims are ranked once, so a batch is NOT the same as n one-row writes (a one-row loop re-ranks
+        after every row, and may evict a row it has just written).  In a bank of equal keys the victims are
+        exactly the slots ``'fifo'`` takes, in the same order.  The id maps live on the host, so the selected
+        slots are copied there: one device-to-host read per OVERFLOWING run; appends and the other two
+        policies read nothing back."""
         M, count, cursor = self.max_memories, self.memory_count, self._write_cursor
         n_app = min(n, max(M - count, 0))
         slots = np.empty(n, dtype=np.int64)
@@ -398,6 +412,13 @@ class HippocampalFormation(nn.Module):
         if rest:
             if self._overflow == 'reference':
                 slots[n_app:] = 0                  # count % max_memories with count == max_memories (:200-202)
+            elif self._overflow == 'weakest':
+                if rest > count:                   # (create_episodic_memories splits such runs)
+                    raise ValueError(f"'weakest' cannot evict {rest} rows from a bank that holds {count}")
+                rows, _ = ops.bank_select_weakest(self.memory_metadata, count, time.time() if now is None else now,
+                                                  cursor % M, rest)
+                slots[n_app:] = rows.cpu().numpy()
+                cursor += rest
             else:
                 slots[n_app:] = (cursor + np.arange(rest, dtype=np.int64)) % M
                 cursor += rest
@@ -431,9 +452,9 @@ class HippocampalFormation(nn.Module):
 
     def _write_rows(self, ids: Sequence[str], feats: torch.Tensor, now: float) -> None:
         """Write a run of rows that contains no centroid-rebuild boundary."""
-        slots, n_app, new_count, new_cursor = self._plan_slots(len(ids))
+        slots, n_app, new_count, new_cursor = self._plan_slots(len(ids), now)
         self._store_rows(ids, feats, slots, n_app, new_count, new_cursor, now,
-                         online=self.use_centroid_index and self._index_ready)
+                         online=self.use_centroid_index and self._index_ready, selected=True)
 
     def write_at(self, ids: Sequence[str], feats: torch.Tensor, slots: np.ndarray, n_app: int, now: float,
                  cids: Optional[torch.Tensor] = None) -> None:
@@ -456,7 +477,8 @@ class HippocampalFormation(nn.Module):
                          online=False, cids=cids)
 
     def _store_rows(self, ids, feats, slots: np.ndarray, n_app: int, new_count: int, new_cursor: int, now: float,
-                    online: bool, cids: Optional[torch.Tensor] = None) -> None:
+                    online: bool, cids: Optional[torch.Tensor] = None, selected: bool = False) -> None:
+        """``selected``: the slots come from ``_plan_slots`` (not from a caller of ``write_at``)."""
         c0 = self.memory_count
         meta_v0 = self.memory_metadata._version
         slot_t = torch.from_numpy(slots).to(self.device)
@@ -465,7 +487,12 @@ class HippocampalFormation(nn.Module):
         # sends every write to slot 0): the last write wins, as in the reference's sequential loop.  The
         # serial centroid kernel walks the rows in order; the parallel kernel gets the survivors only.
         # (appends and a FIFO ring that does not lap itself name every slot once: no need to look)
-        ring_distinct = self._overflow != 'reference' and slots.size - n_app <= self.max_memories
+        if self._overflow == 'weakest':
+            # a selection names every victim once, and victims are rows held before the write: distinct as long
+            # as no more rows are evicted than were held (_plan_slots refuses more)
+            ring_distinct = selected and slots.size - n_app <= c0
+        else:
+            ring_distinct = self._overflow != 'reference' and slots.size - n_app <= self.max_memories
         keep = None if (slots.size == n_app or ring_distinct) else self._last_occurrences(slots, n_app)
         keep_t = None if keep is None else torch.from_numpy(keep).to(self.device)
         uniq_t = slot_t if keep is None else slot_t[keep_t].contiguous()
@@ -492,7 +519,10 @@ class HippocampalFormation(nn.Module):
             self._idx_to_id[c0:c0 + n_app] = list(ids[:n_app])
         if len(slot_list) > n_app:
             over = slot_list[n_app:]
-            if ring_distinct and over[-1] - over[0] == len(over) - 1:      # one contiguous run of the ring: a slice
+            run = ring_distinct and over[-1] - over[0] == len(over) - 1
+            if run and self._overflow == 'weakest':                        # (a selection need not ascend)
+                run = bool((np.diff(slots[n_app:]) == 1).all())
+            if run:                                                        # one contiguous run of the ring: a slice
                 self._idx_to_id[over[0]:over[-1] + 1] = list(ids[n_app:])
             else:
                 for mid, slot in zip(ids[n_app:], over):
@@ -552,6 +582,9 @@ class HippocampalFormation(nn.Module):
         while i < n:
             # run length until the next insert that triggers a rebuild
             run = n - i
+            if self._overflow == 'weakest':
+                # a run evicts at most the rows held before it: run - room <= count, that is run <= max_memories
+                run = min(run, self.max_memories)
             if self.use_centroid_index:
                 interval = max(1, int(self.centroids_update_interval))
                 if self.memory_count < self.max_memories:
@@ -574,7 +607,8 @@ class HippocampalFormation(nn.Module):
                      use_candidates: Optional[bool] = None, check_overflow: bool = True,
                      fallback_empty: bool = True,
                      probe_ids: Optional[torch.Tensor] = None, _retry: int = 0,
-                     bound_exchange=None) -> Tuple[torch.Tensor, torch.Tensor]:
+                     bound_exchange=None, reinforce: Optional[float] = None,
+                     reinforce_cap: float = 1.0) -> Tuple[torch.Tensor, torch.Tensor]:
         """Batched recall: ``(scores [nq, k'], rows [nq, k'])`` with ``k' = min(k, count)``;
         rows are bank row indices (int32), ``-1`` where a query has fewer than ``k'`` candidates.
 
@@ -590,7 +624,16 @@ class HippocampalFormation(nn.Module):
         (``sharded.ShardedHippocampus``): ``(fn, parts)`` -- the inverted-list recall runs in stages per pass of
         at most 8192 queries and ``fn(bounds [n, 2]) -> bound [n]`` combines every shard's bounds in between (a
         collective: it is called exactly ``2 ceil(nq / 8192)`` times -- sampled bounds, then the filtered
-        candidates' bounds -- whatever path this bank takes)."""
+        candidates' bounds -- whatever path this bank takes).  ``reinforce``: when given, the rows this call
+        returns are reinforced by that amount up to ``reinforce_cap`` (``reinforce()``), once, after the results
+        are final; None (default) launches nothing."""
+        if reinforce is not None:
+            # the plain call (with its own retries and fallbacks) first: the rows are final when it returns
+            scores, rows = self.recall_batch(queries, k=k, locations=locations, now=now, use_candidates=use_candidates,
+                                             check_overflow=check_overflow, fallback_empty=fallback_empty,
+                                             probe_ids=probe_ids, _retry=_retry, bound_exchange=bound_exchange)
+            self.reinforce(rows, amount=reinforce, cap=reinforce_cap)
+            return scores, rows
         self._last_flag = None                        # set only by a candidate-mode recall that read its flag
         if self.memory_count == 0:
             self._drain_exchanges(queries.shape[0], bound_exchange)
@@ -833,6 +876,36 @@ class HippocampalFormation(nn.Module):
 
     def decay(self, rate: float = 0.01) -> None:
         self.decay_memories(decay_rate=rate)
+
+    # ------------------------------------------------------------------ retention
+    def reinforce(self, rows, amount: float = 0.1, cap: float = 1.0) -> None:
+        """Strengthen the memories at bank rows ``rows`` (int, any shape, e.g. what ``recall_batch`` returned;
+        ``-1`` and rows outside the bank are ignored): ``strength = min(strength + amount, cap)`` where it is
+        below ``cap``, once per distinct row however often it occurs.  ``cap`` defaults to the strength a write
+        gives.  With ``overflow='weakest'`` reinforced rows are the last to be evicted."""
+        if self.memory_count == 0:
+            return
+        if not isinstance(rows, torch.Tensor):
+            rows = torch.as_tensor(np.asarray(rows))
+        rows = rows.to(device=self.device, dtype=torch.int32).contiguous()
+        if rows.numel() == 0:
+            return
+        ops.bank_reinforce(self.memory_metadata, self.memory_count, rows, float(amount), float(cap))
+        if self._ivf is not None:
+            self._ivf.rowc_live = False                 # strengths changed under the cached score constants
+
+    def retention_keys(self, now: Optional[float] = None) -> torch.Tensor:
+        """fp32 [memory_count]: ``strength * exp(-(now - timestamp) / 3600)`` of every held row, the key
+        ``overflow='weakest'`` evicts by (read-only)."""
+        now = time.time() if now is None else now
+        return ops.bank_retention_keys(self.memory_metadata, self.memory_count, now)
+
+    def weakest(self, n: int, now: Optional[float] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``(rows int64 [n], keys fp32 [n])``: the ``n`` rows a write at ``now`` would evict first, in that
+        order, with the current write cursor (read-only; ``1 <= n <= memory_count``)."""
+        now = time.time() if now is None else now
+        return ops.bank_select_weakest(self.memory_metadata, self.memory_count, now,
+                                       self._write_cursor % self.max_memories, int(n))
 
     def rebuild_centroids(self, perm: Optional[torch.Tensor] = None) -> None:
         """One Lloyd iteration from a random sample of rows (reference ``:345-377``).

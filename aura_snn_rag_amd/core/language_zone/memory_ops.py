@@ -14,19 +14,21 @@ Use either as free functions or through ``BatchedMemoryMixin``::
 from __future__ import annotations
 
 import uuid
-from typing import Tuple
+from typing import Optional, Tuple
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
 
-def retrieve_memories(hippocampus, query: torch.Tensor, k: int = 5, dtype=None
+def retrieve_memories(hippocampus, query: torch.Tensor, k: int = 5, dtype=None,
+                      reinforce: Optional[float] = None, reinforce_cap: float = 1.0
                       ) -> Tuple[torch.Tensor, torch.Tensor]:
     """``query`` [B, D] (already projected) -> (memory_features [B, k, D], memory_scores [B, k]).
 
     Same contract as the reference loop (``memory_augmented_layer.py:106-130``): slots beyond the
-    number of hits stay zero."""
+    number of hits stay zero.  ``reinforce`` (default off): strengthen the retrieved rows by that amount up to
+    ``reinforce_cap`` (``HippocampalFormation.recall_batch(reinforce=...)``)."""
     B, D = query.shape
     dtype = dtype or query.dtype
     dev = query.device
@@ -34,7 +36,8 @@ def retrieve_memories(hippocampus, query: torch.Tensor, k: int = 5, dtype=None
     scores = torch.zeros(B, k, device=dev, dtype=dtype)
     if hippocampus is None or hippocampus.memory_count == 0:
         return feats, scores
-    s, rows = hippocampus.recall_batch(query.detach().float(), k=k)      # [B, k'] (k' <= k)
+    kw = {} if reinforce is None else dict(reinforce=reinforce, reinforce_cap=reinforce_cap)
+    s, rows = hippocampus.recall_batch(query.detach().float(), k=k, **kw)      # [B, k'] (k' <= k)
     kk = s.shape[1]
     valid = rows >= 0
     feats[:, :kk] = hippocampus.gather_features(rows).to(dtype)            # -1 rows gather zeros
@@ -100,9 +103,11 @@ class MemoryInjection(nn.Module):
         self.dropout = nn.Dropout(dropout)
         self.query_proj = nn.Linear(embedding_dim, embedding_dim)
 
-    def retrieve_memories(self, hidden_states: torch.Tensor, k: int = 5):
+    def retrieve_memories(self, hidden_states: torch.Tensor, k: int = 5, reinforce: Optional[float] = None,
+                          reinforce_cap: float = 1.0):
         query = self.query_proj(hidden_states.mean(dim=1))
-        return retrieve_memories(self.hippocampus, query, k=k, dtype=hidden_states.dtype)
+        return retrieve_memories(self.hippocampus, query, k=k, dtype=hidden_states.dtype, reinforce=reinforce,
+                                 reinforce_cap=reinforce_cap)
 
     def inject_memories(self, hidden_states, memory_features, memory_scores):
         if self.memory_injection == "cross_attention":
@@ -123,9 +128,11 @@ class BatchedMemoryMixin:
     """Overrides ``retrieve_memories`` / ``store_memory`` of the reference layer with the batched
     HIP path; ``inject_memories`` and everything else stay the layer's own."""
 
-    def retrieve_memories(self, hidden_states: torch.Tensor, k: int = 5):
+    def retrieve_memories(self, hidden_states: torch.Tensor, k: int = 5, reinforce: Optional[float] = None,
+                          reinforce_cap: float = 1.0):
         query = self.query_proj(hidden_states.mean(dim=1))
-        return retrieve_memories(self.hippocampus, query, k=k, dtype=hidden_states.dtype)
+        return retrieve_memories(self.hippocampus, query, k=k, dtype=hidden_states.dtype, reinforce=reinforce,
+                                 reinforce_cap=reinforce_cap)
 
     def store_memory(self, hidden_states: torch.Tensor):
         store_memory(self.hippocampus, hidden_states, event_tag=f"layer_{id(self)}")

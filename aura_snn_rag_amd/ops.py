@@ -389,6 +389,69 @@ def _overflow_flag(device) -> torch.Tensor:
     return f
 
 
+def _workspace_view(device, nbytes: int) -> torch.Tensor:
+    """The first ``nbytes`` of this (device, stream)'s scratch as a uint8 tensor (what a kernel left there)."""
+    base = _workspace(device, nbytes)
+    buf = _workspaces[_wkey(device)][2]
+    off = base - buf.data_ptr()
+    return buf[off:off + nbytes]
+
+
+def _check_meta(meta, count: int, who: str) -> None:
+    _need(meta, "meta", torch.float32)
+    if meta.dim() != 2 or meta.shape[1] != 4 or not (0 <= count <= meta.shape[0]):
+        raise ValueError(f"{who}: meta must be [rows, 4] with count <= rows")
+
+
+def bank_retention_keys(meta, count: int, now: float) -> torch.Tensor:
+    """fp32 [count]: ``strength * expf(-(now - timestamp) / 3600)`` of rows [0, count) -- the part of the recall
+    score that belongs to the row alone, and the key of the ``'weakest'`` overflow policy."""
+    _check_meta(meta, count, "bank_retention_keys")
+    out = torch.empty(count, dtype=torch.float32, device=meta.device)
+    check(lib().aura_bank_retention_keys(_p(meta), count, now, _p(out), _stream()), "aura_bank_retention_keys")
+    return out
+
+
+def bank_select_weakest(meta, count: int, now: float, cursor: int, n: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The first ``n`` rows (int64 [n]) of the eviction order of rows [0, count) and their keys (fp32 [n]):
+    ascending ``(key, (row - cursor) mod count)``, a NaN key first.  The passes over the ``count`` rows are one
+    radix select in the library; the n selected entries are then ordered by one ``torch.sort`` of their
+    64-bit composites.  No host sync."""
+    _check_meta(meta, count, "bank_select_weakest")
+    if not (1 <= n <= count) or cursor < 0:
+        raise ValueError(f"bank_select_weakest: need 1 <= n <= count and cursor >= 0 (n={n}, count={count}, cursor={cursor})")
+    L = lib()
+    nbytes = L.aura_bank_select_weakest_workspace_bytes(count, n)
+    if nbytes < 0:
+        raise ValueError("bank_select_weakest: unsupported size")
+    base = _workspace(meta.device, nbytes)
+    slots = torch.empty(n, dtype=torch.int64, device=meta.device)
+    keys = torch.empty(n, dtype=torch.float32, device=meta.device)
+    check(L.aura_bank_select_weakest(_p(meta), count, now, cursor, n, _p(slots), _p(keys), base, nbytes, _stream()),
+          "aura_bank_select_weakest")
+    if n == 1:
+        return slots, keys
+    # (the sort reads the workspace before any later call on this stream can overwrite it)
+    order = torch.sort(_workspace_view(meta.device, 8 * n).view(torch.int64)).indices
+    return slots[order], keys[order]
+
+
+def bank_reinforce(meta, count: int, rows, amount: float, cap: float = 1.0) -> None:
+    """``meta[r][0] = min(meta[r][0] + amount, cap)`` where it is below ``cap``, once for every distinct row id
+    of ``rows`` (int32, any shape) inside [0, count); ``-1`` and other ids outside are ignored."""
+    _check_meta(meta, count, "bank_reinforce")
+    _need(rows, "rows", torch.int32)
+    if not (amount >= 0.0) or cap != cap:
+        raise ValueError("bank_reinforce: amount must be >= 0 and cap a number")
+    if rows.device != meta.device:
+        raise ValueError("bank_reinforce: rows and meta are on different devices")
+    L = lib()
+    nbytes = L.aura_bank_reinforce_workspace_bytes(count)
+    base = _workspace(meta.device, nbytes)
+    check(L.aura_bank_reinforce(_p(meta), count, _p(rows), rows.numel(), amount, cap, base, nbytes, _stream()),
+          "aura_bank_reinforce")
+
+
 def knn_search(bank, inv_norm, meta, queries, k: int, now: float, count: Optional[int] = None,
                loc=None, q_loc=None, idx_base: int = 0, force_dense: bool = False,
                centroids=None, nprobe: int = 0, check_overflow: bool = True,

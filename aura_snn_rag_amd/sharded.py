@@ -108,6 +108,7 @@ class ShardedHippocampus:
         import time as _time
         from . import ops as _ops
         self.local = local
+        self._refuse_weakest()
         self.ops = _ops if ops_module is None else ops_module
         self.group = group
         self.R = int(local.max_memories)
@@ -154,11 +155,21 @@ class ShardedHippocampus:
     def use_centroid_index(self) -> bool:
         return self.local.use_centroid_index
 
+    def _refuse_weakest(self) -> None:
+        """Raised from local state alone, so on every rank alike and before any collective."""
+        if getattr(self.local, '_overflow', None) == 'weakest':
+            raise ValueError("ShardedHippocampus does not support overflow='weakest': the slots of a sharded bank are "
+                             "planned globally, and a global weakest-first order needs a selection across shards "
+                             "(local select, all-gather of the candidates, merge) that is not implemented; use "
+                             "'reference' or 'fifo' (reinforce() on the local bank of a shard works as on any bank)")
+
     # ------------------------------------------------------------------ write
     def write(self, memory_ids, features) -> None:
         """Collective batched write: identical to ``HippocampalFormation.create_episodic_memories`` on one
-        bank of ``total_rows`` rows, including the rebuild every ``centroids_update_interval`` inserts."""
+        bank of ``total_rows`` rows, including the rebuild every ``centroids_update_interval`` inserts
+        (``overflow='reference'`` or ``'fifo'``; ``'weakest'`` raises ``ValueError``)."""
         import numpy as np
+        self._refuse_weakest()
         loc = self.local
         feats = loc._features_to_device(features)
         n = len(memory_ids)

@@ -119,6 +119,30 @@ int aura_bank_write_online(float* bank, float* loc, float* meta, float* inv_norm
 /* meta[i][0] *= (1 - rate) for i < count.  Replaces decay_memories, hippocampal.py:334. */
 int aura_bank_decay(float* meta, float rate, int64_t count, void* stream);
 
+/* Retention: which rows a full bank gives up first, and reinforcement of the rows a recall returned.
+ * [build-side] no upstream counterpart (the reference's full bank overwrites slot 0).
+ *   key(r) = meta[r][0] * expf(-(now - meta[r][1]) / 3600)          (strength x the recall's temporal factor)
+ * Eviction order of rows [0, count): (key, (r - cursor) mod count) ascending, a NaN key first, -0 == +0.
+ * aura_bank_retention_keys: out[r] = key(r), r < count.
+ * aura_bank_select_weakest: the first n rows of the eviction order (1 <= n <= count, 0 <= cursor) by a radix
+ *   select over the composite  ordered_u32(key) << 32 | rotated row : the metadata is read once (16 B per row),
+ *   every further pass reads 4 B per row.  out_slots / out_keys (device, [n]) receive the n rows and their keys
+ *   in the compaction's arrival order, and the first n int64 of the workspace the rows' composites with the top
+ *   bit flipped (ascending as signed integers = the eviction order): sorting those n values orders the
+ *   selection (ops.bank_select_weakest does).  workspace: *_workspace_bytes(count, n) bytes, 256-byte aligned.
+ * aura_bank_reinforce: for every DISTINCT r in rows[0 .. n_rows) with 0 <= r < count (others are ignored):
+ *   s = meta[r][0]; if (s < cap) meta[r][0] = fminf(s + amount, cap) -- once per call however often r occurs
+ *   (a bitmap of count bits in the workspace, cleared by the call).  amount >= 0.
+ * All three read 16-byte metadata rows: meta must be 16-byte aligned. */
+int aura_bank_retention_keys(const float* meta, int64_t count, float now, float* out, void* stream);
+int64_t aura_bank_select_weakest_workspace_bytes(int64_t count, int64_t n);
+int aura_bank_select_weakest(const float* meta, int64_t count, float now, int64_t cursor, int64_t n,
+                             int64_t* out_slots, float* out_keys, void* workspace, int64_t workspace_bytes,
+                             void* stream);
+int64_t aura_bank_reinforce_workspace_bytes(int64_t count);
+int aura_bank_reinforce(float* meta, int64_t count, const int32_t* rows, int64_t n_rows, float amount, float cap,
+                        void* workspace, int64_t workspace_bytes, void* stream);
+
 /* Workspace size (bytes) aura_knn_search needs for (N, nq, k). */
 int64_t aura_knn_workspace_bytes(int64_t N, int64_t nq, int k);
 
