@@ -608,7 +608,9 @@ class HippocampalFormation(nn.Module):
                      fallback_empty: bool = True,
                      probe_ids: Optional[torch.Tensor] = None, _retry: int = 0,
                      bound_exchange=None, reinforce: Optional[float] = None,
-                     reinforce_cap: float = 1.0) -> Tuple[torch.Tensor, torch.Tensor]:
+                     reinforce_cap: float = 1.0, diversity: Optional[float] = None,
+                     max_similarity: Optional[float] = None,
+                     fetch_k: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """Batched recall: ``(scores [nq, k'], rows [nq, k'])`` with ``k' = min(k, count)``;
         rows are bank row indices (int32), ``-1`` where a query has fewer than ``k'`` candidates.
 
@@ -626,7 +628,18 @@ class HippocampalFormation(nn.Module):
         collective: it is called exactly ``2 ceil(nq / 8192)`` times -- sampled bounds, then the filtered
         candidates' bounds -- whatever path this bank takes).  ``reinforce``: when given, the rows this call
         returns are reinforced by that amount up to ``reinforce_cap`` (``reinforce()``), once, after the results
-        are final; None (default) launches nothing."""
+        are final; None (default) launches nothing.  ``diversity`` / ``max_similarity`` (both None by default:
+        nothing changes and nothing more is launched): diverse recall -- the call fetches the top
+        ``F = min(fetch_k or max(32, 4 k'), 128, count)`` rows as above and one kernel picks ``k'`` of them greedily
+        (``ops.diverse_select``): a candidate whose cosine to an earlier pick reaches ``max_similarity`` (in
+        ``(-1, 1]``) is skipped, the others rank by ``(1 - diversity) * score - diversity * (largest cosine to an
+        earlier pick)``, ``diversity`` in ``[0, 1]``.  Rows come back in pick order with their recall scores, ``-1`` /
+        ``-inf`` where fewer than ``k'`` were eligible; ``reinforce`` then applies to the rows returned."""
+        if diversity is not None or max_similarity is not None:
+            return self._recall_diverse(queries, k, diversity, max_similarity, fetch_k, bound_exchange, reinforce,
+                                        reinforce_cap, dict(locations=locations, now=now, use_candidates=use_candidates,
+                                                            check_overflow=check_overflow, fallback_empty=fallback_empty,
+                                                            probe_ids=probe_ids, _retry=_retry))
         if reinforce is not None:
             # the plain call (with its own retries and fallbacks) first: the rows are final when it returns
             scores, rows = self.recall_batch(queries, k=k, locations=locations, now=now, use_candidates=use_candidates,
@@ -682,6 +695,35 @@ class HippocampalFormation(nn.Module):
             scores, rows = self._recall_fp32(q, kk, now, nprobe, q_loc is None and full_index, kw)
         if check_overflow and fallback_empty:
             self._fill_empty_queries(q, q_loc, kk, now, scores, rows, kw)
+        return scores, rows
+
+    DIVERSE_MIN_FETCH = 32             # candidates fetched per query unless fetch_k says otherwise: max(32, 4 k)
+
+    def _recall_diverse(self, queries, k: int, diversity, max_similarity, fetch_k, bound_exchange, reinforce,
+                        reinforce_cap: float, kw) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``recall_batch`` with ``diversity`` / ``max_similarity``: one plain recall of F candidates (its retries and
+        fallbacks included, whatever path the bank takes), one selection kernel, then the reinforcement."""
+        d = 0.0 if diversity is None else float(diversity)
+        if not (0.0 <= d <= 1.0):
+            raise ValueError(f"diversity must be in [0, 1], got {diversity}")
+        if max_similarity is not None and not (-1.0 < float(max_similarity) <= 1.0):
+            raise ValueError(f"max_similarity must be in (-1, 1], got {max_similarity}")
+        if bound_exchange is not None:
+            raise ValueError("diverse recall needs the candidates' rows on this device: not with bound_exchange "
+                             "(a shard of a row-sharded bank)")
+        if self.memory_count == 0:
+            return self.recall_batch(queries, k=k, **kw)
+        kk = min(int(k), self.memory_count)
+        F = min(int(fetch_k) if fetch_k else max(self.DIVERSE_MIN_FETCH, 4 * kk), ops.DIVERSE_MAX_CANDIDATES,
+                self.memory_count)
+        if F < kk:
+            raise ValueError(f"diverse recall selects k={kk} rows among F={F} fetched candidates: needs k <= fetch_k <= "
+                             f"{ops.DIVERSE_MAX_CANDIDATES}")
+        cand_s, cand_r = self.recall_batch(queries, k=F, **kw)
+        scores, rows = ops.diverse_select(self.memory_features, self._inv_norm, self.memory_count, cand_r.contiguous(),
+                                          cand_s.contiguous(), kk, d, max_similarity)
+        if reinforce is not None:
+            self.reinforce(rows, amount=reinforce, cap=reinforce_cap)
         return scores, rows
 
     def _query_locations(self, locations, nq: int) -> Optional[torch.Tensor]:
@@ -814,12 +856,16 @@ class HippocampalFormation(nn.Module):
 
     def retrieve_similar_memories(self, query_features: torch.Tensor,
                                   location: Optional[torch.Tensor] = None,
-                                  k: int = 5) -> List[Tuple[str, float]]:
-        """Top-k ``(memory_id, score)`` for one query (reference ``:245-319``)."""
+                                  k: int = 5, *, diversity: Optional[float] = None,
+                                  max_similarity: Optional[float] = None,
+                                  fetch_k: Optional[int] = None) -> List[Tuple[str, float]]:
+        """Top-k ``(memory_id, score)`` for one query (reference ``:245-319``).  The keyword arguments are
+        ``recall_batch``'s diverse recall (default off)."""
         if self.memory_count == 0:
             return []
         q = self._features_to_device(query_features, rows=1)
-        scores, rows = self.recall_batch(q, k=k, locations=location)
+        scores, rows = self.recall_batch(q, k=k, locations=location, diversity=diversity,
+                                         max_similarity=max_similarity, fetch_k=fetch_k)
         out = []
         for s, r in zip(scores[0].tolist(), rows[0].tolist()):
             mid = self.id_of_row(r) if r >= 0 else None

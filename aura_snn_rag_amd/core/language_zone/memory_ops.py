@@ -22,13 +22,16 @@ import torch.nn.functional as F
 
 
 def retrieve_memories(hippocampus, query: torch.Tensor, k: int = 5, dtype=None,
-                      reinforce: Optional[float] = None, reinforce_cap: float = 1.0
-                      ) -> Tuple[torch.Tensor, torch.Tensor]:
+                      reinforce: Optional[float] = None, reinforce_cap: float = 1.0,
+                      diversity: Optional[float] = None, max_similarity: Optional[float] = None,
+                      fetch_k: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """``query`` [B, D] (already projected) -> (memory_features [B, k, D], memory_scores [B, k]).
 
     Same contract as the reference loop (``memory_augmented_layer.py:106-130``): slots beyond the
     number of hits stay zero.  ``reinforce`` (default off): strengthen the retrieved rows by that amount up to
-    ``reinforce_cap`` (``HippocampalFormation.recall_batch(reinforce=...)``)."""
+    ``reinforce_cap`` (``HippocampalFormation.recall_batch(reinforce=...)``).  ``diversity`` / ``max_similarity`` /
+    ``fetch_k`` (default off): diverse recall, so that near-copies of one memory do not fill the k slots
+    (``HippocampalFormation.recall_batch(diversity=..., max_similarity=...)``)."""
     B, D = query.shape
     dtype = dtype or query.dtype
     dev = query.device
@@ -37,6 +40,8 @@ def retrieve_memories(hippocampus, query: torch.Tensor, k: int = 5, dtype=None,
     if hippocampus is None or hippocampus.memory_count == 0:
         return feats, scores
     kw = {} if reinforce is None else dict(reinforce=reinforce, reinforce_cap=reinforce_cap)
+    if diversity is not None or max_similarity is not None:
+        kw.update(diversity=diversity, max_similarity=max_similarity, fetch_k=fetch_k)
     s, rows = hippocampus.recall_batch(query.detach().float(), k=k, **kw)      # [B, k'] (k' <= k)
     kk = s.shape[1]
     valid = rows >= 0
@@ -104,10 +109,12 @@ class MemoryInjection(nn.Module):
         self.query_proj = nn.Linear(embedding_dim, embedding_dim)
 
     def retrieve_memories(self, hidden_states: torch.Tensor, k: int = 5, reinforce: Optional[float] = None,
-                          reinforce_cap: float = 1.0):
+                          reinforce_cap: float = 1.0, *, diversity: Optional[float] = None,
+                          max_similarity: Optional[float] = None, fetch_k: Optional[int] = None):
         query = self.query_proj(hidden_states.mean(dim=1))
         return retrieve_memories(self.hippocampus, query, k=k, dtype=hidden_states.dtype, reinforce=reinforce,
-                                 reinforce_cap=reinforce_cap)
+                                 reinforce_cap=reinforce_cap, diversity=diversity, max_similarity=max_similarity,
+                                 fetch_k=fetch_k)
 
     def inject_memories(self, hidden_states, memory_features, memory_scores):
         if self.memory_injection == "cross_attention":
@@ -129,10 +136,12 @@ class BatchedMemoryMixin:
     HIP path; ``inject_memories`` and everything else stay the layer's own."""
 
     def retrieve_memories(self, hidden_states: torch.Tensor, k: int = 5, reinforce: Optional[float] = None,
-                          reinforce_cap: float = 1.0):
+                          reinforce_cap: float = 1.0, *, diversity: Optional[float] = None,
+                          max_similarity: Optional[float] = None, fetch_k: Optional[int] = None):
         query = self.query_proj(hidden_states.mean(dim=1))
         return retrieve_memories(self.hippocampus, query, k=k, dtype=hidden_states.dtype, reinforce=reinforce,
-                                 reinforce_cap=reinforce_cap)
+                                 reinforce_cap=reinforce_cap, diversity=diversity, max_similarity=max_similarity,
+                                 fetch_k=fetch_k)
 
     def store_memory(self, hidden_states: torch.Tensor):
         store_memory(self.hippocampus, hidden_states, event_tag=f"layer_{id(self)}")

@@ -452,6 +452,51 @@ def bank_reinforce(meta, count: int, rows, amount: float, cap: float = 1.0) -> N
           "aura_bank_reinforce")
 
 
+DIVERSE_MAX_CANDIDATES = 128
+
+
+def diverse_select(bank, inv_norm, count: int, cand_rows, cand_scores, k: int, diversity: float = 0.0,
+                   max_similarity: Optional[float] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Greedy diverse selection of ``k`` rows per query among the ``F`` candidates of a recall (``cand_rows`` int32
+    [nq, F] and ``cand_scores`` fp32 [nq, F] in rank order) -> ``(scores [nq, k], rows [nq, k])`` in pick order,
+    the candidates' own rows and score bits, ``-inf`` / ``-1`` where fewer than ``k`` were eligible.  A candidate
+    whose cosine to an earlier pick reaches ``max_similarity`` is skipped (None: no limit); the others are ranked
+    by ``(1 - diversity) * score - diversity * (largest cosine to an earlier pick)``.  The rule in full:
+    ``include/aura_hip.h``.  One launch, no host sync."""
+    _need(bank, "bank", torch.float32); _need(inv_norm, "inv_norm", torch.float32)
+    _need(cand_rows, "cand_rows", torch.int32); _need(cand_scores, "cand_scores", torch.float32)
+    if bank.dim() != 2 or not (0 <= count <= bank.shape[0]) or inv_norm.numel() != bank.shape[0]:
+        raise ValueError("diverse_select: bank must be [rows, D] with count <= rows and one inv_norm per row")
+    M, D = bank.shape
+    if cand_rows.dim() != 2 or cand_scores.shape != cand_rows.shape:
+        raise ValueError("diverse_select: cand_rows and cand_scores must both be [nq, F]")
+    nq, F = cand_rows.shape
+    if not (1 <= k <= F <= DIVERSE_MAX_CANDIDATES):
+        raise ValueError(f"diverse_select: need 1 <= k <= F <= {DIVERSE_MAX_CANDIDATES} (k={k}, F={F})")
+    if D % 4 != 0 or not (4 <= D <= 4096):
+        raise ValueError(f"diverse_select: D={D} must be a multiple of 4 in [4, 4096]")
+    if not (0.0 <= diversity <= 1.0):
+        raise ValueError("diverse_select: diversity must be in [0, 1]")
+    tau = 2.0 if max_similarity is None else float(max_similarity)
+    if tau != tau:
+        raise ValueError("diverse_select: max_similarity must be a number")
+    if not (cand_rows.device == cand_scores.device == inv_norm.device == bank.device):
+        raise ValueError("diverse_select: tensors are on different devices")
+    out_s = torch.empty(nq, k, dtype=torch.float32, device=bank.device)
+    out_i = torch.empty(nq, k, dtype=torch.int32, device=bank.device)
+    if nq == 0:
+        return out_s, out_i
+    L = lib()
+    nbytes = L.aura_diverse_select_workspace_bytes(nq, F, k)
+    if nbytes < 0:
+        raise ValueError("diverse_select: unsupported size")
+    base = _workspace(bank.device, nbytes)
+    check(L.aura_diverse_select(_p(bank), _p(inv_norm), count, D, _p(cand_rows), _p(cand_scores), nq, F, k,
+                                float(diversity), tau, _p(out_s), _p(out_i), base, nbytes, _stream()),
+          "aura_diverse_select")
+    return out_s, out_i
+
+
 def knn_search(bank, inv_norm, meta, queries, k: int, now: float, count: Optional[int] = None,
                loc=None, q_loc=None, idx_base: int = 0, force_dense: bool = False,
                centroids=None, nprobe: int = 0, check_overflow: bool = True,

@@ -143,6 +143,27 @@ int64_t aura_bank_reinforce_workspace_bytes(int64_t count);
 int aura_bank_reinforce(float* meta, int64_t count, const int32_t* rows, int64_t n_rows, float amount, float cap,
                         void* workspace, int64_t workspace_bytes, void* stream);
 
+/* Diverse recall: a greedy maximal-marginal-relevance selection of k rows among the F candidates a recall
+ * returned (csrc/aura_diverse.hip).  [build-side] no upstream counterpart.
+ * Per query: F candidates in rank order, cand_rows[q][j] (int32) and cand_scores[q][j] (fp32), j = 0..F-1.  A
+ * candidate is valid if 0 <= row < count and its score is not NaN; the others (the -1 padding) are ignored.
+ *   cos(i, j) = fp32 dot product over D of bank[row_i] * inv_norm[row_i] and bank[row_j] * inv_norm[row_j].
+ *   S = the candidates picked so far, m(c) = max over j in S of cos(c, j).
+ *   eligible: valid, not picked, and (S empty or m(c) < max_similarity)   (any value above 1 switches it off);
+ *   value:    (1 - diversity) * score[c] while S is empty, else (1 - diversity) * score[c] - diversity * m(c);
+ *   pick the eligible candidate of largest value, equal values -> the smallest j; stop after k picks or when
+ *   nobody is eligible.
+ * out_rows / out_scores [nq][k]: the picks in pick order, the candidates' rows and score bits; the unfilled tail is
+ * row -1, score -inf.  The first pick is candidate 0; diversity = 0 with max_similarity > 1 returns candidates
+ * 0..k-1 unchanged.  0 <= diversity <= 1; 1 <= k <= F <= 128; D % 4 == 0, 4 <= D <= 4096; bank 16-byte aligned.
+ * One launch, no atomics; the F x F cosines live in LDS, so *_workspace_bytes is 0 for every supported shape
+ * (negative for an unsupported one) and workspace may be NULL. */
+int64_t aura_diverse_select_workspace_bytes(int64_t nq, int64_t F, int64_t k);
+int aura_diverse_select(const float* bank, const float* inv_norm, int64_t count, int64_t D, const int32_t* cand_rows,
+                        const float* cand_scores, int64_t nq, int64_t F, int64_t k, float diversity,
+                        float max_similarity, float* out_scores, int32_t* out_rows, void* workspace,
+                        int64_t workspace_bytes, void* stream);
+
 /* Workspace size (bytes) aura_knn_search needs for (N, nq, k). */
 int64_t aura_knn_workspace_bytes(int64_t N, int64_t nq, int k);
 
