@@ -483,17 +483,32 @@ class HippocampalFormation(nn.Module):
         meta_v0 = self.memory_metadata._version
         slot_t = torch.from_numpy(slots).to(self.device)
         eff_k = min(self.centroids_k, self.centroids.shape[0])
-        # A batch that overwrites may name a slot more than once (a full bank in the reference's mode
-        # sends every write to slot 0): the last write wins, as in the reference's sequential loop.  The
-        # serial centroid kernel walks the rows in order; the parallel kernel gets the survivors only.
-        # (appends and a FIFO ring that does not lap itself name every slot once: no need to look)
-        if self._overflow == 'weakest':
-            # a selection names every victim once, and victims are rows held before the write: distinct as long
-            # as no more rows are evicted than were held (_plan_slots refuses more)
-            ring_distinct = selected and slots.size - n_app <= c0
+        # A batch that overwrites may name a slot more than once, in three ways: a full bank in the reference's
+        # mode sends every write to slot 0; a FIFO ring laps itself (more than max_memories overwrites); a FIFO
+        # ring wraps onto the slots the SAME batch has just appended (a batch that first fills the bank and then
+        # overwrites from the cursor on reaches [c0, c0 + n_app) once cursor + overwrites passes c0).  The last
+        # write wins, as in the reference's sequential loop.  The serial centroid kernel walks the rows in order;
+        # the parallel kernel orders nothing between rows, so it gets the survivors only.
+        # This function decides, and it vouches for distinct slots (``ring_distinct``) only where that follows
+        # from the plan: pure appends; a selection of victims held before the write; a ring run that neither laps
+        # itself nor reaches the appended run.  Everything else -- and every overwrite whose slots a caller of
+        # ``write_at`` chose -- is looked at on the host (``_last_occurrences``).
+        rest = slots.size - n_app
+        if not selected:
+            ring_distinct = False
+        elif self._overflow == 'weakest':
+            # a selection names every victim once, and victims are rows held before the write (< c0, the
+            # appended run starts at c0): distinct as long as no more rows are evicted than were held
+            # (_plan_slots refuses more)
+            ring_distinct = rest <= c0
+        elif self._overflow == 'fifo':
+            # the run [cursor, cursor + rest) mod M: distinct from itself up to M rows; with appends in the same
+            # batch it also has to end before the first appended slot
+            start = self._write_cursor % self.max_memories
+            ring_distinct = rest <= self.max_memories and (n_app == 0 or start + rest <= c0)
         else:
-            ring_distinct = self._overflow != 'reference' and slots.size - n_app <= self.max_memories
-        keep = None if (slots.size == n_app or ring_distinct) else self._last_occurrences(slots, n_app)
+            ring_distinct = False
+        keep = None if (rest == 0 or ring_distinct) else self._last_occurrences(slots, n_app)
         keep_t = None if keep is None else torch.from_numpy(keep).to(self.device)
         uniq_t = slot_t if keep is None else slot_t[keep_t].contiguous()
         if keep is not None and not online:

@@ -43,6 +43,12 @@ CASES = [
     (400, 1024, 17, True, False),
     (300, 960, 256, False, False),      # the widest row whose elements all live on waves 1-15 (wave 0 only decides)
     (120, 964, 64, False, False),       # one step wider: wave 0 owns elements again
+    # D > 1024: the unpipelined phase B (online_assign_kernel), more than one element per thread
+    (300, 1028, 256, False, False),
+    (257, 1536, 256, True, False),
+    (600, 2048, 64, False, True),       # counts start at 0 (a 600-row call, two chunks, at D = 1536: test_gpu_write_paths.py)
+    (130, 1030, 200, False, False),     # D % 4 != 0
+    (64, 4096, 256, False, False),
 ]
 
 

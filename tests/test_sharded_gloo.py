@@ -246,3 +246,59 @@ def test_two_rank_bulk_write_rebuild_recall_and_persistence(tmp_path, monkeypatc
     for p in parts:
         assert p["reload_equal"] and p["count2"] == 2 * R and p["cursor2"] == p["cursor"] == 5
     assert parts[0]["id5"] == "w4"                               # the ring overwrote global slots 0..4 (rank 0's)
+
+
+# ----------------------------------------------------------------------------------------------
+# A batch that fills the sharded bank and wraps onto the slots it has just appended (global M = 8,
+# two shards of 4, empty bank, one batch of 10: the smallest case): each owner gets its local part
+# of the global plan through write_at, with the repeated slots in it.  The strict stand-in refuses
+# a repeated slot at the parallel kernel; the shards side by side are the single bank written one
+# row at a time.
+# ----------------------------------------------------------------------------------------------
+def _wrap_worker(rank, world, port, out, batches):
+    from aura_snn_rag_amd.core import hippocampal as H
+    from aura_snn_rag_amd.sharded import ShardedHippocampus
+    from tests import cpu_stub_strict as strict
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    H.ops = strict
+    H.time.time = lambda: NOW
+    D, M = 8, 8
+    kw = dict(_bank_kw(D, M // world), use_centroid_index=False)
+    local = H.HippocampalFormation(**kw)
+    sh = ShardedHippocampus(local, M, ops_module=strict, now_fn=lambda: NOW)
+    feats = _clustered_rows(sum(batches), D, 5)
+    lo = 0
+    for n in batches:
+        sh.write([f"m{j}" for j in range(lo, lo + n)], feats[lo:lo + n])
+        lo += n
+    torch.save(dict(feats=local.memory_features.clone(), meta=local.memory_metadata.clone(), inv=local._inv_norm.clone(),
+                    ids=dict(local.id_to_idx), by_slot=list(local._idx_to_id), count=sh.memory_count,
+                    cursor=sh._write_cursor), out + f".{rank}")
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+@pytest.mark.parametrize("batches", ((10,), (3, 13), (16,), (5, 4, 9)))
+def test_two_rank_batch_that_wraps_onto_its_own_appends(tmp_path, monkeypatch, batches):
+    out = str(tmp_path / "wrap")
+    mp.spawn(_wrap_worker, args=(2, _free_port(), out, batches), nprocs=2, join=True)
+    from aura_snn_rag_amd.core import hippocampal as H
+    monkeypatch.setattr(H, "ops", stub)
+    monkeypatch.setattr(H.time, "time", lambda: NOW)
+    D, M = 8, 8
+    hf = H.HippocampalFormation(**dict(_bank_kw(D, M), use_centroid_index=False))
+    feats = _clustered_rows(sum(batches), D, 5)
+    for i in range(feats.shape[0]):                              # the reference's loop
+        hf.create_episodic_memory(f"m{i}", "e", feats[i])
+    parts = [torch.load(out + f".{r}") for r in range(2)]
+    assert torch.equal(torch.cat([p["feats"] for p in parts]), hf.memory_features)
+    assert torch.equal(torch.cat([p["meta"] for p in parts]), hf.memory_metadata)
+    assert torch.equal(torch.cat([p["inv"] for p in parts]), hf._inv_norm)
+    ids = {}
+    for r, p in enumerate(parts):
+        ids.update({k_: v + r * (M // 2) for k_, v in p["ids"].items()})
+    assert ids == hf.id_to_idx
+    assert parts[0]["by_slot"] + parts[1]["by_slot"] == hf._idx_to_id
+    for p in parts:
+        assert p["count"] == hf.memory_count and p["cursor"] == hf._write_cursor
