@@ -108,6 +108,21 @@ class _IvfState:
 
 OVERFLOW_POLICIES = ('reference', 'fifo', 'weakest')
 
+_INSTANCE_DEFAULT = object()          # create_episodic_memories(merge_similarity=...): "what the bank was built with"
+
+
+@dataclass
+class ConsolidationReport:
+    """What a consolidating write did with its ``n`` rows (host tensors and lists).  ``merged[i]``: row i repeated a
+    memory and was not stored; ``ids[i]``: the id of the memory row i became (its own id if it was stored, else the id
+    of the memory it repeats); ``rows[i]``: the slot ``s`` that holds that memory when the call returns, with
+    ``id_of_row(s) == ids[i]``, or -1 if this same call overwrote it again."""
+    merged: torch.Tensor
+    rows: torch.Tensor
+    ids: List[Optional[str]]
+    n_stored: int
+    n_merged: int
+
 
 class HippocampalFormation(nn.Module):
     # above this many rows the inverted lists (each probed list read once per batch) beat a masked
@@ -126,8 +141,16 @@ class HippocampalFormation(nn.Module):
                  device: str = 'cuda',
                  use_centroid_index: bool = True,
                  overflow: str = 'reference',
-                 bf16_shadow: bool = True):
+                 bf16_shadow: bool = True,
+                 merge_similarity: Optional[float] = None,
+                 merge_reinforce: float = 0.1,
+                 merge_cap: float = 1.0):
         super().__init__()
+        # consolidating writes (create_episodic_memories): None = every row is stored, today's behaviour
+        self._check_merge(merge_similarity, merge_reinforce, merge_cap)
+        self.merge_similarity = merge_similarity
+        self.merge_reinforce = merge_reinforce
+        self.merge_cap = merge_cap
         self.spatial_dims = spatial_dimensions
         self.device = torch.device(device if torch.cuda.is_available() else 'cpu')
         dev = self.device
@@ -185,6 +208,9 @@ class HippocampalFormation(nn.Module):
         self._ivf_pending = None                  # (order, seg_off) left by rebuild_centroids for the next re-pack
         self._lists = None                        # fp32 fallback lists (list_rows, list_off, list_len, longest)
         self._lists_dirty = True
+        # rows may be held that no inverted list files (centroid id < 0: positioned or bulk writes after the index was
+        # built, metadata edited by the user); the next rebuild_centroids assigns every row again
+        self._unlisted_rows = False
 
         if overflow not in OVERFLOW_POLICIES:
             raise ValueError(f"overflow must be 'reference', 'fifo' or 'weakest', got {overflow!r}")
@@ -196,6 +222,7 @@ class HippocampalFormation(nn.Module):
     def _invalidate_norms(self) -> None:
         self._norms_valid_upto = 0
         self._shadow_valid_upto = 0
+        self._unlisted_rows = True
         self._invalidate_lists()
 
     def _invalidate_lists(self) -> None:
@@ -343,7 +370,10 @@ class HippocampalFormation(nn.Module):
 
     def refresh_norms(self) -> None:
         """Recompute the cached row norms and drop the bf16 shadows (call after writing
-        ``memory_features`` or ``memory_metadata[:, 2]`` directly)."""
+        ``memory_features`` or ``memory_metadata[:, 2]`` directly).  As after ``load_state_dict``, rows may then be
+        held that no inverted list files, so until the next ``rebuild_centroids`` ``find_repeats`` (consolidating
+        writes) scans the row-ordered bf16 shadow instead of the list-sorted one: on an indexed bank that is a second
+        image of the bank (2 bytes per element) and one conversion pass."""
         self._invalidate_norms()
         if self.memory_count:
             self._ensure_norms()
@@ -483,6 +513,8 @@ class HippocampalFormation(nn.Module):
         meta_v0 = self.memory_metadata._version
         slot_t = torch.from_numpy(slots).to(self.device)
         eff_k = min(self.centroids_k, self.centroids.shape[0])
+        if not online:
+            self._unlisted_rows = True
         # A batch that overwrites may name a slot more than once, in three ways: a full bank in the reference's
         # mode sends every write to slot 0; a FIFO ring laps itself (more than max_memories overwrites); a FIFO
         # ring wraps onto the slots the SAME batch has just appended (a batch that first fills the bank and then
@@ -567,6 +599,7 @@ class HippocampalFormation(nn.Module):
             return 0
         s0 = self.memory_count
         meta_v0 = self.memory_metadata._version
+        self._unlisted_rows = True
         slot_t = torch.arange(s0, s0 + n, dtype=torch.int64, device=self.device)
         ops.bank_write(self.memory_features, self.memory_locations, self.memory_metadata,
                        self._inv_norm, feats[:n].contiguous(), slot_t,
@@ -581,18 +614,44 @@ class HippocampalFormation(nn.Module):
         return n
 
     def create_episodic_memory(self, memory_id: str, event_id: str, features: torch.Tensor,
-                               associated_experts: List[str] = None) -> None:
+                               associated_experts: List[str] = None,
+                               merge_similarity=_INSTANCE_DEFAULT) -> Optional[ConsolidationReport]:
         """Store one memory (reference ``:195-243``).  ``event_id`` / ``associated_experts`` are
-        accepted and unused, as in the reference."""
-        self.create_episodic_memories([memory_id], self._features_to_device(features, rows=1))
+        accepted and unused, as in the reference.  ``merge_similarity``: as ``create_episodic_memories``."""
+        return self.create_episodic_memories([memory_id], self._features_to_device(features, rows=1),
+                                             merge_similarity=merge_similarity)
 
-    def create_episodic_memories(self, memory_ids: Sequence[str], features: torch.Tensor) -> None:
+    def create_episodic_memories(self, memory_ids: Sequence[str], features: torch.Tensor,
+                                 merge_similarity=_INSTANCE_DEFAULT) -> Optional[ConsolidationReport]:
         """Batched one-shot write: identical to calling ``create_episodic_memory`` once per row,
-        including the rebuild every ``centroids_update_interval`` inserts (``:242-243``)."""
+        including the rebuild every ``centroids_update_interval`` inserts (``:242-243``).
+
+        ``merge_similarity`` (default: the value the bank was constructed with; None there: off, nothing changes,
+        nothing more is launched and the call returns None): a consolidating write.  A row whose cosine to a held
+        memory, or to an earlier row of the batch that is stored, reaches the threshold (in ``(0, 1]``) is NOT stored
+        and its id is not registered; the held memory it repeats is reinforced by ``self.merge_reinforce`` up to
+        ``self.merge_cap`` and its timestamp refreshed (an in-batch leader has just been written at full strength).
+        The batch is cut into chunks of at most ``ops.CONSOLIDATE_MAX_BATCH`` rows; per chunk: ``find_repeats`` (one
+        host read), then ``reinforce`` + ``touch`` of the distinct stored targets -- BEFORE the write, so that under
+        ``overflow='weakest'`` a memory that has just been repeated is not the one evicted -- then the kept rows go
+        through the unchanged write path (every overflow policy applies; the rebuild cadence counts kept rows only).
+        Returns a ``ConsolidationReport``.  The first observation stands: the repeat's features are not blended into
+        the stored row.  ``bulk_write`` and ``write_at`` (the seeding path and the sharded bank's building block) do
+        not consolidate, and ``ShardedHippocampus`` has no cross-rank search."""
+        tau = self.merge_similarity if merge_similarity is _INSTANCE_DEFAULT else merge_similarity
+        if tau is not None:
+            self._check_merge(tau, self.merge_reinforce, self.merge_cap)
         feats = self._features_to_device(features)
         n = len(memory_ids)
         if feats.shape[0] != n:
             raise ValueError(f"{n} ids but {feats.shape[0]} feature rows")
+        if tau is None:
+            self._write_batch(memory_ids, feats)
+            return None
+        return self._write_consolidated(memory_ids, feats, float(tau))
+
+    def _write_batch(self, memory_ids: Sequence[str], feats: torch.Tensor) -> None:
+        n = len(memory_ids)
         i = 0
         while i < n:
             # run length until the next insert that triggers a rebuild
@@ -612,6 +671,129 @@ class HippocampalFormation(nn.Module):
             if (self.use_centroid_index and self.memory_count % self.centroids_update_interval == 0
                     and self.memory_count > self.centroids_k):
                 self.rebuild_centroids()
+
+    # ------------------------------------------------------------------ consolidating writes
+    @staticmethod
+    def _check_merge(similarity, reinforce, cap) -> None:
+        if similarity is not None:
+            try:
+                ok = 0.0 < float(similarity) <= 1.0
+            except (TypeError, ValueError):
+                ok = False
+            if not ok:
+                raise ValueError(f"merge_similarity must be None or in (0, 1], got {similarity!r}")
+        if not (float(reinforce) >= 0.0):
+            raise ValueError(f"merge_reinforce must be >= 0, got {reinforce!r}")
+        if float(cap) != float(cap):
+            raise ValueError("merge_cap must be a number")
+
+    def find_repeats(self, features: torch.Tensor, threshold: float,
+                     now: Optional[float] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """Which of the (at most ``ops.CONSOLIDATE_MAX_BATCH``) rows ``features`` repeat a held memory or an earlier
+        row of the batch at cosine >= ``threshold``: ``(stored_target int32 [n], batch_leader int32 [n], cos fp32
+        [n])`` as HOST tensors (the rule: ``include/aura_hip.h``, ``aura_bank_find_repeats``).  Read-only: nothing is
+        written to the bank.  The search covers every held row exactly, whether or not the centroid index is on; it
+        scans the list-sorted bf16 shadow in candidate mode, the row-ordered shadow otherwise, and the fp32 bank where
+        no shadow applies.  One device-to-host read brings the results, the scan's overflow flag and the inverted
+        lists' "a row was dropped" flag: stale lists are re-packed and the call repeated once (a dropped row must
+        never become a missed duplicate), an overflowing survivor list repeats the call on the fp32 scan.  ``now`` is
+        accepted for symmetry with ``recall_batch``; a cosine has no time term."""
+        if threshold is None:
+            raise ValueError("find_repeats needs a threshold in (0, 1]")
+        self._check_merge(threshold, 0.0, 1.0)
+        f = self._features_to_device(features)
+        n = f.shape[0]
+        if n > ops.CONSOLIDATE_MAX_BATCH:
+            raise ValueError(f"find_repeats takes at most {ops.CONSOLIDATE_MAX_BATCH} rows per call, got {n}")
+        if self.memory_count:
+            self._ensure_norms()
+        # an image must hold EVERY held row: the inverted lists do unless rows without a list may exist
+        mode = 'lists' if (self._candidate_mode() and self.centroids.shape[0] == 256 and
+                           not self._unlisted_rows) else 'shadow'
+        repacked = False
+        while True:                                    # lists -> lists (re-packed) -> shadow -> fp32: at most 4 rounds
+            kw, ivf = {}, None
+            if mode == 'lists':
+                ivf = self._ensure_ivf()
+                if ivf is None:
+                    mode = 'shadow'
+                else:
+                    kw = dict(image=ivf.sorted_bf16, image_rows=ivf.sorted_rows, n_image=ivf.n_sorted, rho=self._rho,
+                              lists_flag=ivf.flag)
+            if mode == 'shadow':
+                shadow = self._ensure_shadow()
+                if shadow is None:
+                    mode = 'fp32'
+                else:
+                    kw = dict(image=shadow, rho=self._rho)
+            packed = ops.find_repeats(self.memory_features, self._inv_norm, self.memory_count, f, float(threshold),
+                                      **kw)[3].cpu()                       # THE host read
+            overflow, stale = int(packed[3 * n]), int(packed[3 * n + 1])
+            if ivf is not None and stale:
+                ivf.valid = False                      # a write outgrew a list's slack: re-pack and once more;
+                mode = 'shadow' if repacked else 'lists'                  # stale again: the row-ordered shadow
+                repacked = True
+                continue
+            if overflow and mode != 'fp32':
+                mode = 'fp32'                          # a survivor list overflowed: the dense scan cannot
+                continue
+            break
+        return packed[:n], packed[n:2 * n], packed[2 * n:3 * n].view(torch.float32)
+
+    def touch(self, rows, now: Optional[float] = None) -> None:
+        """Refresh the timestamp of the memories at bank rows ``rows`` (int, any shape; ``-1`` and rows outside the
+        bank are ignored) to ``now`` (default: the clock), as a write would."""
+        if self.memory_count == 0:
+            return
+        now = time.time() if now is None else now
+        if not isinstance(rows, torch.Tensor):
+            rows = torch.as_tensor(np.asarray(rows))
+        if rows.numel() == 0:
+            return
+        host = rows.detach().cpu().reshape(-1).numpy().astype(np.int64)
+        ops.bank_touch(self.memory_metadata, self.memory_count,
+                       rows.to(device=self.device, dtype=torch.int32).contiguous(), now)
+        host = host[(host >= 0) & (host < self.memory_count)]
+        self._slot_time[host] = now
+        if self._ivf is not None:
+            self._ivf.rowc_live = False                 # timestamps changed under the cached score constants
+
+    def _write_consolidated(self, memory_ids: Sequence[str], feats: torch.Tensor, tau: float) -> ConsolidationReport:
+        n = len(memory_ids)
+        merged = torch.zeros(n, dtype=torch.bool)
+        mem_ids: List[Optional[str]] = [None] * n       # the memory every row became
+        slot = np.full(n, -1, dtype=np.int64)           # where that memory was when its chunk was done
+        step = ops.CONSOLIDATE_MAX_BATCH
+        for lo in range(0, n, step):
+            hi = min(n, lo + step)
+            f = feats[lo:hi]
+            now = time.time()
+            stored, leader, _ = self.find_repeats(f, tau, now=now)
+            stored, leader = stored.numpy().astype(np.int64), leader.numpy().astype(np.int64)
+            kept = np.nonzero((stored < 0) & (leader < 0))[0]
+            for i in np.nonzero(stored >= 0)[0].tolist():               # ids of the targets as they are held NOW
+                mem_ids[lo + i], slot[lo + i] = self.id_of_row(int(stored[i])), stored[i]
+            targets = np.unique(stored[stored >= 0])
+            if targets.size:
+                t = torch.from_numpy(targets)
+                self.reinforce(t, amount=self.merge_reinforce, cap=self.merge_cap)
+                self.touch(t, now=now)
+            if kept.size:
+                kept_ids = [memory_ids[lo + i] for i in kept.tolist()]
+                kept_f = f if kept.size == hi - lo else f[torch.from_numpy(kept).to(f.device)].contiguous()
+                self._write_batch(kept_ids, kept_f)
+                for i, mid in zip(kept.tolist(), kept_ids):
+                    mem_ids[lo + i], slot[lo + i] = mid, self.id_to_idx[mid]
+            for i in np.nonzero((stored < 0) & (leader >= 0))[0].tolist():
+                j = lo + int(leader[i])
+                mem_ids[lo + i], slot[lo + i] = mem_ids[j], slot[j]
+            merged[lo:hi] = torch.from_numpy((stored >= 0) | (leader >= 0))
+        # a memory this same call overwrote again (a full bank) is reported at -1
+        live = np.fromiter((s >= 0 and self.id_of_row(int(s)) == m for s, m in zip(slot.tolist(), mem_ids)),
+                           dtype=bool, count=n)
+        rows = torch.from_numpy(np.where(live, slot, -1))
+        n_merged = int(merged.sum())
+        return ConsolidationReport(merged=merged, rows=rows, ids=mem_ids, n_stored=n - n_merged, n_merged=n_merged)
 
     # ------------------------------------------------------------------ recall
     def _candidate_mode(self) -> bool:
@@ -996,6 +1178,7 @@ class HippocampalFormation(nn.Module):
                                            meta=self.memory_metadata, update_means=False)
         self.centroid_counts = counts
         self._index_ready = True
+        self._unlisted_rows = False                   # every held row has just been assigned to a list
         self._invalidate_lists()
         if k == 256 and seg_off.numel() == 257:
             self._ivf_pending = (order, seg_off)

@@ -50,13 +50,19 @@ def retrieve_memories(hippocampus, query: torch.Tensor, k: int = 5, dtype=None,
     return feats, scores
 
 
-def store_memory(hippocampus, hidden_states: torch.Tensor, event_tag: str = "layer") -> None:
-    """Mean-pool each batch item and store it (``memory_augmented_layer.py:132-153``)."""
+def store_memory(hippocampus, hidden_states: torch.Tensor, event_tag: str = "layer",
+                 merge_similarity: Optional[float] = None):
+    """Mean-pool each batch item and store it (``memory_augmented_layer.py:132-153``).  ``merge_similarity`` (default
+    off): a consolidating write -- a pooled row that repeats a held memory at that cosine strengthens it instead of
+    taking a slot (``HippocampalFormation.create_episodic_memories(merge_similarity=...)``, whose report is returned);
+    a bank constructed with a threshold consolidates without it."""
     if hippocampus is None:
-        return
+        return None
     feats = hidden_states.detach().float().mean(dim=1)                      # [B, D]
     ids = [str(uuid.uuid4())[:8] for _ in range(feats.shape[0])]
-    hippocampus.create_episodic_memories(ids, feats)
+    if merge_similarity is None:
+        return hippocampus.create_episodic_memories(ids, feats)
+    return hippocampus.create_episodic_memories(ids, feats, merge_similarity=merge_similarity)
 
 
 def inject_concat(hidden_states, memory_features, memory_scores):
@@ -143,5 +149,6 @@ class BatchedMemoryMixin:
                                  reinforce_cap=reinforce_cap, diversity=diversity, max_similarity=max_similarity,
                                  fetch_k=fetch_k)
 
-    def store_memory(self, hidden_states: torch.Tensor):
-        store_memory(self.hippocampus, hidden_states, event_tag=f"layer_{id(self)}")
+    def store_memory(self, hidden_states: torch.Tensor, merge_similarity: Optional[float] = None):
+        return store_memory(self.hippocampus, hidden_states, event_tag=f"layer_{id(self)}",
+                            merge_similarity=merge_similarity)

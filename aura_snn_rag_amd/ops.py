@@ -452,6 +452,85 @@ def bank_reinforce(meta, count: int, rows, amount: float, cap: float = 1.0) -> N
           "aura_bank_reinforce")
 
 
+CONSOLIDATE_MAX_BATCH = 1024
+CONSOLIDATE_MAX_IMAGE_DIM = 768
+
+
+def find_repeats(bank, inv_norm, count: int, feats, tau: float, image=None, image_rows=None,
+                 n_image: Optional[int] = None, rho=None, lists_flag=None):
+    """Which rows of the batch ``feats`` (fp32 [n, D], n <= 1024) repeat a row of ``bank[:count]`` or an earlier row of
+    the batch, at cosine >= ``tau`` (the rule in full: ``include/aura_hip.h``) ->
+    ``(stored_target int32 [n], batch_leader int32 [n], cos fp32 [n], packed int32 [3 n + 2])``.  The three results are
+    views of ``packed``; ``packed[3 n]`` is the call's overflow flag (non-zero: a survivor list of the image scan
+    overflowed, the results are incomplete -- repeat without an image) and ``packed[3 n + 1]`` a copy of
+    ``lists_flag`` (int32 [1], device; 0 without one), so that ONE device-to-host read of ``packed`` brings the
+    results and both flags.  ``image``: a current bf16 image of the normalised rows -- the row-ordered shadow
+    (``image_rows`` None) or the list-sorted shadow with ``image_rows = sorted_rows`` and ``n_image = n_sorted`` --
+    with ``rho`` as ``bank_shadow_update`` leaves it; None: the dense fp32 scan.  No host sync."""
+    _need(bank, "bank", torch.float32); _need(inv_norm, "inv_norm", torch.float32); _need(feats, "feats", torch.float32)
+    if bank.dim() != 2 or not (0 <= count <= bank.shape[0]) or inv_norm.numel() != bank.shape[0]:
+        raise ValueError("find_repeats: bank must be [rows, D] with count <= rows and one inv_norm per row")
+    M, D = bank.shape
+    if feats.dim() != 2 or feats.shape[1] != D:
+        raise ValueError(f"find_repeats: feats must be [n, {D}]")
+    n = feats.shape[0]
+    if n > CONSOLIDATE_MAX_BATCH:
+        raise ValueError(f"find_repeats: at most {CONSOLIDATE_MAX_BATCH} rows per call, got {n}")
+    tau = float(tau)
+    if not (0.0 < tau <= 1.0):
+        raise ValueError(f"find_repeats: tau must be in (0, 1], got {tau}")
+    if not (1 <= D <= 4096):
+        raise ValueError(f"find_repeats: D={D} must be in [1, 4096]")
+    if feats.device != bank.device or inv_norm.device != bank.device:
+        raise ValueError("find_repeats: tensors are on different devices")
+    ni = 0
+    if image is not None:
+        _need(image, "image", torch.bfloat16); _need(rho, "rho", torch.float32)
+        if D % 8 or D > CONSOLIDATE_MAX_IMAGE_DIM or image.dim() != 2 or image.shape[1] != D or rho.numel() != M:
+            raise ValueError("find_repeats: an image needs D % 8 == 0, D <= 768, [rows, D] bf16 and one rho per bank row")
+        if image_rows is None:
+            ni = count if n_image is None else int(n_image)
+            if ni != count or image.shape[0] < count:
+                raise ValueError("find_repeats: a row-ordered image holds exactly the first count rows")
+        else:
+            _need(image_rows, "image_rows", torch.int32)
+            ni = image_rows.numel() if n_image is None else int(n_image)
+            if not (0 <= ni <= min(image_rows.numel(), image.shape[0])):
+                raise ValueError("find_repeats: n_image exceeds the image")
+        if image.device != bank.device or rho.device != bank.device or \
+                (image_rows is not None and image_rows.device != bank.device):
+            raise ValueError("find_repeats: tensors are on different devices")
+    elif image_rows is not None:
+        raise ValueError("find_repeats: image_rows without an image")
+    packed = torch.zeros(3 * n + 2, dtype=torch.int32, device=bank.device)
+    stored, leader, cos = packed[:n], packed[n:2 * n], packed[2 * n:3 * n].view(torch.float32)
+    if lists_flag is not None:
+        _need(lists_flag, "lists_flag", torch.int32)
+        packed[3 * n + 1:].copy_(lists_flag.reshape(-1)[:1])
+    if n == 0:
+        return stored, leader, cos, packed
+    L = lib()
+    nbytes = L.aura_bank_find_repeats_workspace_bytes(n)
+    if nbytes < 0:
+        raise ValueError("find_repeats: unsupported size")
+    base = _workspace(bank.device, nbytes)
+    check(L.aura_bank_find_repeats(_p(bank), _p(inv_norm), count, D, _p(image), _p(image_rows), ni, _p(rho),
+                                   _p(feats), n, tau, _p(stored), _p(leader), _p(cos), _p(packed[3 * n:]),
+                                   base, nbytes, _stream()), "aura_bank_find_repeats")
+    return stored, leader, cos, packed
+
+
+def bank_touch(meta, count: int, rows, now: float) -> None:
+    """``meta[r][1] = now`` for every row id of ``rows`` (int32, any shape) inside [0, count); others are ignored."""
+    _check_meta(meta, count, "bank_touch")
+    _need(rows, "rows", torch.int32)
+    if rows.device != meta.device:
+        raise ValueError("bank_touch: rows and meta are on different devices")
+    if now != now:
+        raise ValueError("bank_touch: now must be a number")
+    check(lib().aura_bank_touch(_p(meta), count, _p(rows), rows.numel(), float(now), _stream()), "aura_bank_touch")
+
+
 DIVERSE_MAX_CANDIDATES = 128
 
 

@@ -164,6 +164,47 @@ int aura_diverse_select(const float* bank, const float* inv_norm, int64_t count,
                         float max_similarity, float* out_scores, int32_t* out_rows, void* workspace,
                         int64_t workspace_bytes, void* stream);
 
+/* Consolidating writes: which rows of a batch repeat a memory the bank holds, or an earlier row of the same batch
+ * (csrc/aura_consolidate.hip).  [build-side] no upstream counterpart (the reference stores every row).
+ * Inputs: the N held rows bank[0 .. N), a batch of n <= 1024 new rows f_0 .. f_{n-1} (feats [n][D]) and a threshold
+ * tau in (0, 1].
+ *   cos(x, y) = the dot product of the two rows, each scaled by 1 / max(||.||, 1e-12), evaluated in fp32; bank rows
+ *     use the stored inv_norm.  Any fp32 evaluation within (D + 8) 2^-24 of the exact value is acceptable, so two
+ *     evaluations differ by at most tol = 2 (D + 8) 2^-24: decisions closer than tol to tau, or between two targets
+ *     closer than tol to each other, may fall either way.
+ *   stored_target[i] = the held row r of largest cos(f_i, r) if that cosine is >= tau, else -1; bit-identical bank
+ *     rows tie to the lowest r.  The search covers EVERY held row and is exact, whatever image is passed.
+ *   batch_leader: walk i = 0 .. n-1 in order.  A row with a stored target is a repeat and never a leader.  Among the
+ *     others, row i repeats the KEPT earlier row j < i of largest cos(f_i, f_j) >= tau (ties -> the lowest j):
+ *     batch_leader[i] = j; otherwise row i is kept and batch_leader[i] = -1.
+ *   cos_out[i] = the cosine to whatever row i repeats, -inf for a kept row.
+ *   A row with a NaN or Inf component and a row of norm 0 are kept and are nobody's target (their cosines are NaN
+ *     or 0).  The norm is the fp32 one: a batch row whose SQUARED norm overflows fp32 (||f|| > 1.8e19) or underflows
+ *     to 0 (||f|| < 1e-23) counts as such a row.
+ * The scan.  image_bf16 != NULL: a CURRENT bf16 image of the normalised held rows ([n_image][D], D % 8 == 0,
+ *   D <= 768, 16-byte aligned) -- the row-ordered shadow (image_rows == NULL, n_image = N: image row i is bank row i)
+ *   or the list-sorted shadow of the inverted lists (image_rows = sorted_rows, n_image = n_sorted; -1 entries are
+ *   padding or holes) -- with rho [rows of the bank] as aura_bank_shadow_update leaves it.  One pass over the image
+ *   on the bf16 matrix pipe against the batch's normalised bf16 rows; a pair survives when cos_bf16 + err >= tau
+ *   with the prefilter's bound err = rho_row + rho_q + rho_row rho_q + 2 D 2^-24 + 1e-5 (aura_knn_search_ex);
+ *   survivors go to per-row lists of 256 entries and a second launch re-scores them in fp32 from the fp32 bank.  A
+ *   list that overflows sets *overflow_out (device int32, reset by every call) to non-zero: the results are then
+ *   incomplete and the caller repeats the call with image_bf16 == NULL.
+ *   image_bf16 == NULL: a dense fp32 scan of the fp32 bank (any D <= 4096), the per-row maximum by a packed
+ *   (ordered cosine bits, ~row) 64-bit atomicMax; it cannot overflow.
+ * The n x n cosines of the batch are computed in fp32 on the matrix pipe (lower triangle); only rows that have a
+ *   pair >= tau among rows without a stored target enter the ordered walk.
+ * stored_target, batch_leader: int32 [n]; cos_out: fp32 [n]; workspace: *_workspace_bytes(n) bytes (negative for an
+ * unsupported n), 256-byte aligned.  Nothing is written to the bank.
+ * aura_bank_touch: meta[r][1] = now for every 0 <= r < count among rows[0 .. n) (int32; others are ignored;
+ *   duplicates store the same value). */
+int64_t aura_bank_find_repeats_workspace_bytes(int64_t n);
+int aura_bank_find_repeats(const float* bank, const float* inv_norm, int64_t N, int64_t D, const uint16_t* image_bf16,
+                           const int32_t* image_rows, int64_t n_image, const float* rho, const float* feats, int64_t n,
+                           float tau, int32_t* stored_target, int32_t* batch_leader, float* cos_out,
+                           int32_t* overflow_out, void* workspace, int64_t workspace_bytes, void* stream);
+int aura_bank_touch(float* meta, int64_t count, const int32_t* rows, int64_t n, float now, void* stream);
+
 /* Workspace size (bytes) aura_knn_search needs for (N, nq, k). */
 int64_t aura_knn_workspace_bytes(int64_t N, int64_t nq, int k);
 

@@ -1,0 +1,190 @@
+"""Measurements of consolidating writes -> profiles/consolidate_bench.json.
+
+    python tools/consolidate_bench.py [--rows 1000000] [--dim 768] [--out profiles/consolidate_bench.json]
+
+Needs a GPU (no fallback).  One process, one bank (index on, rebuilt, room for the rows the write streams append).
+Every figure is the median over WINDOWS windows of at least WINDOW_S of work each (min and max beside it), after a
+warm-up, the things compared taken in alternating order inside each round (tools/diverse_bench.py's scheme).
+
+  per batch size n in (256, 1024), the batch half noisy copies of held rows, half fresh rows:
+    find_repeats_kernels   ops.find_repeats on the list-sorted image, launches only            (device events)
+    find_repeats           HippocampalFormation.find_repeats: image choice + launches + THE host read     (host clock)
+    recall_k1_kernels      recall_batch(k=1, use_candidates=False, check_overflow=False), n queries  (device events)
+    recall_k1              recall_batch(k=1, use_candidates=False): the exact two-stage scan of the same bank with the
+                           same number of queries, its flag read included -- the bar: find_repeats may take at most
+                           1.10 x this                                                                  (host clock)
+  Before anything is timed the image scan's result is compared with the dense fp32 scan's on the same batch.
+  floors: one pass over the image at the copy rate of DESIGN.md 4.3b (1.54 GB in 271 us) and 2 N n D FLOP at the
+  bf16 matrix peak; the fraction of each that find_repeats_kernels reaches is reported.
+
+  write rate, batches of 256 rows appended to the same bank (no centroid rebuild inside the windows), rows / s:
+    plain_0 / merge_0      a stream without repeats, without / with merge_similarity = 0.9
+    plain_50 / merge_50    a stream whose rows are half noisy copies of held rows
+
+``--only trace``: find_repeats alone, both batch sizes, for ``rocprofv3 --kernel-trace --stats -- python
+tools/consolidate_bench.py --only trace`` in a run of its own."""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import bench  # noqa: E402
+from tools.diverse_bench import events_window, wall_window, summary  # noqa: E402
+
+COPY_BYTES_PER_S = 1.54e9 / 271e-6
+PEAK_BF16_MATRIX_FLOPS = 2.5e15
+WINDOWS = 5
+WINDOW_S = 0.3
+TAU = 0.9
+BATCHES = (256, 1024)
+WRITE_BATCH = 256
+HEADROOM = 1 << 16
+BAR = 1.10
+
+
+def alternated(fns, window):
+    iters = {}
+    for name, fn in fns.items():
+        for _ in range(3):
+            fn()
+        ms = window(fn, 3)
+        iters[name] = max(3, int(WINDOW_S * 1e3 / max(ms, 1e-3)) + 1)
+    out = {name: [] for name in fns}
+    names = list(fns)
+    for rnd in range(WINDOWS):
+        for name in (names if rnd % 2 == 0 else names[::-1]):
+            out[name].append(window(fns[name], iters[name]))
+    return out, iters
+
+
+def make_batch(hf, n, repeats, g):
+    """n rows: the first ``repeats`` are held rows + 0.05 randn (cosine about 0.9988), the rest fresh."""
+    D = hf.memory_features.shape[1]
+    pick = torch.randint(0, hf.memory_count, (repeats,), generator=g, device=hf.device)
+    rows = torch.cat([hf.memory_features[pick] + 0.05 * torch.randn(repeats, D, generator=g, device=hf.device),
+                      torch.randn(n - repeats, D, generator=g, device=hf.device)])
+    return rows[torch.randperm(n, generator=g, device=hf.device)].contiguous()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rows", type=int, default=1_000_000)
+    ap.add_argument("--dim", type=int, default=768)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "consolidate_bench.json"))
+    ap.add_argument("--only", choices=("trace",), default=None)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("consolidate_bench.py measures on the GPU; none found (nothing is measured on the CPU)")
+    from aura_snn_rag_amd import ops
+    from aura_snn_rag_amd.core.hippocampal import HippocampalFormation
+    dev = torch.device("cuda", 0)
+    D = a.dim
+    hf = HippocampalFormation(feature_dim=D, max_memories=a.rows + HEADROOM, n_place_cells=8, n_time_cells=4,
+                              n_grid_cells=4, device="cuda", use_centroid_index=True)
+    hf.centroids_update_interval = 10 ** 9
+    bench.fill_bank(hf, a.rows, D, 1234, dev)
+    hf.rebuild_centroids(perm=torch.randperm(a.rows, generator=torch.Generator().manual_seed(7)))
+    now = float(hf.memory_metadata[0, 1].item())
+    g = torch.Generator(device=dev).manual_seed(99)
+    batches = {n: make_batch(hf, n, n // 2, g) for n in BATCHES}
+    if a.only == "trace":
+        for n in BATCHES:
+            for _ in range(30):
+                hf.find_repeats(batches[n], TAU)
+        torch.cuda.synchronize()
+        return
+    out = {"device": torch.cuda.get_device_name(0), "rows": a.rows, "dim": D, "index": True, "tau": TAU,
+           "windows": WINDOWS, "window_s_at_least": WINDOW_S, "copy_bytes_per_s_assumed": COPY_BYTES_PER_S,
+           "peak_bf16_matrix_flops_assumed": PEAK_BF16_MATRIX_FLOPS, "bar": BAR, "find_repeats": [], "write_rate": {}}
+    ok = True
+    for n in BATCHES:
+        f = batches[n]
+        st, bl, _ = hf.find_repeats(f, TAU)
+        ivf = hf._ivf
+        assert ivf is not None and ivf.valid, "the bank was expected to scan the list-sorted image"
+        dense = ops.find_repeats(hf.memory_features, hf._inv_norm, hf.memory_count, f, TAU)[3].cpu()
+        same = bool(torch.equal(dense[:n], st)) and bool(torch.equal(dense[n:2 * n], bl))
+        image_bytes = ivf.n_sorted * D * 2
+
+        def kernels():
+            return ops.find_repeats(hf.memory_features, hf._inv_norm, hf.memory_count, f, TAU, image=ivf.sorted_bf16,
+                                    image_rows=ivf.sorted_rows, n_image=ivf.n_sorted, rho=hf._rho, lists_flag=ivf.flag)
+        ev, ev_iters = alternated({
+            "find_repeats_kernels": kernels,
+            "recall_k1_kernels": lambda: hf.recall_batch(f, k=1, now=now, use_candidates=False, check_overflow=False)},
+            events_window)
+        wl, wl_iters = alternated({
+            "find_repeats": lambda: hf.find_repeats(f, TAU),
+            "recall_k1": lambda: hf.recall_batch(f, k=1, now=now, use_candidates=False)}, wall_window)
+        km = statistics.median(ev["find_repeats_kernels"])
+        fr, rc = statistics.median(wl["find_repeats"]), statistics.median(wl["recall_k1"])
+        floor_bytes_ms = 1e3 * image_bytes / COPY_BYTES_PER_S
+        floor_flop_ms = 1e3 * 2.0 * ivf.n_sorted * n * D / PEAK_BF16_MATRIX_FLOPS
+        res = {"n": n, "repeats_in_batch": int((st >= 0).sum()), "image_rows": ivf.n_sorted, "image_bytes": image_bytes,
+               "image_scan_equals_dense_scan": same,
+               **{k: summary(v) for k, v in {**ev, **wl}.items()}, "calls_per_window": {**ev_iters, **wl_iters},
+               "find_repeats_over_recall_k1": fr / rc, "bar_met": fr <= BAR * rc,
+               "kernels_over_recall_k1_kernels": km / statistics.median(ev["recall_k1_kernels"]),
+               "floor_image_pass_ms": floor_bytes_ms, "floor_matrix_pipe_ms": floor_flop_ms,
+               "fraction_of_image_pass_floor": floor_bytes_ms / km, "fraction_of_matrix_pipe_floor": floor_flop_ms / km}
+        print(res, flush=True)
+        out["find_repeats"].append(res)
+        ok = ok and same
+    # ---- write rate
+    serial = [0]
+
+    per_writer = 3 + 5 * WINDOWS                   # warm-up calls + timed calls of one writer
+
+    def writer(repeats, tau):
+        # batches and ids are made BEFORE the windows: only the write is timed.  (Copies are taken of rows held now;
+        # the rows the streams append in between are fresh ones.)
+        todo = []
+        for _ in range(per_writer):
+            todo.append(([f"w{serial[0]}-{i}" for i in range(WRITE_BATCH)], make_batch(hf, WRITE_BATCH, repeats, g)))
+            serial[0] += 1
+
+        def fn():
+            ids, f = todo.pop()
+            hf.create_episodic_memories(ids, f, merge_similarity=tau)
+        return fn
+    wr, wr_iters = {}, {}
+    for share, rep in (("0", 0), ("50", WRITE_BATCH // 2)):
+        fns = {f"plain_{share}": writer(rep, None), f"merge_{share}": writer(rep, TAU)}
+        for name, fn in fns.items():
+            for _ in range(3):
+                fn()
+            wr_iters[name] = 5
+            wr[name] = []
+        names = list(fns)
+        for rnd in range(WINDOWS):
+            for name in (names if rnd % 2 == 0 else names[::-1]):
+                wr[name].append(wall_window(fns[name], wr_iters[name]))
+    for name, ms in wr.items():
+        s = summary(ms)
+        s["rows_per_s"] = WRITE_BATCH / (s["median_ms"] * 1e-3)
+        out["write_rate"][name] = s
+    out["write_rate"]["batch"] = WRITE_BATCH
+    out["write_rate"]["batches_per_window"] = 5
+    out["write_rate"]["bank_rows_at_the_end"] = hf.memory_count
+    for share in ("0", "50"):
+        out["write_rate"][f"merge_over_plain_{share}"] = (out["write_rate"][f"merge_{share}"]["median_ms"] /
+                                                          out["write_rate"][f"plain_{share}"]["median_ms"])
+    print(out["write_rate"], flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as fh:
+        json.dump(out, fh, indent=1)
+    print("wrote", a.out)
+    if not ok:
+        raise SystemExit("the image scan and the dense scan disagree")
+    missed = [r["n"] for r in out["find_repeats"] if not r["bar_met"]]
+    if missed:
+        raise SystemExit(f"find_repeats takes more than {BAR} x recall_batch(k=1, use_candidates=False) at n = {missed}")
+
+
+if __name__ == "__main__":
+    main()
