@@ -52,6 +52,9 @@ SIGNATURES = {
     "aura_bank_find_repeats_workspace_bytes": (I64, [I64]),
     "aura_bank_find_repeats": (I, [P, P, I64, I64, P, P, I64, P, P, I64, F, P, P, P, P, P, I64, P]),
     "aura_bank_touch": (I, [P, I64, P, I64, F, P]),
+    "aura_bank_compact_round_rows": (I64, []),
+    "aura_bank_compact_workspace_bytes": (I64, [I64, I64, I]),
+    "aura_bank_compact": (I, [P, P, P, P, P, P, I64, I64, I64, P, I64, I64, P, I64, P]),
     "aura_knn_workspace_bytes": (I64, [I64, I64, I]),
     "aura_knn_search": (I, [P, P, P, P, I, P, P, F, I64, I64, I64, I, I32, P, P, P, I64, P]),
     "aura_knn_search_ex": (I, [P, P, P, P, I, P, P, F, I64, I64, I64, I, I32, P, P, P, I64, I, P,

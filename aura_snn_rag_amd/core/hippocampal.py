@@ -124,6 +124,25 @@ class ConsolidationReport:
     n_merged: int
 
 
+@dataclass
+class CompactionReport:
+    """What ``forget`` / ``prune`` removed: ``old_to_new`` (host int64, one entry per row held BEFORE the call) is the
+    row every memory has now, -1 for a forgotten one."""
+    n_removed: int
+    old_to_new: np.ndarray
+
+
+@dataclass
+class BankConsolidationReport:
+    """What ``consolidate`` did with the ``n_before`` held rows: ``n_kept`` remain, ``n_merged`` repeated a kept memory
+    and are gone; ``old_to_new`` (host int64 [n_before]) is the row every memory has now -- for a merged row the row of
+    the memory it merged into."""
+    n_before: int
+    n_kept: int
+    n_merged: int
+    old_to_new: np.ndarray
+
+
 class HippocampalFormation(nn.Module):
     # above this many rows the inverted lists (each probed list read once per batch) beat a masked
     # pass over every row
@@ -581,7 +600,8 @@ class HippocampalFormation(nn.Module):
         if mid is None:
             for s0, s1, prefix, n0 in reversed(self._implicit_ids):
                 if s0 <= row < s1:
-                    return f"{prefix}{n0 + row - s0}"
+                    # (after a compaction took rows out of the range: the surviving original indices, an array)
+                    return f"{prefix}{n0 + row - s0}" if isinstance(n0, int) else f"{prefix}{int(n0[row - s0])}"
         return mid
 
     def bulk_write(self, features: torch.Tensor, id_prefix: str = "bulk-", first_index: int = 0,
@@ -687,8 +707,8 @@ class HippocampalFormation(nn.Module):
         if float(cap) != float(cap):
             raise ValueError("merge_cap must be a number")
 
-    def find_repeats(self, features: torch.Tensor, threshold: float,
-                     now: Optional[float] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    def find_repeats(self, features: torch.Tensor, threshold: float, now: Optional[float] = None, *,
+                     _use_lists: bool = True) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """Which of the (at most ``ops.CONSOLIDATE_MAX_BATCH``) rows ``features`` repeat a held memory or an earlier
         row of the batch at cosine >= ``threshold``: ``(stored_target int32 [n], batch_leader int32 [n], cos fp32
         [n])`` as HOST tensors (the rule: ``include/aura_hip.h``, ``aura_bank_find_repeats``).  Read-only: nothing is
@@ -708,7 +728,8 @@ class HippocampalFormation(nn.Module):
         if self.memory_count:
             self._ensure_norms()
         # an image must hold EVERY held row: the inverted lists do unless rows without a list may exist
-        mode = 'lists' if (self._candidate_mode() and self.centroids.shape[0] == 256 and
+        # (``_use_lists=False``: ``consolidate``, whose held set is a prefix of the bank that the lists do not describe)
+        mode = 'lists' if (_use_lists and self._candidate_mode() and self.centroids.shape[0] == 256 and
                            not self._unlisted_rows) else 'shadow'
         repacked = False
         while True:                                    # lists -> lists (re-packed) -> shadow -> fp32: at most 4 rounds
@@ -794,6 +815,247 @@ class HippocampalFormation(nn.Module):
         rows = torch.from_numpy(np.where(live, slot, -1))
         n_merged = int(merged.sum())
         return ConsolidationReport(merged=merged, rows=rows, ids=mem_ids, n_stored=n - n_merged, n_merged=n_merged)
+
+    # ------------------------------------------------------------------ forgetting, pruning, consolidating held rows
+    def _ring_start(self) -> int:
+        """Row of the oldest memory of a wrapped ring, 0 where plain row order is the age order."""
+        M = self.max_memories
+        if self._overflow in ('fifo', 'weakest') and self.memory_count == M:
+            return self._write_cursor % M
+        return 0
+
+    def _shadow_travels(self) -> bool:
+        return self._shadow is not None and self._rho is not None and self._shadow.device == self.memory_features.device
+
+    def _move_rows(self, src: np.ndarray, dst0: int) -> None:
+        """Rows ``src`` (ascending) of the bank's row arrays -> rows ``dst0 ..`` (``ops.bank_compact``); the bf16
+        shadow and rho travel when they exist."""
+        sh = self._shadow_travels()
+        ops.bank_compact(self.memory_features, self.memory_locations, self.memory_metadata, self._inv_norm, src, dst0,
+                         shadow=self._shadow if sh else None, rho=self._rho if sh else None)
+
+    def _compact(self, kill: np.ndarray) -> np.ndarray:
+        """Take the rows ``kill`` (host int64, ascending, distinct, inside the bank) out: the survivors move to rows
+        0 .. in ring order, oldest first.  Returns ``old_to_new``."""
+        count = self.memory_count
+        self._ensure_norms()
+        keep = np.ones(count, dtype=bool)
+        keep[kill] = False
+        gone = None
+        if kill.size:                                   # the centroid ids of the rows that leave, before anything moves
+            gone = self.memory_metadata[torch.from_numpy(kill).to(self.device), 2]
+        full = self._shadow_travels() and self._shadow_valid_upto >= count
+        start = self._ring_start()
+        if start == 0:
+            order = np.nonzero(keep)[0]
+            self._move_rows(order, 0)
+            shadow_upto = order.size if full else int(keep[:min(self._shadow_valid_upto, count)].sum())
+        else:
+            # a wrapped ring: the survivors of [start, M) come first.  Those of [0, start) are staged (a temporary
+            # of at most `start` rows), the tail moves down in place, the staged head is copied in behind it.
+            head = np.nonzero(keep[:start])[0]
+            tail = start + np.nonzero(keep[start:])[0]
+            arrays = [self.memory_features, self.memory_locations, self.memory_metadata, self._inv_norm]
+            if self._shadow_travels():
+                arrays += [self._shadow, self._rho]
+            head_t = torch.from_numpy(head).to(self.device)
+            staged = [a.index_select(0, head_t) for a in arrays] if head.size else []
+            self._move_rows(tail, 0)
+            for a, t in zip(arrays, staged):
+                a[tail.size:tail.size + head.size].copy_(t)
+            order = np.concatenate([tail, head])
+            shadow_upto = order.size if full else 0
+        self._finish_compaction(order, count, gone, shadow_upto)
+        old_to_new = np.full(count, -1, dtype=np.int64)
+        old_to_new[order] = np.arange(order.size, dtype=np.int64)
+        return old_to_new
+
+    def _finish_compaction(self, order: np.ndarray, count: int, gone: Optional[torch.Tensor], shadow_upto: int) -> None:
+        """New row i holds what row ``order[i]`` of the ``count`` rows held before: clear the freed tail, bring the
+        derived state and the host maps in line.  ``gone``: the centroid ids (metadata column 2) of the rows that left."""
+        k = int(order.size)
+        for a in (self.memory_features, self.memory_locations, self.memory_metadata):
+            a[k:count].zero_()                          # what was forgotten does not stay in the state_dict
+        if gone is not None and gone.numel():
+            ck = self.centroid_counts.shape[0]
+            cid = gone[(gone >= 0) & (gone < ck)].long()
+            self.centroid_counts.sub_(torch.bincount(cid, minlength=ck).to(self.centroid_counts.dtype)).clamp_(min=0)
+        self.memory_count, self._write_cursor = k, 0
+        self._norms_valid_upto = k
+        self._shadow_valid_upto = min(shadow_upto, k)
+        self._invalidate_lists()
+        # host maps
+        inv = np.full(count, -1, dtype=np.int64)
+        inv[order] = np.arange(k, dtype=np.int64)
+        times = self._slot_time[order].copy()
+        self._slot_time[:count] = 0.0
+        self._slot_time[:k] = times
+        held = np.empty(count, dtype=object)
+        held[:] = self._idx_to_id[:count]
+        self._idx_to_id[:count] = held[order].tolist() + [None] * (count - k)
+        self.id_to_idx = {mid: int(inv[slot]) for mid, slot in self.id_to_idx.items() if slot < count and inv[slot] >= 0}
+        implicit = []
+        for s0, s1, prefix, n0 in self._implicit_ids:
+            s1 = min(s1, count)
+            if s1 <= s0:
+                continue
+            new_rows = inv[s0:s1]
+            alive = new_rows >= 0
+            if not alive.any():
+                continue
+            orig = (n0 + np.arange(s1 - s0, dtype=np.int64)) if isinstance(n0, int) else n0[:s1 - s0]
+            new_rows, orig = new_rows[alive], orig[alive]
+            # the survivors of a range stay together; a rotated ring cuts a range in two at most
+            cuts = (np.nonzero(np.diff(new_rows) != 1)[0] + 1).tolist()
+            for a, b in zip([0] + cuts, cuts + [new_rows.size]):
+                r0, o = int(new_rows[a]), orig[a:b]
+                whole = int(o[-1] - o[0]) == b - a - 1            # (indices ascend: nothing was taken out in between)
+                implicit.append((r0, r0 + b - a, prefix, int(o[0]) if whole else o.copy()))
+        self._implicit_ids = implicit
+
+    def forget(self, rows=None, ids: Optional[Sequence[str]] = None) -> CompactionReport:
+        """Take memories out of the bank.  ``rows``: bank rows (int tensor or array of any shape; ``-1``, rows outside
+        the bank and duplicates are ignored); ``ids``: explicit memory ids as found in ``id_to_idx`` (an unknown id
+        raises ``KeyError`` before anything changes; bulk rows with implicit ids are forgotten by row).
+
+        The survivors are moved to rows ``0 .. count' - 1`` in place by one kernel (``aura_bank_compact``: features,
+        locations, metadata, the cached 1/||row||, and the bf16 shadow with its residuals when they exist -- nothing
+        is converted again), in ring order, oldest first: plain row order for a bank that never wrapped, starting at
+        ``cursor % max_memories`` for a full bank under ``'fifo'`` / ``'weakest'``.  ``memory_count`` becomes the
+        number of survivors and the write cursor 0: later writes append, and once the bank is full again they
+        overwrite the oldest first.  The freed tail of features, locations and metadata is zeroed.  The inverted lists
+        are rebuilt by the next recall that needs them; ``centroid_counts`` lose the removed rows' counts, the
+        centroid MEANS stay as they are (the next ``rebuild_centroids`` recomputes them).  ``id_to_idx``,
+        ``episodic_memories`` and ``id_of_row`` follow; forgotten ids disappear.  An empty kill set launches nothing
+        and changes nothing.  One host copy of ``rows`` if it lives on the device; nothing else is read back.
+        Not available through ``ShardedHippocampus`` (its global rows would shift)."""
+        count = self.memory_count
+        kill: List[np.ndarray] = []
+        if rows is not None:
+            r = rows.detach().cpu().numpy() if isinstance(rows, torch.Tensor) else np.asarray(rows)
+            r = r.reshape(-1).astype(np.int64)
+            kill.append(r[(r >= 0) & (r < count)])
+        stale = []
+        if ids is not None:
+            slots = [self.id_to_idx[mid] for mid in ids]            # KeyError: nothing has changed yet
+            for mid, slot in zip(ids, slots):
+                if slot < count and self._idx_to_id[slot] == mid:
+                    kill.append(np.array([slot], dtype=np.int64))
+                else:
+                    stale.append(mid)                               # its row was overwritten long ago: the id just goes
+        for mid in stale:
+            self.id_to_idx.pop(mid, None)
+        k = np.unique(np.concatenate(kill)) if kill else np.zeros(0, dtype=np.int64)
+        if k.size == 0:
+            return CompactionReport(0, np.arange(count, dtype=np.int64))
+        return CompactionReport(int(k.size), self._compact(k))
+
+    def prune(self, min_strength: Optional[float] = None, min_key: Optional[float] = None,
+              now: Optional[float] = None) -> CompactionReport:
+        """Forget the memories whose strength is below ``min_strength`` or whose ``retention_keys(now)`` (strength
+        times ``exp(-age / 3600)``, what ``overflow='weakest'`` evicts by) is below ``min_key`` -- the pruning the
+        reference's ``decay_memories`` leaves unfinished (``:336-339``: a free list for weak memories, then ``pass``).
+        One comparison on the device and one host read of the rows that go; then ``forget``."""
+        if min_strength is None and min_key is None:
+            raise ValueError("prune needs min_strength or min_key")
+        count = self.memory_count
+        if count == 0:
+            return CompactionReport(0, np.zeros(0, dtype=np.int64))
+        weak = torch.zeros(count, dtype=torch.bool, device=self.memory_metadata.device)
+        if min_strength is not None:
+            weak |= self.memory_metadata[:count, 0] < float(min_strength)
+        if min_key is not None:
+            weak |= self.retention_keys(now) < float(min_key)
+        return self.forget(rows=torch.nonzero(weak).flatten())
+
+    def consolidate(self, similarity: Optional[float] = None, rebuild: bool = True) -> BankConsolidationReport:
+        """Merge the near-copies the bank already holds (rows from ``bulk_write``, ``write_at``, a checkpoint, or
+        written before ``merge_similarity`` was set).  The rule: the bank becomes what writing its rows, oldest first,
+        into an empty bank with ``create_episodic_memories(merge_similarity=similarity)`` in chunks of
+        ``ops.CONSOLIDATE_MAX_BATCH`` would have left -- every row is kept unless its cosine to a row kept before it
+        reaches ``similarity`` (default ``self.merge_similarity``; both None: ``ValueError``); rows with a NaN / Inf
+        component or of norm 0 are kept.
+
+        In place: a wrapped ring is first put in age order (``forget``'s move with nothing to forget); then, slab by
+        slab of 1024 rows, ``find_repeats`` decides the slab (a view of the bank) against the decided prefix -- the
+        row-ordered bf16 shadow when it applies, the dense fp32 scan below ``SHADOW_MIN_ROWS`` rows or where no shadow
+        is kept; the centroid index is not consulted -- and ``aura_bank_compact`` moves the slab's kept rows down behind
+        the prefix.  One host read per slab, as in the write path.  A kept memory takes the largest strength and the
+        latest timestamp among itself and the rows merged into it; the distinct STORED targets of a slab are then
+        reinforced once by ``merge_reinforce`` up to ``merge_cap``, as a consolidating write does per chunk.  The kept
+        row's features stand (nothing is blended).  With ``rebuild`` the pass ends in ``rebuild_centroids()`` when the
+        index is in use and more than ``centroids_k`` rows remain; otherwise the inverted lists are invalidated and
+        ``centroid_counts`` corrected as ``forget`` does (the centroid means stay).  If a slab fails, the undecided
+        remainder is moved down unchanged and the host maps are committed before the error is raised again: the bank
+        stays consistent and nothing undecided is lost."""
+        tau = self.merge_similarity if similarity is None else similarity
+        if tau is None:
+            raise ValueError("consolidate needs a similarity in (0, 1] (none given and the bank has no merge_similarity)")
+        self._check_merge(tau, self.merge_reinforce, self.merge_cap)
+        tau = float(tau)
+        n_before = self.memory_count
+        first = None
+        if self._ring_start():
+            first = self._compact(np.zeros(0, dtype=np.int64))
+        count = self.memory_count
+        if count == 0:
+            return BankConsolidationReport(0, 0, 0, np.zeros(0, dtype=np.int64))
+        self._ensure_norms()
+        dev = self.device
+        full = self._shadow_travels() and self._shadow_valid_upto >= count
+        order = np.empty(count, dtype=np.int64)             # order[new row] = the row it came from
+        old_to_new = np.full(count, -1, dtype=np.int64)
+        gone: List[torch.Tensor] = []                       # centroid ids of the merged rows
+        n_kept = lo = 0
+        strength, stamp = self.memory_metadata[:, 0], self.memory_metadata[:, 1]
+        try:
+            while lo < count:
+                hi = min(count, lo + ops.CONSOLIDATE_MAX_BATCH)   # a slab: what one find_repeats call decides
+                self.memory_count = n_kept                  # the held set of this slab: the decided prefix
+                stored, leader, _ = self.find_repeats(self.memory_features[lo:hi], tau, _use_lists=False)
+                stored, leader = stored.numpy().astype(np.int64), leader.numpy().astype(np.int64)
+                kept = (stored < 0) & (leader < 0)
+                kept_local = np.nonzero(kept)[0]
+                merged_local = np.nonzero(~kept)[0]
+                if merged_local.size:
+                    # where the memory a merged row repeats is NOW (stored targets are in place, leaders still in the slab)
+                    target = np.where(stored >= 0, stored, lo + leader)[merged_local]
+                    m_t = torch.from_numpy(lo + merged_local).to(dev)
+                    t_t = torch.from_numpy(target).to(dev)
+                    strength.scatter_reduce_(0, t_t, strength[m_t], 'amax', include_self=True)
+                    stamp.scatter_reduce_(0, t_t, stamp[m_t], 'amax', include_self=True)
+                    gone.append(self.memory_metadata[m_t, 2])
+                    old_target = np.where(stored >= 0, order[np.maximum(stored, 0)], lo + leader)[merged_local]
+                    np.maximum.at(self._slot_time, old_target, self._slot_time[lo + merged_local])
+                    targets = np.unique(stored[stored >= 0])
+                    if targets.size:
+                        self.reinforce(torch.from_numpy(targets), amount=self.merge_reinforce, cap=self.merge_cap)
+                self._move_rows(lo + kept_local, n_kept)
+                new_of_local = np.full(hi - lo, -1, dtype=np.int64)
+                new_of_local[kept_local] = n_kept + np.arange(kept_local.size, dtype=np.int64)
+                new_of_local[merged_local] = np.where(stored >= 0, stored, new_of_local[np.maximum(leader, 0)])[merged_local]
+                old_to_new[lo:hi] = new_of_local
+                order[n_kept:n_kept + kept_local.size] = lo + kept_local
+                n_kept += kept_local.size
+                if not full:                                # rows arrived that the shadow has not converted
+                    self._shadow_valid_upto = min(self._shadow_valid_upto, n_kept - kept_local.size)
+                lo = hi
+        finally:
+            rest = np.arange(lo, count, dtype=np.int64)     # undecided rows (none unless a slab failed): kept as they are
+            if rest.size:
+                self._move_rows(rest, n_kept)
+                old_to_new[rest] = n_kept + np.arange(rest.size, dtype=np.int64)
+                order[n_kept:n_kept + rest.size] = rest
+            shadow_upto = n_kept + rest.size if full else min(self._shadow_valid_upto, n_kept)
+            self.memory_count = count
+            self._finish_compaction(order[:n_kept + rest.size], count, torch.cat(gone) if gone else None, shadow_upto)
+        if self._ivf is not None:
+            self._ivf.rowc_live = False
+        if rebuild and self.use_centroid_index and self.memory_count > self.centroids_k:
+            self.rebuild_centroids()
+        if first is not None:
+            old_to_new = old_to_new[first]                  # (putting the ring in order removed nothing)
+        return BankConsolidationReport(n_before=n_before, n_kept=n_kept, n_merged=count - n_kept, old_to_new=old_to_new)
 
     # ------------------------------------------------------------------ recall
     def _candidate_mode(self) -> bool:
@@ -1074,7 +1336,9 @@ class HippocampalFormation(nn.Module):
     def bank_state(self) -> Dict[str, Any]:
         """Host-side state the reference forgets to checkpoint (``memory_count``, index flag, id
         maps live outside its ``state_dict``, so a reloaded bank reports 0 memories).  Save this
-        beside ``state_dict()``; the tensors themselves stay in the ``state_dict`` unchanged."""
+        beside ``state_dict()``; the tensors themselves stay in the ``state_dict`` unchanged.  An implicit id range
+        that a compaction took rows out of carries the surviving original indices (an int64 array) in place of its
+        first index; states saved before compaction existed load unchanged."""
         n = self.memory_count
         return {"memory_count": n, "index_ready": bool(self._index_ready),
                 "write_cursor": self._write_cursor, "centroids_k": self.centroids_k,
@@ -1098,7 +1362,8 @@ class HippocampalFormation(nn.Module):
         self._idx_to_id = list(state["ids_by_slot"]) + [None] * (self.max_memories - n)
         self.id_to_idx = dict(state.get("id_to_idx") or
                               {mid: i for i, mid in enumerate(state["ids_by_slot"]) if mid is not None})
-        self._implicit_ids = [tuple(x) for x in state.get("implicit_ids", [])]
+        self._implicit_ids = [(int(s0), int(s1), prefix, int(n0) if isinstance(n0, (int, np.integer))
+                               else np.asarray(n0, dtype=np.int64)) for s0, s1, prefix, n0 in state.get("implicit_ids", [])]
         self._slot_time[:] = 0.0
         st = state.get("slot_time")
         self._slot_time[:n] = np.frombuffer(st, dtype=np.float64)[:n] if st is not None else time.time()

@@ -130,6 +130,10 @@ class MemoryInjection(nn.Module):
             return inject_concat(hidden_states, memory_features, memory_scores)
         return inject_gate(hidden_states, memory_features, memory_scores, self.memory_proj, self.memory_gate)
 
+    def consolidate_memory(self, similarity: Optional[float] = None):
+        """Merge the near-copies the bank holds (``HippocampalFormation.consolidate``)."""
+        return self.hippocampus.consolidate(similarity=similarity)
+
     def forward(self, hidden_states: torch.Tensor, use_memory: bool = True) -> torch.Tensor:
         if use_memory and self.hippocampus is not None and self.hippocampus.memory_count > 0:
             mf, ms = self.retrieve_memories(hidden_states, k=self.num_retrieved)
@@ -152,3 +156,7 @@ class BatchedMemoryMixin:
     def store_memory(self, hidden_states: torch.Tensor, merge_similarity: Optional[float] = None):
         return store_memory(self.hippocampus, hidden_states, event_tag=f"layer_{id(self)}",
                             merge_similarity=merge_similarity)
+
+    def consolidate_memory(self, similarity: Optional[float] = None):
+        """Merge the near-copies the bank holds (``HippocampalFormation.consolidate``)."""
+        return self.hippocampus.consolidate(similarity=similarity)

@@ -11,6 +11,7 @@ import time
 import warnings
 from typing import Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -529,6 +530,59 @@ def bank_touch(meta, count: int, rows, now: float) -> None:
     if now != now:
         raise ValueError("bank_touch: now must be a number")
     check(lib().aura_bank_touch(_p(meta), count, _p(rows), rows.numel(), float(now), _stream()), "aura_bank_touch")
+
+
+def bank_compact_round_rows() -> int:
+    """Rows per round of ``bank_compact`` (the sizes at which its launches change)."""
+    return int(lib().aura_bank_compact_round_rows())
+
+
+def bank_compact(bank, loc, meta, inv_norm, src, dst0: int = 0, shadow=None, rho=None) -> int:
+    """In-place compaction: row ``src[i]`` of ``bank`` [rows, D], ``loc`` [rows, S], ``meta`` [rows, 4], ``inv_norm``
+    [rows] and -- when given, both or neither -- the row-ordered bf16 ``shadow`` [rows, D] and ``rho`` [rows] moves to
+    row ``dst0 + i``, as if every source were read before any destination is written (``include/aura_hip.h``).
+    ``src``: a HOST integer array, strictly ascending, ``dst0 + i <= src[i] < rows`` -- checked here with numpy.  The
+    leading rows that are in place already are cut off here, the rest is uploaded once: a move that moves nothing
+    launches nothing.  Returns the number of rows that change place.  No host sync; the shared workspace."""
+    _need(bank, "bank", torch.float32); _need(loc, "loc", torch.float32); _need(meta, "meta", torch.float32)
+    _need(inv_norm, "inv_norm", torch.float32)
+    if bank.dim() != 2 or loc.dim() != 2 or meta.dim() != 2 or meta.shape[1] != 4:
+        raise ValueError("bank_compact: bank [rows, D], loc [rows, S] and meta [rows, 4] expected")
+    rows, D = bank.shape
+    S = loc.shape[1]
+    if loc.shape[0] != rows or meta.shape[0] != rows or inv_norm.numel() != rows:
+        raise ValueError("bank_compact: the arrays disagree on the number of rows")
+    if (shadow is None) != (rho is None):
+        raise ValueError("bank_compact: shadow and rho go together")
+    if shadow is not None:
+        _need(shadow, "shadow", torch.bfloat16); _need(rho, "rho", torch.float32)
+        if shadow.shape != bank.shape or rho.numel() != rows or D % 8:
+            raise ValueError("bank_compact: the shadow is [rows, D] bf16 with D % 8 == 0, rho one value per row")
+    for t in (loc, meta, inv_norm, shadow, rho):
+        if t is not None and t.device != bank.device:
+            raise ValueError("bank_compact: tensors are on different devices")
+    s = np.ascontiguousarray(np.asarray(src).reshape(-1), dtype=np.int64)
+    n, dst0 = s.size, int(dst0)
+    if dst0 < 0 or dst0 + n > rows or rows > 0x7fffffff:
+        raise ValueError(f"bank_compact: dst0={dst0} and n={n} do not fit {rows} rows")
+    if n == 0:
+        return 0
+    # how far every row moves, plus dst0: src ascends strictly exactly when this never decreases
+    shift = s - np.arange(n, dtype=np.int64)
+    if s[-1] >= rows or shift[0] < dst0 or (n > 1 and bool((shift[1:] < shift[:-1]).any())):
+        raise ValueError("bank_compact: src must ascend strictly with dst0 + i <= src[i] < rows")
+    fixed = int(np.searchsorted(shift, dst0, side="right"))       # rows in place already: a prefix
+    if fixed == n:
+        return 0
+    L = lib()
+    nbytes = L.aura_bank_compact_workspace_bytes(D, S, 1 if shadow is not None else 0)
+    if nbytes < 0:
+        raise ValueError(f"bank_compact: unsupported shape D={D}, S={S}")
+    base = _workspace(bank.device, nbytes)
+    src_t = torch.from_numpy(s[fixed:].astype(np.int32)).to(bank.device)
+    check(L.aura_bank_compact(_p(bank), _p(loc), _p(meta), _p(inv_norm), _p(shadow), _p(rho), rows, D, S, _p(src_t),
+                              n - fixed, dst0 + fixed, base, nbytes, _stream()), "aura_bank_compact")
+    return n - fixed
 
 
 DIVERSE_MAX_CANDIDATES = 128

@@ -101,6 +101,10 @@ class ShardedHippocampus:
     * ``recall_batch``: local recall (the shard's own prefilter shadow / inverted lists, candidate
       mode included) -> global row ids -> all-gather of ``nq * k * 8`` bytes per rank -> merge.
 
+    ``forget``, ``prune`` and ``consolidate`` of the single bank have no collective form here: taking rows out
+    of one shard would shift the global rows of every later one, and a near-copy search would have to cross
+    ranks.  Do not call them on ``local`` of a sharded bank.
+
     ``ops`` is injected (the HIP ops in the product, the CPU stand-ins in the gloo tests)."""
 
     def __init__(self, local, total_rows: int, ops_module=None, group=None, now_fn=None,

@@ -205,6 +205,32 @@ int aura_bank_find_repeats(const float* bank, const float* inv_norm, int64_t N, 
                            int32_t* overflow_out, void* workspace, int64_t workspace_bytes, void* stream);
 int aura_bank_touch(float* meta, int64_t count, const int32_t* rows, int64_t n, float now, void* stream);
 
+/* In-place compaction of the bank (csrc/aura_compact.hip): the primitive under forgetting, pruning and the
+ * consolidation of held rows.  [build-side] no upstream counterpart (the reference's pruning ends in `pass`).
+ * For every i < n, row src[i] of every array moves to row dst0 + i.  The arrays: bank [rows][D], loc [rows][S],
+ * meta [rows][4], inv_norm [rows] and, when given, the row-ordered bf16 shadow [rows][D] and rho [rows] (both or
+ * neither; a shadow needs D % 8 == 0).  src (device int32 [n]) ascends strictly and dst0 + i <= src[i] < rows.
+ * The result is as if every source row were read before any destination is written.  Rows outside dst0 .. dst0 + n - 1
+ * are not written (the caller clears the freed tail).  A row with dst0 + i == src[i] causes no traffic.
+ * Rows are taken in rounds of aura_bank_compact_round_rows() = 4096 in ascending order.  A round whose whole
+ * destination range lies below its first source goes straight to its place (one read and one write per byte); any
+ * other round is gathered into one half of the workspace and stored from it by the next launch, which also takes the
+ * next round: rounds + 1 launches per call, all on the caller's stream, no allocation, no host synchronisation (the
+ * device decides from src which kind a round is).  n == 0 launches nothing.
+ * 16-byte accesses when D % 4 == 0 and bank is 16-byte aligned, 4-byte ones otherwise.  An entry of src that breaks
+ * dst0 + i <= src[i] < rows is skipped before it becomes an address; an order that does not ascend gives an
+ * unspecified arrangement of in-range rows.
+ * workspace: *_workspace_bytes(D, S, has_shadow) bytes -- two halves of 4096 rows of every array, independent of rows
+ * and n; negative for an unsupported shape (1 <= D <= 4096, 0 <= S <= 4096) -- 256-byte aligned.
+ * AURA_E_INVAL: a null array, shadow without rho or the reverse, a negative size, dst0 + n > rows, rows >= 2^31,
+ * a workspace that is too small; AURA_E_ALIGN: workspace not 256-byte, shadow not 16-byte, another array not 4-byte
+ * aligned. */
+int64_t aura_bank_compact_round_rows(void);
+int64_t aura_bank_compact_workspace_bytes(int64_t D, int64_t S, int has_shadow);
+int aura_bank_compact(float* bank, float* loc, float* meta, float* inv_norm, uint16_t* shadow_bf16, float* rho,
+                      int64_t rows, int64_t D, int64_t S, const int32_t* src, int64_t n, int64_t dst0, void* workspace,
+                      int64_t workspace_bytes, void* stream);
+
 /* Workspace size (bytes) aura_knn_search needs for (N, nq, k). */
 int64_t aura_knn_workspace_bytes(int64_t N, int64_t nq, int k);
 
