@@ -55,6 +55,10 @@ SIGNATURES = {
     "aura_bank_compact_round_rows": (I64, []),
     "aura_bank_compact_workspace_bytes": (I64, [I64, I64, I]),
     "aura_bank_compact": (I, [P, P, P, P, P, P, I64, I64, I64, P, I64, I64, P, I64, P]),
+    "aura_bank_set_tags": (I, [P, I64, P, P, I64, P]),
+    "aura_knn_scoped_workspace_bytes": (I64, [I64, I64, I64, I64, I64]),
+    "aura_knn_search_scoped": (I, [P, P, P, P, I, P, P, F, I64, I64, I64, I, P, I64, I64, I64, I, F, F, F, P, P, P, I64,
+                                   P, P]),
     "aura_knn_workspace_bytes": (I64, [I64, I64, I]),
     "aura_knn_search": (I, [P, P, P, P, I, P, P, F, I64, I64, I64, I, I32, P, P, P, I64, P]),
     "aura_knn_search_ex": (I, [P, P, P, P, I, P, P, F, I64, I64, I64, I, I32, P, P, P, I64, I, P,

@@ -27,6 +27,10 @@ Reference defects on this path (SURVEY.md 8a "hazards") and what this class does
     scores, wrong ids: FIXED (rows are reported); ``k`` is clamped to the number of candidates
     instead of raising; ``location=`` works with candidates.
   * fp32 timestamps / fp32 ``age`` (``:215,296``): REPRODUCED (deterministic given the clock).
+  * ``event_id`` / ``associated_experts`` are accepted and dropped (``:195-243``), metadata column 3 is "reserved":
+    REPRODUCED by default.  Build-side: a write may carry an integer ``tag`` (``tags=``), kept in that column, and
+    ``recall_batch(tags=..., newer_than=..., older_than=..., min_strength=...)`` recalls exactly within a scope
+    (``aura_knn_search_scoped``); a bank that never uses tags is bit for bit what it was.
 """
 from __future__ import annotations
 
@@ -107,6 +111,8 @@ class _IvfState:
 
 
 OVERFLOW_POLICIES = ('reference', 'fifo', 'weakest')
+
+TAG_LIMIT = 1 << 24                   # tags are integers in [0, 2^24): exact as the fp32 of metadata column 3
 
 _INSTANCE_DEFAULT = object()          # create_episodic_memories(merge_similarity=...): "what the bank was built with"
 
@@ -499,21 +505,88 @@ class HippocampalFormation(nn.Module):
         self._ivf_pending = None
         self._ivf_after_write(uniq_t, int(uniq_t.numel()), meta_v0)
 
-    def _write_rows(self, ids: Sequence[str], feats: torch.Tensor, now: float) -> None:
+    def _write_rows(self, ids: Sequence[str], feats: torch.Tensor, now: float,
+                    tags: Optional[np.ndarray] = None) -> None:
         """Write a run of rows that contains no centroid-rebuild boundary."""
         slots, n_app, new_count, new_cursor = self._plan_slots(len(ids), now)
         self._store_rows(ids, feats, slots, n_app, new_count, new_cursor, now,
-                         online=self.use_centroid_index and self._index_ready, selected=True)
+                         online=self.use_centroid_index and self._index_ready, selected=True, tags=tags)
+
+    # ------------------------------------------------------------------ tags
+    @staticmethod
+    def _check_tags(tags, n: int) -> Optional[np.ndarray]:
+        """``tags`` of a write (None, an int for every row, or one int per row) as int32 [n], or None."""
+        if tags is None:
+            return None
+        if isinstance(tags, torch.Tensor):
+            tags = tags.detach().cpu().numpy()
+        t = np.asarray(tags)
+        if t.dtype.kind not in "iu":
+            raise ValueError(f"tags must be integers, got dtype {t.dtype}")
+        t = t.astype(np.int64)
+        if t.ndim == 0:
+            t = np.full(n, int(t), dtype=np.int64)
+        t = t.reshape(-1)
+        if t.size != n:
+            raise ValueError(f"{t.size} tags for {n} rows")
+        if t.size and (int(t.min()) < 0 or int(t.max()) >= TAG_LIMIT):
+            raise ValueError(f"tags must be in [0, 2^24 = {TAG_LIMIT}), got {int(t.min())} .. {int(t.max())}")
+        return t.astype(np.int32)
+
+    def _stamp_tags(self, slots: np.ndarray, tags: np.ndarray) -> None:
+        """Column 3 of the DISTINCT held rows ``slots`` <- ``tags``, one launch (``aura_bank_set_tags``).  Through the
+        library, not an in-place torch op: ``_ivf_after_write`` reads a changed ``memory_metadata._version`` as "the
+        cached score constants are stale", and a tag is no part of a score."""
+        if slots.size == 0:
+            return
+        ops.bank_set_tags(self.memory_metadata, self.memory_count,
+                          torch.from_numpy(np.ascontiguousarray(slots, dtype=np.int64)).to(self.device),
+                          torch.from_numpy(np.ascontiguousarray(tags, dtype=np.int32)).to(self.device))
+
+    @property
+    def memory_tags(self) -> torch.Tensor:
+        """int32 [memory_count]: the tag of every held row (``memory_metadata[:count, 3]``; 0 = untagged).  Read-only:
+        a copy in another dtype, writing to it changes nothing -- use ``retag``."""
+        return self.memory_metadata[:self.memory_count, 3].to(torch.int32)
+
+    def retag(self, rows=None, ids: Optional[Sequence[str]] = None, tag=0) -> int:
+        """Give the held memories at bank rows ``rows`` (ints of any shape; ``-1``, rows outside the bank and
+        duplicates are ignored) and / or with the explicit ids ``ids`` (an unknown id raises ``KeyError`` before
+        anything changes) the tag ``tag``: one int for all of them, or -- with ``rows`` alone, when every row is held
+        and distinct -- one int per row.  ``tag=0`` removes a tag.  One launch; returns the number of rows stamped."""
+        count = self.memory_count
+        picked: List[np.ndarray] = []
+        if rows is not None:
+            r = rows.detach().cpu().numpy() if isinstance(rows, torch.Tensor) else np.asarray(rows)
+            picked.append(r.reshape(-1).astype(np.int64))
+        if ids is not None:
+            slots = [self.id_to_idx[mid] for mid in ids]            # KeyError: nothing has changed yet
+            picked.append(np.asarray([s for mid, s in zip(ids, slots) if s < count and self._idx_to_id[s] == mid],
+                                     dtype=np.int64))
+        if not picked:
+            raise ValueError("retag needs rows or ids")
+        allr = np.concatenate(picked)
+        if (tag.dim() if isinstance(tag, torch.Tensor) else np.ndim(tag)) == 0:
+            held = np.unique(allr[(allr >= 0) & (allr < count)])
+            t = self._check_tags(tag, held.size)
+        else:
+            t = self._check_tags(tag, allr.size)
+            if ids is not None or allr.size != np.unique(allr).size or (allr.size and (allr.min() < 0 or allr.max() >= count)):
+                raise ValueError("retag: one tag per row needs rows alone, every one held and distinct")
+            held = allr
+        self._stamp_tags(held, t)
+        return int(held.size)
 
     def write_at(self, ids: Sequence[str], feats: torch.Tensor, slots: np.ndarray, n_app: int, now: float,
-                 cids: Optional[torch.Tensor] = None) -> None:
+                 cids: Optional[torch.Tensor] = None, tags=None) -> None:
         """Positioned write, the building block of a row-sharded bank (``sharded.ShardedHippocampus``):
         row i goes to local slot ``slots[i]``; the first ``n_app`` slots extend the bank
         (``memory_count .. memory_count + n_app - 1``), the rest overwrite.  No centroid update happens
         here: ``cids`` (fp32 [n], device) are the centroid ids the caller assigned against the
-        replicated centroid table (None: -1, "no list")."""
+        replicated centroid table (None: -1, "no list").  ``tags``: as ``create_episodic_memories``."""
         feats = self._features_to_device(feats)
         slots = np.ascontiguousarray(slots, dtype=np.int64)
+        tags = self._check_tags(tags, len(ids))
         if feats.shape[0] != len(ids) or slots.size != len(ids):
             raise ValueError("write_at: ids, feats and slots disagree")
         if slots.size == 0:
@@ -523,11 +596,13 @@ class HippocampalFormation(nn.Module):
         if slots.min() < 0 or slots.max() >= self.max_memories or slots[n_app:].max(initial=-1) >= self.memory_count + n_app:
             raise ValueError("write_at: slot out of range")
         self._store_rows(ids, feats, slots, n_app, self.memory_count + n_app, self._write_cursor, now,
-                         online=False, cids=cids)
+                         online=False, cids=cids, tags=tags)
 
     def _store_rows(self, ids, feats, slots: np.ndarray, n_app: int, new_count: int, new_cursor: int, now: float,
-                    online: bool, cids: Optional[torch.Tensor] = None, selected: bool = False) -> None:
-        """``selected``: the slots come from ``_plan_slots`` (not from a caller of ``write_at``)."""
+                    online: bool, cids: Optional[torch.Tensor] = None, selected: bool = False,
+                    tags: Optional[np.ndarray] = None) -> None:
+        """``selected``: the slots come from ``_plan_slots`` (not from a caller of ``write_at``).  ``tags`` (int32 [n],
+        checked): stamped after the write, by the row that finally owns each slot."""
         c0 = self.memory_count
         meta_v0 = self.memory_metadata._version
         slot_t = torch.from_numpy(slots).to(self.device)
@@ -577,6 +652,11 @@ class HippocampalFormation(nn.Module):
             c = cids.to(device=self.device, dtype=torch.float32)
             self.memory_metadata[uniq_t, 2] = c if keep is None else c[keep_t]
         self.memory_count, self._write_cursor = new_count, new_cursor
+        if tags is not None:                           # (the write itself left 0.0, "untagged", in column 3)
+            if keep is None:
+                self._stamp_tags(slots, tags)
+            else:
+                self._stamp_tags(slots[keep], tags[keep])
         self._after_write(slot_t, uniq_t, slots, c0, n_app, meta_v0)
         self._slot_time[slots] = time.time()
         slot_list = slots.tolist()
@@ -605,15 +685,17 @@ class HippocampalFormation(nn.Module):
         return mid
 
     def bulk_write(self, features: torch.Tensor, id_prefix: str = "bulk-", first_index: int = 0,
-                   rebuild: bool = True) -> int:
+                   rebuild: bool = True, tags=None) -> int:
         """Seeding path for very large ingests (BASELINE config 5): rows go to the bank through the
         batched write kernel with NO per-row Python objects (ids are implicit,
         ``f"{id_prefix}{first_index + i}"``, resolved by ``id_of_row``) and NO online centroid
         update; with ``rebuild`` the centroid index is rebuilt once at the end.  This deliberately
         departs from the reference's rebuild-every-512-inserts schedule, which is quadratic in the
         bank size; use ``create_episodic_memories`` for reference-identical semantics.
+        ``tags`` (an int, or one int per row of ``features``): as ``create_episodic_memories``.
         Returns the number of rows written (stops at ``max_memories``)."""
         feats = self._features_to_device(features)
+        tags = self._check_tags(tags, feats.shape[0])
         n = min(feats.shape[0], self.max_memories - self.memory_count)
         if n <= 0:
             return 0
@@ -626,6 +708,8 @@ class HippocampalFormation(nn.Module):
                        self.current_location.to(device=self.device, dtype=torch.float32).contiguous(),
                        time.time())
         self.memory_count = s0 + n
+        if tags is not None:
+            self._stamp_tags(np.arange(s0, s0 + n, dtype=np.int64), tags[:n])
         self._after_write(slot_t, slot_t, np.arange(s0, s0 + n, dtype=np.int64), s0, n, meta_v0)
         self._slot_time[s0:s0 + n] = time.time()
         self._implicit_ids.append((s0, s0 + n, id_prefix, first_index))
@@ -635,14 +719,15 @@ class HippocampalFormation(nn.Module):
 
     def create_episodic_memory(self, memory_id: str, event_id: str, features: torch.Tensor,
                                associated_experts: List[str] = None,
-                               merge_similarity=_INSTANCE_DEFAULT) -> Optional[ConsolidationReport]:
+                               merge_similarity=_INSTANCE_DEFAULT, tag: Optional[int] = None
+                               ) -> Optional[ConsolidationReport]:
         """Store one memory (reference ``:195-243``).  ``event_id`` / ``associated_experts`` are
-        accepted and unused, as in the reference.  ``merge_similarity``: as ``create_episodic_memories``."""
+        accepted and unused, as in the reference.  ``merge_similarity`` and ``tag``: as ``create_episodic_memories``."""
         return self.create_episodic_memories([memory_id], self._features_to_device(features, rows=1),
-                                             merge_similarity=merge_similarity)
+                                             merge_similarity=merge_similarity, tags=tag)
 
     def create_episodic_memories(self, memory_ids: Sequence[str], features: torch.Tensor,
-                                 merge_similarity=_INSTANCE_DEFAULT) -> Optional[ConsolidationReport]:
+                                 merge_similarity=_INSTANCE_DEFAULT, tags=None) -> Optional[ConsolidationReport]:
         """Batched one-shot write: identical to calling ``create_episodic_memory`` once per row,
         including the rebuild every ``centroids_update_interval`` inserts (``:242-243``).
 
@@ -657,7 +742,15 @@ class HippocampalFormation(nn.Module):
         through the unchanged write path (every overflow policy applies; the rebuild cadence counts kept rows only).
         Returns a ``ConsolidationReport``.  The first observation stands: the repeat's features are not blended into
         the stored row.  ``bulk_write`` and ``write_at`` (the seeding path and the sharded bank's building block) do
-        not consolidate, and ``ShardedHippocampus`` has no cross-rank search."""
+        not consolidate, and ``ShardedHippocampus`` has no cross-rank search.
+
+        ``tags`` (default None: nothing changes and nothing more is launched): an int for every row, or a host
+        sequence / int array of one int per row, each in ``[0, 2^24)``.  The rows go through the unchanged write path
+        (which leaves 0, "untagged", in metadata column 3); one more launch then stamps the column
+        (``ops.bank_set_tags``).  Where a run writes a slot more than once (a full bank under ``overflow='reference'``
+        rewrites slot 0), the row that finally owns the slot stamps it.  An untagged write over a tagged slot leaves it
+        untagged.  ``tags`` together with a consolidating write raises ``ValueError``: ``find_repeats`` is
+        scope-blind, and a near-copy from one scope must not vanish into a memory of another."""
         tau = self.merge_similarity if merge_similarity is _INSTANCE_DEFAULT else merge_similarity
         if tau is not None:
             self._check_merge(tau, self.merge_reinforce, self.merge_cap)
@@ -665,12 +758,17 @@ class HippocampalFormation(nn.Module):
         n = len(memory_ids)
         if feats.shape[0] != n:
             raise ValueError(f"{n} ids but {feats.shape[0]} feature rows")
+        tags = self._check_tags(tags, n)
+        if tags is not None and tau is not None:
+            raise ValueError("tags cannot go with merge_similarity: a consolidating write searches the whole bank, so a "
+                             "near-copy from one scope would merge into a memory of another (write tagged rows with "
+                             "merge_similarity=None)")
         if tau is None:
-            self._write_batch(memory_ids, feats)
+            self._write_batch(memory_ids, feats, tags)
             return None
         return self._write_consolidated(memory_ids, feats, float(tau))
 
-    def _write_batch(self, memory_ids: Sequence[str], feats: torch.Tensor) -> None:
+    def _write_batch(self, memory_ids: Sequence[str], feats: torch.Tensor, tags: Optional[np.ndarray] = None) -> None:
         n = len(memory_ids)
         i = 0
         while i < n:
@@ -686,7 +784,10 @@ class HippocampalFormation(nn.Module):
                     run = min(run, to_boundary, self.max_memories - self.memory_count)
                 elif self.memory_count % interval == 0 and self.memory_count > self.centroids_k:
                     run = 1   # full bank whose size divides the interval: rebuild after every write
-            self._write_rows(memory_ids[i:i + run], feats[i:i + run], time.time())
+            if tags is None:
+                self._write_rows(memory_ids[i:i + run], feats[i:i + run], time.time())
+            else:
+                self._write_rows(memory_ids[i:i + run], feats[i:i + run], time.time(), tags=tags[i:i + run])
             i += run
             if (self.use_centroid_index and self.memory_count % self.centroids_update_interval == 0
                     and self.memory_count > self.centroids_k):
@@ -913,10 +1014,12 @@ class HippocampalFormation(nn.Module):
                 implicit.append((r0, r0 + b - a, prefix, int(o[0]) if whole else o.copy()))
         self._implicit_ids = implicit
 
-    def forget(self, rows=None, ids: Optional[Sequence[str]] = None) -> CompactionReport:
+    def forget(self, rows=None, ids: Optional[Sequence[str]] = None, tags=None) -> CompactionReport:
         """Take memories out of the bank.  ``rows``: bank rows (int tensor or array of any shape; ``-1``, rows outside
         the bank and duplicates are ignored); ``ids``: explicit memory ids as found in ``id_to_idx`` (an unknown id
-        raises ``KeyError`` before anything changes; bulk rows with implicit ids are forgotten by row).
+        raises ``KeyError`` before anything changes; bulk rows with implicit ids are forgotten by row); ``tags``: an int
+        or a sequence of ints -- every held memory that carries one of these tags goes ("forget this session"; 0
+        forgets the untagged rows), at the price of one device-to-host read of the tag column.
 
         The survivors are moved to rows ``0 .. count' - 1`` in place by one kernel (``aura_bank_compact``: features,
         locations, metadata, the cached 1/||row||, and the bf16 shadow with its residuals when they exist -- nothing
@@ -945,6 +1048,12 @@ class HippocampalFormation(nn.Module):
                     stale.append(mid)                               # its row was overwritten long ago: the id just goes
         for mid in stale:
             self.id_to_idx.pop(mid, None)
+        if tags is not None and count:
+            t = (tags.detach().cpu().numpy() if isinstance(tags, torch.Tensor) else np.asarray(tags)).reshape(-1)
+            want = np.unique(self._check_tags(t, t.size)) if t.size else t
+            if want.size:
+                held = self.memory_metadata[:count, 3].cpu().numpy().astype(np.int64)    # THE host read
+                kill.append(np.nonzero(np.isin(held, want))[0].astype(np.int64))
         k = np.unique(np.concatenate(kill)) if kill else np.zeros(0, dtype=np.int64)
         if k.size == 0:
             return CompactionReport(0, np.arange(count, dtype=np.int64))
@@ -987,7 +1096,10 @@ class HippocampalFormation(nn.Module):
         index is in use and more than ``centroids_k`` rows remain; otherwise the inverted lists are invalidated and
         ``centroid_counts`` corrected as ``forget`` does (the centroid means stay).  If a slab fails, the undecided
         remainder is moved down unchanged and the host maps are committed before the error is raised again: the bank
-        stays consistent and nothing undecided is lost."""
+        stays consistent and nothing undecided is lost.
+
+        Scope-blind: tags play no part.  Near-copies merge across tags, and the kept (older) row keeps its own tag; a
+        scope-aware search is a later change."""
         tau = self.merge_similarity if similarity is None else similarity
         if tau is None:
             raise ValueError("consolidate needs a similarity in (0, 1] (none given and the bank has no merge_similarity)")
@@ -1069,7 +1181,9 @@ class HippocampalFormation(nn.Module):
                      bound_exchange=None, reinforce: Optional[float] = None,
                      reinforce_cap: float = 1.0, diversity: Optional[float] = None,
                      max_similarity: Optional[float] = None,
-                     fetch_k: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+                     fetch_k: Optional[int] = None, tags=None, newer_than: Optional[float] = None,
+                     older_than: Optional[float] = None,
+                     min_strength: Optional[float] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """Batched recall: ``(scores [nq, k'], rows [nq, k'])`` with ``k' = min(k, count)``;
         rows are bank row indices (int32), ``-1`` where a query has fewer than ``k'`` candidates.
 
@@ -1093,17 +1207,40 @@ class HippocampalFormation(nn.Module):
         (``ops.diverse_select``): a candidate whose cosine to an earlier pick reaches ``max_similarity`` (in
         ``(-1, 1]``) is skipped, the others rank by ``(1 - diversity) * score - diversity * (largest cosine to an
         earlier pick)``, ``diversity`` in ``[0, 1]``.  Rows come back in pick order with their recall scores, ``-1`` /
-        ``-inf`` where fewer than ``k'`` were eligible; ``reinforce`` then applies to the rows returned."""
+        ``-inf`` where fewer than ``k'`` were eligible; ``reinforce`` then applies to the rows returned.
+
+        Scoped recall -- ``tags``, ``newer_than``, ``older_than``, ``min_strength`` (all None by default: nothing
+        changes and nothing more is launched).  Row ``r`` is in query ``i``'s scope iff ``tags[i] < 0 or
+        int(memory_metadata[r, 3]) == tags[i]``, ``memory_metadata[r, 1] >= float32(newer_than)``,
+        ``memory_metadata[r, 1] <= float32(older_than)`` and ``memory_metadata[r, 0] >= min_strength`` (a condition
+        left at None is not applied).  ``tags``: an int for all queries or one per query (host ints); None or a negative
+        entry takes any tag, 0 the untagged rows.  The other three are per-call scalars; the time bounds are compared
+        with the fp32 timestamps the bank stores, which are 128 s apart at today's epoch values, so a window is no finer
+        than that.  The result is the top ``k'`` of the scope by the same combined score (``locations`` included),
+        descending, equal scores to the lower row, padded with ``-inf`` / ``-1`` where the scope has fewer than ``k'``
+        rows.  It is always exact over the scope and its cost follows the size of the scope, not of the bank
+        (``ops.knn_search_scoped``: a per-call scope build, no index to keep current); the centroid index plays no
+        part, so ``use_candidates=True`` with a scope raises ``ValueError``.  ``k'`` may be at most
+        ``ops.SCOPED_MAX_K`` = 128.  ``reinforce`` and ``diversity`` / ``max_similarity`` compose: the scope goes to the
+        inner plain call.  ``check_overflow`` here reads the scoped call's flag back (one host sync)."""
+        scope = dict(tags=tags, newer_than=newer_than, older_than=older_than, min_strength=min_strength)
+        scoped = any(v is not None for v in scope.values())
+        if scoped:
+            if use_candidates:
+                raise ValueError("a scoped recall (tags / newer_than / older_than / min_strength) is always exact over "
+                                 "its scope and does not use the centroid index: not with use_candidates=True")
+            if bound_exchange is not None:
+                raise ValueError("a scoped recall is not available with bound_exchange (a shard of a row-sharded bank)")
         if diversity is not None or max_similarity is not None:
             return self._recall_diverse(queries, k, diversity, max_similarity, fetch_k, bound_exchange, reinforce,
                                         reinforce_cap, dict(locations=locations, now=now, use_candidates=use_candidates,
                                                             check_overflow=check_overflow, fallback_empty=fallback_empty,
-                                                            probe_ids=probe_ids, _retry=_retry))
+                                                            probe_ids=probe_ids, _retry=_retry, **scope))
         if reinforce is not None:
             # the plain call (with its own retries and fallbacks) first: the rows are final when it returns
             scores, rows = self.recall_batch(queries, k=k, locations=locations, now=now, use_candidates=use_candidates,
                                              check_overflow=check_overflow, fallback_empty=fallback_empty,
-                                             probe_ids=probe_ids, _retry=_retry, bound_exchange=bound_exchange)
+                                             probe_ids=probe_ids, _retry=_retry, bound_exchange=bound_exchange, **scope)
             self.reinforce(rows, amount=reinforce, cap=reinforce_cap)
             return scores, rows
         self._last_flag = None                        # set only by a candidate-mode recall that read its flag
@@ -1116,6 +1253,13 @@ class HippocampalFormation(nn.Module):
         kk = min(int(k), self.memory_count)
         now = time.time() if now is None else now
         q_loc = self._query_locations(locations, q.shape[0])
+        if scoped:
+            if kk > ops.SCOPED_MAX_K:
+                raise ValueError(f"a scoped recall returns at most ops.SCOPED_MAX_K = {ops.SCOPED_MAX_K} rows per "
+                                 f"query, got k = {kk}")
+            return ops.knn_search_scoped(self.memory_features, self._inv_norm, self.memory_metadata, q, kk, now,
+                                         self.memory_count, loc=self.memory_locations if q_loc is not None else None,
+                                         q_loc=q_loc, check_flag=check_overflow, **scope)
         cand = self._candidate_mode() if use_candidates is None else (use_candidates and self._candidate_mode())
         kw = dict(count=self.memory_count, loc=self.memory_locations if q_loc is not None else None,
                   q_loc=q_loc, check_overflow=check_overflow)
@@ -1317,14 +1461,17 @@ class HippocampalFormation(nn.Module):
                                   location: Optional[torch.Tensor] = None,
                                   k: int = 5, *, diversity: Optional[float] = None,
                                   max_similarity: Optional[float] = None,
-                                  fetch_k: Optional[int] = None) -> List[Tuple[str, float]]:
+                                  fetch_k: Optional[int] = None, tags=None, newer_than: Optional[float] = None,
+                                  older_than: Optional[float] = None,
+                                  min_strength: Optional[float] = None) -> List[Tuple[str, float]]:
         """Top-k ``(memory_id, score)`` for one query (reference ``:245-319``).  The keyword arguments are
-        ``recall_batch``'s diverse recall (default off)."""
+        ``recall_batch``'s diverse recall and scoped recall (both off by default; ``tags``: one int)."""
         if self.memory_count == 0:
             return []
         q = self._features_to_device(query_features, rows=1)
         scores, rows = self.recall_batch(q, k=k, locations=location, diversity=diversity,
-                                         max_similarity=max_similarity, fetch_k=fetch_k)
+                                         max_similarity=max_similarity, fetch_k=fetch_k, tags=tags,
+                                         newer_than=newer_than, older_than=older_than, min_strength=min_strength)
         out = []
         for s, r in zip(scores[0].tolist(), rows[0].tolist()):
             mid = self.id_of_row(r) if r >= 0 else None

@@ -24,14 +24,18 @@ import torch.nn.functional as F
 def retrieve_memories(hippocampus, query: torch.Tensor, k: int = 5, dtype=None,
                       reinforce: Optional[float] = None, reinforce_cap: float = 1.0,
                       diversity: Optional[float] = None, max_similarity: Optional[float] = None,
-                      fetch_k: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+                      fetch_k: Optional[int] = None, tags=None, newer_than: Optional[float] = None,
+                      older_than: Optional[float] = None,
+                      min_strength: Optional[float] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """``query`` [B, D] (already projected) -> (memory_features [B, k, D], memory_scores [B, k]).
 
     Same contract as the reference loop (``memory_augmented_layer.py:106-130``): slots beyond the
     number of hits stay zero.  ``reinforce`` (default off): strengthen the retrieved rows by that amount up to
     ``reinforce_cap`` (``HippocampalFormation.recall_batch(reinforce=...)``).  ``diversity`` / ``max_similarity`` /
     ``fetch_k`` (default off): diverse recall, so that near-copies of one memory do not fill the k slots
-    (``HippocampalFormation.recall_batch(diversity=..., max_similarity=...)``)."""
+    (``HippocampalFormation.recall_batch(diversity=..., max_similarity=...)``).  ``tags`` (an int, or one per batch
+    item) / ``newer_than`` / ``older_than`` / ``min_strength`` (default off): scoped recall -- only memories of that
+    tag, time window and strength are retrieved, exactly (``HippocampalFormation.recall_batch(tags=...)``)."""
     B, D = query.shape
     dtype = dtype or query.dtype
     dev = query.device
@@ -42,6 +46,9 @@ def retrieve_memories(hippocampus, query: torch.Tensor, k: int = 5, dtype=None,
     kw = {} if reinforce is None else dict(reinforce=reinforce, reinforce_cap=reinforce_cap)
     if diversity is not None or max_similarity is not None:
         kw.update(diversity=diversity, max_similarity=max_similarity, fetch_k=fetch_k)
+    for name, v in (("tags", tags), ("newer_than", newer_than), ("older_than", older_than), ("min_strength", min_strength)):
+        if v is not None:
+            kw[name] = v
     s, rows = hippocampus.recall_batch(query.detach().float(), k=k, **kw)      # [B, k'] (k' <= k)
     kk = s.shape[1]
     valid = rows >= 0
@@ -51,18 +58,21 @@ def retrieve_memories(hippocampus, query: torch.Tensor, k: int = 5, dtype=None,
 
 
 def store_memory(hippocampus, hidden_states: torch.Tensor, event_tag: str = "layer",
-                 merge_similarity: Optional[float] = None):
+                 merge_similarity: Optional[float] = None, tag=None):
     """Mean-pool each batch item and store it (``memory_augmented_layer.py:132-153``).  ``merge_similarity`` (default
     off): a consolidating write -- a pooled row that repeats a held memory at that cosine strengthens it instead of
     taking a slot (``HippocampalFormation.create_episodic_memories(merge_similarity=...)``, whose report is returned);
-    a bank constructed with a threshold consolidates without it."""
+    a bank constructed with a threshold consolidates without it.  ``tag`` (default off; an int, or one per batch item):
+    the stored memories carry it (``HippocampalFormation.create_episodic_memories(tags=...)``) and
+    ``retrieve_memories(tags=...)`` recalls within it; not together with a consolidating write."""
     if hippocampus is None:
         return None
     feats = hidden_states.detach().float().mean(dim=1)                      # [B, D]
     ids = [str(uuid.uuid4())[:8] for _ in range(feats.shape[0])]
+    kw = {} if tag is None else dict(tags=tag)
     if merge_similarity is None:
-        return hippocampus.create_episodic_memories(ids, feats)
-    return hippocampus.create_episodic_memories(ids, feats, merge_similarity=merge_similarity)
+        return hippocampus.create_episodic_memories(ids, feats, **kw)
+    return hippocampus.create_episodic_memories(ids, feats, merge_similarity=merge_similarity, **kw)
 
 
 def inject_concat(hidden_states, memory_features, memory_scores):
@@ -116,11 +126,14 @@ class MemoryInjection(nn.Module):
 
     def retrieve_memories(self, hidden_states: torch.Tensor, k: int = 5, reinforce: Optional[float] = None,
                           reinforce_cap: float = 1.0, *, diversity: Optional[float] = None,
-                          max_similarity: Optional[float] = None, fetch_k: Optional[int] = None):
+                          max_similarity: Optional[float] = None, fetch_k: Optional[int] = None, tags=None,
+                          newer_than: Optional[float] = None, older_than: Optional[float] = None,
+                          min_strength: Optional[float] = None):
         query = self.query_proj(hidden_states.mean(dim=1))
         return retrieve_memories(self.hippocampus, query, k=k, dtype=hidden_states.dtype, reinforce=reinforce,
                                  reinforce_cap=reinforce_cap, diversity=diversity, max_similarity=max_similarity,
-                                 fetch_k=fetch_k)
+                                 fetch_k=fetch_k, tags=tags, newer_than=newer_than, older_than=older_than,
+                                 min_strength=min_strength)
 
     def inject_memories(self, hidden_states, memory_features, memory_scores):
         if self.memory_injection == "cross_attention":
@@ -147,15 +160,18 @@ class BatchedMemoryMixin:
 
     def retrieve_memories(self, hidden_states: torch.Tensor, k: int = 5, reinforce: Optional[float] = None,
                           reinforce_cap: float = 1.0, *, diversity: Optional[float] = None,
-                          max_similarity: Optional[float] = None, fetch_k: Optional[int] = None):
+                          max_similarity: Optional[float] = None, fetch_k: Optional[int] = None, tags=None,
+                          newer_than: Optional[float] = None, older_than: Optional[float] = None,
+                          min_strength: Optional[float] = None):
         query = self.query_proj(hidden_states.mean(dim=1))
         return retrieve_memories(self.hippocampus, query, k=k, dtype=hidden_states.dtype, reinforce=reinforce,
                                  reinforce_cap=reinforce_cap, diversity=diversity, max_similarity=max_similarity,
-                                 fetch_k=fetch_k)
+                                 fetch_k=fetch_k, tags=tags, newer_than=newer_than, older_than=older_than,
+                                 min_strength=min_strength)
 
-    def store_memory(self, hidden_states: torch.Tensor, merge_similarity: Optional[float] = None):
+    def store_memory(self, hidden_states: torch.Tensor, merge_similarity: Optional[float] = None, tag=None):
         return store_memory(self.hippocampus, hidden_states, event_tag=f"layer_{id(self)}",
-                            merge_similarity=merge_similarity)
+                            merge_similarity=merge_similarity, tag=tag)
 
     def consolidate_memory(self, similarity: Optional[float] = None):
         """Merge the near-copies the bank holds (``HippocampalFormation.consolidate``)."""

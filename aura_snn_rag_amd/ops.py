@@ -630,6 +630,165 @@ def diverse_select(bank, inv_norm, count: int, cand_rows, cand_scores, k: int, d
     return out_s, out_i
 
 
+TAG_LIMIT = 1 << 24                 # tags are integers in [0, 2^24): exact as the fp32 of metadata column 3
+SCOPED_MAX_K = 128
+SCOPED_MAX_SCOPES = 256             # distinct scopes per library call (knn_search_scoped chunks the queries beyond)
+SCOPED_MAX_SPLITS = 64
+SCOPED_TILE_QUERIES = 64
+SCOPED_FLAG_BAD_ROW, SCOPED_FLAG_BAD_PLAN = 1, 2
+
+
+def bank_set_tags(meta, count: int, slots, tags) -> None:
+    """``meta[slots[i]][3] = tags[i]``: the tag stamp of the write paths and of ``retag``.  ``slots`` (int64 [n], device)
+    must be distinct and inside [0, count); ``tags`` (int32 [n], device) inside [0, 2^24) -- the callers check both on
+    the host, the kernel skips an entry that breaks either.  One launch, no host sync."""
+    _check_meta(meta, count, "bank_set_tags")
+    _need(slots, "slots", torch.int64); _need(tags, "tags", torch.int32)
+    if slots.dim() != 1 or tags.shape != slots.shape:
+        raise ValueError("bank_set_tags: slots and tags must both be [n]")
+    if slots.device != meta.device or tags.device != meta.device:
+        raise ValueError("bank_set_tags: tensors are on different devices")
+    if slots.numel() == 0:
+        return
+    check(lib().aura_bank_set_tags(_p(meta), count, _p(slots), _p(tags), slots.numel(), _stream()), "aura_bank_set_tags")
+
+
+def scoped_query_tags(tags, nq: int) -> np.ndarray:
+    """``tags`` of a scoped recall (None, an int, or one int per query; negative = any tag) as int32 [nq] with every
+    "any" entry at -1; raises ``ValueError`` on a length mismatch or a tag >= 2^24."""
+    if tags is None:
+        return np.full(nq, -1, dtype=np.int32)
+    if isinstance(tags, torch.Tensor):
+        tags = tags.detach().cpu().numpy()
+    t = np.asarray(tags)
+    if t.dtype.kind not in "iu":
+        raise ValueError(f"tags must be integers, got dtype {t.dtype}")
+    t = t.astype(np.int64)
+    if t.ndim == 0:
+        t = np.full(nq, int(t), dtype=np.int64)
+    t = t.reshape(-1)
+    if t.size != nq:
+        raise ValueError(f"{t.size} tags for {nq} queries")
+    if t.size and int(t.max()) >= TAG_LIMIT:
+        raise ValueError(f"tags must be below 2^24 = {TAG_LIMIT}, got {int(t.max())}")
+    return np.where(t < 0, -1, t).astype(np.int32)
+
+
+def scoped_plan(qtags: np.ndarray):
+    """The plan ``aura_knn_search_scoped`` takes for per-query tags ``qtags`` (int32 [nq], -1 = any):
+    ``(plan int32, n_scopes, n_tiles)`` -- the distinct tags ascending, then per tile of at most 64 queries of one
+    scope its scope index, first position and length in ``q_order``, then ``q_order`` (the queries grouped by scope,
+    in their own order within a scope)."""
+    scope_tags, inverse = np.unique(qtags, return_inverse=True)
+    order = np.argsort(inverse, kind="stable").astype(np.int32)
+    sizes = np.bincount(inverse, minlength=scope_tags.size)
+    t_scope, t_q0, t_nq = [], [], []
+    q0 = 0
+    for s, m in enumerate(sizes.tolist()):
+        for lo in range(0, m, SCOPED_TILE_QUERIES):
+            t_scope.append(s); t_q0.append(q0 + lo); t_nq.append(min(SCOPED_TILE_QUERIES, m - lo))
+        q0 += m
+    plan = np.concatenate([scope_tags.astype(np.int32), np.asarray(t_scope, dtype=np.int32),
+                           np.asarray(t_q0, dtype=np.int32), np.asarray(t_nq, dtype=np.int32), order])
+    return plan, int(scope_tags.size), len(t_scope)
+
+
+def knn_search_scoped(bank, inv_norm, meta, queries, k: int, now: float, count: int, tags=None,
+                      newer_than: Optional[float] = None, older_than: Optional[float] = None,
+                      min_strength: Optional[float] = None, loc=None, q_loc=None, check_flag: bool = True,
+                      splits: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Exact recall within a scope -> ``(scores [nq, k] fp32, rows [nq, k] int32)``.  Row ``r < count`` is in query
+    ``i``'s scope iff ``tags[i] < 0 or int(meta[r][3]) == tags[i]``, ``meta[r][1] >= float32(newer_than)``,
+    ``meta[r][1] <= float32(older_than)`` and ``meta[r][0] >= min_strength`` (a condition given as None is not applied);
+    the result is the top ``k`` of the scope by the combined score of ``knn_search``, descending, equal scores to the
+    lower row, ``-inf`` / ``-1`` where the scope has fewer than ``k`` rows (the rule in full: ``include/aura_hip.h``).
+    ``tags``: None (any tag), an int for all queries or one per query (host ints; negative = any; 0 = untagged rows).
+    The host sorts and uniques the tags into a plan (one small upload); more than ``SCOPED_MAX_SCOPES`` distinct tags
+    are served in several library calls over subsets of the queries -- a pair's score bits do not depend on what
+    shares a call.  ``splits`` (default: chosen from the number of query tiles): how many workgroups share a tile's
+    row list.  ``check_flag`` reads the call's flag back (one host sync) and raises ``AuraDeviceError`` if a scope
+    list held a row outside the bank or the plan was inconsistent."""
+    _need(bank, "bank", torch.float32); _need(inv_norm, "inv_norm", torch.float32)
+    _need(meta, "meta", torch.float32); _need(queries, "queries", torch.float32)
+    if bank.dim() != 2 or queries.dim() != 2 or queries.shape[1] != bank.shape[1]:
+        raise ValueError(f"knn_search_scoped: queries must be [nq, {bank.shape[-1]}]")
+    M, D = bank.shape
+    nq = queries.shape[0]
+    count = int(count)
+    if not (0 < count <= M) or count >= (1 << 30) or meta.shape != (M, 4) or inv_norm.numel() != M:
+        raise ValueError("knn_search_scoped: bad bank/count")
+    if not (1 <= D <= 4096):
+        raise ValueError(f"knn_search_scoped: D={D} must be in [1, 4096]")
+    if not (1 <= k <= min(count, SCOPED_MAX_K)):
+        raise ValueError(f"knn_search_scoped: k={k} must be in [1, min(count, {SCOPED_MAX_K})] "
+                         f"(a scoped recall returns at most {SCOPED_MAX_K} rows per query)")
+    sd = 0
+    if q_loc is not None:
+        _need(loc, "loc", torch.float32); _need(q_loc, "q_loc", torch.float32)
+        sd = loc.shape[1]
+        if q_loc.shape != (nq, sd) or loc.shape[0] != M or not (1 <= sd <= 4):
+            raise ValueError("knn_search_scoped: location shape mismatch")
+    for t in (inv_norm, meta, queries, loc if q_loc is not None else None, q_loc):
+        if t is not None and t.device != bank.device:
+            raise ValueError("knn_search_scoped: tensors are on different devices")
+    qtags = scoped_query_tags(tags, nq)
+    cond, bounds = 0, []
+    for bit, v, name in ((1, newer_than, "newer_than"), (2, older_than, "older_than"), (4, min_strength, "min_strength")):
+        v32 = 0.0
+        if v is not None:
+            v32 = float(np.float32(v))
+            if v32 != v32:
+                raise ValueError(f"knn_search_scoped: {name} must be a number")
+            cond |= bit
+        bounds.append(v32)
+    dev = bank.device
+    out_s = torch.empty(nq, k, dtype=torch.float32, device=dev)
+    out_i = torch.empty(nq, k, dtype=torch.int32, device=dev)
+    if nq == 0:
+        return out_s, out_i
+    L = lib()
+    flag = _overflow_flag(dev)
+
+    def run(qt, q, ql, dst_s, dst_i):
+        plan, n_scopes, n_tiles = scoped_plan(qt)
+        sp = splits
+        if sp is None:                    # about 1024 workgroups, no more than the longest possible list has row tiles
+            sp = max(1, min(SCOPED_MAX_SPLITS, -(-1024 // n_tiles), -(-count // 128)))
+        if not (1 <= sp <= SCOPED_MAX_SPLITS):
+            raise ValueError(f"knn_search_scoped: splits must be in [1, {SCOPED_MAX_SPLITS}]")
+        n = q.shape[0]
+        nbytes = L.aura_knn_scoped_workspace_bytes(count, n, k, n_scopes, sp)
+        if nbytes < 0:
+            raise ValueError("knn_search_scoped: unsupported size")
+        base = _workspace(dev, nbytes)
+        plan_t = torch.from_numpy(plan).to(dev)
+        check(L.aura_knn_search_scoped(_p(bank), _p(inv_norm), _p(meta), _p(loc) if ql is not None else None, sd, _p(q),
+                                       _p(ql), now, count, D, n, k, _p(plan_t), n_scopes, n_tiles, sp, cond, bounds[0],
+                                       bounds[1], bounds[2], _p(dst_s), _p(dst_i), base, nbytes, _p(flag), _stream()),
+              "aura_knn_search_scoped")
+        if check_flag:
+            f = int(flag.item())
+            if f:
+                raise AuraDeviceError(
+                    f"aura_knn_search_scoped flagged its call ({f}: "
+                    f"{'a scope list held a row outside the bank' if f & SCOPED_FLAG_BAD_ROW else 'an inconsistent plan'})"
+                    f": the results are not valid")
+
+    distinct = np.unique(qtags)
+    if distinct.size <= SCOPED_MAX_SCOPES:
+        run(qtags, queries, q_loc, out_s, out_i)
+        return out_s, out_i
+    for lo in range(0, distinct.size, SCOPED_MAX_SCOPES):       # many distinct tags: subsets of the queries
+        sel = np.nonzero(np.isin(qtags, distinct[lo:lo + SCOPED_MAX_SCOPES]))[0]
+        sel_t = torch.from_numpy(sel).to(dev)
+        s_part = torch.empty(sel.size, k, dtype=torch.float32, device=dev)
+        i_part = torch.empty(sel.size, k, dtype=torch.int32, device=dev)
+        run(qtags[sel], queries.index_select(0, sel_t), None if q_loc is None else q_loc.index_select(0, sel_t),
+            s_part, i_part)
+        out_s[sel_t], out_i[sel_t] = s_part, i_part
+    return out_s, out_i
+
+
 def knn_search(bank, inv_norm, meta, queries, k: int, now: float, count: Optional[int] = None,
                loc=None, q_loc=None, idx_base: int = 0, force_dense: bool = False,
                centroids=None, nprobe: int = 0, check_overflow: bool = True,

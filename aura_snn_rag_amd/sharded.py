@@ -167,12 +167,25 @@ class ShardedHippocampus:
                              "(local select, all-gather of the candidates, merge) that is not implemented; use "
                              "'reference' or 'fifo' (reinforce() on the local bank of a shard works as on any bank)")
 
+    @staticmethod
+    def _refuse_scope(what: str, **given) -> None:
+        """Tags and scoped recall are a single-bank feature: raised from the arguments alone, on every rank alike and
+        before any collective."""
+        named = [name for name, v in given.items() if v is not None]
+        if named:
+            raise ValueError(f"ShardedHippocampus.{what} does not take {', '.join(named)}: tags and scoped recall are "
+                             f"not available on a row-sharded bank (a scope would span the shards: every rank would "
+                             f"have to build its part of the scope and the merge would need the scopes' global "
+                             f"sizes); tag and recall on a single HippocampalFormation")
+
     # ------------------------------------------------------------------ write
-    def write(self, memory_ids, features) -> None:
+    def write(self, memory_ids, features, tags=None) -> None:
         """Collective batched write: identical to ``HippocampalFormation.create_episodic_memories`` on one
         bank of ``total_rows`` rows, including the rebuild every ``centroids_update_interval`` inserts
-        (``overflow='reference'`` or ``'fifo'``; ``'weakest'`` raises ``ValueError``)."""
+        (``overflow='reference'`` or ``'fifo'``; ``'weakest'`` raises ``ValueError``).  ``tags`` is refused
+        (``ValueError``): cross-rank scopes are not implemented."""
         import numpy as np
+        self._refuse_scope("write", tags=tags)
         self._refuse_weakest()
         loc = self.local
         feats = loc._features_to_device(features)
@@ -246,13 +259,15 @@ class ShardedHippocampus:
                     and self.memory_count > loc.centroids_k):
                 self.rebuild_centroids()
 
-    def bulk_write(self, features, first_index: int = 0, id_prefix: str = "bulk-") -> int:
+    def bulk_write(self, features, first_index: int = 0, id_prefix: str = "bulk-", tags=None) -> int:
         """Seeding path: every rank passes ITS OWN rows (already routed: e.g. rank g reads the g-th slice
         of the corpus); rows are appended to the local shard, no centroid update.  Returns the new global
         count; call ``rebuild_centroids`` once at the end.  Shards must be filled evenly by the caller
         (global row ids are ``rank * R + local row``).  ``write`` plans slots globally (slot // R owns the row),
         which only agrees with independently filled shards once every shard before the last non-empty one is
-        full; the first ``write`` after a ``bulk_write`` checks that collectively and raises on every rank."""
+        full; the first ``write`` after a ``bulk_write`` checks that collectively and raises on every rank.
+        ``tags`` is refused (``ValueError``)."""
+        self._refuse_scope("bulk_write", tags=tags)
         self.local.bulk_write(features, id_prefix=id_prefix, first_index=first_index, rebuild=False)
         c = torch.tensor([self.local.memory_count], dtype=torch.int64, device=self.local.memory_features.device)
         self.memory_count = int(self._all_reduce(c).item())
@@ -382,10 +397,14 @@ class ShardedHippocampus:
 
     def recall_batch(self, queries: torch.Tensor, k: int = 5, now: Optional[float] = None,
                      all_gather_queries: bool = False, use_candidates: Optional[bool] = None,
-                     check_overflow: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
+                     check_overflow: bool = True, tags=None, newer_than=None, older_than=None,
+                     min_strength=None) -> Tuple[torch.Tensor, torch.Tensor]:
         """Global top-k ``(scores [nq, k], GLOBAL rows [nq, k])`` (``-1`` where fewer than k rows can
         score).  ``all_gather_queries``: every rank brings its own ``nq`` queries and receives their
-        results (the serving layout of ``bench.py --gpus N``)."""
+        results (the serving layout of ``bench.py --gpus N``).  The scope arguments of
+        ``HippocampalFormation.recall_batch`` are refused (``ValueError``)."""
+        self._refuse_scope("recall_batch", tags=tags, newer_than=newer_than, older_than=older_than,
+                           min_strength=min_strength)
         q = self.local._features_to_device(queries)
         self._recall_kw = dict(now=self._now() if now is None else now, use_candidates=use_candidates,
                                check_overflow=check_overflow)

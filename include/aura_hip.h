@@ -231,6 +231,54 @@ int aura_bank_compact(float* bank, float* loc, float* meta, float* inv_norm, uin
                       int64_t rows, int64_t D, int64_t S, const int32_t* src, int64_t n, int64_t dst0, void* workspace,
                       int64_t workspace_bytes, void* stream);
 
+/* Scoped recall: tags on memories and the exact top-k over a per-query subset of the held rows
+ * (csrc/aura_scoped.hip).  [build-side] no upstream counterpart (the reference accepts event_id and drops it;
+ * column 3 of its memory_metadata is "reserved").
+ * A tag is an integer in [0, 2^24) held as a float in meta[r][3]; 0 = untagged, what every write leaves there.
+ * aura_bank_set_tags: meta[slots[i]][3] = (float)tags[i] for i < n, plain vector stores; an entry with a slot outside
+ *   [0, count) or a tag outside [0, 2^24) is skipped before it becomes an address.  slots (device int64 [n]) must be
+ *   distinct (the caller keeps the last write to a slot); tags device int32 [n].  One launch; n == 0 launches nothing.
+ * aura_knn_search_scoped.  Row r < count is in query i's scope iff ALL of
+ *     tag_i < 0  or  (int)meta[r][3] == tag_i                       (tag_i = -1: any tag; 0: the untagged rows)
+ *     conditions & 1 == 0  or  meta[r][1] >= newer_than             (fp32 comparisons on the stored fp32 timestamps,
+ *     conditions & 2 == 0  or  meta[r][1] <= older_than              which are 128 s apart at today's epoch values)
+ *     conditions & 4 == 0  or  meta[r][0] >= min_strength
+ *   hold; rows at or beyond count never match, whatever their column 3 holds.  Per query the result is the top k rows
+ *   of its scope by the combined score of aura_knn_search ((0.5 cos + 0.3 spatial + 0.2 exp(-(now - ts) / 3600)) *
+ *   strength, the same fp32 arithmetic; q_loc == NULL: spatial = 0), descending, equal scores -> the lower row; a scope
+ *   of fewer than k rows leaves the tail at score -inf, row -1.  Always exact over the scope; the centroid index plays
+ *   no part.  The score bits of a (query, row) pair do not depend on which other queries or rows share the call: the
+ *   dot product is accumulated in one fixed order along D (v_mfma_f32_32x32x2_f32, exact fp32).
+ *   The plan (device int32, built by the host, which knows the queries' tags): with S = n_scopes distinct scopes and
+ *   T = n_tiles query tiles,
+ *     plan[0 .. S)            the scopes' tags, strictly ascending, "any tag" = -1 first when a query uses it;
+ *     plan[S .. S + T)        tile_scope: the scope (index) of every query tile;
+ *     plan[S + T .. S + 2T)   tile_q0, plan[S + 2T .. S + 3T) tile_nq: the tile's queries are
+ *                             q_order[tile_q0 .. tile_q0 + tile_nq), 1 <= tile_nq <= 64, all of ONE scope;
+ *     plan[S + 3T .. + nq)    q_order: the query indices grouped by scope (a permutation of 0 .. nq - 1).
+ *   S <= 256 per call (a caller with more distinct tags chunks its queries), 1 <= k <= 128, 1 <= splits <= 64,
+ *   1 <= count < 2^30, 1 <= D <= 4096 (16-byte loads when D % 4 == 0 and bank and queries are 16-byte aligned, 4-byte
+ *   loads otherwise); meta 16-byte aligned; spatial_dims <= 4 with q_loc.
+ *   The launches: query norms; a count pass over meta[0 .. count) (16 B per row) per block of 256 rows; an exclusive
+ *   prefix over blocks and scopes; a scatter pass that leaves every scope's row ids in ascending order (a stable
+ *   compaction: no atomic decides a position, the order does not depend on the launch geometry); the scan, grid
+ *   (T, splits): a tile's queries against their scope's gathered rows, 128 at a time, split s taking row tiles s,
+ *   s + splits, ..., each query's sorted top-k kept in registers; for splits > 1 a merge of the splits' lists.  The work
+ *   of the scan follows sum_i |scope(i)| / 64, not the bank.  Nothing is read back between the launches, nothing is
+ *   allocated: workspace is *_workspace_bytes(count, nq, k, n_scopes, splits) bytes (negative: unsupported), 256-byte
+ *   aligned.
+ *   *flag_out (device int32, reset by every call): bit 0 = a scope list held a row id outside [0, count) (skipped
+ *   before it became an address), bit 1 = the plan named a scope, tile or query that does not exist (that tile is
+ *   skipped).  Either means the results are not to be trusted; neither can fault. */
+int aura_bank_set_tags(float* meta, int64_t count, const int64_t* slots, const int32_t* tags, int64_t n, void* stream);
+int64_t aura_knn_scoped_workspace_bytes(int64_t count, int64_t nq, int64_t k, int64_t n_scopes, int64_t splits);
+int aura_knn_search_scoped(const float* bank, const float* inv_norm, const float* meta, const float* loc,
+                           int spatial_dims, const float* queries, const float* q_loc, float now, int64_t count,
+                           int64_t D, int64_t nq, int k, const int32_t* plan, int64_t n_scopes, int64_t n_tiles,
+                           int64_t splits, int conditions, float newer_than, float older_than, float min_strength,
+                           float* out_scores, int32_t* out_rows, void* workspace, int64_t workspace_bytes,
+                           int32_t* flag_out, void* stream);
+
 /* Workspace size (bytes) aura_knn_search needs for (N, nq, k). */
 int64_t aura_knn_workspace_bytes(int64_t N, int64_t nq, int k);
 
