@@ -30,7 +30,9 @@ Reference defects on this path (SURVEY.md 8a "hazards") and what this class does
   * ``event_id`` / ``associated_experts`` are accepted and dropped (``:195-243``), metadata column 3 is "reserved":
     REPRODUCED by default.  Build-side: a write may carry an integer ``tag`` (``tags=``), kept in that column, and
     ``recall_batch(tags=..., newer_than=..., older_than=..., min_strength=...)`` recalls exactly within a scope
-    (``aura_knn_search_scoped``); a bank that never uses tags is bit for bit what it was.
+    (``aura_knn_search_scoped``); a bank that never uses tags is bit for bit what it was.  Consolidation can stay
+    within tags (``merge_within_tags``, ``find_repeats(tags=...)``, ``consolidate(within_tags=...)``:
+    ``aura_bank_find_repeats_scoped``); off by default, and then scope-blind as before.
 """
 from __future__ import annotations
 
@@ -169,13 +171,16 @@ class HippocampalFormation(nn.Module):
                  bf16_shadow: bool = True,
                  merge_similarity: Optional[float] = None,
                  merge_reinforce: float = 0.1,
-                 merge_cap: float = 1.0):
+                 merge_cap: float = 1.0,
+                 merge_within_tags: bool = False):
         super().__init__()
         # consolidating writes (create_episodic_memories): None = every row is stored, today's behaviour
         self._check_merge(merge_similarity, merge_reinforce, merge_cap)
         self.merge_similarity = merge_similarity
         self.merge_reinforce = merge_reinforce
         self.merge_cap = merge_cap
+        # consolidation within tags (consolidating writes and consolidate()): False = scope-blind, today's behaviour
+        self.merge_within_tags = bool(merge_within_tags)
         self.spatial_dims = spatial_dimensions
         self.device = torch.device(device if torch.cuda.is_available() else 'cpu')
         dev = self.device
@@ -719,15 +724,18 @@ class HippocampalFormation(nn.Module):
 
     def create_episodic_memory(self, memory_id: str, event_id: str, features: torch.Tensor,
                                associated_experts: List[str] = None,
-                               merge_similarity=_INSTANCE_DEFAULT, tag: Optional[int] = None
-                               ) -> Optional[ConsolidationReport]:
+                               merge_similarity=_INSTANCE_DEFAULT, tag: Optional[int] = None,
+                               merge_within_tags=_INSTANCE_DEFAULT) -> Optional[ConsolidationReport]:
         """Store one memory (reference ``:195-243``).  ``event_id`` / ``associated_experts`` are
-        accepted and unused, as in the reference.  ``merge_similarity`` and ``tag``: as ``create_episodic_memories``."""
+        accepted and unused, as in the reference.  ``merge_similarity``, ``tag`` and ``merge_within_tags``: as
+        ``create_episodic_memories``."""
         return self.create_episodic_memories([memory_id], self._features_to_device(features, rows=1),
-                                             merge_similarity=merge_similarity, tags=tag)
+                                             merge_similarity=merge_similarity, tags=tag,
+                                             merge_within_tags=merge_within_tags)
 
     def create_episodic_memories(self, memory_ids: Sequence[str], features: torch.Tensor,
-                                 merge_similarity=_INSTANCE_DEFAULT, tags=None) -> Optional[ConsolidationReport]:
+                                 merge_similarity=_INSTANCE_DEFAULT, tags=None,
+                                 merge_within_tags=_INSTANCE_DEFAULT) -> Optional[ConsolidationReport]:
         """Batched one-shot write: identical to calling ``create_episodic_memory`` once per row,
         including the rebuild every ``centroids_update_interval`` inserts (``:242-243``).
 
@@ -749,9 +757,17 @@ class HippocampalFormation(nn.Module):
         (which leaves 0, "untagged", in metadata column 3); one more launch then stamps the column
         (``ops.bank_set_tags``).  Where a run writes a slot more than once (a full bank under ``overflow='reference'``
         rewrites slot 0), the row that finally owns the slot stamps it.  An untagged write over a tagged slot leaves it
-        untagged.  ``tags`` together with a consolidating write raises ``ValueError``: ``find_repeats`` is
-        scope-blind, and a near-copy from one scope must not vanish into a memory of another."""
+        untagged.
+
+        ``merge_within_tags`` (default: the value the bank was constructed with, False there): consolidation within
+        tags.  Off, ``tags`` together with a consolidating write raises ``ValueError``: the plain ``find_repeats`` is
+        scope-blind, and a near-copy from one scope must not vanish into a memory of another.  On, the two go together:
+        a row repeats only a held memory, or a stored earlier row of the batch, that carries ITS tag
+        (``find_repeats(tags=...)``, ``aura_bank_find_repeats_scoped``); rows without a tag are tag 0 and merge only
+        into untagged memories.  Per chunk the order stays reinforce, touch, write, and the kept rows are written WITH
+        their tags before the next chunk searches."""
         tau = self.merge_similarity if merge_similarity is _INSTANCE_DEFAULT else merge_similarity
+        within = self.merge_within_tags if merge_within_tags is _INSTANCE_DEFAULT else bool(merge_within_tags)
         if tau is not None:
             self._check_merge(tau, self.merge_reinforce, self.merge_cap)
         feats = self._features_to_device(features)
@@ -759,14 +775,16 @@ class HippocampalFormation(nn.Module):
         if feats.shape[0] != n:
             raise ValueError(f"{n} ids but {feats.shape[0]} feature rows")
         tags = self._check_tags(tags, n)
-        if tags is not None and tau is not None:
+        if tags is not None and tau is not None and not within:
             raise ValueError("tags cannot go with merge_similarity: a consolidating write searches the whole bank, so a "
                              "near-copy from one scope would merge into a memory of another (write tagged rows with "
-                             "merge_similarity=None)")
+                             "merge_similarity=None, or consolidate within tags with merge_within_tags=True)")
         if tau is None:
             self._write_batch(memory_ids, feats, tags)
             return None
-        return self._write_consolidated(memory_ids, feats, float(tau))
+        if not within:
+            return self._write_consolidated(memory_ids, feats, float(tau))
+        return self._write_consolidated(memory_ids, feats, float(tau), tags=tags, within_tags=True)
 
     def _write_batch(self, memory_ids: Sequence[str], feats: torch.Tensor, tags: Optional[np.ndarray] = None) -> None:
         n = len(memory_ids)
@@ -809,7 +827,7 @@ class HippocampalFormation(nn.Module):
             raise ValueError("merge_cap must be a number")
 
     def find_repeats(self, features: torch.Tensor, threshold: float, now: Optional[float] = None, *,
-                     _use_lists: bool = True) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+                     tags=None, _use_lists: bool = True) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """Which of the (at most ``ops.CONSOLIDATE_MAX_BATCH``) rows ``features`` repeat a held memory or an earlier
         row of the batch at cosine >= ``threshold``: ``(stored_target int32 [n], batch_leader int32 [n], cos fp32
         [n])`` as HOST tensors (the rule: ``include/aura_hip.h``, ``aura_bank_find_repeats``).  Read-only: nothing is
@@ -818,7 +836,14 @@ class HippocampalFormation(nn.Module):
         no shadow applies.  One device-to-host read brings the results, the scan's overflow flag and the inverted
         lists' "a row was dropped" flag: stale lists are re-packed and the call repeated once (a dropped row must
         never become a missed duplicate), an overflowing survivor list repeats the call on the fp32 scan.  ``now`` is
-        accepted for symmetry with ``recall_batch``; a cosine has no time term."""
+        accepted for symmetry with ``recall_batch``; a cosine has no time term.
+
+        ``tags`` (default None: the scope-blind search, exactly as it was): one int for every row, a host sequence of
+        one int per row, or an int32 tensor [n] (used where it lives if it is on the bank's device).  The search then
+        stays within tags (``ops.find_repeats_scoped``): a held row is a candidate for row i only if it carries
+        ``tags[i]``, an earlier row of the batch only if it carries the same tag; 0 is the scope of the untagged rows
+        and a tag outside ``[0, 2^24)`` matches nothing.  The same three scans and the same fallbacks; rows of other
+        tags never enter a survivor list, so other scopes' near-copies cannot overflow one."""
         if threshold is None:
             raise ValueError("find_repeats needs a threshold in (0, 1]")
         self._check_merge(threshold, 0.0, 1.0)
@@ -826,6 +851,7 @@ class HippocampalFormation(nn.Module):
         n = f.shape[0]
         if n > ops.CONSOLIDATE_MAX_BATCH:
             raise ValueError(f"find_repeats takes at most {ops.CONSOLIDATE_MAX_BATCH} rows per call, got {n}")
+        t_dev = None if tags is None else self._search_tags(tags, n)
         if self.memory_count:
             self._ensure_norms()
         # an image must hold EVERY held row: the inverted lists do unless rows without a list may exist
@@ -848,8 +874,12 @@ class HippocampalFormation(nn.Module):
                     mode = 'fp32'
                 else:
                     kw = dict(image=shadow, rho=self._rho)
-            packed = ops.find_repeats(self.memory_features, self._inv_norm, self.memory_count, f, float(threshold),
-                                      **kw)[3].cpu()                       # THE host read
+            if t_dev is None:
+                packed = ops.find_repeats(self.memory_features, self._inv_norm, self.memory_count, f, float(threshold),
+                                          **kw)[3].cpu()                   # THE host read
+            else:
+                packed = ops.find_repeats_scoped(self.memory_features, self._inv_norm, self.memory_metadata,
+                                                 self.memory_count, f, t_dev, float(threshold), **kw)[3].cpu()
             overflow, stale = int(packed[3 * n]), int(packed[3 * n + 1])
             if ivf is not None and stale:
                 ivf.valid = False                      # a write outgrew a list's slack: re-pack and once more;
@@ -861,6 +891,30 @@ class HippocampalFormation(nn.Module):
                 continue
             break
         return packed[:n], packed[n:2 * n], packed[2 * n:3 * n].view(torch.float32)
+
+    def _search_tags(self, tags, n: int) -> torch.Tensor:
+        """``find_repeats(tags=...)`` as int32 [n] on the bank's device.  Nothing is refused for its value: a tag
+        outside ``[0, 2^24)`` matches nothing (host values are clipped to -1 / 2^24 so that they fit int32)."""
+        if isinstance(tags, torch.Tensor):
+            if tags.dtype not in (torch.int32, torch.int64, torch.int16, torch.int8, torch.uint8):
+                raise ValueError(f"tags must be integers, got dtype {tags.dtype}")
+            t = tags.detach().reshape(-1)
+            if t.dtype != torch.int32:
+                t = t.clamp(-1, TAG_LIMIT).to(torch.int32)
+            t = t.to(self.memory_features.device).contiguous()
+            if t.numel() == 1 and n != 1:
+                t = t.expand(n).contiguous()
+        else:
+            a = np.asarray(tags)
+            if a.dtype.kind not in "iu":
+                raise ValueError(f"tags must be integers, got dtype {a.dtype}")
+            a = np.clip(a.astype(np.int64), -1, TAG_LIMIT).astype(np.int32).reshape(-1)
+            if a.size == 1 and n != 1:
+                a = np.full(n, a[0], dtype=np.int32)
+            t = torch.from_numpy(np.ascontiguousarray(a)).to(self.memory_features.device)
+        if t.numel() != n:
+            raise ValueError(f"{t.numel()} tags for {n} rows")
+        return t
 
     def touch(self, rows, now: Optional[float] = None) -> None:
         """Refresh the timestamp of the memories at bank rows ``rows`` (int, any shape; ``-1`` and rows outside the
@@ -880,7 +934,10 @@ class HippocampalFormation(nn.Module):
         if self._ivf is not None:
             self._ivf.rowc_live = False                 # timestamps changed under the cached score constants
 
-    def _write_consolidated(self, memory_ids: Sequence[str], feats: torch.Tensor, tau: float) -> ConsolidationReport:
+    def _write_consolidated(self, memory_ids: Sequence[str], feats: torch.Tensor, tau: float,
+                            tags: Optional[np.ndarray] = None, within_tags: bool = False) -> ConsolidationReport:
+        """``within_tags``: every chunk is searched with its rows' tags (``tags`` int32 [n], checked; None: all 0,
+        "untagged") and its kept rows are written with them."""
         n = len(memory_ids)
         merged = torch.zeros(n, dtype=torch.bool)
         mem_ids: List[Optional[str]] = [None] * n       # the memory every row became
@@ -890,7 +947,10 @@ class HippocampalFormation(nn.Module):
             hi = min(n, lo + step)
             f = feats[lo:hi]
             now = time.time()
-            stored, leader, _ = self.find_repeats(f, tau, now=now)
+            if within_tags:
+                stored, leader, _ = self.find_repeats(f, tau, now=now, tags=0 if tags is None else tags[lo:hi])
+            else:
+                stored, leader, _ = self.find_repeats(f, tau, now=now)
             stored, leader = stored.numpy().astype(np.int64), leader.numpy().astype(np.int64)
             kept = np.nonzero((stored < 0) & (leader < 0))[0]
             for i in np.nonzero(stored >= 0)[0].tolist():               # ids of the targets as they are held NOW
@@ -903,7 +963,10 @@ class HippocampalFormation(nn.Module):
             if kept.size:
                 kept_ids = [memory_ids[lo + i] for i in kept.tolist()]
                 kept_f = f if kept.size == hi - lo else f[torch.from_numpy(kept).to(f.device)].contiguous()
-                self._write_batch(kept_ids, kept_f)
+                if tags is None:
+                    self._write_batch(kept_ids, kept_f)
+                else:
+                    self._write_batch(kept_ids, kept_f, tags[lo:hi][kept])
                 for i, mid in zip(kept.tolist(), kept_ids):
                     mem_ids[lo + i], slot[lo + i] = mid, self.id_to_idx[mid]
             for i in np.nonzero((stored < 0) & (leader >= 0))[0].tolist():
@@ -1077,7 +1140,8 @@ class HippocampalFormation(nn.Module):
             weak |= self.retention_keys(now) < float(min_key)
         return self.forget(rows=torch.nonzero(weak).flatten())
 
-    def consolidate(self, similarity: Optional[float] = None, rebuild: bool = True) -> BankConsolidationReport:
+    def consolidate(self, similarity: Optional[float] = None, rebuild: bool = True,
+                    within_tags: Optional[bool] = None) -> BankConsolidationReport:
         """Merge the near-copies the bank already holds (rows from ``bulk_write``, ``write_at``, a checkpoint, or
         written before ``merge_similarity`` was set).  The rule: the bank becomes what writing its rows, oldest first,
         into an empty bank with ``create_episodic_memories(merge_similarity=similarity)`` in chunks of
@@ -1098,9 +1162,15 @@ class HippocampalFormation(nn.Module):
         remainder is moved down unchanged and the host maps are committed before the error is raised again: the bank
         stays consistent and nothing undecided is lost.
 
-        Scope-blind: tags play no part.  Near-copies merge across tags, and the kept (older) row keeps its own tag; a
-        scope-aware search is a later change."""
+        ``within_tags`` (None: ``self.merge_within_tags``, False unless the bank was built otherwise).  Off, the pass is
+        scope-blind: tags play no part, near-copies merge across tags and the kept (older) row keeps its own tag.  On,
+        every slab is searched with the slab rows' own tags -- taken on the device from ``memory_metadata[lo:hi, 3]``,
+        nothing more is read back -- so a row merges only into a kept row of ITS tag (0, "untagged", is a scope like any
+        other): the bank becomes what writing its rows oldest first, each with its tag, through
+        ``create_episodic_memories(..., tags=..., merge_within_tags=True)`` would have left.  Every kept row keeps its
+        own tag; strength and timestamp take the maximum as above."""
         tau = self.merge_similarity if similarity is None else similarity
+        within = self.merge_within_tags if within_tags is None else bool(within_tags)
         if tau is None:
             raise ValueError("consolidate needs a similarity in (0, 1] (none given and the bank has no merge_similarity)")
         self._check_merge(tau, self.merge_reinforce, self.merge_cap)
@@ -1124,7 +1194,11 @@ class HippocampalFormation(nn.Module):
             while lo < count:
                 hi = min(count, lo + ops.CONSOLIDATE_MAX_BATCH)   # a slab: what one find_repeats call decides
                 self.memory_count = n_kept                  # the held set of this slab: the decided prefix
-                stored, leader, _ = self.find_repeats(self.memory_features[lo:hi], tau, _use_lists=False)
+                if within:
+                    stored, leader, _ = self.find_repeats(self.memory_features[lo:hi], tau, _use_lists=False,
+                                                          tags=self.memory_metadata[lo:hi, 3].to(torch.int32))
+                else:
+                    stored, leader, _ = self.find_repeats(self.memory_features[lo:hi], tau, _use_lists=False)
                 stored, leader = stored.numpy().astype(np.int64), leader.numpy().astype(np.int64)
                 kept = (stored < 0) & (leader < 0)
                 kept_local = np.nonzero(kept)[0]

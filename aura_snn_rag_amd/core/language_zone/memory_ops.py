@@ -58,18 +58,22 @@ def retrieve_memories(hippocampus, query: torch.Tensor, k: int = 5, dtype=None,
 
 
 def store_memory(hippocampus, hidden_states: torch.Tensor, event_tag: str = "layer",
-                 merge_similarity: Optional[float] = None, tag=None):
+                 merge_similarity: Optional[float] = None, tag=None, merge_within_tags: Optional[bool] = None):
     """Mean-pool each batch item and store it (``memory_augmented_layer.py:132-153``).  ``merge_similarity`` (default
     off): a consolidating write -- a pooled row that repeats a held memory at that cosine strengthens it instead of
     taking a slot (``HippocampalFormation.create_episodic_memories(merge_similarity=...)``, whose report is returned);
     a bank constructed with a threshold consolidates without it.  ``tag`` (default off; an int, or one per batch item):
     the stored memories carry it (``HippocampalFormation.create_episodic_memories(tags=...)``) and
-    ``retrieve_memories(tags=...)`` recalls within it; not together with a consolidating write."""
+    ``retrieve_memories(tags=...)`` recalls within it; together with a consolidating write only when the consolidation
+    stays within tags.  ``merge_within_tags`` (default None: what the bank was constructed with): a pooled row then
+    merges only into a memory of its own tag (``create_episodic_memories(merge_within_tags=...)``)."""
     if hippocampus is None:
         return None
     feats = hidden_states.detach().float().mean(dim=1)                      # [B, D]
     ids = [str(uuid.uuid4())[:8] for _ in range(feats.shape[0])]
     kw = {} if tag is None else dict(tags=tag)
+    if merge_within_tags is not None:
+        kw["merge_within_tags"] = merge_within_tags
     if merge_similarity is None:
         return hippocampus.create_episodic_memories(ids, feats, **kw)
     return hippocampus.create_episodic_memories(ids, feats, merge_similarity=merge_similarity, **kw)
@@ -135,6 +139,11 @@ class MemoryInjection(nn.Module):
                                  fetch_k=fetch_k, tags=tags, newer_than=newer_than, older_than=older_than,
                                  min_strength=min_strength)
 
+    def store_memory(self, hidden_states: torch.Tensor, merge_similarity: Optional[float] = None, tag=None,
+                     merge_within_tags: Optional[bool] = None):
+        return store_memory(self.hippocampus, hidden_states, event_tag=f"layer_{id(self)}",
+                            merge_similarity=merge_similarity, tag=tag, merge_within_tags=merge_within_tags)
+
     def inject_memories(self, hidden_states, memory_features, memory_scores):
         if self.memory_injection == "cross_attention":
             return inject_cross_attention(hidden_states, memory_features, self.memory_norm, self.memory_attention,
@@ -143,9 +152,12 @@ class MemoryInjection(nn.Module):
             return inject_concat(hidden_states, memory_features, memory_scores)
         return inject_gate(hidden_states, memory_features, memory_scores, self.memory_proj, self.memory_gate)
 
-    def consolidate_memory(self, similarity: Optional[float] = None):
-        """Merge the near-copies the bank holds (``HippocampalFormation.consolidate``)."""
-        return self.hippocampus.consolidate(similarity=similarity)
+    def consolidate_memory(self, similarity: Optional[float] = None, within_tags: Optional[bool] = None):
+        """Merge the near-copies the bank holds (``HippocampalFormation.consolidate``); ``within_tags`` (None: the
+        bank's default): only among memories of one tag."""
+        if within_tags is None:
+            return self.hippocampus.consolidate(similarity=similarity)
+        return self.hippocampus.consolidate(similarity=similarity, within_tags=within_tags)
 
     def forward(self, hidden_states: torch.Tensor, use_memory: bool = True) -> torch.Tensor:
         if use_memory and self.hippocampus is not None and self.hippocampus.memory_count > 0:
@@ -169,10 +181,14 @@ class BatchedMemoryMixin:
                                  fetch_k=fetch_k, tags=tags, newer_than=newer_than, older_than=older_than,
                                  min_strength=min_strength)
 
-    def store_memory(self, hidden_states: torch.Tensor, merge_similarity: Optional[float] = None, tag=None):
+    def store_memory(self, hidden_states: torch.Tensor, merge_similarity: Optional[float] = None, tag=None,
+                     merge_within_tags: Optional[bool] = None):
         return store_memory(self.hippocampus, hidden_states, event_tag=f"layer_{id(self)}",
-                            merge_similarity=merge_similarity, tag=tag)
+                            merge_similarity=merge_similarity, tag=tag, merge_within_tags=merge_within_tags)
 
-    def consolidate_memory(self, similarity: Optional[float] = None):
-        """Merge the near-copies the bank holds (``HippocampalFormation.consolidate``)."""
-        return self.hippocampus.consolidate(similarity=similarity)
+    def consolidate_memory(self, similarity: Optional[float] = None, within_tags: Optional[bool] = None):
+        """Merge the near-copies the bank holds (``HippocampalFormation.consolidate``); ``within_tags`` (None: the
+        bank's default): only among memories of one tag."""
+        if within_tags is None:
+            return self.hippocampus.consolidate(similarity=similarity)
+        return self.hippocampus.consolidate(similarity=similarity, within_tags=within_tags)

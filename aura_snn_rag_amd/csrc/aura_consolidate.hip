@@ -6,7 +6,11 @@
 // 1 / max(||.||, 1e-12); stored_target[i] = the held row of largest cos(f_i, r) >= tau (equal cosines -> the lowest
 // r), else -1; rows without a stored target are walked in order and repeat the KEPT earlier row of largest cosine
 // >= tau (equal -> the lowest j), else they are kept; rows with a NaN / Inf component or of norm 0 are kept and are
-// nobody's target.
+// nobody's target.  aura_bank_find_repeats_scoped applies the same rule within tags: a held row is eligible for a batch
+// row only when its tag (metadata column 3) equals the batch row's, an in-batch pair only when both rows carry one tag.
+// The predicate is one SCOPED template parameter of the scan, dense and walk kernels: it sits where a pair is decided
+// (before a survivor is appended, before the packed atomicMax, before pend[] is set, before a kept row offers its Gram
+// entry), and the unscoped instantiations compile to what they were without it.
 //
 // Launches of one call (all on the caller's stream, no allocation, no host synchronisation):
 //   prep      1 / ||f_i||, the degenerate flag, the counters' reset and -- with an image -- the batch's normalised
@@ -79,6 +83,7 @@ struct Workspace {
     uint16_t* qhat;     // [n_pad][768] normalised bf16 rows
     int32_t* list;      // [n_pad][CS_CAP]
     float* gram;        // [n_pad][n_pad]
+    int32_t* tag;       // [n_pad] scoped calls: the batch rows' tags, -1 for padding and for a tag outside [0, 2^24)
     int64_t bytes;
 };
 
@@ -97,6 +102,7 @@ inline Workspace carve(void* base, int n_pad) {
     w.qhat = reinterpret_cast<uint16_t*>(take(2LL * n_pad * CS_MAX_IMAGE_D));
     w.list = reinterpret_cast<int32_t*>(take(4LL * n_pad * CS_CAP));
     w.gram = reinterpret_cast<float*>(take(4LL * n_pad * n_pad));
+    w.tag = reinterpret_cast<int32_t*>(take(4LL * n_pad));
     w.bytes = o;
     return w;
 }
@@ -113,6 +119,12 @@ __device__ __forceinline__ u64 cs_shfl_xor(u64 v, int off) {
     return ((u64)hi << 32) | lo;
 }
 
+// The tag of held row `row` as aura_knn_search_scoped reads it; -2 (no batch tag equals it) for anything that is no tag.
+__device__ __forceinline__ int cs_row_tag(const float* __restrict__ meta, int64_t row) {
+    const float t = meta[row * 4 + 3];
+    return (t > -1.0f && t < 16777216.0f) ? (int)t : -2;
+}
+
 // Query part of the prefilter's error bound, the two-stage recall's formula (aura_knn_coarse.inl):
 // rho_q = 1.001 sqrt(e2) + (D/2 + 3) 2^-24, times (1 + 2^-7).
 __device__ __forceinline__ float cs_eq_from_e2(float e2, float D) {
@@ -122,7 +134,8 @@ __device__ __forceinline__ float cs_eq_from_e2(float e2, float D) {
 // ---- prep: one wave per batch row (rows [n, n_pad) are padding)
 __global__ __launch_bounds__(256) void cs_prep_kernel(const float* __restrict__ x, int n, int n_pad, int64_t D,
                                                       int qstride, Workspace w, int with_image,
-                                                      int32_t* __restrict__ overflow) {
+                                                      int32_t* __restrict__ overflow,
+                                                      const int32_t* __restrict__ batch_tags) {
     const int lane = threadIdx.x & 63;
     const int q = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (blockIdx.x == 0 && threadIdx.x == 0) *overflow = 0;
@@ -161,23 +174,29 @@ __global__ __launch_bounds__(256) void cs_prep_kernel(const float* __restrict__ 
         w.cnt[q] = 0;
         w.pend[q] = 0;
         w.best[q] = 0;
+        if (batch_tags) {
+            const int32_t t = q < n ? batch_tags[q] : -1;
+            w.tag[q] = (t >= 0 && t < (1 << 24)) ? t : -1;
+        }
     }
 }
 
 // ---- image scan.  KS = 16-column steps held per image row (a multiple of 8: the swizzle works on 16 chunks).
-template <int KS>
+template <int KS, bool SCOPED>
 __global__ __launch_bounds__(256, 1) void cs_scan_kernel(const uint16_t* __restrict__ image,
                                                          const int32_t* __restrict__ image_rows, int64_t n_image,
                                                          int64_t N, int D, const float* __restrict__ rho,
                                                          const uint16_t* __restrict__ qhat,
                                                          const float* __restrict__ eq, int n_tiles, float tau,
                                                          float fix, int32_t* __restrict__ cnt,
-                                                         int32_t* __restrict__ list) {
+                                                         int32_t* __restrict__ list, const float* __restrict__ meta,
+                                                         const int32_t* __restrict__ btag) {
     constexpr int CPR = 2 * KS;                 // 16-byte chunks per batch row
     constexpr int TILE = 32 * CPR;              // chunks per tile of 32 batch rows
     constexpr int PF = TILE / 256;              // chunks a thread stages per tile
     extern __shared__ u32x4 cs_smem[];          // [2][32][CPR], chunk index XOR (row & 15)
     __shared__ float s_eq[2][32];               // the tile's query parts of the bound, staged with it
+    __shared__ int s_tag[2][32];                // SCOPED: the tile's batch tags (unused and dropped otherwise)
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int r = lane & 31, h = lane >> 5;
     const int64_t row0 = (int64_t)blockIdx.x * 128 + wave * 32;
@@ -211,10 +230,12 @@ __global__ __launch_bounds__(256, 1) void cs_scan_kernel(const uint16_t* __restr
     const u32x4* qsrc = reinterpret_cast<const u32x4*>(qhat);
     u32x4 pre[PF];
     float pre_eq = 0.0f;
+    int pre_tag = -1;
     auto gload = [&](int t) {
 #pragma unroll
         for (int i = 0; i < PF; ++i) pre[i] = qsrc[(int64_t)t * TILE + tid + i * 256];
         if (tid < 32) pre_eq = eq[t * 32 + tid];
+        if (SCOPED && tid < 32) pre_tag = btag[t * 32 + tid];
     };
     auto sstore = [&](int buf) {
 #pragma unroll
@@ -223,6 +244,7 @@ __global__ __launch_bounds__(256, 1) void cs_scan_kernel(const uint16_t* __restr
             cs_smem[buf * TILE + q * CPR + (ch ^ (q & 15))] = pre[i];
         }
         if (tid < 32) s_eq[buf][tid] = pre_eq;
+        if (SCOPED && tid < 32) s_tag[buf][tid] = pre_tag;
     };
     gload(0);
     sstore(0);
@@ -255,13 +277,34 @@ __global__ __launch_bounds__(256, 1) void cs_scan_kernel(const uint16_t* __restr
         const int q = t * 32 + r;
         const float eqv = s_eq[t & 1][r];
         const float aq = 1.0f + eqv, tq = tau - eqv - fix;
+        if constexpr (SCOPED) {
+            // The survivors of the lane as a bit mask, then a loop over the set bits: almost always none.  The tag of
+            // the bank row (of image_rows[ir] with a list-sorted image) is read from meta here, in the rare branch,
+            // after the range check of br and before the append -- no tag is held across the tile loop, and a pair of
+            // another tag never enters a list: other scopes' copies cannot fill the 256 entries.
+            uint32_t m = 0;
 #pragma unroll
-        for (int e = 0; e < 16; ++e) {
-            if (acc[e] + rho_e[e] * aq >= tq) {
+            for (int e = 0; e < 16; ++e) m |= (acc[e] + rho_e[e] * aq >= tq) ? (1u << e) : 0u;
+            const int qtag = s_tag[t & 1][r];
+            while (m) {
+                const int e = __ffs(m) - 1;
+                m &= m - 1;
                 const int64_t ir = row0 + (e & 3) + 8 * (e >> 2) + 4 * h;
-                const int64_t br = image_rows ? (int64_t)image_rows[ir] : ir;      // (valid: rho_e is not NaN)
-                const int pos = atomicAdd(&cnt[q], 1);
-                if (pos < CS_CAP) list[(int64_t)q * CS_CAP + pos] = (int32_t)br;
+                const int64_t br = image_rows ? (int64_t)image_rows[ir] : ir;
+                if (br >= 0 && br < N && cs_row_tag(meta, br) == qtag) {
+                    const int pos = atomicAdd(&cnt[q], 1);
+                    if (pos < CS_CAP) list[(int64_t)q * CS_CAP + pos] = (int32_t)br;
+                }
+            }
+        } else {
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                if (acc[e] + rho_e[e] * aq >= tq) {
+                    const int64_t ir = row0 + (e & 3) + 8 * (e >> 2) + 4 * h;
+                    const int64_t br = image_rows ? (int64_t)image_rows[ir] : ir;      // (valid: rho_e is not NaN)
+                    const int pos = atomicAdd(&cnt[q], 1);
+                    if (pos < CS_CAP) list[(int64_t)q * CS_CAP + pos] = (int32_t)br;
+                }
             }
         }
         if (t + 1 < n_tiles) sstore((t + 1) & 1);
@@ -336,12 +379,14 @@ __device__ __forceinline__ float4 cs_load4(const float* row, int64_t k0, int64_t
     return v;
 }
 
-template <bool VEC, int MODE>
+template <bool VEC, int MODE, bool SCOPED>
 __global__ __launch_bounds__(256) void cs_dense_kernel(const float* __restrict__ A, const float* __restrict__ ainv,
                                                        int64_t NA, const float* __restrict__ B,
                                                        const float* __restrict__ binv, int nB, int64_t D, float tau,
                                                        u64* __restrict__ best, float* __restrict__ G, int ldg,
-                                                       const int32_t* __restrict__ elig, int32_t* __restrict__ pend) {
+                                                       const int32_t* __restrict__ elig, int32_t* __restrict__ pend,
+                                                       const float* __restrict__ meta,
+                                                       const int32_t* __restrict__ btag) {
     __shared__ __attribute__((aligned(16))) float As[32 * CS_STRIDE];
     __shared__ __attribute__((aligned(16))) float Bs[128 * CS_STRIDE];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -400,12 +445,14 @@ __global__ __launch_bounds__(256) void cs_dense_kernel(const float* __restrict__
     }
     // element e of lane (li, lh): A row (e & 3) + 8 (e >> 2) + 4 lh, B row li of the wave
     const int j = b0 + wave * 32 + li;
+    const int tj = SCOPED ? btag[j] : 0;                              // (j < n_pad: the grid covers exactly n_pad)
     if (MODE == 0) {
         u64 key = 0;
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
             const int64_t row = a0 + (e & 3) + 8 * (e >> 2) + 4 * lh;
-            if (row < NA && acc[e] >= tau) key = cs_max(key, cs_pack(acc[e], (int)row));
+            if (row < NA && acc[e] >= tau && (!SCOPED || cs_row_tag(meta, row) == tj))
+                key = cs_max(key, cs_pack(acc[e], (int)row));
         }
         key = cs_max(key, cs_shfl_xor(key, 32));
         if (lh == 0 && key && j < nB) atomicMax(&best[j], key);
@@ -415,12 +462,14 @@ __global__ __launch_bounds__(256) void cs_dense_kernel(const float* __restrict__
         for (int e = 0; e < 16; ++e) {
             const int i = (int)a0 + (e & 3) + 8 * (e >> 2) + 4 * lh;       // (i, j < ldg: the grid covers n_pad)
             G[(int64_t)i * ldg + j] = acc[e];
-            if (ej && j < i && i < nB && acc[e] >= tau && elig[i]) pend[i] = 1;
+            if (ej && j < i && i < nB && acc[e] >= tau && elig[i] && (!SCOPED || (tj >= 0 && btag[i] == tj)))
+                pend[i] = 1;
         }
     }
 }
 
 // ---- the ordered walk, one workgroup of 1024 threads: thread i owns batch row i
+template <bool SCOPED>
 __global__ __launch_bounds__(1024) void cs_walk_kernel(int n, int ldg, float tau, Workspace w,
                                                        int32_t* __restrict__ batch_leader,
                                                        float* __restrict__ cos_out) {
@@ -428,7 +477,9 @@ __global__ __launch_bounds__(1024) void cs_walk_kernel(int n, int ldg, float tau
     __shared__ int s_plist[CS_MAX_BATCH];
     __shared__ int s_wcount[16];
     __shared__ u64 s_key[16];
+    __shared__ int s_tag[CS_MAX_BATCH];            // SCOPED: the batch tags (unused and dropped otherwise)
     const int i = threadIdx.x, wave = i >> 6, lane = i & 63;
+    if (SCOPED) s_tag[i] = i < n ? w.tag[i] : -1;
     const bool el = i < n && w.elig[i];
     const bool pd = el && w.pend[i];
     s_kept[i] = (el && !pd) ? 1 : 0;
@@ -444,7 +495,7 @@ __global__ __launch_bounds__(1024) void cs_walk_kernel(int n, int ldg, float tau
     for (int p = 0; p < total; ++p) {
         const int row = s_plist[p];
         u64 key = 0;
-        if (i < row && s_kept[i]) {
+        if (i < row && s_kept[i] && (!SCOPED || (s_tag[i] >= 0 && s_tag[i] == s_tag[row]))) {
             const float c = w.gram[(int64_t)row * ldg + i];
             if (c >= tau) key = cs_pack(c, i);
         }
@@ -475,31 +526,96 @@ __global__ __launch_bounds__(256) void cs_touch_kernel(float* __restrict__ meta,
     if (r >= 0 && (int64_t)r < count) meta[(int64_t)r * 4 + 1] = now;      // duplicates store the same value
 }
 
-template <int KS>
+template <int KS, bool SCOPED>
 int launch_scan(const uint16_t* image, const int32_t* image_rows, int64_t n_image, int64_t N, int D, const float* rho,
-                const Workspace& w, int n_tiles, float tau, float fix, hipStream_t s) {
+                const Workspace& w, int n_tiles, float tau, float fix, const float* meta, hipStream_t s) {
     constexpr int lds = 2 * 32 * 2 * KS * 16;
     if (lds > 64 * 1024) {
-        const int rc = ensure_lds_attr_c(reinterpret_cast<const void*>(&cs_scan_kernel<KS>), lds);
+        const int rc = ensure_lds_attr_c(reinterpret_cast<const void*>(&cs_scan_kernel<KS, SCOPED>), lds);
         if (rc != AURA_OK) return rc;
     }
     const unsigned blocks = (unsigned)((n_image + 127) / 128);
-    hipLaunchKernelGGL(cs_scan_kernel<KS>, dim3(blocks), dim3(256), lds, s, image, image_rows, n_image, N, D, rho,
-                       w.qhat, w.eq, n_tiles, tau, fix, w.cnt, w.list);
+    hipLaunchKernelGGL((cs_scan_kernel<KS, SCOPED>), dim3(blocks), dim3(256), lds, s, image, image_rows, n_image, N, D,
+                       rho, w.qhat, w.eq, n_tiles, tau, fix, w.cnt, w.list, meta, w.tag);
     return check_launch_c();
 }
 
-template <int MODE>
+template <int MODE, bool SCOPED>
 int launch_dense(bool vec, const float* A, const float* ainv, int64_t NA, const float* B, const float* binv, int nB,
-                 int n_pad, int64_t D, float tau, const Workspace& w, hipStream_t s) {
+                 int n_pad, int64_t D, float tau, const Workspace& w, const float* meta, hipStream_t s) {
     const int64_t rowsA = MODE == 0 ? NA : n_pad;
     const dim3 grid((unsigned)((rowsA + 31) / 32), (unsigned)(n_pad / 128));
     if (vec)
-        hipLaunchKernelGGL((cs_dense_kernel<true, MODE>), grid, dim3(256), 0, s, A, ainv, NA, B, binv, nB, D, tau,
-                           w.best, w.gram, n_pad, w.elig, w.pend);
+        hipLaunchKernelGGL((cs_dense_kernel<true, MODE, SCOPED>), grid, dim3(256), 0, s, A, ainv, NA, B, binv, nB, D, tau,
+                           w.best, w.gram, n_pad, w.elig, w.pend, meta, w.tag);
     else
-        hipLaunchKernelGGL((cs_dense_kernel<false, MODE>), grid, dim3(256), 0, s, A, ainv, NA, B, binv, nB, D, tau,
-                           w.best, w.gram, n_pad, w.elig, w.pend);
+        hipLaunchKernelGGL((cs_dense_kernel<false, MODE, SCOPED>), grid, dim3(256), 0, s, A, ainv, NA, B, binv, nB, D, tau,
+                           w.best, w.gram, n_pad, w.elig, w.pend, meta, w.tag);
+    return check_launch_c();
+}
+
+
+template <bool SCOPED>
+int find_repeats_impl(const float* bank, const float* inv_norm, int64_t N, int64_t D, const uint16_t* image_bf16,
+                      const int32_t* image_rows, int64_t n_image, const float* rho, const float* feats, int64_t n,
+                      float tau, int32_t* stored_target, int32_t* batch_leader, float* cos_out, int32_t* overflow_out,
+                      void* workspace, int64_t workspace_bytes, void* stream, const float* meta,
+                      const int32_t* batch_tags) {
+    const int64_t need = (n < 0 || n > CS_MAX_BATCH) ? -1 : carve(nullptr, pad_batch(n > 0 ? n : 1)).bytes;
+    if (need < 0 || N < 0 || N > 0x7fffffffLL || D < 1 || D > 4096) return AURA_E_INVAL;
+    if (!(tau > 0.0f && tau <= 1.0f)) return AURA_E_INVAL;
+    if (!overflow_out) return AURA_E_INVAL;
+    if (n == 0) return AURA_OK;
+    if (!feats || !stored_target || !batch_leader || !cos_out || !workspace || workspace_bytes < need) return AURA_E_INVAL;
+    if (N > 0 && (!bank || !inv_norm)) return AURA_E_INVAL;
+    if (SCOPED && (!batch_tags || (N > 0 && !meta))) return AURA_E_INVAL;
+    if (SCOPED && ((reinterpret_cast<uintptr_t>(meta) | reinterpret_cast<uintptr_t>(batch_tags)) & 3)) return AURA_E_ALIGN;
+    if (reinterpret_cast<uintptr_t>(workspace) & 255) return AURA_E_ALIGN;
+    const bool with_image = image_bf16 != nullptr && N > 0;
+    if (with_image) {
+        if (D % 8 != 0 || D > CS_MAX_IMAGE_D || n_image < 0 || n_image > 0x7fffffffLL || !rho) return AURA_E_INVAL;
+        if (reinterpret_cast<uintptr_t>(image_bf16) & 15) return AURA_E_ALIGN;
+    }
+    const bool vec = D % 4 == 0 && !(reinterpret_cast<uintptr_t>(bank) & 15) && !(reinterpret_cast<uintptr_t>(feats) & 15);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int nn = (int)n, n_pad = pad_batch(n);
+    const Workspace w = carve(workspace, n_pad);
+    const int ks = with_image ? (int)((D + 127) / 128) * 8 : 0;          // 16-column steps, a multiple of 8
+    hipLaunchKernelGGL(cs_prep_kernel, dim3((unsigned)(n_pad / 4)), dim3(256), 0, s, feats, nn, n_pad, D, ks * 16, w,
+                       with_image ? 1 : 0, overflow_out, SCOPED ? batch_tags : nullptr);
+    int rc = check_launch_c();
+    if (rc != AURA_OK) return rc;
+    if (with_image && n_image > 0) {
+        // the error bound's fixed part, as the header states it for the prefilter
+        const float fix = 2.0f * (float)D * 5.9604645e-8f + 1e-5f;
+        const int n_tiles = (nn + 31) / 32;
+        switch (ks) {
+        case 8: rc = launch_scan<8, SCOPED>(image_bf16, image_rows, n_image, N, (int)D, rho, w, n_tiles, tau, fix, meta, s); break;
+        case 16: rc = launch_scan<16, SCOPED>(image_bf16, image_rows, n_image, N, (int)D, rho, w, n_tiles, tau, fix, meta, s); break;
+        case 24: rc = launch_scan<24, SCOPED>(image_bf16, image_rows, n_image, N, (int)D, rho, w, n_tiles, tau, fix, meta, s); break;
+        case 32: rc = launch_scan<32, SCOPED>(image_bf16, image_rows, n_image, N, (int)D, rho, w, n_tiles, tau, fix, meta, s); break;
+        case 40: rc = launch_scan<40, SCOPED>(image_bf16, image_rows, n_image, N, (int)D, rho, w, n_tiles, tau, fix, meta, s); break;
+        default: rc = launch_scan<48, SCOPED>(image_bf16, image_rows, n_image, N, (int)D, rho, w, n_tiles, tau, fix, meta, s); break;
+        }
+        if (rc != AURA_OK) return rc;
+    }
+    if (with_image) {
+        hipLaunchKernelGGL(cs_rescore_kernel, dim3((unsigned)nn), dim3(256), 0, s, bank, inv_norm, N, D, feats, tau, w,
+                           stored_target, cos_out, overflow_out);
+    } else {
+        if (N > 0) {
+            rc = launch_dense<0, SCOPED>(vec, bank, inv_norm, N, feats, w.qinv, nn, n_pad, D, tau, w, meta, s);
+            if (rc != AURA_OK) return rc;
+        }
+        hipLaunchKernelGGL(cs_finalise_kernel, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, s, nn, w, stored_target,
+                           cos_out);
+    }
+    rc = check_launch_c();
+    if (rc != AURA_OK) return rc;
+    const bool vecq = D % 4 == 0 && !(reinterpret_cast<uintptr_t>(feats) & 15);
+    rc = launch_dense<1, SCOPED>(vecq, feats, w.qinv, nn, feats, w.qinv, nn, n_pad, D, tau, w, meta, s);
+    if (rc != AURA_OK) return rc;
+    hipLaunchKernelGGL(cs_walk_kernel<SCOPED>, dim3(1), dim3(1024), 0, s, nn, n_pad, tau, w, batch_leader, cos_out);
     return check_launch_c();
 }
 
@@ -516,60 +632,19 @@ int aura_bank_find_repeats(const float* bank, const float* inv_norm, int64_t N, 
                            const int32_t* image_rows, int64_t n_image, const float* rho, const float* feats, int64_t n,
                            float tau, int32_t* stored_target, int32_t* batch_leader, float* cos_out,
                            int32_t* overflow_out, void* workspace, int64_t workspace_bytes, void* stream) {
-    const int64_t need = aura_bank_find_repeats_workspace_bytes(n);
-    if (need < 0 || N < 0 || N > 0x7fffffffLL || D < 1 || D > 4096) return AURA_E_INVAL;
-    if (!(tau > 0.0f && tau <= 1.0f)) return AURA_E_INVAL;
-    if (!overflow_out) return AURA_E_INVAL;
-    if (n == 0) return AURA_OK;
-    if (!feats || !stored_target || !batch_leader || !cos_out || !workspace || workspace_bytes < need) return AURA_E_INVAL;
-    if (N > 0 && (!bank || !inv_norm)) return AURA_E_INVAL;
-    if (reinterpret_cast<uintptr_t>(workspace) & 255) return AURA_E_ALIGN;
-    const bool with_image = image_bf16 != nullptr && N > 0;
-    if (with_image) {
-        if (D % 8 != 0 || D > CS_MAX_IMAGE_D || n_image < 0 || n_image > 0x7fffffffLL || !rho) return AURA_E_INVAL;
-        if (reinterpret_cast<uintptr_t>(image_bf16) & 15) return AURA_E_ALIGN;
-    }
-    const bool vec = D % 4 == 0 && !(reinterpret_cast<uintptr_t>(bank) & 15) && !(reinterpret_cast<uintptr_t>(feats) & 15);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int nn = (int)n, n_pad = pad_batch(n);
-    const Workspace w = carve(workspace, n_pad);
-    const int ks = with_image ? (int)((D + 127) / 128) * 8 : 0;          // 16-column steps, a multiple of 8
-    hipLaunchKernelGGL(cs_prep_kernel, dim3((unsigned)(n_pad / 4)), dim3(256), 0, s, feats, nn, n_pad, D, ks * 16, w,
-                       with_image ? 1 : 0, overflow_out);
-    int rc = check_launch_c();
-    if (rc != AURA_OK) return rc;
-    if (with_image && n_image > 0) {
-        // the error bound's fixed part, as the header states it for the prefilter
-        const float fix = 2.0f * (float)D * 5.9604645e-8f + 1e-5f;
-        const int n_tiles = (nn + 31) / 32;
-        switch (ks) {
-        case 8: rc = launch_scan<8>(image_bf16, image_rows, n_image, N, (int)D, rho, w, n_tiles, tau, fix, s); break;
-        case 16: rc = launch_scan<16>(image_bf16, image_rows, n_image, N, (int)D, rho, w, n_tiles, tau, fix, s); break;
-        case 24: rc = launch_scan<24>(image_bf16, image_rows, n_image, N, (int)D, rho, w, n_tiles, tau, fix, s); break;
-        case 32: rc = launch_scan<32>(image_bf16, image_rows, n_image, N, (int)D, rho, w, n_tiles, tau, fix, s); break;
-        case 40: rc = launch_scan<40>(image_bf16, image_rows, n_image, N, (int)D, rho, w, n_tiles, tau, fix, s); break;
-        default: rc = launch_scan<48>(image_bf16, image_rows, n_image, N, (int)D, rho, w, n_tiles, tau, fix, s); break;
-        }
-        if (rc != AURA_OK) return rc;
-    }
-    if (with_image) {
-        hipLaunchKernelGGL(cs_rescore_kernel, dim3((unsigned)nn), dim3(256), 0, s, bank, inv_norm, N, D, feats, tau, w,
-                           stored_target, cos_out, overflow_out);
-    } else {
-        if (N > 0) {
-            rc = launch_dense<0>(vec, bank, inv_norm, N, feats, w.qinv, nn, n_pad, D, tau, w, s);
-            if (rc != AURA_OK) return rc;
-        }
-        hipLaunchKernelGGL(cs_finalise_kernel, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, s, nn, w, stored_target,
-                           cos_out);
-    }
-    rc = check_launch_c();
-    if (rc != AURA_OK) return rc;
-    const bool vecq = D % 4 == 0 && !(reinterpret_cast<uintptr_t>(feats) & 15);
-    rc = launch_dense<1>(vecq, feats, w.qinv, nn, feats, w.qinv, nn, n_pad, D, tau, w, s);
-    if (rc != AURA_OK) return rc;
-    hipLaunchKernelGGL(cs_walk_kernel, dim3(1), dim3(1024), 0, s, nn, n_pad, tau, w, batch_leader, cos_out);
-    return check_launch_c();
+    return find_repeats_impl<false>(bank, inv_norm, N, D, image_bf16, image_rows, n_image, rho, feats, n, tau,
+                                    stored_target, batch_leader, cos_out, overflow_out, workspace, workspace_bytes, stream,
+                                    nullptr, nullptr);
+}
+
+int aura_bank_find_repeats_scoped(const float* bank, const float* inv_norm, int64_t N, int64_t D,
+                                  const uint16_t* image_bf16, const int32_t* image_rows, int64_t n_image,
+                                  const float* rho, const float* feats, int64_t n, float tau, int32_t* stored_target,
+                                  int32_t* batch_leader, float* cos_out, int32_t* overflow_out, void* workspace,
+                                  int64_t workspace_bytes, void* stream, const float* meta, const int32_t* batch_tags) {
+    return find_repeats_impl<true>(bank, inv_norm, N, D, image_bf16, image_rows, n_image, rho, feats, n, tau,
+                                   stored_target, batch_leader, cos_out, overflow_out, workspace, workspace_bytes, stream,
+                                   meta, batch_tags);
 }
 
 int aura_bank_touch(float* meta, int64_t count, const int32_t* rows, int64_t n, float now, void* stream) {

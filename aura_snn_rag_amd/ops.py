@@ -468,6 +468,23 @@ def find_repeats(bank, inv_norm, count: int, feats, tau: float, image=None, imag
     results and both flags.  ``image``: a current bf16 image of the normalised rows -- the row-ordered shadow
     (``image_rows`` None) or the list-sorted shadow with ``image_rows = sorted_rows`` and ``n_image = n_sorted`` --
     with ``rho`` as ``bank_shadow_update`` leaves it; None: the dense fp32 scan.  No host sync."""
+    return _find_repeats(bank, inv_norm, count, feats, tau, image, image_rows, n_image, rho, lists_flag, None, None)
+
+
+def find_repeats_scoped(bank, inv_norm, meta, count: int, feats, tags, tau: float, image=None, image_rows=None,
+                        n_image: Optional[int] = None, rho=None, lists_flag=None):
+    """``find_repeats`` within tags (``aura_bank_find_repeats_scoped``; the rule: ``include/aura_hip.h``): a held row is
+    eligible for batch row i only when ``int(meta[r, 3]) == tags[i]``, an in-batch pair only when both rows carry the
+    same tag; tag 0 is a scope like any other, a tag outside ``[0, 2^24)`` matches nothing (that row is kept).  ``meta``:
+    the bank's metadata (fp32 [rows, 4]); ``tags``: int32 [n] on the bank's device.  Same validation, same four results
+    and ``packed`` layout, same image arguments and flags as ``find_repeats``; the cost is that call's plus one 4-byte
+    load per surviving pair.  No host sync."""
+    if meta is None or tags is None:
+        raise ValueError("find_repeats_scoped: meta and tags are required")
+    return _find_repeats(bank, inv_norm, count, feats, tau, image, image_rows, n_image, rho, lists_flag, meta, tags)
+
+
+def _find_repeats(bank, inv_norm, count, feats, tau, image, image_rows, n_image, rho, lists_flag, meta, tags):
     _need(bank, "bank", torch.float32); _need(inv_norm, "inv_norm", torch.float32); _need(feats, "feats", torch.float32)
     if bank.dim() != 2 or not (0 <= count <= bank.shape[0]) or inv_norm.numel() != bank.shape[0]:
         raise ValueError("find_repeats: bank must be [rows, D] with count <= rows and one inv_norm per row")
@@ -503,6 +520,13 @@ def find_repeats(bank, inv_norm, count: int, feats, tau: float, image=None, imag
             raise ValueError("find_repeats: tensors are on different devices")
     elif image_rows is not None:
         raise ValueError("find_repeats: image_rows without an image")
+    if meta is not None:
+        _check_meta(meta, count, "find_repeats_scoped")
+        _need(tags, "tags", torch.int32)
+        if meta.shape[0] != M or tags.dim() != 1 or tags.numel() != n:
+            raise ValueError(f"find_repeats_scoped: meta must be [{M}, 4] and tags int32 [{n}]")
+        if meta.device != bank.device or tags.device != bank.device:
+            raise ValueError("find_repeats_scoped: tensors are on different devices")
     packed = torch.zeros(3 * n + 2, dtype=torch.int32, device=bank.device)
     stored, leader, cos = packed[:n], packed[n:2 * n], packed[2 * n:3 * n].view(torch.float32)
     if lists_flag is not None:
@@ -515,9 +539,12 @@ def find_repeats(bank, inv_norm, count: int, feats, tau: float, image=None, imag
     if nbytes < 0:
         raise ValueError("find_repeats: unsupported size")
     base = _workspace(bank.device, nbytes)
-    check(L.aura_bank_find_repeats(_p(bank), _p(inv_norm), count, D, _p(image), _p(image_rows), ni, _p(rho),
-                                   _p(feats), n, tau, _p(stored), _p(leader), _p(cos), _p(packed[3 * n:]),
-                                   base, nbytes, _stream()), "aura_bank_find_repeats")
+    args = (_p(bank), _p(inv_norm), count, D, _p(image), _p(image_rows), ni, _p(rho), _p(feats), n, tau, _p(stored),
+            _p(leader), _p(cos), _p(packed[3 * n:]), base, nbytes, _stream())
+    if meta is None:
+        check(L.aura_bank_find_repeats(*args), "aura_bank_find_repeats")
+    else:
+        check(L.aura_bank_find_repeats_scoped(*args, _p(meta), _p(tags)), "aura_bank_find_repeats_scoped")
     return stored, leader, cos, packed
 
 

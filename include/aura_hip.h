@@ -205,6 +205,31 @@ int aura_bank_find_repeats(const float* bank, const float* inv_norm, int64_t N, 
                            int32_t* overflow_out, void* workspace, int64_t workspace_bytes, void* stream);
 int aura_bank_touch(float* meta, int64_t count, const int32_t* rows, int64_t n, float now, void* stream);
 
+/* Consolidation within tags (csrc/aura_consolidate.hip): aura_bank_find_repeats with two more inputs and nothing else
+ * of its rule changed.
+ *   meta [rows of the bank][4]: the bank's metadata; column 3 holds the tag as a float, read as
+ *     aura_knn_search_scoped reads it (a value outside (-1, 2^24) is no tag and matches nothing).
+ *   batch_tags int32 [n], on the device: one tag per batch row.
+ * Eligibility.  A held row r < N is eligible for batch row i iff (int)meta[r][3] == batch_tags[i]; an in-batch pair
+ *   (i, j) is eligible iff batch_tags[i] == batch_tags[j].  Tag 0, "untagged", is a scope like any other.  A batch tag
+ *   outside [0, 2^24) matches nothing -- no held row and no other batch row, not even one with the same value -- so
+ *   that row is kept and is nobody's leader.
+ * Results.  stored_target[i] = the ELIGIBLE held row of largest cosine >= tau, bit-identical rows tie to the lowest
+ *   eligible r; the ordered walk considers only KEPT earlier rows of the same tag.  The cosine, the degenerate rows,
+ *   cos_out and tol = 2 (D + 8) 2^-24 are unchanged.  Equivalently: the rule above applied to cosine matrices in which
+ *   every ineligible pair is -inf.
+ * All three scans take the predicate where a pair is decided, never afterwards: the image scan before a survivor is
+ *   appended to a list (rows of other tags cannot fill the 256 entries; with a list-sorted image the tag is that of bank
+ *   row image_rows[ir], read from meta, so the image needs no upkeep when a tag changes), the dense scan before the
+ *   packed atomicMax, the Gram before a row is marked pending, the walk before a kept row offers its cosine.  The
+ *   overflow flag, the workspace (the same *_workspace_bytes) and every other argument are those of
+ *   aura_bank_find_repeats.  AURA_E_INVAL also for batch_tags == NULL, or meta == NULL with N > 0. */
+int aura_bank_find_repeats_scoped(const float* bank, const float* inv_norm, int64_t N, int64_t D,
+                                  const uint16_t* image_bf16, const int32_t* image_rows, int64_t n_image,
+                                  const float* rho, const float* feats, int64_t n, float tau, int32_t* stored_target,
+                                  int32_t* batch_leader, float* cos_out, int32_t* overflow_out, void* workspace,
+                                  int64_t workspace_bytes, void* stream, const float* meta, const int32_t* batch_tags);
+
 /* In-place compaction of the bank (csrc/aura_compact.hip): the primitive under forgetting, pruning and the
  * consolidation of held rows.  [build-side] no upstream counterpart (the reference's pruning ends in `pass`).
  * For every i < n, row src[i] of every array moves to row dst0 + i.  The arrays: bank [rows][D], loc [rows][S],

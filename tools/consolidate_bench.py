@@ -20,6 +20,17 @@ warm-up, the things compared taken in alternating order inside each round (tools
   write rate, batches of 256 rows appended to the same bank (no centroid rebuild inside the windows), rows / s:
     plain_0 / merge_0      a stream without repeats, without / with merge_similarity = 0.9
     plain_50 / merge_50    a stream whose rows are half noisy copies of held rows
+    merge_tagged_0 / merge_tagged_50   the same streams as tagged merging writes (tags=..., merge_within_tags=True): a
+                           copy carries the tag of the row it copies, a fresh row one of the 64 tags
+
+  consolidation within tags ("within tags"): the bank's rows carry tags spread evenly over 64 values
+  (row r: r % 64); a batch row that repeats a held row carries that row's tag, so both searches find the same repeats.
+  Per batch size, alternated in one process on the same bank and batch, the unscoped call taken TWICE (a, b) so that the
+  spread of the unscoped measurement itself is known before the two are compared:
+    unscoped_a / scoped / unscoped_b                  ops.find_repeats / ops.find_repeats_scoped, launches  (device events)
+    call_unscoped_a / call_scoped / call_unscoped_b   HippocampalFormation.find_repeats(tags=None / tags)   (host clock)
+  The bar: the scoped search costs what the unscoped one costs -- its median may not exceed the largest window of the
+  unscoped call in the same run (the margin is the unscoped call's own spread, nothing else).
 
 ``--only trace``: find_repeats alone, both batch sizes, for ``rocprofv3 --kernel-trace --stats -- python
 tools/consolidate_bench.py --only trace`` in a run of its own."""
@@ -45,6 +56,7 @@ BATCHES = (256, 1024)
 WRITE_BATCH = 256
 HEADROOM = 1 << 16
 BAR = 1.10
+N_TAGS = 64
 
 
 def alternated(fns, window):
@@ -62,13 +74,26 @@ def alternated(fns, window):
     return out, iters
 
 
-def make_batch(hf, n, repeats, g):
-    """n rows: the first ``repeats`` are held rows + 0.05 randn (cosine about 0.9988), the rest fresh."""
+def make_batch(hf, n, repeats, g, sources=False):
+    """n rows: the first ``repeats`` are held rows + 0.05 randn (cosine about 0.9988), the rest fresh.  ``sources``:
+    also the held row every row copies, -1 for a fresh one."""
     D = hf.memory_features.shape[1]
     pick = torch.randint(0, hf.memory_count, (repeats,), generator=g, device=hf.device)
     rows = torch.cat([hf.memory_features[pick] + 0.05 * torch.randn(repeats, D, generator=g, device=hf.device),
                       torch.randn(n - repeats, D, generator=g, device=hf.device)])
-    return rows[torch.randperm(n, generator=g, device=hf.device)].contiguous()
+    perm = torch.randperm(n, generator=g, device=hf.device)
+    rows = rows[perm].contiguous()
+    if not sources:
+        return rows
+    src = torch.cat([pick, torch.full((n - repeats,), -1, dtype=pick.dtype, device=hf.device)])[perm]
+    return rows, src
+
+
+def tags_for(hf, src, g):
+    """int32 tags of a batch: a copy carries the tag of the row it copies, a fresh row one of the N_TAGS tags."""
+    held = hf.memory_metadata[src.clamp(min=0), 3].to(torch.int32)
+    fresh = torch.randint(0, N_TAGS, src.shape, generator=g, device=hf.device, dtype=torch.int32)
+    return torch.where(src >= 0, held, fresh).contiguous()
 
 
 def main():
@@ -90,8 +115,13 @@ def main():
     bench.fill_bank(hf, a.rows, D, 1234, dev)
     hf.rebuild_centroids(perm=torch.randperm(a.rows, generator=torch.Generator().manual_seed(7)))
     now = float(hf.memory_metadata[0, 1].item())
+    # tags spread evenly over N_TAGS values (the unscoped calls do not read them)
+    hf.retag(rows=torch.arange(a.rows), tag=torch.arange(a.rows) % N_TAGS)
     g = torch.Generator(device=dev).manual_seed(99)
-    batches = {n: make_batch(hf, n, n // 2, g) for n in BATCHES}
+    batches, batch_tags = {}, {}
+    for n in BATCHES:
+        batches[n], src = make_batch(hf, n, n // 2, g, sources=True)
+        batch_tags[n] = tags_for(hf, src, g)
     if a.only == "trace":
         for n in BATCHES:
             for _ in range(30):
@@ -100,7 +130,8 @@ def main():
         return
     out = {"device": torch.cuda.get_device_name(0), "rows": a.rows, "dim": D, "index": True, "tau": TAU,
            "windows": WINDOWS, "window_s_at_least": WINDOW_S, "copy_bytes_per_s_assumed": COPY_BYTES_PER_S,
-           "peak_bf16_matrix_flops_assumed": PEAK_BF16_MATRIX_FLOPS, "bar": BAR, "find_repeats": [], "write_rate": {}}
+           "peak_bf16_matrix_flops_assumed": PEAK_BF16_MATRIX_FLOPS, "bar": BAR, "find_repeats": [], "write_rate": {},
+           "n_tags": N_TAGS, "find_repeats_within_tags": []}
     ok = True
     for n in BATCHES:
         f = batches[n]
@@ -135,26 +166,59 @@ def main():
         print(res, flush=True)
         out["find_repeats"].append(res)
         ok = ok and same
+        # ---- the same batch within tags, next to the unscoped call (taken twice: its own spread is the margin)
+        bt = batch_tags[n]
+        st_s, bl_s, _ = hf.find_repeats(f, TAU, tags=bt)
+        same_s = bool(torch.equal(st_s, st)) and bool(torch.equal(bl_s, bl))      # (every repeat carries its target's tag)
+
+        def kernels_scoped():
+            return ops.find_repeats_scoped(hf.memory_features, hf._inv_norm, hf.memory_metadata, hf.memory_count, f, bt,
+                                           TAU, image=ivf.sorted_bf16, image_rows=ivf.sorted_rows, n_image=ivf.n_sorted,
+                                           rho=hf._rho, lists_flag=ivf.flag)
+        ev, ev_iters = alternated({"unscoped_a": kernels, "scoped": kernels_scoped, "unscoped_b": kernels}, events_window)
+        wl, wl_iters = alternated({"call_unscoped_a": lambda: hf.find_repeats(f, TAU),
+                                   "call_scoped": lambda: hf.find_repeats(f, TAU, tags=bt),
+                                   "call_unscoped_b": lambda: hf.find_repeats(f, TAU)}, wall_window)
+        res = {"n": n, "scoped_equals_unscoped_on_this_batch": same_s,
+               **{k: summary(v) for k, v in {**ev, **wl}.items()}, "calls_per_window": {**ev_iters, **wl_iters}}
+        for key, (a_, s_, b_) in {"kernels": ("unscoped_a", "scoped", "unscoped_b"),
+                                  "call": ("call_unscoped_a", "call_scoped", "call_unscoped_b")}.items():
+            both = {**ev, **wl}
+            un = both[a_] + both[b_]
+            med_un, med_sc = statistics.median(un), statistics.median(both[s_])
+            res[key] = {"unscoped_median_ms": med_un, "unscoped_min_ms": min(un), "unscoped_max_ms": max(un),
+                        "unscoped_a_over_b": statistics.median(both[a_]) / statistics.median(both[b_]),
+                        "unscoped_spread": (max(un) - min(un)) / med_un, "scoped_median_ms": med_sc,
+                        "scoped_over_unscoped": med_sc / med_un, "bar_met": med_sc <= max(un)}
+        print(res, flush=True)
+        out["find_repeats_within_tags"].append(res)
+        ok = ok and same_s
     # ---- write rate
     serial = [0]
 
     per_writer = 3 + 5 * WINDOWS                   # warm-up calls + timed calls of one writer
 
-    def writer(repeats, tau):
+    def writer(repeats, tau, tagged=False):
         # batches and ids are made BEFORE the windows: only the write is timed.  (Copies are taken of rows held now;
         # the rows the streams append in between are fresh ones.)
         todo = []
         for _ in range(per_writer):
-            todo.append(([f"w{serial[0]}-{i}" for i in range(WRITE_BATCH)], make_batch(hf, WRITE_BATCH, repeats, g)))
+            f, src = make_batch(hf, WRITE_BATCH, repeats, g, sources=True)
+            tags = tags_for(hf, src, g).cpu().numpy() if tagged else None
+            todo.append(([f"w{serial[0]}-{i}" for i in range(WRITE_BATCH)], f, tags))
             serial[0] += 1
 
         def fn():
-            ids, f = todo.pop()
-            hf.create_episodic_memories(ids, f, merge_similarity=tau)
+            ids, f, tags = todo.pop()
+            if tagged:
+                hf.create_episodic_memories(ids, f, merge_similarity=tau, tags=tags, merge_within_tags=True)
+            else:
+                hf.create_episodic_memories(ids, f, merge_similarity=tau)
         return fn
     wr, wr_iters = {}, {}
     for share, rep in (("0", 0), ("50", WRITE_BATCH // 2)):
-        fns = {f"plain_{share}": writer(rep, None), f"merge_{share}": writer(rep, TAU)}
+        fns = {f"plain_{share}": writer(rep, None), f"merge_{share}": writer(rep, TAU),
+               f"merge_tagged_{share}": writer(rep, TAU, tagged=True)}
         for name, fn in fns.items():
             for _ in range(3):
                 fn()
@@ -174,6 +238,8 @@ def main():
     for share in ("0", "50"):
         out["write_rate"][f"merge_over_plain_{share}"] = (out["write_rate"][f"merge_{share}"]["median_ms"] /
                                                           out["write_rate"][f"plain_{share}"]["median_ms"])
+        out["write_rate"][f"merge_tagged_over_merge_{share}"] = (out["write_rate"][f"merge_tagged_{share}"]["median_ms"] /
+                                                                 out["write_rate"][f"merge_{share}"]["median_ms"])
     print(out["write_rate"], flush=True)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as fh:
@@ -181,6 +247,11 @@ def main():
     print("wrote", a.out)
     if not ok:
         raise SystemExit("the image scan and the dense scan disagree")
+    for r in out["find_repeats_within_tags"]:
+        for key in ("kernels", "call"):
+            if not r[key]["bar_met"]:
+                print(f"within tags, n = {r['n']}, {key}: the scoped median {r[key]['scoped_median_ms']:.4f} ms lies above "
+                      f"every unscoped window (max {r[key]['unscoped_max_ms']:.4f} ms): the bar is MISSED")
     missed = [r["n"] for r in out["find_repeats"] if not r["bar_met"]]
     if missed:
         raise SystemExit(f"find_repeats takes more than {BAR} x recall_batch(k=1, use_candidates=False) at n = {missed}")
