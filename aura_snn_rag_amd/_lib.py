@@ -45,6 +45,11 @@ SIGNATURES = {
     "aura_bank_retention_keys": (I, [P, I64, F, P, P]),
     "aura_bank_select_weakest_workspace_bytes": (I64, [I64, I64]),
     "aura_bank_select_weakest": (I, [P, I64, F, I64, I64, P, P, P, I64, P]),
+    "aura_bank_select_weakest_masked_workspace_bytes": (I64, [I64, I64]),
+    "aura_bank_select_weakest_masked": (I, [P, I64, F, I64, I64, P, P, P, P, I64, P]),
+    "aura_bank_tag_counts": (I, [P, I64, P, I64, P, P]),
+    "aura_bank_select_weakest_scoped_workspace_bytes": (I64, [I64, I64]),
+    "aura_bank_select_weakest_scoped": (I, [P, I64, F, P, P, P, P, I64, I64, P, P, P, P, P, P, I64, P]),
     "aura_bank_reinforce_workspace_bytes": (I64, [I64]),
     "aura_bank_reinforce": (I, [P, I64, P, I64, F, F, P, I64, P]),
     "aura_diverse_select_workspace_bytes": (I64, [I64, I64, I64]),

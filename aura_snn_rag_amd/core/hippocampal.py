@@ -39,6 +39,7 @@ from __future__ import annotations
 import time
 from dataclasses import dataclass, field
 from collections.abc import Mapping
+from types import MappingProxyType
 from typing import Any, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -172,7 +173,8 @@ class HippocampalFormation(nn.Module):
                  merge_similarity: Optional[float] = None,
                  merge_reinforce: float = 0.1,
                  merge_cap: float = 1.0,
-                 merge_within_tags: bool = False):
+                 merge_within_tags: bool = False,
+                 tag_quota=None):
         super().__init__()
         # consolidating writes (create_episodic_memories): None = every row is stored, today's behaviour
         self._check_merge(merge_similarity, merge_reinforce, merge_cap)
@@ -246,6 +248,17 @@ class HippocampalFormation(nn.Module):
             raise ValueError(f"overflow must be 'reference', 'fifo' or 'weakest', got {overflow!r}")
         self._overflow = overflow
         self._write_cursor = 0
+        # per-tag quotas (the rule: include/aura_hip.h, "Per-tag quotas"): None = off, today's behaviour
+        self._tag_quota_default: Optional[int] = None   # every tag except 0
+        self._tag_quota_map: Dict[int, int] = {}        # named tags (0 may be named)
+        self._tag_origin: Dict[int, int] = {}           # tie origin c_t per limited tag (missing: 0)
+        self._pending_origins: Optional[Dict[int, int]] = None    # left by _plan_slots for the write that follows
+        if tag_quota is not None:
+            if isinstance(tag_quota, Mapping):
+                for t, q in tag_quota.items():
+                    self.set_tag_quota(t, q)
+            else:
+                self.set_tag_quota(None, tag_quota)
         self.register_load_state_dict_post_hook(lambda module, incompatible: module._invalidate_norms())
 
     # ------------------------------------------------------------------ plumbing
@@ -452,7 +465,7 @@ class HippocampalFormation(nn.Module):
         return {"time_cells": time_rates.flatten(), "elapsed": elapsed}
 
     # ------------------------------------------------------------------ write
-    def _plan_slots(self, n: int, now: Optional[float] = None):
+    def _plan_slots(self, n: int, now: Optional[float] = None, tags: Optional[np.ndarray] = None):
         """Slots (int64 ndarray) for the next n writes, how many of them append, and the counters they
         leave behind (nothing is mutated until the kernel launch has been accepted).
 
@@ -463,7 +476,14 @@ class HippocampalFormation(nn.Module):
         after every row, and may evict a row it has just written).  In a bank of equal keys the victims are
         exactly the slots ``'fifo'`` takes, in the same order.  The id maps live on the host, so the selected
         slots are copied there: one device-to-host read per OVERFLOWING run; appends and the other two
-        policies read nothing back."""
+        policies read nothing back.
+
+        ``tags`` (the run's tags, int [n]) matter only to a bank with ``tag_quota``: a run that carries a limited tag
+        is planned by ``_plan_slots_quota``; any other run reads and launches exactly what it did."""
+        if tags is not None and (self._tag_quota_map or self._tag_quota_default is not None):
+            scopes = self._limited_in(tags)
+            if scopes:
+                return self._plan_slots_quota(n, time.time() if now is None else now, scopes)
         M, count, cursor = self.max_memories, self.memory_count, self._write_cursor
         n_app = min(n, max(M - count, 0))
         slots = np.empty(n, dtype=np.int64)
@@ -483,6 +503,152 @@ class HippocampalFormation(nn.Module):
                 slots[n_app:] = (cursor + np.arange(rest, dtype=np.int64)) % M
                 cursor += rest
         return slots, n_app, count + n_app, cursor
+
+    # ------------------------------------------------------------------ per-tag quotas
+    @staticmethod
+    def _check_quota_tag(tag) -> int:
+        if isinstance(tag, bool) or not isinstance(tag, (int, np.integer)) or not (0 <= int(tag) < TAG_LIMIT):
+            raise ValueError(f"tag_quota: a tag must be an integer in [0, 2^24 = {TAG_LIMIT}), got {tag!r}")
+        return int(tag)
+
+    def set_tag_quota(self, tag, quota) -> None:
+        """Limit tag ``tag`` to ``quota`` rows (an int >= 1; None removes the limit).  ``tag=None`` sets the quota of
+        EVERY tag except 0 that is not named on its own.  Needs ``overflow='weakest'`` (``ValueError`` otherwise): a
+        write into a tag at its quota replaces that tag's own weakest memories (the rule: ``include/aura_hip.h``,
+        "Per-tag quotas").  Nothing is enforced here: a tag that already holds more keeps its rows -- it neither grows
+        nor shrinks on writes -- until ``enforce_tag_quotas()``."""
+        if tag is not None:
+            tag = self._check_quota_tag(tag)
+        if quota is None:
+            if tag is None:
+                self._tag_quota_default = None
+            else:
+                self._tag_quota_map.pop(tag, None)
+            return
+        if isinstance(quota, bool) or not isinstance(quota, (int, np.integer)) or int(quota) < 1:
+            raise ValueError(f"tag_quota: a quota must be an integer >= 1, got {quota!r}")
+        if self._overflow != 'weakest':
+            raise ValueError(f"tag_quota needs overflow='weakest' (a tag at its quota evicts its own weakest rows), "
+                             f"this bank has overflow={self._overflow!r}")
+        if tag is None:
+            self._tag_quota_default = int(quota)
+        else:
+            self._tag_quota_map[tag] = int(quota)
+
+    @property
+    def tag_quotas(self) -> Mapping:
+        """Read-only ``{tag: quota}``; the key ``None`` holds the quota of every tag except 0 not named on its own."""
+        view = dict(self._tag_quota_map)
+        if self._tag_quota_default is not None:
+            view[None] = self._tag_quota_default
+        return MappingProxyType(view)
+
+    def _quota_of(self, tag: int) -> Optional[int]:
+        q = self._tag_quota_map.get(tag)
+        if q is None and tag != 0:
+            q = self._tag_quota_default
+        return q
+
+    def _limited_in(self, tags: np.ndarray) -> List[Tuple[int, int, int]]:
+        """``(tag, rows of it, quota)`` for every limited tag among ``tags``, ascending by tag."""
+        uniq, n_in = np.unique(np.asarray(tags), return_counts=True)
+        out = []
+        for t, m in zip(uniq.tolist(), n_in.tolist()):
+            q = self._quota_of(int(t))
+            if q is not None:
+                out.append((int(t), int(m), q))
+        return out
+
+    def _quota_run(self, tags: np.ndarray) -> int:
+        """The longest prefix of ``tags`` that holds at most q(t) rows of each limited tag t."""
+        run = int(tags.size)
+        for t, m, q in self._limited_in(tags):
+            if m > q:
+                run = min(run, int(np.nonzero(tags == t)[0][q]))
+        return run
+
+    def _plan_slots_quota(self, n: int, now: float, scopes: List[Tuple[int, int, int]]):
+        """``_plan_slots`` for a run that carries limited tags (``scopes``: ``_limited_in`` of its tags): steps 1 - 4 of
+        the rule.  One launch sequence and one host read bring held_t, x_t and the tag victims of every scope
+        (``ops.bank_select_weakest_scoped``); a second read only when global victims are needed, which are selected
+        with the tag victims masked out.  The new tie origins wait in ``_pending_origins`` for the write."""
+        M, count, cursor = self.max_memories, self.memory_count, self._write_cursor
+        scope_tags = [t for t, _, _ in scopes]
+        n_in = [m for _, m, _ in scopes]
+        for t, m, q in scopes:
+            if m > q:                                      # (_write_batch cuts such runs)
+                raise ValueError(f"a run holds at most quota = {q} rows of tag {t}, got {m}")
+        tagv = np.zeros(0, dtype=np.int64)
+        origins: Dict[int, int] = {}
+        bitmap = None
+        if count:
+            packed, bitmap = ops.bank_select_weakest_scoped(self.memory_metadata, count, now, scope_tags,
+                                                            [self._tag_origin.get(t, 0) for t in scope_tags], n_in,
+                                                            [q for _, _, q in scopes])
+            _, _, victims = ops.scoped_selection_decode(packed.cpu(), n_in)      # THE host read
+            for t, v in zip(scope_tags, victims):
+                if v.size:
+                    origins[t] = int(v[-1]) + 1
+            tagv = np.concatenate(victims).astype(np.int64)
+        rem = n - int(tagv.size)
+        n_app = min(rem, max(M - count, 0))
+        g = rem - n_app
+        glob = np.zeros(0, dtype=np.int64)
+        if g:
+            if g > count - tagv.size:
+                raise ValueError(f"'weakest' cannot evict {g + tagv.size} rows from a bank that holds {count}")
+            if tagv.size:
+                rows, _ = ops.bank_select_weakest_masked(self.memory_metadata, count, now, cursor % M, g, bitmap)
+            else:
+                rows, _ = ops.bank_select_weakest(self.memory_metadata, count, now, cursor % M, g)
+            glob = rows.cpu().numpy().astype(np.int64)     # the second read
+            cursor += g
+        slots = np.concatenate([np.arange(count, count + n_app, dtype=np.int64), tagv, glob])
+        self._pending_origins = origins
+        return slots, n_app, count + n_app, cursor
+
+    def _limited_tags_held(self) -> List[int]:
+        """The limited tags: the named ones, and -- with a quota for every tag -- the tags the bank holds (a read of
+        the distinct values of the tag column)."""
+        tags = set(self._tag_quota_map)
+        if self._tag_quota_default is not None and self.memory_count:
+            tags.update(t for t in torch.unique(self.memory_tags).cpu().tolist() if 0 < t < TAG_LIMIT)
+        return sorted(tags)
+
+    def tag_counts(self, tags=None) -> Dict[int, int]:
+        """``{tag: rows held}`` for ``tags`` (an int or ints; default: the limited tags), counted on the device by one
+        pass over the metadata per 64 tags (``ops.bank_tag_counts``) and read back once."""
+        if tags is None:
+            want = self._limited_tags_held()
+        else:
+            t = (tags.detach().cpu().numpy() if isinstance(tags, torch.Tensor) else np.asarray(tags)).reshape(-1)
+            want = sorted(set(self._check_tags(t, t.size).tolist())) if t.size else []
+        if not want:
+            return {}
+        if self.memory_count == 0:
+            return {t: 0 for t in want}
+        counts = ops.bank_tag_counts(self.memory_metadata, self.memory_count, want).cpu().tolist()
+        return dict(zip(want, counts))
+
+    def enforce_tag_quotas(self, now: Optional[float] = None) -> CompactionReport:
+        """Bring every limited tag that holds more than its quota down to it: the first ``held_t - q(t)`` rows of the
+        tag's eviction order at ``now`` (default: the clock) are forgotten through ``forget`` (one compaction; the tie
+        origins follow).  Two host reads: the counts, then the victims.  Returns ``forget``'s report."""
+        count = self.memory_count
+        over = [(t, h, self._quota_of(t)) for t, h in self.tag_counts().items() if h > self._quota_of(t)]
+        if not over:
+            return CompactionReport(0, np.arange(count, dtype=np.int64))
+        now = time.time() if now is None else now
+        scope_tags = [t for t, _, _ in over]
+        n_in = [h - q for _, h, q in over]                  # incoming = the excess: x_t = min(in, held + in - q) = held - q
+        packed, _ = ops.bank_select_weakest_scoped(self.memory_metadata, count, now, scope_tags,
+                                                   [self._tag_origin.get(t, 0) for t in scope_tags], n_in,
+                                                   [q for _, _, q in over])
+        _, _, victims = ops.scoped_selection_decode(packed.cpu(), n_in)
+        for t, v in zip(scope_tags, victims):
+            if v.size:
+                self._tag_origin[t] = int(v[-1]) + 1
+        return self.forget(rows=np.concatenate(victims))
 
     @staticmethod
     def _last_occurrences(slots: np.ndarray, n_app: int) -> Optional[np.ndarray]:
@@ -511,11 +677,18 @@ class HippocampalFormation(nn.Module):
         self._ivf_after_write(uniq_t, int(uniq_t.numel()), meta_v0)
 
     def _write_rows(self, ids: Sequence[str], feats: torch.Tensor, now: float,
-                    tags: Optional[np.ndarray] = None) -> None:
-        """Write a run of rows that contains no centroid-rebuild boundary."""
-        slots, n_app, new_count, new_cursor = self._plan_slots(len(ids), now)
+                    tags: Optional[np.ndarray] = None, plan_tags: Optional[np.ndarray] = None) -> None:
+        """Write a run of rows that contains no centroid-rebuild boundary.  ``plan_tags``: the run's tags as the quota
+        rule sees them (None: no quota is set, or no row of the run can be limited)."""
+        if plan_tags is None:
+            slots, n_app, new_count, new_cursor = self._plan_slots(len(ids), now)
+        else:
+            slots, n_app, new_count, new_cursor = self._plan_slots(len(ids), now, tags=plan_tags)
+        origins, self._pending_origins = self._pending_origins, None
         self._store_rows(ids, feats, slots, n_app, new_count, new_cursor, now,
                          online=self.use_centroid_index and self._index_ready, selected=True, tags=tags)
+        if origins:                                        # (the write was accepted)
+            self._tag_origin.update(origins)
 
     # ------------------------------------------------------------------ tags
     @staticmethod
@@ -789,6 +962,10 @@ class HippocampalFormation(nn.Module):
     def _write_batch(self, memory_ids: Sequence[str], feats: torch.Tensor, tags: Optional[np.ndarray] = None) -> None:
         n = len(memory_ids)
         i = 0
+        plan_tags = None
+        if self._tag_quota_map or self._tag_quota_default is not None:
+            # rows without a tag are tag 0, which is limited only when it is named
+            plan_tags = tags if tags is not None else (np.zeros(n, dtype=np.int32) if 0 in self._tag_quota_map else None)
         while i < n:
             # run length until the next insert that triggers a rebuild
             run = n - i
@@ -802,7 +979,11 @@ class HippocampalFormation(nn.Module):
                     run = min(run, to_boundary, self.max_memories - self.memory_count)
                 elif self.memory_count % interval == 0 and self.memory_count > self.centroids_k:
                     run = 1   # full bank whose size divides the interval: rebuild after every write
-            if tags is None:
+            if plan_tags is not None:
+                run = self._quota_run(plan_tags[i:i + run])   # at most q(t) rows of a limited tag per run
+                self._write_rows(memory_ids[i:i + run], feats[i:i + run], time.time(),
+                                 tags=None if tags is None else tags[i:i + run], plan_tags=plan_tags[i:i + run])
+            elif tags is None:
                 self._write_rows(memory_ids[i:i + run], feats[i:i + run], time.time())
             else:
                 self._write_rows(memory_ids[i:i + run], feats[i:i + run], time.time(), tags=tags[i:i + run])
@@ -1038,6 +1219,13 @@ class HippocampalFormation(nn.Module):
         """New row i holds what row ``order[i]`` of the ``count`` rows held before: clear the freed tail, bring the
         derived state and the host maps in line.  ``gone``: the centroid ids (metadata column 2) of the rows that left."""
         k = int(order.size)
+        if self._tag_origin and count:
+            # a tie origin becomes the number of survivors that come before it in ring order (``order`` is in ring
+            # order from the ring's start, so the survivors' ring positions ascend)
+            start = self._ring_start()
+            pos = (order - start) % count
+            self._tag_origin = {t: int(np.searchsorted(pos, (c % count - start) % count, side='left'))
+                                for t, c in self._tag_origin.items()}
         for a in (self.memory_features, self.memory_locations, self.memory_metadata):
             a[k:count].zero_()                          # what was forgotten does not stay in the state_dict
         if gone is not None and gone.numel():
@@ -1561,13 +1749,17 @@ class HippocampalFormation(nn.Module):
         that a compaction took rows out of carries the surviving original indices (an int64 array) in place of its
         first index; states saved before compaction existed load unchanged."""
         n = self.memory_count
-        return {"memory_count": n, "index_ready": bool(self._index_ready),
-                "write_cursor": self._write_cursor, "centroids_k": self.centroids_k,
-                "centroids_update_interval": self.centroids_update_interval,
-                "ids_by_slot": list(self._idx_to_id[:n]),
-                "id_to_idx": dict(self.id_to_idx),
-                "slot_time": self._slot_time[:n].tobytes(),            # float64 host clock per slot
-                "implicit_ids": list(self._implicit_ids)}
+        state = {"memory_count": n, "index_ready": bool(self._index_ready),
+                 "write_cursor": self._write_cursor, "centroids_k": self.centroids_k,
+                 "centroids_update_interval": self.centroids_update_interval,
+                 "ids_by_slot": list(self._idx_to_id[:n]),
+                 "id_to_idx": dict(self.id_to_idx),
+                 "slot_time": self._slot_time[:n].tobytes(),            # float64 host clock per slot
+                 "implicit_ids": list(self._implicit_ids)}
+        if self._tag_quota_map or self._tag_quota_default is not None:  # (only then: other states keep their keys)
+            state["tag_quota"] = {"default": self._tag_quota_default, "tags": dict(self._tag_quota_map)}
+            state["tag_origin"] = dict(self._tag_origin)
+        return state
 
     def load_bank_state(self, state: Dict[str, Any]) -> None:
         """Inverse of ``bank_state`` (call after ``load_state_dict``)."""
@@ -1588,6 +1780,13 @@ class HippocampalFormation(nn.Module):
         self._slot_time[:] = 0.0
         st = state.get("slot_time")
         self._slot_time[:n] = np.frombuffer(st, dtype=np.float64)[:n] if st is not None else time.time()
+        self._tag_origin = {}
+        if "tag_quota" in state:                        # quotas travel with their tie origins; without: this bank's own
+            self._tag_quota_default, self._tag_quota_map = None, {}
+            self.set_tag_quota(None, state["tag_quota"].get("default"))
+            for t, q in state["tag_quota"].get("tags", {}).items():
+                self.set_tag_quota(int(t), q)
+            self._tag_origin = {int(t): int(c) for t, c in state.get("tag_origin", {}).items()}
         self._invalidate_norms()
 
     def gather_features(self, rows: torch.Tensor) -> torch.Tensor:

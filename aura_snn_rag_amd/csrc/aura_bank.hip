@@ -288,23 +288,7 @@ __global__ __launch_bounds__(256) void kmeans_commit_kernel(const int32_t* __res
 // A bank of equal keys (never decayed or reinforced) is seen by pass 0 (min == max): the threshold is
 // then the rotated row n - 1 itself and nothing but pass 0 and the compaction reads the rows.
 // ------------------------------------------------------------------------------------------
-__device__ __forceinline__ float retention_key(float strength, float timestamp, float now) {
-    return strength * expf(-(now - timestamp) / 3600.0f);
-}
-
-// order-preserving map fp32 -> u32: NaN lowest (0), then -inf .. -0 == +0 .. +inf
-__device__ __forceinline__ uint32_t retention_ordered(float key) {
-    if (key != key) return 0u;
-    if (key == 0.0f) return 0x80000000u;
-    const uint32_t u = __float_as_uint(key);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-__device__ __forceinline__ uint64_t retention_comp(uint32_t okey, int64_t r, int64_t cursor, int64_t count) {
-    int64_t rot = r - cursor;
-    if (rot < 0) rot += count;
-    return ((uint64_t)okey << 32) | (uint64_t)rot;
-}
+#include "aura_retention.inl"
 
 constexpr int SEL_BINS = 4096;          // 12-bit digits
 constexpr int SEL_MAX_PASSES = 6;       // 3 digits of the key + at most 3 of a 31-bit rotated row
@@ -394,10 +378,22 @@ __global__ __launch_bounds__(256) void retention_keys_kernel(const float4* __res
     }
 }
 
+// A row whose bit is set in a caller's bitmap (aura_bank_select_weakest_masked: the tag victims of the same run) takes
+// no part: pass 0 files it under an ordered key no float maps to (0xffffffff would be a positive NaN, and NaN maps to
+// 0), above +inf, so the digit passes need not know of the bitmap, and the compaction leaves it out by its bit.  With
+// such a row present min != max, so the equal-keys shortcut (which counts ring positions) is not taken.
+constexpr uint32_t SEL_MASKED_KEY = 0xffffffffu;
+
+__device__ __forceinline__ bool sel_masked(const uint32_t* __restrict__ bitmap, int64_t r) {
+    return (bitmap[r >> 5] >> (r & 31)) & 1u;
+}
+
 // pass 0: ordered keys + histogram of their top 12 bits + min / max
+template <bool MASKED>
 __global__ __launch_bounds__(256) void select_keys_kernel(const float4* __restrict__ meta, int64_t count, float now,
                                                           uint32_t* __restrict__ okeys, uint32_t* __restrict__ hist,
-                                                          SelState* __restrict__ st0) {
+                                                          SelState* __restrict__ st0,
+                                                          const uint32_t* __restrict__ bitmap) {
     __shared__ uint32_t s_hist[SEL_BINS];
     __shared__ uint32_t s_mm[2];
     for (int b = threadIdx.x; b < SEL_BINS; b += 256) s_hist[b] = 0;
@@ -414,7 +410,10 @@ __global__ __launch_bounds__(256) void select_keys_kernel(const float4* __restri
         for (int j = 0; j < 4; ++j) {
             const int64_t r = r0 + j * stride;
             if (r >= count) break;
-            const uint32_t ok = retention_ordered(retention_key(m[j].x, m[j].y, now));
+            uint32_t ok = retention_ordered(retention_key(m[j].x, m[j].y, now));
+            if constexpr (MASKED) {
+                if (sel_masked(bitmap, r)) ok = SEL_MASKED_KEY;
+            }
             okeys[r] = ok;
             kmax = max(kmax, ok); kmin_inv = max(kmin_inv, ~ok);
             const uint32_t d = ok >> 20;
@@ -480,8 +479,12 @@ __global__ __launch_bounds__(256) void select_pass_kernel(const uint32_t* __rest
 }
 
 // a selected row goes to the workgroup's list
+template <bool MASKED>
 __device__ __forceinline__ void sel_collect(uint32_t ok, int64_t r, int64_t cursor, int64_t count, unsigned long long thr,
-                                            uint32_t* s_n, int32_t* s_rows) {
+                                            uint32_t* s_n, int32_t* s_rows, const uint32_t* __restrict__ bitmap) {
+    if constexpr (MASKED) {
+        if (sel_masked(bitmap, r)) return;
+    }
     if (retention_comp(ok, r, cursor, count) <= thr) s_rows[atomicAdd(s_n, 1u)] = (int32_t)r;
 }
 
@@ -509,6 +512,7 @@ __device__ __forceinline__ void sel_write_list(uint32_t* s_n, uint32_t* s_base, 
 }
 
 // the last narrowing, then every row at or below the threshold, in arrival order
+template <bool MASKED>
 __global__ __launch_bounds__(256) void select_compact_kernel(const uint32_t* __restrict__ okeys,
                                                              const float4* __restrict__ meta, int64_t count, float now,
                                                              int64_t cursor, uint32_t n, int first, int prev_shift,
@@ -518,7 +522,8 @@ __global__ __launch_bounds__(256) void select_compact_kernel(const uint32_t* __r
                                                              uint32_t* __restrict__ out_count,
                                                              int64_t* __restrict__ out_slots,
                                                              float* __restrict__ out_keys,
-                                                             int64_t* __restrict__ out_comp) {
+                                                             int64_t* __restrict__ out_comp,
+                                                             const uint32_t* __restrict__ bitmap) {
     __shared__ uint32_t s_scan[256];
     __shared__ SelState s_out;
     __shared__ int32_t s_rows[SEL_LIST];
@@ -534,10 +539,10 @@ __global__ __launch_bounds__(256) void select_compact_kernel(const uint32_t* __r
         const int64_t g = g0 + threadIdx.x;
         if (g < groups) {
             const uint4 k4 = reinterpret_cast<const uint4*>(okeys)[g];
-            sel_collect(k4.x, 4 * g, cursor, count, thr, &s_n, s_rows);
-            sel_collect(k4.y, 4 * g + 1, cursor, count, thr, &s_n, s_rows);
-            sel_collect(k4.z, 4 * g + 2, cursor, count, thr, &s_n, s_rows);
-            sel_collect(k4.w, 4 * g + 3, cursor, count, thr, &s_n, s_rows);
+            sel_collect<MASKED>(k4.x, 4 * g, cursor, count, thr, &s_n, s_rows, bitmap);
+            sel_collect<MASKED>(k4.y, 4 * g + 1, cursor, count, thr, &s_n, s_rows, bitmap);
+            sel_collect<MASKED>(k4.z, 4 * g + 2, cursor, count, thr, &s_n, s_rows, bitmap);
+            sel_collect<MASKED>(k4.w, 4 * g + 3, cursor, count, thr, &s_n, s_rows, bitmap);
         }
         __syncthreads();
         const uint32_t held = s_n;                          // (read by all before anyone adds again)
@@ -547,7 +552,7 @@ __global__ __launch_bounds__(256) void select_compact_kernel(const uint32_t* __r
     }
     if (blockIdx.x == 0 && (int64_t)threadIdx.x < (count & 3)) {
         const int64_t r = 4 * groups + threadIdx.x;
-        sel_collect(okeys[r], r, cursor, count, thr, &s_n, s_rows);
+        sel_collect<MASKED>(okeys[r], r, cursor, count, thr, &s_n, s_rows, bitmap);
     }
     __syncthreads();
     sel_write_list(&s_n, &s_base, s_rows, okeys, meta, now, cursor, count, n, out_count, out_slots, out_keys, out_comp);
@@ -695,12 +700,16 @@ int64_t aura_bank_select_weakest_workspace_bytes(int64_t count, int64_t n) {
            (int64_t)SEL_MAX_PASSES * SEL_COPIES * SEL_BINS * 4 + align256(4 * count);
 }
 
-int aura_bank_select_weakest(const float* meta, int64_t count, float now, int64_t cursor, int64_t n,
-                             int64_t* out_slots, float* out_keys, void* workspace, int64_t workspace_bytes,
-                             void* stream) {
+// the launches of both selections; MASKED: rows whose bit is set in `bitmap` (count bits) take no part
+extern "C++" {
+template <bool MASKED>
+static int select_weakest_launch(const float* meta, int64_t count, float now, int64_t cursor, int64_t n,
+                                 const uint32_t* bitmap, int64_t* out_slots, float* out_keys, void* workspace,
+                                 int64_t workspace_bytes, void* stream) {
     if (count < 1 || count > 0x7ffffff0LL || n < 1 || n > count || cursor < 0) return AURA_E_INVAL;
-    if (!meta || !out_slots || !out_keys || !workspace) return AURA_E_INVAL;
+    if (!meta || !out_slots || !out_keys || !workspace || (MASKED && !bitmap)) return AURA_E_INVAL;
     if ((reinterpret_cast<uintptr_t>(meta) & 15) || (reinterpret_cast<uintptr_t>(workspace) & 255)) return AURA_E_ALIGN;
+    if (MASKED && (reinterpret_cast<uintptr_t>(bitmap) & 3)) return AURA_E_ALIGN;
     if (workspace_bytes < aura_bank_select_weakest_workspace_bytes(count, n)) return AURA_E_INVAL;
     cursor %= count;
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -718,7 +727,8 @@ int aura_bank_select_weakest(const float* meta, int64_t count, float now, int64_
     const float4* meta4 = reinterpret_cast<const float4*>(meta);
     int64_t blocks = (count + 255) / 256;
     if (blocks > SEL_MAX_BLOCKS) blocks = SEL_MAX_BLOCKS;
-    hipLaunchKernelGGL(select_keys_kernel, dim3((unsigned)blocks), dim3(256), 0, s, meta4, count, now, okeys, hist, st);
+    hipLaunchKernelGGL(select_keys_kernel<MASKED>, dim3((unsigned)blocks), dim3(256), 0, s, meta4, count, now, okeys,
+                       hist, st, bitmap);
     int rc = check_launch_b();
     if (rc) return rc;
     int64_t blocks4 = (count / 4 + 255) / 256;
@@ -731,10 +741,30 @@ int aura_bank_select_weakest(const float* meta, int64_t count, float now, int64_
         rc = check_launch_b();
         if (rc) return rc;
     }
-    hipLaunchKernelGGL(select_compact_kernel, dim3((unsigned)blocks4), dim3(256), 0, s, okeys, meta4, count, now, cursor,
-                       (uint32_t)n, P == 1 ? 1 : 0, shifts[P - 1], widths[P - 1], st + (P - 1), st + P,
-                       hist + (int64_t)(P - 1) * SEL_COPIES * SEL_BINS, &st[0].out_count, out_slots, out_keys, out_comp);
+    hipLaunchKernelGGL(select_compact_kernel<MASKED>, dim3((unsigned)blocks4), dim3(256), 0, s, okeys, meta4, count, now,
+                       cursor, (uint32_t)n, P == 1 ? 1 : 0, shifts[P - 1], widths[P - 1], st + (P - 1), st + P,
+                       hist + (int64_t)(P - 1) * SEL_COPIES * SEL_BINS, &st[0].out_count, out_slots, out_keys, out_comp,
+                       bitmap);
     return check_launch_b();
+}
+}  // extern "C++"
+
+int aura_bank_select_weakest(const float* meta, int64_t count, float now, int64_t cursor, int64_t n,
+                             int64_t* out_slots, float* out_keys, void* workspace, int64_t workspace_bytes,
+                             void* stream) {
+    return select_weakest_launch<false>(meta, count, now, cursor, n, nullptr, out_slots, out_keys, workspace,
+                                        workspace_bytes, stream);
+}
+
+int64_t aura_bank_select_weakest_masked_workspace_bytes(int64_t count, int64_t n) {
+    return aura_bank_select_weakest_workspace_bytes(count, n);
+}
+
+int aura_bank_select_weakest_masked(const float* meta, int64_t count, float now, int64_t cursor, int64_t n,
+                                    const uint32_t* bitmap, int64_t* out_slots, float* out_keys, void* workspace,
+                                    int64_t workspace_bytes, void* stream) {
+    return select_weakest_launch<true>(meta, count, now, cursor, n, bitmap, out_slots, out_keys, workspace,
+                                       workspace_bytes, stream);
 }
 
 int64_t aura_bank_reinforce_workspace_bytes(int64_t count) {

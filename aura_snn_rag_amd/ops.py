@@ -437,6 +437,126 @@ def bank_select_weakest(meta, count: int, now: float, cursor: int, n: int) -> Tu
     return slots[order], keys[order]
 
 
+QUOTA_MAX_SCOPES = 64
+
+
+def _scope_list(values, name: str, S: Optional[int] = None) -> np.ndarray:
+    a = np.asarray(values, dtype=np.int64).reshape(-1)
+    if S is not None and a.size != S:
+        raise ValueError(f"{name}: {a.size} entries for {S} scopes")
+    return a
+
+
+def bank_tag_counts(meta, count: int, scope_tags) -> torch.Tensor:
+    """int32 [S] (device): how many rows of [0, count) carry each of ``scope_tags`` (host ints in [0, 2^24), distinct
+    and ascending; any number of them: 64 per library call).  One upload, no host sync."""
+    _check_meta(meta, count, "bank_tag_counts")
+    t = _scope_list(scope_tags, "bank_tag_counts")
+    if t.size and (np.any(np.diff(t) <= 0) or t[0] < 0 or t[-1] >= TAG_LIMIT):
+        raise ValueError("bank_tag_counts: scope_tags must be distinct, ascending and inside [0, 2^24)")
+    out = torch.zeros(t.size, dtype=torch.int32, device=meta.device)
+    if t.size == 0:
+        return out
+    tags = torch.from_numpy(t.astype(np.int32)).to(meta.device)
+    L = lib()
+    for s0 in range(0, t.size, QUOTA_MAX_SCOPES):
+        s1 = min(t.size, s0 + QUOTA_MAX_SCOPES)
+        check(L.aura_bank_tag_counts(_p(meta), count, tags.data_ptr() + 4 * s0, s1 - s0, out.data_ptr() + 4 * s0,
+                                     _stream()), "aura_bank_tag_counts")
+    return out
+
+
+def bank_select_weakest_scoped(meta, count: int, now: float, scope_tags, origins, incoming, quotas,
+                               bitmap=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Each scope's own weakest rows (``include/aura_hip.h``, "Per-tag quotas", step 1).  ``scope_tags`` (host ints,
+    distinct, ascending), and per scope its tie origin, the number of incoming rows and its quota (host ints; any number
+    of scopes: 64 per library call, all calls sharing the bitmap).  Returns ``(packed, bitmap)``, both on the device:
+    ``packed`` int64 ``[held (S) | x (S) | slots (T) | composites (T)]`` with ``T = sum(incoming)``, scope s owning the
+    entries ``[sum(incoming[:s]), + incoming[s])`` of the last two parts -- its ``x[s]`` victims in arrival order, then
+    -1 / INT64_MAX (``scoped_selection_decode`` orders them on the host after THE read); ``bitmap`` int32
+    ``[(count + 31) // 32]`` with the victims' bits set on top of what the caller passed in.  One upload, no host sync."""
+    _check_meta(meta, count, "bank_select_weakest_scoped")
+    t = _scope_list(scope_tags, "scope_tags")
+    S = t.size
+    o, n_in, q = (_scope_list(v, name, S) for v, name in ((origins, "origins"), (incoming, "incoming"), (quotas, "quotas")))
+    if count < 1 or S < 1:
+        raise ValueError("bank_select_weakest_scoped: needs a held row and a scope")
+    if np.any(np.diff(t) <= 0) or t[0] < 0 or t[-1] >= TAG_LIMIT:
+        raise ValueError("bank_select_weakest_scoped: scope_tags must be distinct, ascending and inside [0, 2^24)")
+    if np.any(o < 0) or np.any(n_in < 0) or np.any(q < 1) or int(n_in.sum()) > 0x7ffffff0:
+        raise ValueError("bank_select_weakest_scoped: origins and incoming must be >= 0, quotas >= 1")
+    T = int(n_in.sum())
+    i32max = np.iinfo(np.int32).max
+    params = np.stack([t, o % count, np.minimum(n_in, i32max), np.minimum(q, i32max)]).astype(np.int32)
+    params_d = torch.from_numpy(params).to(meta.device)                         # THE upload: [4, S]
+    packed = torch.empty(2 * S + 2 * T, dtype=torch.int64, device=meta.device)
+    words = (count + 31) // 32
+    if bitmap is None:
+        bitmap = torch.zeros(words, dtype=torch.int32, device=meta.device)
+    else:
+        _need(bitmap, "bitmap", torch.int32)
+        if bitmap.numel() < words or bitmap.device != meta.device:
+            raise ValueError("bank_select_weakest_scoped: bitmap must hold count bits on meta's device")
+    L = lib()
+    off = np.concatenate([[0], np.cumsum(n_in)])
+    pp, base_p = params_d.data_ptr(), packed.data_ptr()
+    for s0 in range(0, S, QUOTA_MAX_SCOPES):
+        s1 = min(S, s0 + QUOTA_MAX_SCOPES)
+        nbytes = L.aura_bank_select_weakest_scoped_workspace_bytes(count, s1 - s0)
+        if nbytes < 0:
+            raise ValueError("bank_select_weakest_scoped: unsupported size")
+        ws = _workspace(meta.device, nbytes)
+        cap = int(off[s1] - off[s0])
+        check(L.aura_bank_select_weakest_scoped(
+            _p(meta), count, now, pp + 4 * s0, pp + 4 * (S + s0), pp + 4 * (2 * S + s0), pp + 4 * (3 * S + s0), s1 - s0,
+            cap, base_p + 8 * s0, base_p + 8 * (S + s0), base_p + 8 * (2 * S + int(off[s0])),
+            base_p + 8 * (2 * S + T + int(off[s0])), _p(bitmap), ws, nbytes, _stream()),
+            "aura_bank_select_weakest_scoped")
+    return packed, bitmap
+
+
+def scoped_selection_decode(packed, incoming):
+    """``packed`` of ``bank_select_weakest_scoped`` on the HOST -> ``(held int64 [S], x int64 [S], victims)``:
+    ``victims[s]`` the scope's ``x[s]`` rows in its eviction order (ascending composites)."""
+    p = packed.numpy() if isinstance(packed, torch.Tensor) else np.asarray(packed)
+    n_in = np.asarray(incoming, dtype=np.int64).reshape(-1)
+    S, T = n_in.size, int(n_in.sum())
+    held, x = p[:S].copy(), p[S:2 * S].copy()
+    slots, comp = p[2 * S:2 * S + T], p[2 * S + T:2 * S + 2 * T]
+    victims, o = [], 0
+    for s in range(S):
+        m = int(n_in[s])
+        order = np.argsort(comp[o:o + m], kind="stable")[:int(x[s])]
+        victims.append(slots[o:o + m][order].astype(np.int64))
+        o += m
+    return held, x, victims
+
+
+def bank_select_weakest_masked(meta, count: int, now: float, cursor: int, n: int, bitmap) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``bank_select_weakest`` among the rows whose bit in ``bitmap`` (int32 ``[(count + 31) // 32]``, device) is clear;
+    ``n`` must not exceed their number (entries beyond it come back as row -1).  No host sync."""
+    _check_meta(meta, count, "bank_select_weakest_masked")
+    _need(bitmap, "bitmap", torch.int32)
+    if not (1 <= n <= count) or cursor < 0:
+        raise ValueError(f"bank_select_weakest_masked: need 1 <= n <= count and cursor >= 0 (n={n}, count={count}, cursor={cursor})")
+    if bitmap.numel() < (count + 31) // 32 or bitmap.device != meta.device:
+        raise ValueError("bank_select_weakest_masked: bitmap must hold count bits on meta's device")
+    L = lib()
+    nbytes = L.aura_bank_select_weakest_masked_workspace_bytes(count, n)
+    if nbytes < 0:
+        raise ValueError("bank_select_weakest_masked: unsupported size")
+    base = _workspace(meta.device, nbytes)
+    slots = torch.full((n,), -1, dtype=torch.int64, device=meta.device)
+    keys = torch.zeros(n, dtype=torch.float32, device=meta.device)
+    _workspace_view(meta.device, 8 * n).view(torch.int64).fill_(torch.iinfo(torch.int64).max)   # unfilled: sorted last
+    check(L.aura_bank_select_weakest_masked(_p(meta), count, now, cursor, n, _p(bitmap), _p(slots), _p(keys), base, nbytes,
+                                            _stream()), "aura_bank_select_weakest_masked")
+    if n == 1:
+        return slots, keys
+    order = torch.sort(_workspace_view(meta.device, 8 * n).view(torch.int64)).indices
+    return slots[order], keys[order]
+
+
 def bank_reinforce(meta, count: int, rows, amount: float, cap: float = 1.0) -> None:
     """``meta[r][0] = min(meta[r][0] + amount, cap)`` where it is below ``cap``, once for every distinct row id
     of ``rows`` (int32, any shape) inside [0, count); ``-1`` and other ids outside are ignored."""

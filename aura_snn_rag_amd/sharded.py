@@ -112,6 +112,7 @@ class ShardedHippocampus:
         import time as _time
         from . import ops as _ops
         self.local = local
+        self._refuse_quota()
         self._refuse_weakest()
         self.ops = _ops if ops_module is None else ops_module
         self.group = group
@@ -166,6 +167,18 @@ class ShardedHippocampus:
                              "planned globally, and a global weakest-first order needs a selection across shards "
                              "(local select, all-gather of the candidates, merge) that is not implemented; use "
                              "'reference' or 'fifo' (reinforce() on the local bank of a shard works as on any bank)")
+
+    def _refuse_quota(self) -> None:
+        """Per-tag quotas are a single-bank feature, as tags are: raised from local state alone."""
+        if getattr(self.local, '_tag_quota_map', None) or getattr(self.local, '_tag_quota_default', None) is not None:
+            raise ValueError("ShardedHippocampus does not support tag_quota: a tag's rows would span the shards, and its "
+                             "weakest rows would need a selection across them; set quotas on a single "
+                             "HippocampalFormation")
+
+    def set_tag_quota(self, tag, quota) -> None:
+        """Refused (``ValueError``): quotas are not available on a row-sharded bank."""
+        raise ValueError("ShardedHippocampus does not support tag_quota: a tag's rows would span the shards, and its "
+                         "weakest rows would need a selection across them; set quotas on a single HippocampalFormation")
 
     @staticmethod
     def _refuse_scope(what: str, **given) -> None:

@@ -304,6 +304,70 @@ int aura_knn_search_scoped(const float* bank, const float* inv_norm, const float
                            float* out_scores, int32_t* out_rows, void* workspace, int64_t workspace_bytes,
                            int32_t* flag_out, void* stream);
 
+/* Per-tag quotas: a tag at its limit gives up its OWN weakest memories (csrc/aura_quota.hip, and the masked form of
+ * the selection above in csrc/aura_bank.hip).  [build-side] no upstream counterpart.
+ *
+ * THE RULE.  A bank under overflow='weakest' may carry a quota q(t) >= 1 for some tags t (a "limited" tag; tags without
+ * a quota are unlimited).  Terms:
+ *   key(r)            = meta[r][0] * expf(-(now - meta[r][1]) / 3600), the arithmetic of aura_bank_retention_keys;
+ *   eviction order of tag t: its rows of [0, count) by (key, (r - c_t) mod count) ascending, a NaN key first, -0 == +0;
+ *   c_t               the tag's TIE ORIGIN, kept on the host per limited tag, 0 at first.  (Stored timestamps are fp32,
+ *                     128 s apart: rows written within two minutes tie.  Ranked from the bank's one cursor, the row a
+ *                     tag has just overwritten would be first in ring order again: the tag would churn one slot and
+ *                     keep its oldest rows.  With its own origin behind its last victim a tag of tied keys is a FIFO.)
+ * A batch is cut into runs; a run holds at most q(t) rows of each limited tag t (the longest such prefix, on top of the
+ * cuts the write path makes anyway) and is ranked once, from the rows held before it.  For one run of n rows, in_t of
+ * them of limited tag t, held_t rows of [0, count) carrying t, M the bank's capacity:
+ *   1. tag victims    x_t = min(in_t, max(0, held_t + in_t - q(t))): the first x_t rows of t's eviction order;
+ *                     then c_t <- (the last of them) + 1.
+ *   2. appends        rem = n - sum_t x_t,  n_app = min(rem, M - count).
+ *   3. global victims g = rem - n_app: the first g rows of the bank's usual eviction order (the global cursor) among
+ *                     the rows that are NOT tag victims of this run; then cursor += g.
+ *   4. slots          the run's first n_app rows append; the others overwrite, in this order: the tag victims, scopes in
+ *                     ascending tag order, each scope in its own eviction order; then the global victims in theirs.
+ * Consequences: a quota is a cap, not a reservation (a full bank may take a global victim from a tag under its quota);
+ * a tag over its quota (after a bulk or positioned write, a retag, a lowered quota, a loaded checkpoint: none of them
+ * enforce quotas) neither grows nor shrinks on writes until the host takes the first held_t - q(t) rows of its
+ * eviction order out; rows a consolidating write merges are not stored and do not count.
+ *
+ * aura_bank_tag_counts: out[s] (device int32 [n_scopes]) = the number of rows r < count with (int)meta[r][3] ==
+ *   scope_tags[s] (a column 3 outside (-1, 2^24) carries no tag).  scope_tags: device int32, distinct, strictly
+ *   ascending (the caller's duty: a list that is not finds fewer rows, never a wrong address), 1 <= n_scopes <=
+ *   AURA_QUOTA_MAX_SCOPES.  One pass over the metadata, counts in LDS, one integer add per workgroup and non-empty
+ *   scope.  count == 0 zeroes out and launches nothing.  Needs no workspace.
+ * aura_bank_select_weakest_scoped: for up to AURA_QUOTA_MAX_SCOPES scopes at once, with origin[s], incoming[s] and
+ *   quota[s] (device int32 [n_scopes]; a quota beyond int32 is as good as 2^31 - 1): computes held_s and
+ *   x_s = min(incoming, max(0, held + incoming - quota), held) on the device and selects EXACTLY the first x_s rows of
+ *   scope s's eviction order (step 1 above) by one radix select with n_scopes thresholds over
+ *   ordered_u32(key) << 32 | (r - origin[s]) mod count, 8-bit digits: the metadata is read once (16 B per row), every
+ *   further pass reads 8 B per row.  out_held / out_x (device int64 [n_scopes]); scope s owns the entries
+ *   [off_s, off_s + incoming[s]) of out_slots / out_comp (device int64 [out_capacity], off_s = sum of incoming[j],
+ *   j < s; out_capacity >= the sum of incoming, entries beyond it are never written): its x_s rows in arrival order,
+ *   each with its composite, top bit flipped (ascending as signed integers = the scope's eviction order), then -1 /
+ *   INT64_MAX.  Sorting a scope's entries by composite orders its selection.  Sets bit r of bitmap (device uint32
+ *   [(count + 31) / 32], caller-held, NOT cleared by the call: several calls over disjoint scope subsets share one
+ *   bitmap when a run carries more than 64 limited tags; the scopes' victim sets are disjoint, so the grouping does not
+ *   matter) for every selected row r.  Integer adds and ors only: nothing depends on arrival order but the order within
+ *   a scope's output range.  workspace: *_workspace_bytes(count, n_scopes), 256-byte aligned.
+ * aura_bank_select_weakest_masked: aura_bank_select_weakest among the rows whose bitmap bit is clear (step 3 above).
+ *   n must not exceed the number of such rows (fewer: the remaining entries of out_slots / out_keys are not written).
+ *   The same kernels as the unmasked selection, instantiated with the mask; same outputs, same workspace size.
+ * AURA_E_INVAL / AURA_E_ALIGN as for aura_bank_select_weakest, and for n_scopes outside [1, 64], a null array, a
+ * negative out_capacity; nothing is launched then. */
+#define AURA_QUOTA_MAX_SCOPES 64
+int aura_bank_tag_counts(const float* meta, int64_t count, const int32_t* scope_tags, int64_t n_scopes, int32_t* out,
+                         void* stream);
+int64_t aura_bank_select_weakest_scoped_workspace_bytes(int64_t count, int64_t n_scopes);
+int aura_bank_select_weakest_scoped(const float* meta, int64_t count, float now, const int32_t* scope_tags,
+                                    const int32_t* origin, const int32_t* incoming, const int32_t* quota,
+                                    int64_t n_scopes, int64_t out_capacity, int64_t* out_held, int64_t* out_x,
+                                    int64_t* out_slots, int64_t* out_comp, uint32_t* bitmap, void* workspace,
+                                    int64_t workspace_bytes, void* stream);
+int64_t aura_bank_select_weakest_masked_workspace_bytes(int64_t count, int64_t n);
+int aura_bank_select_weakest_masked(const float* meta, int64_t count, float now, int64_t cursor, int64_t n,
+                                    const uint32_t* bitmap, int64_t* out_slots, float* out_keys, void* workspace,
+                                    int64_t workspace_bytes, void* stream);
+
 /* Workspace size (bytes) aura_knn_search needs for (N, nq, k). */
 int64_t aura_knn_workspace_bytes(int64_t N, int64_t nq, int k);
 
