@@ -15,7 +15,17 @@ Part of every sequence is planned (``_Plan``) so that each case crosses 8192 row
 rebuild in between, overwrites rows the sorted image holds, appends more than ``ops.ivf2_slack(interval)`` rows between
 two re-packs, and goes on after a checkpoint round trip; the rest is drawn.  Each event is asserted from the op log.
 
-Nothing here provokes a fault: every operation keeps to the documented contracts."""
+``test_tag_sequence`` runs the same machine over the tag-aware state: per-tag quotas (tagged writes, ``set_tag_quota``,
+``enforce_tag_quotas``, the tie origins through every compaction and the checkpoint) and merging within tags
+(consolidating writes and ``consolidate`` within tags), with the planned part of ``bank_model.TagPlan`` and the events
+of ``bank_model.tag_events``; after every operation -- after every other one in the four cases with an index
+(``extra_every``) -- it adds the scoped and the scope-blind repeat search over the next 48 rows of the pool against the
+fp64 rule, and those searches and a diverse recall against the rebuilt bank.
+
+Nothing here provokes a fault: every operation keeps to the documented contracts (quotas only with ``'weakest'``, no run
+asks for more victims than rows held, tags stay in [0, 2^24))."""
+import time
+
 import pytest
 import torch
 
@@ -165,9 +175,10 @@ def test_sequence(dev, hmod, policy, index, D):
         return hf
 
     sizes = dict(SIZES, D=D, policy=policy, index=index)
+    t0 = time.perf_counter()
     seq = B.run_sequence(factory, ops, SEED, STEPS, sizes, clock, plan=_Plan(index))
     st = seq.stats
-    print(f"sequence {policy} index={index} D={D}: {st}; ops {[e['op'] for e in seq.log]}; "
+    print(f"sequence {policy} index={index} D={D}: {time.perf_counter() - t0:.1f} s; {st}; ops {[e['op'] for e in seq.log]}; "
           f"counts {[e['count_after'] for e in seq.log]}")
     B.helpers.record_parity(f"sequence {policy} {'index' if index else 'exact'} D={D}", st["exact"], st["queries"],
                             st["near_ties"], positions_differed=st["differed"])
@@ -175,3 +186,70 @@ def test_sequence(dev, hmod, policy, index, D):
     assert not missing, f"never happened: {missing}\n" + "\n".join(str(e) for e in seq.log)
     # (d) the model's own near-ties: topk_equivalent's allowance must not be what makes the comparisons pass
     assert st["near_ties"] <= 0.05 * st["queries"], st
+
+
+# ------------------------------------------------------------------------ per-tag quotas and merging within tags
+QUOTAS = {1: 300, 2: 60, 3: 1500, 4: 5}
+TAG_PROBS = [0.45, 0.15, 0.05, 0.2, 0.004, 0.146]            # tags 0 and 5 are unlimited: they fill the bank
+
+
+def _named():
+    return B.tagcase(QUOTAS, range(6), TAG_PROBS, small=2, mid=3, over=1, free=5)
+
+
+def _every_tag():
+    # tag_quota=40 for each of the tags 1 .. 100 (81 rows each after the first fill), a tenth of the rows untagged; one planned batch carries all 100 limited
+    # tags (two library calls that share one bitmap); the plan names a quota of 600 for the tag whose ties it uses
+    return B.tagcase(40, range(101), [0.1] + [0.009] * 100, small=1, mid=2, over=3, free=0, many=True, mid_quota=600)
+
+
+def _merging():
+    return B.tagcase(None, range(6), TAG_PROBS, small=2, mid=3, over=1, free=5)
+
+
+TAG_CASES = {
+    "quotas-exact-64": ("weakest", False, 64, _named),
+    "quotas-index-64": ("weakest", True, 64, _named),
+    "quotas-index-100": ("weakest", True, 100, _named),   # no bf16 image: the scoped search is the dense fp32 scan
+    "every-tag-index-64": ("weakest", True, 64, _every_tag),
+    "merging-fifo-index-64": ("fifo", True, 64, _merging),
+    "merging-reference-exact-64": ("reference", False, 64, _merging),
+}
+
+
+def run_tag_case(H, clock, ops, name, device="cuda"):
+    """One tag-aware case (``ops`` None: the library; on the CPU, tests/cpu_stub_quota.py with ``device='cpu'``)."""
+    policy, index, D, case = TAG_CASES[name]
+    tc = case()
+
+    def factory():
+        kw = {} if tc["quota"] is None else dict(tag_quota=tc["quota"])
+        hf = H.HippocampalFormation(feature_dim=D, max_memories=M, n_place_cells=8, n_time_cells=4, n_grid_cells=4,
+                                    device=device, use_centroid_index=index, overflow=policy, **kw)
+        hf.centroids_update_interval = INTERVAL
+        return hf
+
+    # (the plan refills twice: a larger pool.  The cases with an index cost three to four times their test_sequence
+    # counterpart with the repeat searches and the diverse recall after every step: there they run after every other one)
+    sizes = dict(SIZES, D=D, policy=policy, index=index, tagcase=tc, pool_rows=26_000, extra_every=2 if index else 1)
+    t0 = time.perf_counter()
+    seq = B.run_sequence(factory, ops, SEED, STEPS, sizes, clock, plan=B.TagPlan(STEPS, tc, index, M, fill=FILL))
+    return seq, time.perf_counter() - t0
+
+
+@pytest.mark.parametrize("name", list(TAG_CASES))
+def test_tag_sequence(dev, hmod, name):
+    H, clock = hmod
+    from aura_snn_rag_amd import ops
+    seq, wall = run_tag_case(H, clock, ops, name)
+    st = seq.stats
+    print(f"tag sequence {name}: {wall:.1f} s; {st}; ops {[e['op'] for e in seq.log]}; "
+          f"counts {[e['count_after'] for e in seq.log]}")
+    B.helpers.record_parity(f"tag sequence {name}", st["exact"], st["queries"], st["near_ties"],
+                            positions_differed=st["differed"], repeat_rows=st["repeat_rows"],
+                            repeat_near_ties_accepted=st["repeat_near_ties"], wall_s=round(wall, 1))
+    image = TAG_CASES[name][1] and seq.hf._use_shadow
+    missing = [what for what, ok in B.tag_events(seq, live=LIVE if image else None).items() if not ok]
+    assert not missing, f"never happened: {missing}\n" + "\n".join(str(e) for e in seq.log)
+    assert st["near_ties"] <= 0.05 * st["queries"], st
+    assert st["repeat_near_ties"] <= 0.01 * st["repeat_rows"], st
