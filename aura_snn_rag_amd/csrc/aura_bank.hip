@@ -15,6 +15,7 @@
 #include <stdint.h>
 
 #include "../../include/aura_hip.h"
+#include "aura_common.inl"
 
 #pragma clang fp contract(off)
 
@@ -24,8 +25,6 @@ namespace {
 
 typedef float f32x8b __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x8b __attribute__((ext_vector_type(8)));
-
-inline int check_launch_b() { return hipGetLastError() == hipSuccess ? AURA_OK : AURA_E_LAUNCH; }
 
 // One wave converts one row: dst[j] = bf16(src[j] * inv) for j < D (D % 8 == 0, 16-byte chunks);
 // returns (on every lane) rho = 1.001 * ||bf16(x) - x||_2 + (D/2 + 3) 2^-24, x = fl(src * inv).
@@ -51,7 +50,7 @@ __device__ __forceinline__ float shadow_convert_row(const float* __restrict__ sr
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) e2 += __shfl_xor(e2, off);
-    return 1.001f * sqrtf(e2) + (0.5f * (float)D + 3.0f) * 5.9604645e-8f;
+    return aura_rho_from_e2(e2, (float)D);
 }
 
 __device__ __forceinline__ void shadow_zero_row(uint16_t* __restrict__ dst, int64_t D, int lane) {
@@ -587,7 +586,7 @@ int aura_bank_shadow_update(const float* bank, const float* inv_norm, uint16_t* 
     if (blocks > 16384) blocks = 16384;
     hipLaunchKernelGGL(bank_shadow_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream),
                        bank, inv_norm, bank_bf16, rho, slots, row0, n, D);
-    return check_launch_b();
+    return aura_check_launch();
 }
 
 int aura_bank_shadow_sorted(const float* bank, const float* inv_norm, const int32_t* sorted_rows,
@@ -602,7 +601,7 @@ int aura_bank_shadow_sorted(const float* bank, const float* inv_norm, const int3
     hipLaunchKernelGGL(bank_shadow_sorted_kernel, dim3((unsigned)blocks), dim3(256), 0,
                        static_cast<hipStream_t>(stream), bank, inv_norm, sorted_rows, sorted_bf16, rho, pos_of_row,
                        n_sorted, D);
-    return check_launch_b();
+    return aura_check_launch();
 }
 
 int aura_ivf2_append(const float* bank, const float* inv_norm, const float* meta, const int64_t* slots,
@@ -620,7 +619,7 @@ int aura_ivf2_append(const float* bank, const float* inv_norm, const float* meta
                        static_cast<hipStream_t>(stream), bank, inv_norm, meta, slots, n, D, sorted_bf16, sorted_rows,
                        pad_off, list_len, pos_of_row, rho, flag, reinterpret_cast<float4*>(row_constants),
                        row_constants_now);
-    return check_launch_b();
+    return aura_check_launch();
 }
 
 int64_t aura_kmeans_means_workspace_bytes(int64_t N, int64_t D, int k) {
@@ -644,12 +643,12 @@ int aura_kmeans_segment_means(const float* bank, const int32_t* order, const int
     if (blocks > 8192) blocks = 8192;
     hipLaunchKernelGGL(kmeans_partial_kernel, dim3((unsigned)blocks), dim3(256), 0, s, bank, order, seg_off,
                        static_cast<float*>(workspace), D, k);
-    int rc = check_launch_b();
+    int rc = aura_check_launch();
     if (rc) return rc;
     const int64_t waves = (int64_t)k * ((D + 255) / 256);
     hipLaunchKernelGGL(kmeans_reduce_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s,
                        static_cast<const float*>(workspace), seg_off, centroids, D, k, sums_only);
-    return check_launch_b();
+    return aura_check_launch();
 }
 
 int aura_kmeans_commit(const int32_t* assign, const int32_t* seg_off, float* meta, float* counts, int64_t N,
@@ -659,12 +658,10 @@ int aura_kmeans_commit(const int32_t* assign, const int32_t* seg_off, float* met
     const int64_t blocks = N > 0 ? (N + 255) / 256 : 1;
     hipLaunchKernelGGL(kmeans_commit_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream),
                        assign, seg_off, meta, counts, N, k);
-    return check_launch_b();
+    return aura_check_launch();
 }
 
 // ---- retention ---------------------------------------------------------------------------
-static inline int64_t align256(int64_t b) { return (b + 255) / 256 * 256; }
-
 // digits of the composite below the three of the key: the bits of the rotated row that `count` needs
 static int sel_passes(int64_t count, int* shifts, int* widths) {
     int P = 0;
@@ -690,14 +687,14 @@ int aura_bank_retention_keys(const float* meta, int64_t count, float now, float*
     if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(retention_keys_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream),
                        reinterpret_cast<const float4*>(meta), count, now, out);
-    return check_launch_b();
+    return aura_check_launch();
 }
 
 // workspace: [n composites (int64)] [SelState x (passes + 1)] [histograms] [ordered keys (u32 x count)]
 int64_t aura_bank_select_weakest_workspace_bytes(int64_t count, int64_t n) {
     if (count < 1 || count > 0x7ffffff0LL || n < 1 || n > count) return -1;
-    return align256(8 * n) + align256((SEL_MAX_PASSES + 1) * (int64_t)sizeof(SelState)) +
-           (int64_t)SEL_MAX_PASSES * SEL_COPIES * SEL_BINS * 4 + align256(4 * count);
+    return aura_align256(8 * n) + aura_align256((SEL_MAX_PASSES + 1) * (int64_t)sizeof(SelState)) +
+           (int64_t)SEL_MAX_PASSES * SEL_COPIES * SEL_BINS * 4 + aura_align256(4 * count);
 }
 
 // the launches of both selections; MASKED: rows whose bit is set in `bitmap` (count bits) take no part
@@ -715,9 +712,9 @@ static int select_weakest_launch(const float* meta, int64_t count, float now, in
     hipStream_t s = static_cast<hipStream_t>(stream);
     char* w = static_cast<char*>(workspace);
     int64_t* out_comp = reinterpret_cast<int64_t*>(w);
-    w += align256(8 * n);
+    w += aura_align256(8 * n);
     SelState* st = reinterpret_cast<SelState*>(w);
-    const int64_t st_bytes = align256((SEL_MAX_PASSES + 1) * (int64_t)sizeof(SelState));
+    const int64_t st_bytes = aura_align256((SEL_MAX_PASSES + 1) * (int64_t)sizeof(SelState));
     uint32_t* hist = reinterpret_cast<uint32_t*>(w + st_bytes);
     const int64_t hist_bytes = (int64_t)SEL_MAX_PASSES * SEL_COPIES * SEL_BINS * 4;
     uint32_t* okeys = reinterpret_cast<uint32_t*>(w + st_bytes + hist_bytes);
@@ -729,7 +726,7 @@ static int select_weakest_launch(const float* meta, int64_t count, float now, in
     if (blocks > SEL_MAX_BLOCKS) blocks = SEL_MAX_BLOCKS;
     hipLaunchKernelGGL(select_keys_kernel<MASKED>, dim3((unsigned)blocks), dim3(256), 0, s, meta4, count, now, okeys,
                        hist, st, bitmap);
-    int rc = check_launch_b();
+    int rc = aura_check_launch();
     if (rc) return rc;
     int64_t blocks4 = (count / 4 + 255) / 256;
     if (blocks4 < 1) blocks4 = 1;
@@ -738,14 +735,14 @@ static int select_weakest_launch(const float* meta, int64_t count, float now, in
         hipLaunchKernelGGL(select_pass_kernel, dim3((unsigned)blocks4), dim3(256), 0, s, okeys, count, cursor, (uint32_t)n,
                            i == 1 ? 1 : 0, shifts[i - 1], widths[i - 1], shifts[i], widths[i], st + (i - 1), st + i,
                            hist + (int64_t)(i - 1) * SEL_COPIES * SEL_BINS, hist + (int64_t)i * SEL_COPIES * SEL_BINS);
-        rc = check_launch_b();
+        rc = aura_check_launch();
         if (rc) return rc;
     }
     hipLaunchKernelGGL(select_compact_kernel<MASKED>, dim3((unsigned)blocks4), dim3(256), 0, s, okeys, meta4, count, now,
                        cursor, (uint32_t)n, P == 1 ? 1 : 0, shifts[P - 1], widths[P - 1], st + (P - 1), st + P,
                        hist + (int64_t)(P - 1) * SEL_COPIES * SEL_BINS, &st[0].out_count, out_slots, out_keys, out_comp,
                        bitmap);
-    return check_launch_b();
+    return aura_check_launch();
 }
 }  // extern "C++"
 
@@ -769,7 +766,7 @@ int aura_bank_select_weakest_masked(const float* meta, int64_t count, float now,
 
 int64_t aura_bank_reinforce_workspace_bytes(int64_t count) {
     if (count < 0 || count > 0x7ffffff0LL) return -1;
-    return align256((count + 31) / 32 * 4);
+    return aura_align256((count + 31) / 32 * 4);
 }
 
 int aura_bank_reinforce(float* meta, int64_t count, const int32_t* rows, int64_t n_rows, float amount, float cap,
@@ -786,7 +783,7 @@ int aura_bank_reinforce(float* meta, int64_t count, const int32_t* rows, int64_t
     if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(bank_reinforce_kernel, dim3((unsigned)blocks), dim3(256), 0, s, meta, count, rows, n_rows, amount,
                        cap, static_cast<uint32_t*>(workspace));
-    return check_launch_b();
+    return aura_check_launch();
 }
 
 }  // extern "C"

@@ -23,15 +23,13 @@
 #include <stdint.h>
 
 #include "../../include/aura_hip.h"
+#include "aura_common.inl"
 
 namespace {
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int CP_ROUND = 4096;           // rows per round (and per workspace half)
-
-inline int check_launch_k() { return hipGetLastError() == hipSuccess ? AURA_OK : AURA_E_LAUNCH; }
-inline int64_t align256(int64_t x) { return (x + 255) / 256 * 256; }
 
 struct RowArrays {
     float* bank;          // [.][D]
@@ -44,7 +42,7 @@ struct RowArrays {
 
 inline RowArrays carve_half(char* p, int64_t& o, int64_t D, int64_t S, bool has_shadow) {
     RowArrays w;
-    auto take = [&](int64_t b) { char* r = p ? p + o : nullptr; o += align256(b); return r; };
+    auto take = [&](int64_t b) { char* r = p ? p + o : nullptr; o += aura_align256(b); return r; };
     w.bank = reinterpret_cast<float*>(take(4LL * CP_ROUND * D));
     w.loc = reinterpret_cast<float*>(take(4LL * CP_ROUND * (S > 0 ? S : 1)));
     w.meta = reinterpret_cast<float*>(take(16LL * CP_ROUND));
@@ -166,7 +164,7 @@ int aura_bank_compact(float* bank, float* loc, float* meta, float* inv_norm, uin
         else
             hipLaunchKernelGGL(cp_round_kernel<false>, dim3((unsigned)(sblocks + gblocks)), dim3(256), 0, st, g, wst, wga,
                                rows, (int)D, (int)S, src, dst0, sa, sn, sblocks, ga, gn);
-        const int rc = check_launch_k();
+        const int rc = aura_check_launch();
         if (rc != AURA_OK) return rc;
     }
     return AURA_OK;

@@ -33,17 +33,13 @@
 #include <math.h>
 #include <stdint.h>
 
-#include <mutex>
-#include <set>
-#include <utility>
-
 #include "../../include/aura_hip.h"
+#include "aura_common.inl"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned long long u64;
@@ -55,21 +51,6 @@ constexpr int CS_CAP = 256;              // survivor slots per batch row
 constexpr int CS_BK = 64;                // dense scan: columns per chunk
 constexpr int CS_STRIDE = CS_BK + 4;     // LDS row stride in floats (as aura_diverse.hip)
 
-inline int check_launch_c() { return hipGetLastError() == hipSuccess ? AURA_OK : AURA_E_LAUNCH; }
-
-inline int ensure_lds_attr_c(const void* fn, int bytes) {
-    static std::mutex mu;
-    static std::set<std::pair<int, const void*>> done;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return AURA_E_LAUNCH;
-    std::lock_guard<std::mutex> g(mu);
-    if (done.count({dev, fn})) return AURA_OK;
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) return AURA_E_LAUNCH;
-    done.insert({dev, fn});
-    return AURA_OK;
-}
-
-inline int64_t align256(int64_t x) { return (x + 255) / 256 * 256; }
 inline int pad_batch(int64_t n) { return (int)((n + 127) / 128 * 128); }
 
 struct Workspace {
@@ -91,7 +72,7 @@ inline Workspace carve(void* base, int n_pad) {
     Workspace w;
     char* p = static_cast<char*>(base);
     int64_t o = 0;
-    auto take = [&](int64_t b) { char* r = p ? p + o : nullptr; o += align256(b); return r; };
+    auto take = [&](int64_t b) { char* r = p ? p + o : nullptr; o += aura_align256(b); return r; };
     w.best = reinterpret_cast<u64*>(take(8LL * n_pad));
     w.cnt = reinterpret_cast<int32_t*>(take(4LL * n_pad));
     w.pend = reinterpret_cast<int32_t*>(take(4LL * n_pad));
@@ -119,16 +100,9 @@ __device__ __forceinline__ u64 cs_shfl_xor(u64 v, int off) {
     return ((u64)hi << 32) | lo;
 }
 
-// The tag of held row `row` as aura_knn_search_scoped reads it; -2 (no batch tag equals it) for anything that is no tag.
+// The tag of held row `row`; aura_no_tag = -2 (no batch tag equals it: those are >= -1) for anything that is no tag.
 __device__ __forceinline__ int cs_row_tag(const float* __restrict__ meta, int64_t row) {
-    const float t = meta[row * 4 + 3];
-    return (t > -1.0f && t < 16777216.0f) ? (int)t : -2;
-}
-
-// Query part of the prefilter's error bound, the two-stage recall's formula (aura_knn_coarse.inl):
-// rho_q = 1.001 sqrt(e2) + (D/2 + 3) 2^-24, times (1 + 2^-7).
-__device__ __forceinline__ float cs_eq_from_e2(float e2, float D) {
-    return (1.001f * sqrtf(e2) + (0.5f * D + 3.0f) * 5.9604645e-8f) * 1.0078125f;
+    return aura_row_tag(meta[row * 4 + 3]);
 }
 
 // ---- prep: one wave per batch row (rows [n, n_pad) are padding)
@@ -168,7 +142,7 @@ __global__ __launch_bounds__(256) void cs_prep_kernel(const float* __restrict__ 
     }
     if (lane == 0) {
         w.qinv[q] = q < n ? iq : 0.0f;
-        w.eq[q] = ok ? cs_eq_from_e2(e2, (float)D) : NAN;
+        w.eq[q] = ok ? aura_eq_from_e2(e2, (float)D) : NAN;
         w.okf[q] = ok ? 1 : 0;
         w.elig[q] = 0;
         w.cnt[q] = 0;
@@ -531,13 +505,13 @@ int launch_scan(const uint16_t* image, const int32_t* image_rows, int64_t n_imag
                 const Workspace& w, int n_tiles, float tau, float fix, const float* meta, hipStream_t s) {
     constexpr int lds = 2 * 32 * 2 * KS * 16;
     if (lds > 64 * 1024) {
-        const int rc = ensure_lds_attr_c(reinterpret_cast<const void*>(&cs_scan_kernel<KS, SCOPED>), lds);
+        const int rc = aura_ensure_lds_attr(reinterpret_cast<const void*>(&cs_scan_kernel<KS, SCOPED>), lds);
         if (rc != AURA_OK) return rc;
     }
     const unsigned blocks = (unsigned)((n_image + 127) / 128);
     hipLaunchKernelGGL((cs_scan_kernel<KS, SCOPED>), dim3(blocks), dim3(256), lds, s, image, image_rows, n_image, N, D,
                        rho, w.qhat, w.eq, n_tiles, tau, fix, w.cnt, w.list, meta, w.tag);
-    return check_launch_c();
+    return aura_check_launch();
 }
 
 template <int MODE, bool SCOPED>
@@ -551,7 +525,7 @@ int launch_dense(bool vec, const float* A, const float* ainv, int64_t NA, const 
     else
         hipLaunchKernelGGL((cs_dense_kernel<false, MODE, SCOPED>), grid, dim3(256), 0, s, A, ainv, NA, B, binv, nB, D, tau,
                            w.best, w.gram, n_pad, w.elig, w.pend, meta, w.tag);
-    return check_launch_c();
+    return aura_check_launch();
 }
 
 
@@ -583,7 +557,7 @@ int find_repeats_impl(const float* bank, const float* inv_norm, int64_t N, int64
     const int ks = with_image ? (int)((D + 127) / 128) * 8 : 0;          // 16-column steps, a multiple of 8
     hipLaunchKernelGGL(cs_prep_kernel, dim3((unsigned)(n_pad / 4)), dim3(256), 0, s, feats, nn, n_pad, D, ks * 16, w,
                        with_image ? 1 : 0, overflow_out, SCOPED ? batch_tags : nullptr);
-    int rc = check_launch_c();
+    int rc = aura_check_launch();
     if (rc != AURA_OK) return rc;
     if (with_image && n_image > 0) {
         // the error bound's fixed part, as the header states it for the prefilter
@@ -610,13 +584,13 @@ int find_repeats_impl(const float* bank, const float* inv_norm, int64_t N, int64
         hipLaunchKernelGGL(cs_finalise_kernel, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, s, nn, w, stored_target,
                            cos_out);
     }
-    rc = check_launch_c();
+    rc = aura_check_launch();
     if (rc != AURA_OK) return rc;
     const bool vecq = D % 4 == 0 && !(reinterpret_cast<uintptr_t>(feats) & 15);
     rc = launch_dense<1, SCOPED>(vecq, feats, w.qinv, nn, feats, w.qinv, nn, n_pad, D, tau, w, meta, s);
     if (rc != AURA_OK) return rc;
     hipLaunchKernelGGL(cs_walk_kernel<SCOPED>, dim3(1), dim3(1024), 0, s, nn, n_pad, tau, w, batch_leader, cos_out);
-    return check_launch_c();
+    return aura_check_launch();
 }
 
 }  // namespace
@@ -653,7 +627,7 @@ int aura_bank_touch(float* meta, int64_t count, const int32_t* rows, int64_t n, 
     if (!meta || !rows) return AURA_E_INVAL;
     hipLaunchKernelGGL(cs_touch_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
                        meta, count, rows, n, now);
-    return check_launch_c();
+    return aura_check_launch();
 }
 
 }  // extern "C"

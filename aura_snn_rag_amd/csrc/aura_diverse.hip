@@ -18,38 +18,18 @@
 #include <math.h>
 #include <stdint.h>
 
-#include <mutex>
-#include <set>
-#include <utility>
-
 #include "../../include/aura_hip.h"
+#include "aura_common.inl"
 
 #pragma clang fp contract(off)
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int DV_THREADS = 256;
 constexpr int DV_BK = 64;               // columns per chunk
 constexpr int DV_STRIDE = DV_BK + 4;    // LDS row stride in floats: 16 rows x 16 B cover the 64 banks once
 constexpr int DV_MAX_F = 128;
 constexpr int64_t DV_MAX_D = 4096;
-
-inline int check_launch_d() { return hipGetLastError() == hipSuccess ? AURA_OK : AURA_E_LAUNCH; }
-
-// hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (device, kernel)
-inline int ensure_lds_attr_d(const void* fn, int bytes) {
-    static std::mutex mu;
-    static std::set<std::pair<int, const void*>> done;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return AURA_E_LAUNCH;
-    std::lock_guard<std::mutex> g(mu);
-    if (done.count({dev, fn})) return AURA_OK;
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) return AURA_E_LAUNCH;
-    done.insert({dev, fn});
-    return AURA_OK;
-}
 
 template <int T>
 constexpr int dv_lds_floats() {
@@ -148,10 +128,7 @@ __global__ __launch_bounds__(DV_THREADS) void diverse_select_kernel(
 #pragma unroll
             for (int kk = 0; kk < DV_BK / 8 / KS; ++kk) {
                 const float4 v = *reinterpret_cast<const float4*>(row + (wave * (DV_BK / 8 / KS) + kk) * 8);
-                acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(v.x, v.x, acc[0], 0, 0, 0);
-                acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(v.y, v.y, acc[0], 0, 0, 0);
-                acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(v.z, v.z, acc[0], 0, 0, 0);
-                acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(v.w, v.w, acc[0], 0, 0, 0);
+                acc[0] = aura_mfma_f32_x4(v, v, acc[0]);
             }
         } else {
 #pragma unroll
@@ -164,10 +141,7 @@ __global__ __launch_bounds__(DV_THREADS) void diverse_select_kernel(
                             smem + ((tile / T) * 32 + li) * DV_STRIDE + 4 * lh + kk * 8);
                         const float4 bv = *reinterpret_cast<const float4*>(
                             smem + ((tile % T) * 32 + li) * DV_STRIDE + 4 * lh + kk * 8);
-                        acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, bv.x, acc[t], 0, 0, 0);
-                        acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, bv.y, acc[t], 0, 0, 0);
-                        acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, bv.z, acc[t], 0, 0, 0);
-                        acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, bv.w, acc[t], 0, 0, 0);
+                        acc[t] = aura_mfma_f32_x4(av, bv, acc[t]);
                     }
                 }
             }
@@ -254,12 +228,12 @@ int launch_diverse(const float* bank, const float* inv_norm, int64_t count, int6
                    int32_t* out_rows, hipStream_t s) {
     constexpr int lds = dv_lds_floats<T>() * (int)sizeof(float);
     if (lds + 3 * DV_MAX_F * 4 > 64 * 1024) {
-        const int rc = ensure_lds_attr_d(reinterpret_cast<const void*>(&diverse_select_kernel<T>), lds);
+        const int rc = aura_ensure_lds_attr(reinterpret_cast<const void*>(&diverse_select_kernel<T>), lds);
         if (rc != AURA_OK) return rc;
     }
     hipLaunchKernelGGL(diverse_select_kernel<T>, dim3((unsigned)nq), dim3(DV_THREADS), lds, s, bank, inv_norm, count, D,
                        cand_rows, cand_scores, F, k, d, tau, out_scores, out_rows);
-    return check_launch_d();
+    return aura_check_launch();
 }
 
 }  // namespace

@@ -26,37 +26,19 @@
 #include <stdlib.h>
 
 #include <mutex>
-#include <set>
-#include <utility>
 #include <vector>
 #include <type_traits>
 
 #include "../../include/aura_hip.h"
+#include "aura_common.inl"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4v_t __attribute__((ext_vector_type(4)));
 
-inline int check_launch() { return hipGetLastError() == hipSuccess ? AURA_OK : AURA_E_LAUNCH; }
 inline int64_t align_up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
-
-// hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (device, kernel); callable from any
-// host thread and for any device of the process
-inline int ensure_lds_attr(const void* fn, int bytes) {
-    static std::mutex mu;
-    static std::set<std::pair<int, const void*>> done;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return AURA_E_LAUNCH;
-    std::lock_guard<std::mutex> g(mu);
-    if (done.count({dev, fn})) return AURA_OK;
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess)
-        return AURA_E_LAUNCH;
-    done.insert({dev, fn});
-    return AURA_OK;
-}
 
 // order-preserving float -> uint32 (larger float <=> larger key); -0 < +0, NaN ends up extreme
 __device__ __forceinline__ uint32_t ord_key(float f) {
@@ -70,7 +52,8 @@ __device__ __forceinline__ float ord_unkey(uint32_t k) {
 
 // ------------------------------------------------------------------------------------------
 // Row norms / query norms:  inv[i] = 1 / max(||x_i||, 1e-12)   (F.normalize, hippocampal.py:273,278)
-// One wave per row, 16-byte loads.
+// One wave per row, 16-byte loads.  aura_scoped.hip's sc_query_norm_kernel sums unfused with a 64-stride instead: the two
+// differ in the last bits, and merging them would move scores.
 // ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void row_inv_norm_kernel(const float* __restrict__ x,
                                                            float* __restrict__ inv, int64_t n,
@@ -1108,7 +1091,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void knn_scan_kernel(const ScanArgs a
             const float4 m = *reinterpret_cast<const float4*>(a.meta + row * 4);
             strength = m.x;
             const float age = a.now - m.y;
-            tw = 0.2f * expf(-age / 3600.0f);
+            tw = 0.2f * expf(-age / 3600.0f);   // aura_time_weight (aura_common.inl), written out: as the score below
             cid = (int)m.z;
             if (a.q_loc)
                 for (int d = 0; d < a.sdims && d < 4; ++d) lx[d] = a.loc[row * a.sdims + d];
@@ -1118,6 +1101,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void knn_scan_kernel(const ScanArgs a
         for (int e = 0; e < 16; ++e) {
             const int ql = wq * 32 + (e & 3) + 8 * (e >> 2) + 4 * lh;
             const int q = q0 + ql;
+            // aura_score_spatial (aura_common.inl), written out: the call changes this kernel's instructions
             const float sim = acc[r][e] * iq[e] * inv_m;
             float comb = 0.5f * sim;
             if (a.q_loc && q < a.nq) {
@@ -1381,8 +1365,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void knn_scan_filter_v2(const ScanArg
                 inv_m = a.inv_norm[row];
                 const float4 m = *reinterpret_cast<const float4*>(a.meta + row * 4);
                 strength = m.x;
-                const float age = a.now - m.y;
-                tw = 0.2f * expf(-age / 3600.0f);
+                tw = aura_time_weight(a.now, m.y);
                 cid = (int)m.z;
                 if (!FAST && a.q_loc)
                     for (int d = 0; d < a.sdims && d < 4; ++d) lx[d] = a.loc[row * a.sdims + d];
@@ -1391,8 +1374,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void knn_scan_filter_v2(const ScanArg
                 unsigned int bits = 0u;
 #pragma unroll
                 for (int e = 0; e < 16; ++e) {
-                    const float sim = acc[r][e] * iq[e] * inv_m;
-                    const float comb = (0.5f * sim + tw) * strength;
+                    const float comb = aura_score(acc[r][e], iq[e], inv_m, tw, strength);
                     acc[r][e] = comb;
                     bits |= (comb >= thrf[e]) ? (1u << e) : 0u;
                 }
@@ -1403,6 +1385,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void knn_scan_filter_v2(const ScanArg
 #pragma unroll
                 for (int e = 0; e < 16; ++e) {
                     const int q = qoff + wave * 32 + (e & 3) + 8 * (e >> 2) + 4 * lh;
+                    // aura_score_spatial (aura_common.inl), written out: the call changes this kernel's instructions
                     const float sim = acc[r][e] * iq[e] * inv_m;
                     float comb = 0.5f * sim;
                     if (a.q_loc && q < a.nq) {
@@ -1747,15 +1730,15 @@ inline int launch_probe(const float* centroids, const float* queries, int64_t D,
     if (D <= PR_QLDS_MAX_D) {
         const size_t lds = ((size_t)16 * ((D + 15) / 16 * 16 + 4) + (size_t)PR_WAVES * 32 * 64) * sizeof(float);
         const int lds_max = (int)((16 * (PR_QLDS_MAX_D + 4) + PR_WAVES * 32 * 64) * 4);
-        if (ensure_lds_attr(reinterpret_cast<const void*>(centroid_probe_kernel<true, true>), lds_max) ||
-            ensure_lds_attr(reinterpret_cast<const void*>(centroid_probe_kernel<true, false>), lds_max))
+        if (aura_ensure_lds_attr(reinterpret_cast<const void*>(centroid_probe_kernel<true, true>), lds_max) ||
+            aura_ensure_lds_attr(reinterpret_cast<const void*>(centroid_probe_kernel<true, false>), lds_max))
             return AURA_E_LAUNCH;
         if (vec) AURA_PROBE(true, true, lds); else AURA_PROBE(true, false, lds);
     } else {
         if (vec) AURA_PROBE(false, true, 0); else AURA_PROBE(false, false, 0);
     }
 #undef AURA_PROBE
-    return hipGetLastError() == hipSuccess ? AURA_OK : AURA_E_LAUNCH;
+    return aura_check_launch();
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1944,10 +1927,7 @@ __global__ __launch_bounds__(IVF_THREADS) void ivf_scan_kernel(const IvfArgs a) 
 #pragma unroll
                 for (int t = 0; t < QT; ++t) {
                     const float4 av = *reinterpret_cast<const float4*>(qrow + t * 32 * LDS_STRIDE + kk * 8);
-                    acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, bv.x, acc[t], 0, 0, 0);
-                    acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, bv.y, acc[t], 0, 0, 0);
-                    acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, bv.z, acc[t], 0, 0, 0);
-                    acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, bv.w, acc[t], 0, 0, 0);
+                    acc[t] = aura_mfma_f32_x4(av, bv, acc[t]);
                 }
             }
             __syncthreads();
@@ -1958,7 +1938,7 @@ __global__ __launch_bounds__(IVF_THREADS) void ivf_scan_kernel(const IvfArgs a) 
         if (rid >= 0) {
             const float inv_m = a.inv_norm[rid];
             const float4 m = *reinterpret_cast<const float4*>(a.meta + (int64_t)rid * 4);
-            const float tw = 0.2f * expf(-(a.now - m.y) / 3600.0f);
+            const float tw = aura_time_weight(a.now, m.y);
 #pragma unroll
             for (int t = 0; t < QT; ++t)
 #pragma unroll
@@ -1966,8 +1946,7 @@ __global__ __launch_bounds__(IVF_THREADS) void ivf_scan_kernel(const IvfArgs a) 
                 const int pk = s_q[t * 32 + (e & 3) + 8 * (e >> 2) + 4 * lh];
                 if (pk < 0) continue;
                 const int q = pk >> 4, p = pk & 15;
-                const float sim = acc[t][e] * a.inv_q[q] * inv_m;
-                const float comb = (0.5f * sim + tw) * m.x;
+                const float comb = aura_score(acc[t][e], a.inv_q[q], inv_m, tw, m.x);
                 const int dst = a.qbase[q * 8 + p] + g * BR + slot;
                 if (dst < a.cap) {
                     a.cand_scores[(int64_t)q * a.cap + dst] = comb;
@@ -2362,11 +2341,11 @@ inline Workspace carve(void* base, int64_t N, int64_t nq, int k) {
 
 inline int launch_select(const SelectArgs& a, int64_t nchunks, int nq, hipStream_t s) {
     // the final select keeps 8192 64-bit keys (64 KiB) + 9 KiB static in LDS
-    if (ensure_lds_attr(reinterpret_cast<const void*>(topk_select_kernel), SEL_LDS_KEYS_HARD * 8)) return AURA_E_LAUNCH;
+    if (aura_ensure_lds_attr(reinterpret_cast<const void*>(topk_select_kernel), SEL_LDS_KEYS_HARD * 8)) return AURA_E_LAUNCH;
     if (a.chunk > SEL_LDS_KEYS_HARD || a.k > SEL_MAX_K) return AURA_E_INVAL;
     hipLaunchKernelGGL(topk_select_kernel, dim3((unsigned)nchunks, (unsigned)nq), dim3(SEL_THREADS),
                        (size_t)a.chunk * 8, s, a);
-    return check_launch();
+    return aura_check_launch();
 }
 
 // Optional per-launch timing of the main (FILTER) scan with HIP events on the launch stream:
@@ -2411,7 +2390,7 @@ int launch_scan(const ScanArgs& a_in, int mode, int64_t ntiles_grid, hipStream_t
         if (vec4) AURA_SCAN(MODE_ASSIGN, true); else AURA_SCAN(MODE_ASSIGN, false);
     }
 #undef AURA_SCAN
-    return check_launch();
+    return aura_check_launch();
 }
 
 inline int device_cu_count() {
@@ -2438,7 +2417,7 @@ inline int launch_filter_v2(const ScanArgs& a, hipStream_t s) {
                               reinterpret_cast<const void*>(knn_scan_filter_v2<false, true>),
                               reinterpret_cast<const void*>(knn_scan_filter_v2<false, false>)};
         for (const void* f : fns)
-            if (ensure_lds_attr(f, (int)lds)) return AURA_E_LAUNCH;
+            if (aura_ensure_lds_attr(f, (int)lds)) return AURA_E_LAUNCH;
     }
     if (a.n_items <= 0) return AURA_OK;
     int64_t grid = device_cu_count();
@@ -2452,7 +2431,7 @@ inline int launch_filter_v2(const ScanArgs& a, hipStream_t s) {
     else if (vec4) hipLaunchKernelGGL((knn_scan_filter_v2<true, false>), g, b, lds, s, a);
     else if (fast) hipLaunchKernelGGL((knn_scan_filter_v2<false, true>), g, b, lds, s, a);
     else hipLaunchKernelGGL((knn_scan_filter_v2<false, false>), g, b, lds, s, a);
-    return check_launch();
+    return aura_check_launch();
 }
 
 // bank rows per workgroup tile for a query block of nq
@@ -2489,13 +2468,13 @@ inline int launch_refine_for(const RefineArgs& r_in, int nqb, int64_t D, int cus
             r.heavy = heavy;
             if (hipMemsetAsync(heavy, 0, 4, s) != hipSuccess) return AURA_E_LAUNCH;
             if (big) {
-                if (ensure_lds_attr(reinterpret_cast<const void*>(coarse_refine_wave16_kernel), 150 * 1024)) return AURA_E_LAUNCH;
+                if (aura_ensure_lds_attr(reinterpret_cast<const void*>(coarse_refine_wave16_kernel), 150 * 1024)) return AURA_E_LAUNCH;
                 hipLaunchKernelGGL(coarse_refine_wave16_kernel, dim3((unsigned)((nqb + 7) / 8)), dim3(RF_THREADS), lds_w, s, r, nqb);
             } else {
-                if (ensure_lds_attr(reinterpret_cast<const void*>(coarse_refine_wave6_kernel), 150 * 1024)) return AURA_E_LAUNCH;
+                if (aura_ensure_lds_attr(reinterpret_cast<const void*>(coarse_refine_wave6_kernel), 150 * 1024)) return AURA_E_LAUNCH;
                 hipLaunchKernelGGL(coarse_refine_wave6_kernel, dim3((unsigned)((nqb + 7) / 8)), dim3(RF_THREADS), lds_w, s, r, nqb);
             }
-            if (check_launch()) return AURA_E_LAUNCH;
+            if (aura_check_launch()) return AURA_E_LAUNCH;
         }
     }
     const int grid_q = r.heavy ? (nqb < 2 * cus ? nqb : 2 * cus) : nqb;   // heavy list: a small grid walks it
@@ -2504,17 +2483,17 @@ inline int launch_refine_for(const RefineArgs& r_in, int nqb, int64_t D, int cus
         size_t lds = (size_t)8 * ROWS * (KC + 4) * 4 + (size_t)Dpad * 4;
         if (lds < (size_t)RF_CAP * 12) lds = (size_t)RF_CAP * 12;
         if (r.heavy) {
-            if (ensure_lds_attr(reinterpret_cast<const void*>(coarse_refine_list_kernel<ROWS, KC>),
+            if (aura_ensure_lds_attr(reinterpret_cast<const void*>(coarse_refine_list_kernel<ROWS, KC>),
                                 8 * ROWS * (KC + 4) * 4 + 768 * 4))
                 return AURA_E_LAUNCH;
             hipLaunchKernelGGL((coarse_refine_list_kernel<ROWS, KC>), dim3((unsigned)grid_q), dim3(RF_THREADS), lds, s, r);
-            return check_launch();
+            return aura_check_launch();
         }
-        if (ensure_lds_attr(reinterpret_cast<const void*>(coarse_refine_kernel<ROWS, KC>),
+        if (aura_ensure_lds_attr(reinterpret_cast<const void*>(coarse_refine_kernel<ROWS, KC>),
                             8 * ROWS * (KC + 4) * 4 + 768 * 4))
             return AURA_E_LAUNCH;
         hipLaunchKernelGGL((coarse_refine_kernel<ROWS, KC>), dim3((unsigned)grid_q), dim3(RF_THREADS), lds, s, r);
-        return check_launch();
+        return aura_check_launch();
     };
     static const int geom = getenv("AURA_RF_GEOM") ? atoi(getenv("AURA_RF_GEOM")) : 0;   // A/B runs
     if (geom == 1) return launch_refine(std::integral_constant<int, 8>{}, std::integral_constant<int, 128>{});
@@ -2628,7 +2607,7 @@ inline int run_coarse_pass(const float* bank, const uint16_t* bank16, const floa
                        qptr, (int64_t)nqb, nq_pad, D, KS, w.qhat, w.inv_q, w.eq,
                        reset_flag ? overflow_out : nullptr, qblocks, meta, inv_norm, use16 ? rho : nullptr, N, now,
                        e_fix, e_cos, w.rowc);
-    if ((rc = check_launch())) return rc;
+    if ((rc = aura_check_launch())) return rc;
     CoarseArgs c{};
     c.bank = bank; c.rowc = w.rowc; c.qhat = w.qhat; c.inv_q = w.inv_q; c.eq = w.eq;
     c.bank16 = use16 ? bank16 : nullptr;
@@ -2657,7 +2636,7 @@ inline int run_coarse_pass(const float* bank, const uint16_t* bank16, const floa
         else AURA_THR(64);
 #undef AURA_THR
     }
-    if ((rc = check_launch())) return rc;
+    if ((rc = aura_check_launch())) return rc;
 
     c.n_tiles = (N + CS_ROWS - 1) / CS_ROWS; c.gmax = nullptr; c.gshift = 0;
     static int tm_left = 3;                                  // AURA_CS_DBG bit 64: phase times of the first launches
@@ -2695,7 +2674,7 @@ inline int run_coarse_pass(const float* bank, const uint16_t* bank16, const floa
         --rtm_left;
         print_refine_phases(s, w.gmax, nqb, "full scan");
     }
-    return check_launch();
+    return aura_check_launch();
 }
 
 }  // namespace
@@ -2709,7 +2688,7 @@ int aura_bank_row_norms(const float* bank, float* inv_norm, int64_t row0, int64_
     if (!bank || !inv_norm) return AURA_E_INVAL;
     hipLaunchKernelGGL(row_inv_norm_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0,
                        static_cast<hipStream_t>(stream), bank + row0 * D, inv_norm + row0, n, D);
-    return check_launch();
+    return aura_check_launch();
 }
 
 int aura_bank_write(float* bank, float* loc, float* meta, float* inv_norm, float* centroids,
@@ -2728,7 +2707,7 @@ int aura_bank_write(float* bank, float* loc, float* meta, float* inv_norm, float
         if (!centroid_counts || eff_k <= 0 || eff_k > 256) return AURA_E_INVAL;
         const size_t lds = (size_t)D * sizeof(float);
         if (lds > 150 * 1024) return AURA_E_INVAL;
-        if (ensure_lds_attr(reinterpret_cast<const void*>(bank_write_centroid_kernel), 150 * 1024)) return AURA_E_LAUNCH;
+        if (aura_ensure_lds_attr(reinterpret_cast<const void*>(bank_write_centroid_kernel), 150 * 1024)) return AURA_E_LAUNCH;
         hipLaunchKernelGGL(bank_write_centroid_kernel, dim3(1), dim3(1024), lds, s, bank, loc, meta,
                            inv_norm, centroids, centroid_counts, eff_k, feats, slots, cur_loc,
                            spatial_dims, now, n, D, vec4);
@@ -2736,7 +2715,7 @@ int aura_bank_write(float* bank, float* loc, float* meta, float* inv_norm, float
         hipLaunchKernelGGL(bank_write_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, bank,
                            loc, meta, inv_norm, feats, slots, cur_loc, spatial_dims, now, -1.0f, n, D, vec4);
     }
-    return check_launch();
+    return aura_check_launch();
 }
 
 int64_t aura_bank_write_online_workspace_bytes(int64_t n) {
@@ -2762,11 +2741,11 @@ int aura_bank_write_online(float* bank, float* loc, float* meta, float* inv_norm
     const int vec4 = (D % 4 == 0) && ((reinterpret_cast<uintptr_t>(feats) & 15) == 0) &&
                      ((reinterpret_cast<uintptr_t>(bank) & 15) == 0) &&
                      ((reinterpret_cast<uintptr_t>(centroids) & 15) == 0);
-    if (ensure_lds_attr(reinterpret_cast<const void*>(online_assign_kernel), 140 * 1024)) return AURA_E_LAUNCH;
+    if (aura_ensure_lds_attr(reinterpret_cast<const void*>(online_assign_kernel), 140 * 1024)) return AURA_E_LAUNCH;
     hipLaunchKernelGGL(bank_write_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, bank, loc, meta, inv_norm,
                        feats, slots, cur_loc, spatial_dims, now, -1.0f, n, D, vec4);
     int rc;
-    if ((rc = check_launch())) return rc;
+    if ((rc = aura_check_launch())) return rc;
     const int64_t ch = n < ONL_CHUNK ? n : ONL_CHUNK;
     float* const d0 = static_cast<float*>(workspace);
     float* const xnorm = reinterpret_cast<float*>(static_cast<char*>(workspace) + align_up(ch * 256 * 4, 256));
@@ -2775,8 +2754,8 @@ int aura_bank_write_online(float* bank, float* loc, float* meta, float* inv_norm
     static const bool simple = getenv("AURA_ONLINE_SIMPLE") != nullptr;   // A/B runs: the unpipelined phase B
     static const bool v1 = getenv("AURA_ONLINE_V1") != nullptr;         // A/B runs: one barrier per row (the pipelined form)
     const bool fast = D <= 1024 && !simple;
-    if (fast && (ensure_lds_attr(reinterpret_cast<const void*>(online_assign_fast_kernel), 8 * 1024) ||
-                 ensure_lds_attr(reinterpret_cast<const void*>(online_assign_fast2_kernel), 8 * 1024))) return AURA_E_LAUNCH;
+    if (fast && (aura_ensure_lds_attr(reinterpret_cast<const void*>(online_assign_fast_kernel), 8 * 1024) ||
+                 aura_ensure_lds_attr(reinterpret_cast<const void*>(online_assign_fast2_kernel), 8 * 1024))) return AURA_E_LAUNCH;
     // fp slack of a computed distance against the exact one, both ways: 2 x (chain of D/64 fmaf + 6 butterfly
     // adds + subtraction, square root) x 2^-24, with a factor 2 in hand
     const float rel = 4.0f * ((float)((D + 63) / 64) + 10.0f) * 5.9604645e-8f;
@@ -2785,22 +2764,22 @@ int aura_bank_write_online(float* bank, float* loc, float* meta, float* inv_norm
         const int64_t nr = (n - r0) < ch ? (n - r0) : ch;
         hipLaunchKernelGGL(online_dist0_kernel, dim3((unsigned)((nr * groups + 3) / 4)), dim3(256), 0, s,
                            feats + r0 * D, centroids, eff_k, nr, D, vec4, d0, xnorm);
-        if ((rc = check_launch())) return rc;
+        if ((rc = aura_check_launch())) return rc;
         if (fast) {
             hipLaunchKernelGGL(online_pred_kernel, dim3((unsigned)((nr + 3) / 4)), dim3(256), 0, s, d0, eff_k, nr, pred);
-            if ((rc = check_launch())) return rc;
+            if ((rc = aura_check_launch())) return rc;
             if (v1) hipLaunchKernelGGL(online_assign_fast_kernel, dim3(1), dim3(1024), lds, s, centroids, centroid_counts,
                                        eff_k, feats + r0 * D, d0, xnorm, pred, cid, nr, D, vec4, rel);
             else hipLaunchKernelGGL(online_assign_fast2_kernel, dim3(1), dim3(1024), lds, s, centroids, centroid_counts,
                                     eff_k, feats + r0 * D, d0, xnorm, pred, cid, nr, D, vec4, rel);
-            if ((rc = check_launch())) return rc;
+            if ((rc = aura_check_launch())) return rc;
             hipLaunchKernelGGL(online_cid_scatter_kernel, dim3((unsigned)((nr + 255) / 256)), dim3(256), 0, s, meta,
                                slots + r0, cid, nr);
         } else {
             hipLaunchKernelGGL(online_assign_kernel, dim3(1), dim3(1024), lds, s, meta, centroids, centroid_counts, eff_k,
                                feats + r0 * D, slots + r0, d0, xnorm, nr, D, vec4, rel);
         }
-        if ((rc = check_launch())) return rc;
+        if ((rc = aura_check_launch())) return rc;
     }
     return AURA_OK;
 }
@@ -2811,7 +2790,7 @@ int aura_bank_decay(float* meta, float rate, int64_t count, void* stream) {
     if (!meta) return AURA_E_INVAL;
     hipLaunchKernelGGL(bank_decay_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0,
                        static_cast<hipStream_t>(stream), meta, 1.0f - rate, count);
-    return check_launch();
+    return aura_check_launch();
 }
 
 int aura_bank_gather(const float* bank, int64_t rows, const int32_t* idx, float* out, int64_t n, int64_t D,
@@ -2821,7 +2800,7 @@ int aura_bank_gather(const float* bank, int64_t rows, const int32_t* idx, float*
     if (!bank || !idx || !out) return AURA_E_INVAL;
     hipLaunchKernelGGL(bank_gather_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0,
                        static_cast<hipStream_t>(stream), bank, idx, out, n, D, rows);
-    return check_launch();
+    return aura_check_launch();
 }
 
 int64_t aura_knn_workspace_bytes(int64_t N, int64_t nq, int k) {
@@ -2859,7 +2838,7 @@ static int knn_search_impl(const float* bank, const uint16_t* bank_bf16, const f
         if (!coarse_eligible(bank, bank_bf16, qptr, q_loc, centroids, N, D, k, flags)) {
             hipLaunchKernelGGL(query_prep_kernel, dim3((unsigned)((nqb + 3) / 4)), dim3(256), 0, s,
                                qptr, w.inv_q, (int64_t)nqb, D, qb0 == 0 ? overflow_out : nullptr);
-            if ((rc = check_launch())) return rc;
+            if ((rc = aura_check_launch())) return rc;
         }
 
         if (coarse_eligible(bank, bank_bf16, qptr, q_loc, centroids, N, D, k, flags)) {
@@ -2952,7 +2931,7 @@ static int knn_search_impl(const float* bank, const uint16_t* bank_bf16, const f
                                (int64_t)THR_MAX_GROUPS, (int)(cols / 32), w.dense, cols, cols, br,
                                tile_step, (int64_t)0, N, k, w.thr, w.cnt, w.cand_scores, w.cand_idx,
                                w.cap);
-            if ((rc = check_launch())) return rc;
+            if ((rc = aura_check_launch())) return rc;
             // 2) main scan appends the rows that reach the bound (sample tiles are skipped)
             const bool prof = g_prof.on && g_prof.used < g_prof.cap;
             if (prof) {
@@ -3117,7 +3096,7 @@ static int knn_search_ivf2_impl(const float* bank, const float* inv_norm, const 
         if (stage_a) {
             hipLaunchKernelGGL(ivf2_rowc_kernel, dim3((unsigned)((n_sorted + 255) / 256)), dim3(256), 0, s,
                                meta, rho, sorted_rows, n_sorted, now, (float)D, w.rowc);
-            if ((rc = check_launch())) return rc;
+            if ((rc = aura_check_launch())) return rc;
         }
         rowc = w.rowc;
     }
@@ -3129,27 +3108,27 @@ static int knn_search_ivf2_impl(const float* bank, const float* inv_norm, const 
         hipLaunchKernelGGL(ivf2_qprep_kernel, dim3((unsigned)((nqb + 1 + 3) / 4)), dim3(256), 0, s,
                            qptr, (int64_t)nqb, D, KS, w.qhat, w.inv_q, w.eq_q, w.qslot, w.lq_cnt,
                            qb0 == 0 ? overflow_out : nullptr, lists_flag);
-        if ((rc = check_launch())) return rc;
+        if ((rc = aura_check_launch())) return rc;
         stage("query prep");
         // the probe launch also fills the per-list query lists (lq_cnt / lq_list); probes that the caller
         // already has (a sharded bank computes them once per query, not once per rank) only fill the lists
         if (probe_ids) {
             hipLaunchKernelGGL(ivf2_lists_from_ids_kernel, dim3((unsigned)((nqb * 8 + 256 * LFI_PER - 1) / (256 * LFI_PER))), dim3(256), 0, s,
                                probe_ids + qb0 * 8, nqb, nprobe, w.lq_cnt, w.lq_list);
-            if ((rc = check_launch())) return rc;
+            if ((rc = aura_check_launch())) return rc;
         } else if ((rc = launch_probe(centroids, qptr, D, nqb, nprobe, w.probe_dist, w.probe, w.probe_ids, s,
                                       w.lq_cnt, w.lq_list, IVF2_MAXQ))) return rc;
         stage("probe");
         hipLaunchKernelGGL(ivf2_plan_kernel, dim3(1), dim3(256), 0, s, w.lq_cnt, pad_off, list_len, w.blk_off,
                            w.blk_list, w.blk_row0, w.blk_stride, w.blk_nq, w.item_off, w.sitem_off, w.nblk,
                            stiles, w_sparse, w_dense, bsh);
-        if ((rc = check_launch())) return rc;
+        if ((rc = aura_check_launch())) return rc;
         stage("plan");
         const int nslot_blocks = (int)((((int64_t)ivf2_maxblk(w.qp, bsh) << bsh) + 255) / 256);   // 256 slots per launch block
         hipLaunchKernelGGL(ivf2_slots_kernel, dim3((unsigned)nslot_blocks), dim3(256), 0, s,
                            w.lq_cnt, w.lq_list, w.blk_off, w.blk_list, w.nblk, w.eq_q, w.slotq, w.qslot, w.thr,
                            w.eq_slot, bsh);
-        if ((rc = check_launch())) return rc;
+        if ((rc = aura_check_launch())) return rc;
         stage("slots");
         }
 
@@ -3193,14 +3172,14 @@ static int knn_search_ivf2_impl(const float* bank, const float* inv_norm, const 
             else AURA_THR2(64);
 #undef AURA_THR2
         }
-        if ((rc = check_launch())) return rc;
+        if ((rc = aura_check_launch())) return rc;
         stage("threshold");
         if (stg == 1) return AURA_OK;
         } else if (stg != 3) {
             // the caller's bound (e.g. combined over the shards of a row-sharded bank) tightens the thresholds
             hipLaunchKernelGGL(ivf2_raise_thr_kernel, dim3((unsigned)((((int64_t)ivf2_maxblk(w.qp, bsh) << bsh) + 255) / 256)), dim3(256), 0, s,
                                w.slotq, w.nblk, bounds, w.thr, bsh);
-            if ((rc = check_launch())) return rc;
+            if ((rc = aura_check_launch())) return rc;
             stage("raise thresholds");
         }
         if (stg != 3) {                                      // (stage 3: the candidates of stage 4 are in the workspace)
@@ -3250,7 +3229,7 @@ static int knn_search_ivf2_impl(const float* bank, const float* inv_norm, const 
             // combine over its shards; stage 3 re-scores against the combined bound
             hipLaunchKernelGGL(coarse_refine_bounds_kernel, dim3((unsigned)((nqb + RF_THREADS / 64 - 1) / (RF_THREADS / 64))),
                                dim3(RF_THREADS), 0, s, r, nqb, k2, bounds);
-            return check_launch();
+            return aura_check_launch();
         }
         if (stg == 3) r.t2_ext = bounds;
         if (trace) {                                         // candidate lists with row ids outside the bank
@@ -3281,7 +3260,7 @@ static int knn_search_ivf2_impl(const float* bank, const float* inv_norm, const 
         if ((rc = launch_refine_for(r, nqb, D, cus, s, w.heavy))) return rc;
         if (host_word && qb0 + w.qp >= nq) {                 // behind the call's last launch: flag + sequence number to the host
             hipLaunchKernelGGL(ivf2_signal_kernel, dim3(1), dim3(64), 0, s, overflow_out, host_word, host_seq);
-            if ((rc = check_launch())) return rc;
+            if ((rc = aura_check_launch())) return rc;
         }
         if (rtm2) {
             --rtm2_left;
@@ -3301,7 +3280,7 @@ int aura_ivf2_row_constants(const float* meta, const float* rho, const int32_t* 
     hipLaunchKernelGGL(ivf2_rowc_kernel, dim3((unsigned)((n_sorted + 255) / 256)), dim3(256), 0,
                        static_cast<hipStream_t>(stream), meta, rho, sorted_rows, n_sorted, now, (float)D,
                        reinterpret_cast<float4*>(row_constants));
-    return check_launch();
+    return aura_check_launch();
 }
 
 int aura_knn_search_ivf2(const float* bank, const float* inv_norm, const float* meta,
@@ -3351,7 +3330,7 @@ int aura_signal_flag(const int32_t* flag_dev, uint32_t* host_word, uint32_t host
     if (!host_word) return AURA_E_INVAL;
     hipLaunchKernelGGL(ivf2_signal_kernel, dim3(1), dim3(64), 0, static_cast<hipStream_t>(stream), flag_dev, host_word,
                        host_seq);
-    return check_launch();
+    return aura_check_launch();
 }
 
 int aura_host_word_free(void* host_word) {
@@ -3482,13 +3461,13 @@ int aura_knn_search_ivf(const float* bank, const float* inv_norm, const float* m
         const int qt = (int64_t)nqb * nprobe >= 48 * 256 ? 2 : 1;
         hipLaunchKernelGGL(query_prep_kernel, dim3((unsigned)((nqb + 3) / 4)), dim3(256), 0, s, qptr,
                            w.inv_q, (int64_t)nqb, D, qb0 == 0 ? overflow_out : nullptr);
-        if ((rc = check_launch())) return rc;
+        if ((rc = aura_check_launch())) return rc;
         if ((rc = launch_probe(centroids, qptr, D, nqb, nprobe, w.probe_dist, w.probe, w.probe_ids, s)))
             return rc;
         hipLaunchKernelGGL(ivf_prepare_kernel, dim3(1), dim3(256), 0, s, w.probe_ids, nprobe, nqb,
                            list_len, w.lq_cnt, w.lq_list, w.qbase, w.cnt, w.item_off, w.work_counter,
                            cap, qt * 32, overflow_out);
-        if ((rc = check_launch())) return rc;
+        if ((rc = aura_check_launch())) return rc;
 
         IvfArgs a{};
         a.bank = bank; a.inv_norm = inv_norm; a.meta = meta; a.queries = qptr; a.inv_q = w.inv_q;
@@ -3510,7 +3489,7 @@ int aura_knn_search_ivf(const float* bank, const float* inv_norm, const float* m
             if (vec4) hipLaunchKernelGGL((ivf_scan_kernel<true, 1>), grid, dim3(IVF_THREADS), lds, s, a);
             else hipLaunchKernelGGL((ivf_scan_kernel<false, 1>), grid, dim3(IVF_THREADS), lds, s, a);
         }
-        if ((rc = check_launch())) return rc;
+        if ((rc = aura_check_launch())) return rc;
         if (prof) (void)hipEventRecord(g_prof.stop[g_prof.used++], s);
 
         // exact top-k of each query's slots (count = total length of its probed lists), in two
@@ -3565,7 +3544,7 @@ int aura_kmeans_assign(const float* bank, const float* centroids, float* cnorm2_
     hipStream_t s = static_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(row_norm2_kernel, dim3((unsigned)((k + 3) / 4)), dim3(256), 0, s, centroids,
                        cnorm2_ws, (int64_t)k, D);
-    int rc = check_launch();
+    int rc = aura_check_launch();
     if (rc) return rc;
     ScanArgs a{};
     a.bank = bank; a.queries = centroids; a.D = D; a.nq = k;
@@ -3588,7 +3567,7 @@ __global__ void clock_probe_kernel(float* out, int spin_ticks) {
 int aura_debug_clock_mhz(float* out_dev, int spin_us, void* stream) {
     if (!out_dev || spin_us < 1 || spin_us > 100000) return AURA_E_INVAL;
     hipLaunchKernelGGL(clock_probe_kernel, dim3(1), dim3(64), 0, static_cast<hipStream_t>(stream), out_dev, spin_us * 100);
-    return check_launch();
+    return aura_check_launch();
 }
 
 int aura_debug_cs_flags(int flags) {

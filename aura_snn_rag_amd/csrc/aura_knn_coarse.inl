@@ -311,13 +311,8 @@ __device__ __forceinline__ void mfma_bf16_q(f32x4v& acc, const bf16x8v& af, cons
     }
 }
 
-// Query part of the error bound from the rounding residual e2 = sum (bf16(x) - x)^2 of the normalised
-// query: eq = rho_q (1 + 2^-7), rho_q = 1.001 sqrt(e2) + (D/2 + 3) 2^-24 (see aura_bank.hip for the
-// second term).  EQ_WORST bounds it for any query (round-to-nearest: ||e_q|| <= 2^-8 ||q_hat||).
-__device__ __forceinline__ float coarse_eq_from_e2(float e2, float D) {
-    return (1.001f * sqrtf(e2) + (0.5f * D + 3.0f) * 5.9604645e-8f) * 1.0078125f;
-}
-// (coarse_eq_worst, coarse_row_constants: aura_rowc.inl)
+// (query part of the error bound: aura_eq_from_e2, aura_common.inl; coarse_eq_worst, coarse_row_constants:
+// aura_rowc.inl)
 
 // Per-call preparation for the two-stage path, one launch:
 //   blocks [0, qblocks): 4 queries each (one wave per query): 1/||q|| (as query_prep_kernel), the
@@ -385,7 +380,7 @@ __global__ __launch_bounds__(256) void coarse_prep_kernel(const float* __restric
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) e2 += __shfl_xor(e2, off);
-    if (lane == 0 && eq_out) eq_out[q] = q < nq ? coarse_eq_from_e2(e2, (float)D) : 0.0f;
+    if (lane == 0 && eq_out) eq_out[q] = q < nq ? aura_eq_from_e2(e2, (float)D) : 0.0f;
 }
 
 // T[q] = k-th largest of the G group maxima: one wave per query, PER keys per lane in registers;
@@ -1279,9 +1274,7 @@ __device__ __forceinline__ void refine_wave_body(const RefineArgs& a, int nq) {
             const int32_t row = s_surv[si];
             const float inv_m = a.inv_norm[row];
             const float4 m = *reinterpret_cast<const float4*>(a.meta + (int64_t)row * 4);
-            const float tw = 0.2f * expf(-(a.now - m.y) / 3600.0f);
-            const float sim = acc * iq * inv_m;
-            const float comb = (0.5f * sim + tw) * m.x;
+            const float comb = aura_score(acc, iq, inv_m, aura_time_weight(a.now, m.y), m.x);
             s_key[si] = ((unsigned long long)ord_key(comb) << 32) | (uint32_t)(~(uint32_t)row);
         }
     }
@@ -1544,9 +1537,7 @@ __device__ __forceinline__ void refine_one_query(const RefineArgs& a, const int 
             const int32_t row = s_surv[si];
             const float inv_m = a.inv_norm[row];
             const float4 m = *reinterpret_cast<const float4*>(a.meta + (int64_t)row * 4);
-            const float tw = 0.2f * expf(-(a.now - m.y) / 3600.0f);
-            const float sim = acc * iq * inv_m;
-            const float comb = (0.5f * sim + tw) * m.x;
+            const float comb = aura_score(acc, iq, inv_m, aura_time_weight(a.now, m.y), m.x);
             s_key[si] = ((unsigned long long)ord_key(comb) << 32) | (uint32_t)(~(uint32_t)row);
         }
     }
@@ -1610,14 +1601,14 @@ template <int KS, bool SRC16, bool MASKED, int NW = 4>
 inline int launch_coarse(const CoarseArgs& a, int mode, int grid, hipStream_t s) {
     const size_t lds = (size_t)cs_lds_slots<SRC16, MASKED, NW>() * (KS * (SRC16 ? 1024 : 2048) + CS_AUX_BYTES) + (size_t)CS_BUF * 12 +
                        (MASKED ? 256 * 32 : 0) + (SRC16 ? 256 * 4 : 0);
-    if (ensure_lds_attr(reinterpret_cast<const void*>(coarse_scan_kernel<KS, CS_MODE_SAMPLE, SRC16, MASKED, false, NW>), (int)lds) ||
-        ensure_lds_attr(reinterpret_cast<const void*>(coarse_scan_kernel<KS, CS_MODE_FILTER, SRC16, MASKED, false, NW>), (int)lds))
+    if (aura_ensure_lds_attr(reinterpret_cast<const void*>(coarse_scan_kernel<KS, CS_MODE_SAMPLE, SRC16, MASKED, false, NW>), (int)lds) ||
+        aura_ensure_lds_attr(reinterpret_cast<const void*>(coarse_scan_kernel<KS, CS_MODE_FILTER, SRC16, MASKED, false, NW>), (int)lds))
         return AURA_E_LAUNCH;
     if (mode == CS_MODE_SAMPLE)
         hipLaunchKernelGGL((coarse_scan_kernel<KS, CS_MODE_SAMPLE, SRC16, MASKED, false, NW>), dim3(grid), dim3(64 * NW), lds, s, a);
     else
         hipLaunchKernelGGL((coarse_scan_kernel<KS, CS_MODE_FILTER, SRC16, MASKED, false, NW>), dim3(grid), dim3(64 * NW), lds, s, a);
-    return check_launch();
+    return aura_check_launch();
 }
 
 inline int dispatch_coarse(const CoarseArgs& a, int mode, int grid, hipStream_t s) {

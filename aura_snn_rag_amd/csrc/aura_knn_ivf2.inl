@@ -222,7 +222,7 @@ __global__ __launch_bounds__(256) void ivf2_qprep_kernel(const float* __restrict
     for (int off = 32; off > 0; off >>= 1) e2 += __shfl_xor(e2, off);
     if (lane == 0) {
         inv[q] = iqv;
-        eq_q[q] = coarse_eq_from_e2(e2, (float)D);          // query part of the error bound (coarse_prep_kernel)
+        eq_q[q] = aura_eq_from_e2(e2, (float)D);          // query part of the error bound (coarse_prep_kernel)
     }
     if (lane < 8) qslot[q * 8 + lane] = -1;                 // probes without a slot (dropped ids) stay -1
 }
@@ -425,12 +425,12 @@ inline int launch_coarse_ivf(const CoarseArgs& a, int mode, int grid, hipStream_
     constexpr int BLKQ = NW * 16 * QBT;
     const size_t lds = (size_t)cs_lds_slots<true, false, NW>() * (KS * 1024 + CS_AUX_BYTES) + (size_t)cs_cand_buf<NW, QBT>() * 12 +
                        BLKQ * 4 + BLKQ * 4;
-    if (ensure_lds_attr(reinterpret_cast<const void*>(coarse_scan_kernel<KS, CS_MODE_SAMPLE, true, false, true, NW, QBT>), (int)lds) ||
-        ensure_lds_attr(reinterpret_cast<const void*>(coarse_scan_kernel<KS, CS_MODE_FILTER, true, false, true, NW, QBT>), (int)lds))
+    if (aura_ensure_lds_attr(reinterpret_cast<const void*>(coarse_scan_kernel<KS, CS_MODE_SAMPLE, true, false, true, NW, QBT>), (int)lds) ||
+        aura_ensure_lds_attr(reinterpret_cast<const void*>(coarse_scan_kernel<KS, CS_MODE_FILTER, true, false, true, NW, QBT>), (int)lds))
         return AURA_E_LAUNCH;
     if (mode == CS_MODE_SAMPLE)
         hipLaunchKernelGGL((coarse_scan_kernel<KS, CS_MODE_SAMPLE, true, false, true, NW, QBT>), dim3(grid), dim3(64 * NW), lds, s, a);
     else
         hipLaunchKernelGGL((coarse_scan_kernel<KS, CS_MODE_FILTER, true, false, true, NW, QBT>), dim3(grid), dim3(64 * NW), lds, s, a);
-    return check_launch();
+    return aura_check_launch();
 }

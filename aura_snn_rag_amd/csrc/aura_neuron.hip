@@ -20,6 +20,7 @@
 #include <stdlib.h>
 
 #include "../../include/aura_hip.h"
+#include "aura_common.inl"
 
 #pragma clang fp contract(off)
 
@@ -560,10 +561,6 @@ __global__ __launch_bounds__(64) void seq_ntw_kernel(Model m, const float* __res
 // ------------------------------------------------------------------------------------------
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
-inline int check_launch() {
-    return hipGetLastError() == hipSuccess ? AURA_OK : AURA_E_LAUNCH;
-}
-
 inline int rtc_grid(int64_t items) {
     // memory-bound streaming: cap at 256 CUs x 8 blocks and grid-stride the rest
     int64_t blocks = (items + 255) / 256;
@@ -604,7 +601,7 @@ int launch_nt(const Model& m, const float* I, float* S, float* st0, float* st1, 
     else
         hipLaunchKernelGGL((seq_nt_kernel<Model, 1>), dim3((unsigned)blocks), dim3(64 * NT_WAVES),
                            0, s, m, I, S, st0, st1, N, T);
-    return check_launch();
+    return aura_check_launch();
 }
 
 template <class Model>
@@ -620,7 +617,7 @@ int launch_rtc_f32(const Model& m, const float* x, float* out, float* st0, float
     else
         hipLaunchKernelGGL((seq_rtc_kernel<Model, float, 1, false, false, false>),
                            dim3(rtc_grid(R * C)), dim3(256), 0, s, m, x, out, st0, st1, R, T, C);
-    return check_launch();
+    return aura_check_launch();
 }
 
 template <typename T, int VEC, bool BF16, bool POW2L>
@@ -640,7 +637,7 @@ int launch_gif(const GifModel<BF16, POW2L>& m, const void* h, void* out, void* v
     else if (mo) AURA_GIF_LAUNCH(false, true);
     else AURA_GIF_LAUNCH(false, false);
 #undef AURA_GIF_LAUNCH
-    return check_launch();
+    return aura_check_launch();
 }
 
 }  // namespace

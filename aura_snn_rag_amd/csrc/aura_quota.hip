@@ -25,6 +25,7 @@
 #include <stdint.h>
 
 #include "../../include/aura_hip.h"
+#include "aura_common.inl"
 
 #pragma clang fp contract(off)
 
@@ -51,13 +52,10 @@ struct QState {                         // one per scope, narrowed in place by t
     uint32_t off;                       // first entry of the scope's output range
 };
 
-inline int check_launch_q() { return hipGetLastError() == hipSuccess ? AURA_OK : AURA_E_LAUNCH; }
-inline int64_t align256(int64_t x) { return (x + 255) / 256 * 256; }
-
 // index of `w` (metadata column 3 as stored) among the ascending scope tags, or -1
 __device__ __forceinline__ int q_scope(float w, const int* s_tags, int S) {
-    if (!(w > -1.0f && w < 16777216.0f)) return -1;
-    const int tag = (int)w;
+    const int tag = aura_row_tag(w);
+    if (tag == aura_no_tag) return -1;
     int lo = 0, hi = S;                 // first index whose tag is >= tag
     while (lo < hi) {
         const int mid = (lo + hi) >> 1;
@@ -339,14 +337,14 @@ int aura_bank_tag_counts(const float* meta, int64_t count, const int32_t* scope_
     if (blocks > Q_MAX_BLOCKS) blocks = Q_MAX_BLOCKS;
     hipLaunchKernelGGL(q_tag_counts_kernel, dim3((unsigned)blocks), dim3(256), 0, s, meta, count, scope_tags,
                        (int)n_scopes, reinterpret_cast<uint32_t*>(out));
-    return check_launch_q();
+    return aura_check_launch();
 }
 
 // workspace: [QState x 64] [64 output cursors] [histograms x passes] [records (8 B x count)]
 int64_t aura_bank_select_weakest_scoped_workspace_bytes(int64_t count, int64_t n_scopes) {
     if (count < 1 || count > 0x7ffffff0LL || n_scopes < 1 || n_scopes > Q_MAX_SCOPES) return -1;
-    return align256(Q_MAX_SCOPES * (int64_t)sizeof(QState)) + align256(Q_MAX_SCOPES * 4) + Q_MAX_PASSES * Q_HIST_BYTES +
-           align256(8 * count);
+    return aura_align256(Q_MAX_SCOPES * (int64_t)sizeof(QState)) + aura_align256(Q_MAX_SCOPES * 4) + Q_MAX_PASSES * Q_HIST_BYTES +
+           aura_align256(8 * count);
 }
 
 int aura_bank_select_weakest_scoped(const float* meta, int64_t count, float now, const int32_t* scope_tags,
@@ -369,9 +367,9 @@ int aura_bank_select_weakest_scoped(const float* meta, int64_t count, float now,
     const int S = (int)n_scopes;
     char* w = static_cast<char*>(workspace);
     QState* st = reinterpret_cast<QState*>(w);
-    w += align256(Q_MAX_SCOPES * (int64_t)sizeof(QState));
+    w += aura_align256(Q_MAX_SCOPES * (int64_t)sizeof(QState));
     uint32_t* out_count = reinterpret_cast<uint32_t*>(w);
-    w += align256(Q_MAX_SCOPES * 4);
+    w += aura_align256(Q_MAX_SCOPES * 4);
     uint32_t* hist = reinterpret_cast<uint32_t*>(w);
     w += Q_MAX_PASSES * Q_HIST_BYTES;
     uint2* rec = reinterpret_cast<uint2*>(w);
@@ -385,24 +383,24 @@ int aura_bank_select_weakest_scoped(const float* meta, int64_t count, float now,
     const dim3 grid((unsigned)blocks), wg(256);
     hipLaunchKernelGGL(q_keys_kernel, grid, wg, 0, s, reinterpret_cast<const float4*>(meta), count, now, scope_tags, S, rec,
                        hist);
-    int rc = check_launch_q();
+    int rc = aura_check_launch();
     if (rc) return rc;
     for (int i = 0; i < P; ++i) {
         uint32_t* h = hist + (int64_t)i * (Q_HIST_BYTES / 4);
         if (i > 0) {
             hipLaunchKernelGGL(q_pass_kernel, grid, wg, 0, s, rec, count, st, origin, S, shifts[i - 1], shifts[i], widths[i],
                                h);
-            rc = check_launch_q();
+            rc = aura_check_launch();
             if (rc) return rc;
         }
         hipLaunchKernelGGL(q_resolve_kernel, dim3((unsigned)S), wg, 0, s, st, h, i == 0 ? 1 : 0, i == P - 1 ? 1 : 0,
                            shifts[i], widths[i], incoming, quota, S, out_capacity, out_held, out_x, out_slots, out_comp);
-        rc = check_launch_q();
+        rc = aura_check_launch();
         if (rc) return rc;
     }
     hipLaunchKernelGGL(q_compact_kernel, grid, wg, 0, s, rec, count, st, origin, S, out_capacity, out_count, out_slots,
                        out_comp, bitmap);
-    return check_launch_q();
+    return aura_check_launch();
 }
 
 }  // extern "C"

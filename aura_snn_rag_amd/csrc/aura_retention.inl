@@ -1,10 +1,11 @@
 // aura_retention.inl -- the retention key and its order, shared by the selections of aura_bank.hip and aura_quota.hip
-// (one definition: the two must rank a row alike to the last bit).  Included inside each file's anonymous namespace.
-//   key(r) = strength(r) * expf(-(now - timestamp(r)) / 3600)
+// (one definition: the two must rank a row alike to the last bit).  Included inside each file's anonymous namespace;
+// needs aura_common.inl.
+//   key(r) = strength(r) * aura_recency(now, timestamp(r))        -- expf(-(now - timestamp) / 3600)
 //   comp(r) = ordered_u32(key(r)) << 32 | (r - origin) mod count      -- ascending comp = the eviction order
 
 __device__ __forceinline__ float retention_key(float strength, float timestamp, float now) {
-    return strength * expf(-(now - timestamp) / 3600.0f);
+    return strength * aura_recency(now, timestamp);
 }
 
 // order-preserving map fp32 -> u32: NaN lowest (0), then -inf .. -0 == +0 .. +inf

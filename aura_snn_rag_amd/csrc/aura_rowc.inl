@@ -1,6 +1,6 @@
 // aura_rowc.inl -- per-row score constants of the two-stage recall, shared by aura_knn.hip (prep kernels,
 // the cached constants of the inverted lists) and aura_bank.hip (aura_ivf2_append keeps a cached table
-// current).  See aura_knn_coarse.inl's header for the bound these constants implement.
+// current).  See aura_knn_coarse.inl's header for the bound these constants implement.  Needs aura_common.inl.
 #pragma once
 
 // E_fix = 2 D 2^-24 + 1e-5: fp32 accumulation of D terms in either pipe + association of the score formulas
@@ -18,7 +18,7 @@ __device__ __forceinline__ float4 coarse_row_constants(const float4 m, float inv
                                                        float now, float e_fix, float e_worst, float eq_worst,
                                                        float w) {
     const float strength = m.x;
-    const float tw = 0.2f * expf(-(now - m.y) / 3600.0f);
+    const float tw = aura_time_weight(now, m.y);
     float A, err;
     if (rho_row) {
         A = 0.5f * strength;

@@ -26,12 +26,12 @@
 #include <stdint.h>
 
 #include "../../include/aura_hip.h"
+#include "aura_common.inl"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef unsigned long long u64;
 
 constexpr int SC_THREADS = 256;
@@ -54,10 +54,6 @@ constexpr int sc_lds_bytes() {
     return (((SC_QT + SC_RT) * SC_STRIDE > SC_QT * SC_SSTRIDE) ? (SC_QT + SC_RT) * SC_STRIDE : SC_QT * SC_SSTRIDE) * 4;
 }
 
-inline int check_launch_s() { return hipGetLastError() == hipSuccess ? AURA_OK : AURA_E_LAUNCH; }
-
-inline int64_t align256(int64_t x) { return (x + 255) / 256 * 256; }
-
 struct ScLayout {
     int64_t counts, total, base, list, inv_q, part_s, part_r, bytes, blocks, list_cap;
 };
@@ -67,13 +63,13 @@ inline ScLayout sc_layout(int64_t count, int64_t nq, int64_t k, int64_t n_scopes
     w.blocks = (count + SC_BUILD_ROWS - 1) / SC_BUILD_ROWS;
     w.list_cap = 2 * count;                 // a row is in at most two scopes of a call: its tag's and "any tag"
     int64_t o = 0;
-    w.counts = o; o += align256(n_scopes * w.blocks * 4);
-    w.total = o;  o += align256(SC_MAX_SCOPES * 4);
-    w.base = o;   o += align256(SC_MAX_SCOPES * 4);
-    w.list = o;   o += align256(w.list_cap * 4);
-    w.inv_q = o;  o += align256(nq * 4);
-    w.part_s = o; o += splits > 1 ? align256(splits * nq * k * 4) : 0;
-    w.part_r = o; o += splits > 1 ? align256(splits * nq * k * 4) : 0;
+    w.counts = o; o += aura_align256(n_scopes * w.blocks * 4);
+    w.total = o;  o += aura_align256(SC_MAX_SCOPES * 4);
+    w.base = o;   o += aura_align256(SC_MAX_SCOPES * 4);
+    w.list = o;   o += aura_align256(w.list_cap * 4);
+    w.inv_q = o;  o += aura_align256(nq * 4);
+    w.part_s = o; o += splits > 1 ? aura_align256(splits * nq * k * 4) : 0;
+    w.part_r = o; o += splits > 1 ? aura_align256(splits * nq * k * 4) : 0;
     w.bytes = o;
     return w;
 }
@@ -98,7 +94,7 @@ __device__ __forceinline__ int sc_code(const float* __restrict__ meta, int64_t r
     const float4 m = *reinterpret_cast<const float4*>(meta + row * 4);
     if (!sc_pass(m, c)) return -2;
     const bool any = S > 0 && s_tags[0] == -1;
-    const int tag = (m.w > -1.0f && m.w < 16777216.0f) ? (int)m.w : -2;
+    const int tag = aura_row_tag(m.w);          // aura_no_tag = -2 equals no scope tag
     int lo = any ? 1 : 0, hi = S;           // first index whose tag is >= tag
     while (lo < hi) {
         const int mid = (lo + hi) >> 1;
@@ -108,6 +104,8 @@ __device__ __forceinline__ int sc_code(const float* __restrict__ meta, int64_t r
     return any ? -1 : -2;
 }
 
+// 1 / ||q||, summed unfused with a 64-stride.  aura_knn.hip's row_inv_norm_kernel uses an fmaf chain over float4s: the two
+// differ in the last bits, and merging them would move scoped scores.
 __global__ __launch_bounds__(SC_THREADS) void sc_query_norm_kernel(const float* __restrict__ queries, int64_t nq,
                                                                    int64_t D, float* __restrict__ inv_q,
                                                                    int32_t* __restrict__ flag) {
@@ -384,7 +382,7 @@ __global__ __launch_bounds__(SC_THREADS) void sc_score_kernel(ScArgs a) {
             __syncthreads();
         }
 
-        // ---- epilogue: the combined score (same arithmetic as aura_knn.hip) into the score tile, which takes the
+        // ---- epilogue: the combined score (aura_common.inl) into the score tile, which takes the
         // staging buffer's place (barrier above).  Accumulator element e of lane (li, lh): query (e & 3) + 8 (e >> 2)
         // + 4 lh of its half, row li of the wave's 32
         {
@@ -396,8 +394,7 @@ __global__ __launch_bounds__(SC_THREADS) void sc_score_kernel(ScArgs a) {
                 inv_m = a.inv_norm[r];
                 const float4 m = *reinterpret_cast<const float4*>(a.meta + (int64_t)r * 4);
                 strength = m.x;
-                const float age = a.now - m.y;
-                tw = 0.2f * expf(-age / 3600.0f);
+                tw = aura_time_weight(a.now, m.y);
                 if (a.q_loc)
                     for (int d = 0; d < a.sdims && d < 4; ++d) lx[d] = a.loc[(int64_t)r * a.sdims + d];
             }
@@ -407,6 +404,7 @@ __global__ __launch_bounds__(SC_THREADS) void sc_score_kernel(ScArgs a) {
                 for (int e = 0; e < 16; ++e) {
                     const int ql = h * 32 + (e & 3) + 8 * (e >> 2) + 4 * lh;
                     const int qi = s_q[ql];
+                    // aura_score_spatial (aura_common.inl), written out: the call makes this kernel 32 instructions longer
                     const float sim = (h ? acc1[e] : acc0[e]) * s_iq[ql] * inv_m;
                     float comb = 0.5f * sim;
                     if (a.q_loc && qi >= 0) {
@@ -507,7 +505,7 @@ int aura_bank_set_tags(float* meta, int64_t count, const int64_t* slots, const i
     if (n > 0x7fffffffLL * 256) return AURA_E_INVAL;
     hipLaunchKernelGGL(sc_set_tags_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
                        static_cast<hipStream_t>(stream), meta, count, slots, tags, n);
-    return check_launch_s();
+    return aura_check_launch();
 }
 
 int64_t aura_knn_scoped_workspace_bytes(int64_t count, int64_t nq, int64_t k, int64_t n_scopes, int64_t splits) {
@@ -548,17 +546,17 @@ int aura_knn_search_scoped(const float* bank, const float* inv_norm, const float
 
     hipLaunchKernelGGL(sc_query_norm_kernel, dim3((unsigned)((nq + 3) / 4)), dim3(SC_THREADS), 0, s, queries, nq, D,
                        inv_q, flag_out);
-    if ((rc = check_launch_s())) return rc;
+    if ((rc = aura_check_launch())) return rc;
     hipLaunchKernelGGL(sc_count_kernel, dim3((unsigned)w.blocks), dim3(SC_THREADS), 0, s, meta, count, c, scope_tags,
                        S, counts, w.blocks);
-    if ((rc = check_launch_s())) return rc;
+    if ((rc = aura_check_launch())) return rc;
     hipLaunchKernelGGL(sc_scan_kernel, dim3((unsigned)S), dim3(SC_THREADS), 0, s, counts, w.blocks, total);
-    if ((rc = check_launch_s())) return rc;
+    if ((rc = aura_check_launch())) return rc;
     hipLaunchKernelGGL(sc_base_kernel, dim3(1), dim3(64), 0, s, total, S, base);
-    if ((rc = check_launch_s())) return rc;
+    if ((rc = aura_check_launch())) return rc;
     hipLaunchKernelGGL(sc_scatter_kernel, dim3((unsigned)w.blocks), dim3(SC_THREADS), 0, s, meta, count, c,
                        scope_tags, S, counts, w.blocks, base, list, w.list_cap);
-    if ((rc = check_launch_s())) return rc;
+    if ((rc = aura_check_launch())) return rc;
 
     ScArgs a{};
     a.bank = bank; a.inv_norm = inv_norm; a.meta = meta; a.loc = loc; a.queries = queries; a.q_loc = q_loc;
@@ -574,11 +572,11 @@ int aura_knn_search_scoped(const float* bank, const float* inv_norm, const float
     const dim3 grid((unsigned)n_tiles, (unsigned)splits);
     if (vec) hipLaunchKernelGGL(sc_score_kernel<true>, grid, dim3(SC_THREADS), sc_lds_bytes(), s, a);
     else hipLaunchKernelGGL(sc_score_kernel<false>, grid, dim3(SC_THREADS), sc_lds_bytes(), s, a);
-    if ((rc = check_launch_s())) return rc;
+    if ((rc = aura_check_launch())) return rc;
     if (splits > 1) {
         hipLaunchKernelGGL(sc_merge_kernel, dim3((unsigned)((nq + 3) / 4)), dim3(SC_THREADS), 0, s, a.dst_s, a.dst_r,
                            nq, k, (int)splits, out_scores, out_rows);
-        if ((rc = check_launch_s())) return rc;
+        if ((rc = aura_check_launch())) return rc;
     }
     return AURA_OK;
 }

@@ -15,6 +15,7 @@
 #include <stdint.h>
 
 #include "../../include/aura_hip.h"
+#include "aura_common.inl"
 
 #pragma clang fp contract(off)
 
@@ -35,7 +36,6 @@ inline int grid_for(int64_t items) {
     int64_t b = (items + 255) / 256;
     return (int)(b > 2048 ? 2048 : (b < 1 ? 1 : b));
 }
-inline int check_launch() { return hipGetLastError() == hipSuccess ? AURA_OK : AURA_E_LAUNCH; }
 
 struct GifP { float decay, Lf, alpha, thr0; };
 
@@ -740,7 +740,7 @@ int aura_gif_train_forward(const float* h, float* spikes, float* v, float* theta
     const GifP p{decay, (float)L, alpha, threshold};
     AURA_VEC_DISPATCH(gif_train_fwd_kernel, rows * (H / 4), rows * H, vec, p, h, spikes, v, theta, save_a,
                       save_theta, rows, T, H);
-    return check_launch();
+    return aura_check_launch();
 }
 
 int aura_gif_backward(const float* save_a, const float* save_theta, const float* g_spikes, float* g_h,
@@ -755,7 +755,7 @@ int aura_gif_backward(const float* save_a, const float* save_theta, const float*
     const GifP p{decay, (float)L, alpha, threshold};
     AURA_VEC_DISPATCH(gif_bwd_kernel, rows * (H / 4), rows * H, vec, p, save_a, save_theta, g_spikes, g_h,
                       g_v, g_theta, rows, T, H);
-    return check_launch();
+    return aura_check_launch();
 }
 
 int aura_gif_train_forward_bf16(const uint16_t* h, uint16_t* spikes, uint16_t* v, uint16_t* theta, uint16_t* save_a,
@@ -772,7 +772,7 @@ int aura_gif_train_forward_bf16(const uint16_t* h, uint16_t* spikes, uint16_t* v
                                 spikes, v, theta, save_a, save_theta, rows, T, H);
     else hipLaunchKernelGGL((gif_train_fwd_bf16_kernel<1>), dim3(grid_for(rows * H)), dim3(256), 0, s, p, h, spikes, v,
                             theta, save_a, save_theta, rows, T, H);
-    return check_launch();
+    return aura_check_launch();
 }
 
 int aura_gif_backward_bf16(const uint16_t* save_a, const uint16_t* save_theta, const uint16_t* g_spikes, uint16_t* g_h,
@@ -789,7 +789,7 @@ int aura_gif_backward_bf16(const uint16_t* save_a, const uint16_t* save_theta, c
                                 save_theta, g_spikes, g_h, g_v, g_theta, rows, T, H);
     else hipLaunchKernelGGL((gif_bwd_bf16_kernel<1>), dim3(grid_for(rows * H)), dim3(256), 0, s, p, save_a, save_theta,
                             g_spikes, g_h, g_v, g_theta, rows, T, H);
-    return check_launch();
+    return aura_check_launch();
 }
 
 int aura_lif_train_forward(const float* x, const float* mem_in, const float* beta,
@@ -803,7 +803,7 @@ int aura_lif_train_forward(const float* x, const float* mem_in, const float* bet
                      aligned16(threshold) && aligned16(spikes) && aligned16(mem_out) && aligned16(pre);
     AURA_VEC_DISPATCH(lif_train_fwd_kernel, B * (size / 4), B * size, vec, x, mem_in, beta, threshold,
                       spikes, mem_out, pre, B, size);
-    return check_launch();
+    return aura_check_launch();
 }
 
 int aura_lif_backward(const float* pre, const float* g_spikes, const float* g_mem, const float* beta,
@@ -819,7 +819,7 @@ int aura_lif_backward(const float* pre, const float* g_spikes, const float* g_me
                      aligned16(g_mem_prev) && aligned16(raw_slope);
     AURA_VEC_DISPATCH(lif_bwd_kernel, B * (size / 4), B * size, vec, pre, g_spikes, g_mem, beta, threshold,
                       slope, g_x, g_mem_prev, raw_slope, B, size);
-    return check_launch();
+    return aura_check_launch();
 }
 
 int aura_gif_prosody_run(const float* h, const float* gains, float* spikes, float* v, float* theta,
@@ -833,7 +833,7 @@ int aura_gif_prosody_run(const float* h, const float* gains, float* spikes, floa
     const GifP p{decay, (float)L, alpha, threshold};
     AURA_VEC_DISPATCH(gif_prosody_kernel, rows * (H / 4), rows * H, vec, p, strength, h, gains, spikes, v,
                       theta, rows, T, H);
-    return check_launch();
+    return aura_check_launch();
 }
 
 int aura_gif_prosody_train_forward(const float* h, const float* gains, float* spikes, float* v, float* theta,
@@ -849,7 +849,7 @@ int aura_gif_prosody_train_forward(const float* h, const float* gains, float* sp
     const GifP p{decay, (float)L, alpha, threshold};
     AURA_VEC_DISPATCH(gif_prosody_train_fwd_kernel, rows * (H / 4), rows * H, vec, p, strength, h, gains, spikes,
                       v, theta, save_a, save_theta, rows, T, H);
-    return check_launch();
+    return aura_check_launch();
 }
 
 int aura_gif_prosody_backward(const float* save_a, const float* save_theta, const float* h, const float* gains,
@@ -865,7 +865,7 @@ int aura_gif_prosody_backward(const float* save_a, const float* save_theta, cons
     const GifP p{decay, (float)L, alpha, threshold};
     AURA_VEC_DISPATCH(gif_prosody_bwd_kernel, rows * (H / 4), rows * H, vec, p, strength, save_a, save_theta, h,
                       gains, g_spikes, g_h, g_gains, g_v, g_theta, rows, T, H);
-    return check_launch();
+    return aura_check_launch();
 }
 
 #define AURA_VEC8_DISPATCH(KERNEL8, KERNEL1, ROWS, H, VECOK, ...)                                        \
@@ -886,7 +886,7 @@ int aura_gif_prosody_run_bf16(const uint16_t* h, const uint16_t* gains, uint16_t
     uint16_t* none = nullptr;
     AURA_VEC8_DISPATCH((gif_prosody_fwd_bf16_kernel<8, false>), (gif_prosody_fwd_bf16_kernel<1, false>), rows, H, vec, p,
                        strength, h, gains, spikes, v, theta, none, none, rows, T, H);
-    return check_launch();
+    return aura_check_launch();
 }
 
 int aura_gif_prosody_train_forward_bf16(const uint16_t* h, const uint16_t* gains, uint16_t* spikes, uint16_t* v,
@@ -902,7 +902,7 @@ int aura_gif_prosody_train_forward_bf16(const uint16_t* h, const uint16_t* gains
     const GifP p{decay, (float)L, alpha, threshold};
     AURA_VEC8_DISPATCH((gif_prosody_fwd_bf16_kernel<8, true>), (gif_prosody_fwd_bf16_kernel<1, true>), rows, H, vec, p,
                        strength, h, gains, spikes, v, theta, save_a, save_theta, rows, T, H);
-    return check_launch();
+    return aura_check_launch();
 }
 
 int aura_gif_prosody_backward_bf16(const uint16_t* save_a, const uint16_t* save_theta, const uint16_t* h,
@@ -918,7 +918,7 @@ int aura_gif_prosody_backward_bf16(const uint16_t* save_a, const uint16_t* save_
     const GifP p{decay, (float)L, alpha, threshold};
     AURA_VEC8_DISPATCH((gif_prosody_bwd_bf16_kernel<8>), (gif_prosody_bwd_bf16_kernel<1>), rows, H, vec, p, strength,
                        save_a, save_theta, h, gains, g_spikes, g_h, g_gains, g_v, g_theta, rows, T, H);
-    return check_launch();
+    return aura_check_launch();
 }
 
 int aura_lif_run_bf16(const uint16_t* x, uint16_t* spikes, uint16_t* mem, const uint16_t* beta,
@@ -933,7 +933,7 @@ int aura_lif_run_bf16(const uint16_t* x, uint16_t* spikes, uint16_t* mem, const 
     const uint16_t* mem_in = mem;
     AURA_VEC8_DISPATCH((lif_bf16_kernel<8, false>), (lif_bf16_kernel<1, false>), B, size, vec, x, mem_in, beta, threshold,
                        spikes, mem, none, B, T, size);
-    return check_launch();
+    return aura_check_launch();
 }
 
 int aura_lif_train_forward_bf16(const uint16_t* x, const uint16_t* mem_in, const uint16_t* beta,
@@ -948,7 +948,7 @@ int aura_lif_train_forward_bf16(const uint16_t* x, const uint16_t* mem_in, const
     const int64_t one = 1;
     AURA_VEC8_DISPATCH((lif_bf16_kernel<8, true>), (lif_bf16_kernel<1, true>), B, size, vec, x, mem_in, beta, threshold,
                        spikes, mem_out, pre, B, one, size);
-    return check_launch();
+    return aura_check_launch();
 }
 
 int aura_lif_backward_bf16(const uint16_t* pre, const uint16_t* g_spikes, const uint16_t* g_mem, const uint16_t* beta,
@@ -964,7 +964,7 @@ int aura_lif_backward_bf16(const uint16_t* pre, const uint16_t* g_spikes, const 
                      aligned16(g_mem_prev);
     AURA_VEC8_DISPATCH((lif_bwd_bf16_kernel<8>), (lif_bwd_bf16_kernel<1>), B, size, vec, pre, g_spikes, g_mem, beta,
                        threshold, slope, g_x, g_mem_prev, raw_slope, B, size);
-    return check_launch();
+    return aura_check_launch();
 }
 
 }  // extern "C"

@@ -8,6 +8,7 @@
 #include <stdint.h>
 
 #include "../../include/aura_hip.h"
+#include "aura_common.inl"
 
 #pragma clang fp contract(off)
 
@@ -157,7 +158,7 @@ extern "C" int aura_addition_linear_backward(const float* x, const float* weight
         hipLaunchKernelGGL((addition_linear_bwd_kernel<false>), dim3((unsigned)gk, (unsigned)gr), dim3(256), 0, s, x,
                            weight_patterns, g_out, g_w, B, in_features, out_features);   // (B == 0: zeros)
     }
-    return hipGetLastError() == hipSuccess ? AURA_OK : AURA_E_LAUNCH;
+    return aura_check_launch();
 }
 
 extern "C" int aura_addition_linear(const float* x, const float* weight_patterns, const float* bias,
@@ -171,5 +172,5 @@ extern "C" int aura_addition_linear(const float* x, const float* weight_patterns
     hipLaunchKernelGGL(addition_linear_kernel, dim3((unsigned)gx, (unsigned)gy), dim3(256), 0,
                        static_cast<hipStream_t>(stream), x, weight_patterns, bias, out, B,
                        in_features, out_features);
-    return hipGetLastError() == hipSuccess ? AURA_OK : AURA_E_LAUNCH;
+    return aura_check_launch();
 }
