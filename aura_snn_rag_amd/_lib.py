@@ -9,7 +9,7 @@ from __future__ import annotations
 import ctypes
 import os
 import threading
-from ctypes import c_char_p, c_float, c_int, c_int32, c_int64, c_uint32, c_void_p
+from ctypes import c_char_p, c_float, c_int, c_int32, c_int64, c_uint32, c_uint64, c_void_p
 from typing import Optional
 
 LIB_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib")
@@ -28,7 +28,7 @@ KNN_FLAG_LISTS_STALE = 128     # bit of the overflow flag: the inverted lists dr
 KNN_FLAG_NO_CANDIDATES = 64   # bit of the overflow flag: a query without any candidate row (not an overflow)
 
 # name -> (restype, argtypes); mirrors include/aura_hip.h one to one
-P, I64, I32, F, I, U32 = c_void_p, c_int64, c_int32, c_float, c_int, c_uint32
+P, I64, I32, F, I, U32, U64 = c_void_p, c_int64, c_int32, c_float, c_int, c_uint32, c_uint64
 SIGNATURES = {
     "aura_version": (c_char_p, []),
     "aura_izh_run_nt": (I, [P, P, P, P, F, F, F, F, F, I64, I64, P]),
@@ -52,6 +52,9 @@ SIGNATURES = {
     "aura_bank_select_weakest_scoped": (I, [P, I64, F, P, P, P, P, I64, I64, P, P, P, P, P, P, I64, P]),
     "aura_bank_reinforce_workspace_bytes": (I64, [I64]),
     "aura_bank_reinforce": (I, [P, I64, P, I64, F, F, P, I64, P]),
+    "aura_bank_replay_keys": (I, [P, I64, F, I, F, P, I64, I, F, F, F, U64, U64, P, P, P]),
+    "aura_bank_replay_workspace_bytes": (I64, [I64, I64]),
+    "aura_bank_replay": (I, [P, I64, F, I, F, P, I64, I, F, F, F, U64, U64, I64, P, P, P, P, I64, P]),
     "aura_diverse_select_workspace_bytes": (I64, [I64, I64, I64]),
     "aura_diverse_select": (I, [P, P, I64, I64, P, P, I64, I64, I64, F, F, P, P, P, I64, P]),
     "aura_bank_find_repeats_workspace_bytes": (I64, [I64]),

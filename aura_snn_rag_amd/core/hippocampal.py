@@ -152,6 +152,18 @@ class BankConsolidationReport:
     old_to_new: np.ndarray
 
 
+@dataclass
+class ReplaySample:
+    """What ``replay`` drew (device tensors; reading none of them is forced by the call): ``rows`` int32 [n], the drawn
+    bank rows in draw order, ``-1`` where the scope held fewer than ``n`` eligible memories; ``keys`` fp32 [n], their
+    draw keys (descending, ``-inf`` at the padding); ``features`` [n, D], ``memory_features[rows]`` with zeros at the
+    padding, or None; ``eligible``, an int64 scalar: how many memories the draw could have taken."""
+    rows: torch.Tensor
+    keys: torch.Tensor
+    features: Optional[torch.Tensor]
+    eligible: torch.Tensor
+
+
 class HippocampalFormation(nn.Module):
     # above this many rows the inverted lists (each probed list read once per batch) beat a masked
     # pass over every row
@@ -174,7 +186,8 @@ class HippocampalFormation(nn.Module):
                  merge_reinforce: float = 0.1,
                  merge_cap: float = 1.0,
                  merge_within_tags: bool = False,
-                 tag_quota=None):
+                 tag_quota=None,
+                 replay_seed: int = 0):
         super().__init__()
         # consolidating writes (create_episodic_memories): None = every row is stored, today's behaviour
         self._check_merge(merge_similarity, merge_reinforce, merge_cap)
@@ -259,6 +272,11 @@ class HippocampalFormation(nn.Module):
                     self.set_tag_quota(t, q)
             else:
                 self.set_tag_quota(None, tag_quota)
+        # replay (the rule: include/aura_hip.h, "Replay"): the seed of every draw and how many replay() has numbered
+        self.replay_seed = int(replay_seed)
+        if not (0 <= self.replay_seed < (1 << 64)):
+            raise ValueError(f"replay_seed must be in [0, 2^64), got {replay_seed!r}")
+        self._replay_draws = 0
         self.register_load_state_dict_post_hook(lambda module, incompatible: module._invalidate_norms())
 
     # ------------------------------------------------------------------ plumbing
@@ -1759,6 +1777,8 @@ class HippocampalFormation(nn.Module):
         if self._tag_quota_map or self._tag_quota_default is not None:  # (only then: other states keep their keys)
             state["tag_quota"] = {"default": self._tag_quota_default, "tags": dict(self._tag_quota_map)}
             state["tag_origin"] = dict(self._tag_origin)
+        if self._replay_draws:                          # (only then: a bank that never replayed keeps its keys)
+            state["replay_draws"] = self._replay_draws
         return state
 
     def load_bank_state(self, state: Dict[str, Any]) -> None:
@@ -1787,6 +1807,7 @@ class HippocampalFormation(nn.Module):
             for t, q in state["tag_quota"].get("tags", {}).items():
                 self.set_tag_quota(int(t), q)
             self._tag_origin = {int(t): int(c) for t, c in state.get("tag_origin", {}).items()}
+        self._replay_draws = int(state.get("replay_draws", 0))
         self._invalidate_norms()
 
     def gather_features(self, rows: torch.Tensor) -> torch.Tensor:
@@ -1834,6 +1855,66 @@ class HippocampalFormation(nn.Module):
         now = time.time() if now is None else now
         return ops.bank_select_weakest(self.memory_metadata, self.memory_count, now,
                                        self._write_cursor % self.max_memories, int(n))
+
+    # ------------------------------------------------------------------ replay
+    def _replay_scope(self, priority, alpha, tags, newer_than, older_than, min_strength, seed, draw) -> Dict[str, Any]:
+        seed = self.replay_seed if seed is None else seed
+        draw = self._replay_draws if draw is None else draw
+        return dict(priority=priority, alpha=alpha, tags=tags, newer_than=newer_than, older_than=older_than,
+                    min_strength=min_strength, seed=seed, draw=draw)
+
+    def replay_keys(self, *, priority: str = 'key', alpha: float = 1.0, tags=None, newer_than: Optional[float] = None,
+                    older_than: Optional[float] = None, min_strength: Optional[float] = None,
+                    seed: Optional[int] = None, draw: Optional[int] = None,
+                    now: Optional[float] = None) -> torch.Tensor:
+        """fp32 [memory_count]: the draw key of every held row for ``(seed, draw)``, ``-inf`` for a row ``replay``
+        could not take (read-only; ``draw=None``: the number the next ``replay()`` will use).  ``replay`` returns the
+        top ``n`` of these by ``(key descending, row ascending)``."""
+        now = time.time() if now is None else now
+        return ops.bank_replay_keys(self.memory_metadata, self.memory_count, now,
+                                    **self._replay_scope(priority, alpha, tags, newer_than, older_than, min_strength,
+                                                         seed, draw))
+
+    def replay(self, n: int, *, priority: str = 'key', alpha: float = 1.0, tags=None,
+               newer_than: Optional[float] = None, older_than: Optional[float] = None,
+               min_strength: Optional[float] = None, seed: Optional[int] = None, draw: Optional[int] = None,
+               now: Optional[float] = None, reinforce: Optional[float] = None, reinforce_cap: float = 1.0,
+               touch: bool = False, return_features: bool = True) -> ReplaySample:
+        """Draw ``n`` held memories nobody asked for, without replacement, seeded: the sample a sleep phase rehearses.
+        A memory is the likelier the larger ``p = exp(alpha * lw)``: the first is row ``r`` with probability
+        ``p_r / sum p``, each later one is drawn the same way from what is left (the rule: ``include/aura_hip.h``,
+        "Replay").  ``priority='key'``: ``p`` = (strength x recency) ^ alpha, the retention key; ``'strength'``;
+        ``'uniform'``.  ``alpha`` in [0, 16]: 0 = uniform over the eligible rows, larger = greedier.  The scope is that
+        of a scoped recall: ``tags`` (None = any, an int, or up to 64 as a union; 0 = untagged), ``newer_than``,
+        ``older_than``, ``min_strength``; under ``'key'`` / ``'strength'`` a memory also needs ``0 < strength < inf``.
+        ``n`` beyond ``memory_count`` is clamped; a scope of fewer eligible memories pads with ``-1``.
+        ``seed`` defaults to the bank's ``replay_seed``.  ``draw=None`` numbers the call with the bank's counter and
+        advances it (successive calls differ; the counter travels in ``bank_state()``); an explicit ``draw`` repeats
+        that draw and advances nothing.  The first ``m`` rows of a draw of ``n`` are the draw of ``m``, and the draw of
+        a scope is the whole bank's order filtered to it.
+        ``reinforce`` (an amount) / ``touch=True`` apply ``reinforce()`` / ``touch()`` to the drawn rows after the draw
+        is final.  No host sync (``touch`` reads the rows back for the host's slot clock, as ``touch()`` does)."""
+        n = int(n)
+        if n < 0:
+            raise ValueError(f"replay: n must be >= 0, got {n}")
+        now = time.time() if now is None else now
+        scope = self._replay_scope(priority, alpha, tags, newer_than, older_than, min_strength, seed, draw)
+        dev = self.memory_features.device
+        n = min(n, self.memory_count)
+        if n == 0:                                      # an empty bank (or n = 0): nothing is drawn or numbered
+            feats = self.memory_features.new_zeros(0, self.memory_features.shape[1]) if return_features else None
+            return ReplaySample(torch.empty(0, dtype=torch.int32, device=dev),
+                                torch.empty(0, dtype=torch.float32, device=dev), feats,
+                                torch.zeros((), dtype=torch.int64, device=dev))
+        rows, keys, eligible = ops.bank_replay(self.memory_metadata, self.memory_count, now, n, **scope)
+        if draw is None:
+            self._replay_draws += 1
+        feats = ops.bank_gather(self.memory_features, rows) if return_features else None
+        if reinforce is not None:
+            self.reinforce(rows, amount=reinforce, cap=reinforce_cap)
+        if touch:
+            self.touch(rows, now=now)
+        return ReplaySample(rows, keys, feats, eligible)
 
     def rebuild_centroids(self, perm: Optional[torch.Tensor] = None) -> None:
         """One Lloyd iteration from a random sample of rows (reference ``:345-377``).

@@ -159,6 +159,13 @@ class MemoryInjection(nn.Module):
             return self.hippocampus.consolidate(similarity=similarity)
         return self.hippocampus.consolidate(similarity=similarity, within_tags=within_tags)
 
+    def replay_memories(self, n: int, **kw):
+        """``(features [n, D], rows int32 [n])``: ``n`` held memories drawn by priority for a sleep phase
+        (``HippocampalFormation.replay`` and its keywords: scope, ``alpha``, ``seed`` / ``draw``, ``reinforce``,
+        ``touch``); zeros / ``-1`` where the scope held fewer."""
+        s = self.hippocampus.replay(n, **kw)
+        return s.features, s.rows
+
     def forward(self, hidden_states: torch.Tensor, use_memory: bool = True) -> torch.Tensor:
         if use_memory and self.hippocampus is not None and self.hippocampus.memory_count > 0:
             mf, ms = self.retrieve_memories(hidden_states, k=self.num_retrieved)
@@ -192,3 +199,10 @@ class BatchedMemoryMixin:
         if within_tags is None:
             return self.hippocampus.consolidate(similarity=similarity)
         return self.hippocampus.consolidate(similarity=similarity, within_tags=within_tags)
+
+    def replay_memories(self, n: int, **kw):
+        """``(features [n, D], rows int32 [n])``: ``n`` held memories drawn by priority for a sleep phase
+        (``HippocampalFormation.replay`` and its keywords: scope, ``alpha``, ``seed`` / ``draw``, ``reinforce``,
+        ``touch``); zeros / ``-1`` where the scope held fewer."""
+        s = self.hippocampus.replay(n, **kw)
+        return s.features, s.rows

@@ -269,104 +269,15 @@ __global__ __launch_bounds__(256) void kmeans_commit_kernel(const int32_t* __res
 // Eviction order: (key, (r - cursor) mod count) ascending, NaN keys first.  As ONE 64-bit composite
 //     comp(r) = ordered_u32(key(r)) << 32 | rotated_row(r)
 // the first n rows of that order are the n smallest composites (all distinct: the rotated row is).
-// aura_bank_select_weakest is a radix select over comp, most significant digit first:
-//   pass 0   reads the metadata once (16 B per row), stores ordered_u32(key) (4 B per row) and
-//            histograms its top 12 bits; also min / max of the ordered keys
-//   pass i   reads the 4-byte ordered keys; every workgroup first narrows the prefix from the previous
-//            pass's histogram (the same 4096-bin scan in every workgroup: no launch in between), then
-//            histograms the next digit of the rows that match the prefix.  Digits: 12 + 12 + 8 bits of
-//            the key, then the bits of the rotated row that `count` needs, 12 at a time.
-//   compact  writes the rows with comp <= threshold (exactly n of them): a workgroup collects its rows in LDS
-//            and reserves their output range with ONE global add (4096 single adds to one address cost 44 us).
-// Histograms live in LDS; a workgroup adds each non-empty bin to the global histogram once (integer adds:
-// the result does not depend on arrival order).  Keys that share their leading bits put every workgroup's
-// adds on the same few addresses (a same-address atomic costs ~1.4 ns: 2048 workgroups x 16 bins took 50 us),
-// so the grid is capped at 512 workgroups and the global histogram is kept in SEL_COPIES copies (workgroup b
-// adds to copy b mod SEL_COPIES; the narrowing step sums them).  A pass whose chosen bin holds exactly the rows still
-// needed ends the selection early (distinct keys: after the key digits); later launches return at once.
-// A bank of equal keys (never decayed or reinforced) is seen by pass 0 (min == max): the threshold is
-// then the rotated row n - 1 itself and nothing but pass 0 and the compaction reads the rows.
+// aura_bank_select_weakest is a radix select over comp, most significant digit first (aura_select.inl, shared with the
+// replay draw of aura_replay.hip): pass 0 below reads the metadata once (16 B per row), stores ordered_u32(key) (4 B per
+// row) and histograms its top 12 bits; the digit passes read the 4-byte keys; the compaction writes the rows with
+// comp <= threshold (exactly n of them).  A bank of equal keys (never decayed or reinforced) is seen by pass 0
+// (min == max): the threshold is then the rotated row n - 1 itself and nothing but pass 0 and the compaction reads
+// the rows.
 // ------------------------------------------------------------------------------------------
 #include "aura_retention.inl"
-
-constexpr int SEL_BINS = 4096;          // 12-bit digits
-constexpr int SEL_MAX_PASSES = 6;       // 3 digits of the key + at most 3 of a 31-bit rotated row
-constexpr int SEL_MAX_BLOCKS = 512;
-constexpr int SEL_COPIES = 4;           // copies of every global histogram
-constexpr int SEL_LIST = 2048;          // selected rows a workgroup of the compaction holds before it writes them out
-
-struct SelState {                       // one per pass: written by workgroup 0 of pass i, read by pass i + 1
-    unsigned long long prefix;          // decided high bits of the threshold; the threshold itself once done
-    uint32_t need;                      // rows still to take among those that match the prefix
-    uint32_t done;
-    uint32_t kmax, kmin_inv;            // [0] only: max / ~min of the ordered keys (pass 0)
-    uint32_t out_count;                 // [0] only: the compaction's cursor
-    uint32_t pad;
-};
-
-__device__ __forceinline__ void sel_flush_hist(const uint32_t* s_hist, int bins, uint32_t* __restrict__ hist) {
-    hist += (blockIdx.x % SEL_COPIES) * SEL_BINS;
-    for (int b = threadIdx.x; b < bins; b += 256) {
-        const uint32_t c = s_hist[b];
-        if (c) atomicAdd(&hist[b], c);
-    }
-}
-
-__device__ __forceinline__ uint32_t sel_bin(const uint32_t* __restrict__ hist, int b) {
-    uint32_t c = 0;
-#pragma unroll
-    for (int j = 0; j < SEL_COPIES; ++j) c += hist[j * SEL_BINS + b];
-    return c;
-}
-
-// Narrow the threshold with the histogram of the pass before (digit at prev_shift, prev_width bits).  Every
-// thread returns the same {prefix, need, done}; workgroup 0 stores it for the next launch.
-__device__ __forceinline__ SelState sel_resolve(const SelState* __restrict__ st_prev, SelState* __restrict__ st_next,
-                                                const uint32_t* __restrict__ hist_prev, int prev_shift, int prev_width,
-                                                bool first, uint32_t n, uint32_t count, uint32_t* s_scan,
-                                                SelState* s_out) {
-    const int tid = threadIdx.x;
-    SelState cur;
-    cur.prefix = 0; cur.need = n; cur.done = 0;
-    if (first) {
-        const uint32_t kmax = st_prev->kmax, kmin = ~st_prev->kmin_inv;
-        if (n >= count) { cur.prefix = ~0ull; cur.done = 1; }                       // every row
-        else if (kmin == kmax) { cur.prefix = ((unsigned long long)kmin << 32) | (n - 1); cur.done = 1; }   // equal keys: the ring
-    } else {
-        cur.prefix = st_prev->prefix; cur.need = st_prev->need; cur.done = st_prev->done;
-    }
-    if (!cur.done) {                                        // (uniform over the grid)
-        const int bins = 1 << prev_width;
-        const int per = (bins + 255) / 256;
-        const int b0 = tid * per, b1 = min(b0 + per, bins);
-        uint32_t sum = 0;
-        for (int b = b0; b < b1; ++b) sum += sel_bin(hist_prev, b);
-        s_scan[tid] = sum;
-        if (tid == 0) { s_out->prefix = 0; s_out->need = 0; s_out->done = 1; }     // (a histogram that holds fewer than `need`: select nothing)
-        __syncthreads();
-        for (int off = 1; off < 256; off <<= 1) {           // inclusive scan
-            const uint32_t add = tid >= off ? s_scan[tid - off] : 0u;
-            __syncthreads();
-            s_scan[tid] += add;
-            __syncthreads();
-        }
-        uint32_t excl = s_scan[tid] - sum;
-        if (excl < cur.need && cur.need <= excl + sum) {    // exactly one thread
-            int b = b0;
-            uint32_t c = sel_bin(hist_prev, b);
-            while (excl + c < cur.need) { excl += c; c = sel_bin(hist_prev, ++b); }
-            const uint32_t need = cur.need - excl;
-            unsigned long long prefix = cur.prefix | ((unsigned long long)b << prev_shift);
-            const bool done = (c == need) || prev_shift == 0;
-            if (done) prefix |= (1ull << prev_shift) - 1ull;          // every row of the bin
-            s_out->prefix = prefix; s_out->need = need; s_out->done = done ? 1u : 0u;
-        }
-        __syncthreads();
-        cur.prefix = s_out->prefix; cur.need = s_out->need; cur.done = s_out->done;
-    }
-    if (blockIdx.x == 0 && tid == 0) { st_next->prefix = cur.prefix; st_next->need = cur.need; st_next->done = cur.done; }
-    return cur;
-}
+#include "aura_select.inl"
 
 // out[r] = key(r)
 __global__ __launch_bounds__(256) void retention_keys_kernel(const float4* __restrict__ meta, int64_t count, float now,
@@ -415,100 +326,37 @@ __global__ __launch_bounds__(256) void select_keys_kernel(const float4* __restri
             }
             okeys[r] = ok;
             kmax = max(kmax, ok); kmin_inv = max(kmin_inv, ~ok);
-            const uint32_t d = ok >> 20;
-            // a wave whose lanes agree (a bank of equal or nearly equal keys) adds once instead of 64 times to one address
-            const uint32_t d0 = __builtin_amdgcn_readfirstlane(d);
-            if (__all(d == d0)) {
-                const unsigned long long act = __ballot(1);
-                if ((int)__lane_id() == __ffsll(act) - 1) atomicAdd(&s_hist[d0], (uint32_t)__popcll(act));
-            } else {
-                atomicAdd(&s_hist[d], 1u);
-            }
+            sel_hist_add(s_hist, ok >> 20);
         }
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        kmax = max(kmax, (uint32_t)__shfl_xor((int)kmax, off));
-        kmin_inv = max(kmin_inv, (uint32_t)__shfl_xor((int)kmin_inv, off));
-    }
-    if ((threadIdx.x & 63) == 0) { atomicMax(&s_mm[0], kmax); atomicMax(&s_mm[1], kmin_inv); }
-    __syncthreads();
-    sel_flush_hist(s_hist, SEL_BINS, hist);
-    if (threadIdx.x == 0) { atomicMax(&st0->kmax, s_mm[0]); atomicMax(&st0->kmin_inv, s_mm[1]); }
+    sel_minmax_flush(kmax, kmin_inv, s_hist, s_mm, hist, st0);
 }
 
-__device__ __forceinline__ void sel_count(uint32_t ok, int64_t r, int64_t cursor, int64_t count, unsigned long long prefix,
-                                          int prev_shift, int shift, uint32_t mask, uint32_t* s_hist) {
-    const uint64_t comp = retention_comp(ok, r, cursor, count);
-    if ((comp >> prev_shift) == (prefix >> prev_shift)) atomicAdd(&s_hist[(uint32_t)(comp >> shift) & mask], 1u);
-}
-
-// pass i >= 1: narrow the prefix, then histogram the digit (shift, width) of the rows that match it
-__global__ __launch_bounds__(256) void select_pass_kernel(const uint32_t* __restrict__ okeys, int64_t count,
-                                                          int64_t cursor, uint32_t n, int first, int prev_shift,
-                                                          int prev_width, int shift, int width,
-                                                          const SelState* __restrict__ st_prev,
-                                                          SelState* __restrict__ st_next,
-                                                          const uint32_t* __restrict__ hist_prev,
-                                                          uint32_t* __restrict__ hist) {
-    __shared__ uint32_t s_hist[SEL_BINS];
-    __shared__ uint32_t s_scan[256];
-    __shared__ SelState s_out;
-    const SelState cur = sel_resolve(st_prev, st_next, hist_prev, prev_shift, prev_width, first != 0, n, (uint32_t)count,
-                                     s_scan, &s_out);
-    if (cur.done) return;
-    const int bins = 1 << width;
-    const uint32_t mask = (uint32_t)bins - 1u;
-    for (int b = threadIdx.x; b < bins; b += 256) s_hist[b] = 0;
-    __syncthreads();
-    const int64_t groups = count >> 2;                      // four keys per 16-byte load
-    for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < groups; g += (int64_t)gridDim.x * 256) {
-        const uint4 k4 = reinterpret_cast<const uint4*>(okeys)[g];
-        sel_count(k4.x, 4 * g, cursor, count, cur.prefix, prev_shift, shift, mask, s_hist);
-        sel_count(k4.y, 4 * g + 1, cursor, count, cur.prefix, prev_shift, shift, mask, s_hist);
-        sel_count(k4.z, 4 * g + 2, cursor, count, cur.prefix, prev_shift, shift, mask, s_hist);
-        sel_count(k4.w, 4 * g + 3, cursor, count, cur.prefix, prev_shift, shift, mask, s_hist);
-    }
-    if (blockIdx.x == 0 && (int64_t)threadIdx.x < (count & 3)) {
-        const int64_t r = 4 * groups + threadIdx.x;
-        sel_count(okeys[r], r, cursor, count, cur.prefix, prev_shift, shift, mask, s_hist);
-    }
-    __syncthreads();
-    sel_flush_hist(s_hist, bins, hist);
-}
-
-// a selected row goes to the workgroup's list
+// what the compaction of the retention selection writes per row: slot, key and the composite; MASKED: rows whose bit is
+// set in the bitmap take no part
 template <bool MASKED>
-__device__ __forceinline__ void sel_collect(uint32_t ok, int64_t r, int64_t cursor, int64_t count, unsigned long long thr,
-                                            uint32_t* s_n, int32_t* s_rows, const uint32_t* __restrict__ bitmap) {
-    if constexpr (MASKED) {
-        if (sel_masked(bitmap, r)) return;
+struct WeakestOut {
+    const uint32_t* __restrict__ okeys;
+    const float4* __restrict__ meta;
+    float now;
+    int64_t cursor, count;
+    int64_t* __restrict__ out_slots;
+    float* __restrict__ out_keys;
+    int64_t* __restrict__ out_comp;
+    const uint32_t* __restrict__ bitmap;
+    __device__ __forceinline__ bool skip(uint32_t, int64_t r) const {
+        if constexpr (MASKED) {
+            if (sel_masked(bitmap, r)) return true;
+        }
+        return false;
     }
-    if (retention_comp(ok, r, cursor, count) <= thr) s_rows[atomicAdd(s_n, 1u)] = (int32_t)r;
-}
-
-// write the workgroup's list behind the rows already written (one global add), then empty it
-__device__ __forceinline__ void sel_write_list(uint32_t* s_n, uint32_t* s_base, const int32_t* s_rows,
-                                               const uint32_t* __restrict__ okeys, const float4* __restrict__ meta,
-                                               float now, int64_t cursor, int64_t count, uint32_t n,
-                                               uint32_t* __restrict__ out_count, int64_t* __restrict__ out_slots,
-                                               float* __restrict__ out_keys, int64_t* __restrict__ out_comp) {
-    const uint32_t cnt = *s_n;
-    if (threadIdx.x == 0 && cnt) *s_base = atomicAdd(out_count, cnt);
-    __syncthreads();
-    for (uint32_t i = threadIdx.x; i < cnt; i += 256) {
-        const uint32_t pos = *s_base + i;
-        if (pos >= n) continue;                             // (cannot happen: exactly n composites are <= the threshold)
-        const int64_t r = s_rows[i];
+    __device__ __forceinline__ void write(uint32_t pos, int64_t r) const {
         const float4 m = meta[r];
         out_slots[pos] = r;
         out_keys[pos] = retention_key(m.x, m.y, now);
         out_comp[pos] = (int64_t)(retention_comp(okeys[r], r, cursor, count) ^ 0x8000000000000000ull);   // sortable as signed
     }
-    __syncthreads();
-    if (threadIdx.x == 0) *s_n = 0;
-    __syncthreads();
-}
+};
 
 // the last narrowing, then every row at or below the threshold, in arrival order
 template <bool MASKED>
@@ -523,38 +371,8 @@ __global__ __launch_bounds__(256) void select_compact_kernel(const uint32_t* __r
                                                              float* __restrict__ out_keys,
                                                              int64_t* __restrict__ out_comp,
                                                              const uint32_t* __restrict__ bitmap) {
-    __shared__ uint32_t s_scan[256];
-    __shared__ SelState s_out;
-    __shared__ int32_t s_rows[SEL_LIST];
-    __shared__ uint32_t s_n, s_base;
-    const SelState cur = sel_resolve(st_prev, st_next, hist_prev, prev_shift, prev_width, first != 0, n, (uint32_t)count,
-                                     s_scan, &s_out);
-    const unsigned long long thr = cur.prefix;              // (the last digit ends at bit 0: the prefix is the threshold)
-    if (threadIdx.x == 0) s_n = 0;
-    __syncthreads();
-    const int64_t groups = count >> 2;
-    // every thread of the workgroup makes the same number of trips (barriers inside); a trip adds at most 1024 rows
-    for (int64_t g0 = (int64_t)blockIdx.x * 256; g0 < groups; g0 += (int64_t)gridDim.x * 256) {
-        const int64_t g = g0 + threadIdx.x;
-        if (g < groups) {
-            const uint4 k4 = reinterpret_cast<const uint4*>(okeys)[g];
-            sel_collect<MASKED>(k4.x, 4 * g, cursor, count, thr, &s_n, s_rows, bitmap);
-            sel_collect<MASKED>(k4.y, 4 * g + 1, cursor, count, thr, &s_n, s_rows, bitmap);
-            sel_collect<MASKED>(k4.z, 4 * g + 2, cursor, count, thr, &s_n, s_rows, bitmap);
-            sel_collect<MASKED>(k4.w, 4 * g + 3, cursor, count, thr, &s_n, s_rows, bitmap);
-        }
-        __syncthreads();
-        const uint32_t held = s_n;                          // (read by all before anyone adds again)
-        __syncthreads();
-        if (held > SEL_LIST - 1024 - 4)                     // (uniform) no room for another trip and the tail
-            sel_write_list(&s_n, &s_base, s_rows, okeys, meta, now, cursor, count, n, out_count, out_slots, out_keys, out_comp);
-    }
-    if (blockIdx.x == 0 && (int64_t)threadIdx.x < (count & 3)) {
-        const int64_t r = 4 * groups + threadIdx.x;
-        sel_collect<MASKED>(okeys[r], r, cursor, count, thr, &s_n, s_rows, bitmap);
-    }
-    __syncthreads();
-    sel_write_list(&s_n, &s_base, s_rows, okeys, meta, now, cursor, count, n, out_count, out_slots, out_keys, out_comp);
+    const WeakestOut<MASKED> out{okeys, meta, now, cursor, count, out_slots, out_keys, out_comp, bitmap};
+    sel_compact(okeys, count, cursor, n, first, prev_shift, prev_width, st_prev, st_next, hist_prev, out_count, out);
 }
 
 // meta[r][0] = min(meta[r][0] + amount, cap) where below cap, once per distinct valid r of rows[0..n_rows): the
@@ -662,22 +480,6 @@ int aura_kmeans_commit(const int32_t* assign, const int32_t* seg_off, float* met
 }
 
 // ---- retention ---------------------------------------------------------------------------
-// digits of the composite below the three of the key: the bits of the rotated row that `count` needs
-static int sel_passes(int64_t count, int* shifts, int* widths) {
-    int P = 0;
-    shifts[P] = 52; widths[P++] = 12;
-    shifts[P] = 40; widths[P++] = 12;
-    shifts[P] = 32; widths[P++] = 8;
-    int s = 0;
-    while (s < 31 && (1LL << s) < count) ++s;               // rotated rows are < count <= 2^s
-    while (s > 0) {
-        const int w = s < 12 ? s : 12;
-        s -= w;
-        shifts[P] = s; widths[P++] = w;
-    }
-    return P;
-}
-
 int aura_bank_retention_keys(const float* meta, int64_t count, float now, float* out, void* stream) {
     if (count < 0 || count > 0x7ffffff0LL) return AURA_E_INVAL;
     if (count == 0) return AURA_OK;
@@ -690,11 +492,9 @@ int aura_bank_retention_keys(const float* meta, int64_t count, float now, float*
     return aura_check_launch();
 }
 
-// workspace: [n composites (int64)] [SelState x (passes + 1)] [histograms] [ordered keys (u32 x count)]
 int64_t aura_bank_select_weakest_workspace_bytes(int64_t count, int64_t n) {
     if (count < 1 || count > 0x7ffffff0LL || n < 1 || n > count) return -1;
-    return aura_align256(8 * n) + aura_align256((SEL_MAX_PASSES + 1) * (int64_t)sizeof(SelState)) +
-           (int64_t)SEL_MAX_PASSES * SEL_COPIES * SEL_BINS * 4 + aura_align256(4 * count);
+    return sel_workspace_bytes(count, n);
 }
 
 // the launches of both selections; MASKED: rows whose bit is set in `bitmap` (count bits) take no part
@@ -710,38 +510,23 @@ static int select_weakest_launch(const float* meta, int64_t count, float now, in
     if (workspace_bytes < aura_bank_select_weakest_workspace_bytes(count, n)) return AURA_E_INVAL;
     cursor %= count;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    char* w = static_cast<char*>(workspace);
-    int64_t* out_comp = reinterpret_cast<int64_t*>(w);
-    w += aura_align256(8 * n);
-    SelState* st = reinterpret_cast<SelState*>(w);
-    const int64_t st_bytes = aura_align256((SEL_MAX_PASSES + 1) * (int64_t)sizeof(SelState));
-    uint32_t* hist = reinterpret_cast<uint32_t*>(w + st_bytes);
-    const int64_t hist_bytes = (int64_t)SEL_MAX_PASSES * SEL_COPIES * SEL_BINS * 4;
-    uint32_t* okeys = reinterpret_cast<uint32_t*>(w + st_bytes + hist_bytes);
-    if (hipMemsetAsync(st, 0, (size_t)(st_bytes + hist_bytes), s) != hipSuccess) return AURA_E_LAUNCH;
+    const SelWorkspace ws = sel_workspace(workspace, n);
+    if (hipMemsetAsync(ws.st, 0, (size_t)ws.clear_bytes, s) != hipSuccess) return AURA_E_LAUNCH;
     int shifts[SEL_MAX_PASSES], widths[SEL_MAX_PASSES];
     const int P = sel_passes(count, shifts, widths);
     const float4* meta4 = reinterpret_cast<const float4*>(meta);
     int64_t blocks = (count + 255) / 256;
     if (blocks > SEL_MAX_BLOCKS) blocks = SEL_MAX_BLOCKS;
-    hipLaunchKernelGGL(select_keys_kernel<MASKED>, dim3((unsigned)blocks), dim3(256), 0, s, meta4, count, now, okeys,
-                       hist, st, bitmap);
+    hipLaunchKernelGGL(select_keys_kernel<MASKED>, dim3((unsigned)blocks), dim3(256), 0, s, meta4, count, now, ws.okeys,
+                       ws.hist, ws.st, bitmap);
     int rc = aura_check_launch();
     if (rc) return rc;
-    int64_t blocks4 = (count / 4 + 255) / 256;
-    if (blocks4 < 1) blocks4 = 1;
-    if (blocks4 > SEL_MAX_BLOCKS) blocks4 = SEL_MAX_BLOCKS;
-    for (int i = 1; i < P; ++i) {
-        hipLaunchKernelGGL(select_pass_kernel, dim3((unsigned)blocks4), dim3(256), 0, s, okeys, count, cursor, (uint32_t)n,
-                           i == 1 ? 1 : 0, shifts[i - 1], widths[i - 1], shifts[i], widths[i], st + (i - 1), st + i,
-                           hist + (int64_t)(i - 1) * SEL_COPIES * SEL_BINS, hist + (int64_t)i * SEL_COPIES * SEL_BINS);
-        rc = aura_check_launch();
-        if (rc) return rc;
-    }
-    hipLaunchKernelGGL(select_compact_kernel<MASKED>, dim3((unsigned)blocks4), dim3(256), 0, s, okeys, meta4, count, now,
-                       cursor, (uint32_t)n, P == 1 ? 1 : 0, shifts[P - 1], widths[P - 1], st + (P - 1), st + P,
-                       hist + (int64_t)(P - 1) * SEL_COPIES * SEL_BINS, &st[0].out_count, out_slots, out_keys, out_comp,
-                       bitmap);
+    rc = sel_launch_passes(ws, count, cursor, n, shifts, widths, P, s);
+    if (rc) return rc;
+    hipLaunchKernelGGL(select_compact_kernel<MASKED>, dim3((unsigned)sel_blocks4(count)), dim3(256), 0, s, ws.okeys, meta4,
+                       count, now, cursor, (uint32_t)n, P == 1 ? 1 : 0, shifts[P - 1], widths[P - 1], ws.st + (P - 1),
+                       ws.st + P, ws.hist + (int64_t)(P - 1) * SEL_COPIES * SEL_BINS, &ws.st[0].out_count, out_slots,
+                       out_keys, ws.out_comp, bitmap);
     return aura_check_launch();
 }
 }  // extern "C++"

@@ -573,6 +573,108 @@ def bank_reinforce(meta, count: int, rows, amount: float, cap: float = 1.0) -> N
           "aura_bank_reinforce")
 
 
+REPLAY_PRIORITIES = {"key": 0, "strength": 1, "uniform": 2}
+REPLAY_MAX_TAGS = 64
+REPLAY_MAX_ALPHA = 16.0
+
+
+def replay_scope_tags(tags) -> np.ndarray:
+    """``tags`` of a replay (None = any tag, an int, or several ints taken as a union; 0 = the untagged rows) as a
+    sorted int32 array of distinct tags (empty = any); raises ``ValueError`` for a tag outside ``[0, 2^24)`` or more
+    than ``REPLAY_MAX_TAGS`` distinct ones."""
+    if tags is None:
+        return np.zeros(0, dtype=np.int32)
+    if isinstance(tags, torch.Tensor):
+        tags = tags.detach().cpu().numpy()
+    t = np.asarray(tags)
+    if t.dtype.kind not in "iu":
+        raise ValueError(f"replay: tags must be integers, got dtype {t.dtype}")
+    t = np.unique(t.astype(np.int64).reshape(-1))
+    if t.size == 0:
+        raise ValueError("replay: an empty tag list (None means any tag)")
+    if t[0] < 0 or t[-1] >= (1 << 24):
+        raise ValueError("replay: tags must be inside [0, 2^24)")
+    if t.size > REPLAY_MAX_TAGS:
+        raise ValueError(f"replay: at most {REPLAY_MAX_TAGS} distinct tags per call, got {t.size}")
+    return np.ascontiguousarray(t.astype(np.int32))
+
+
+def _replay_args(who: str, priority, alpha, tags, newer_than, older_than, min_strength, seed, draw):
+    """The checked arguments both replay ops hand to the library, from ``priority`` to ``draw`` (the tag array is
+    host memory and must outlive the call: the caller keeps the tuple)."""
+    if priority not in REPLAY_PRIORITIES:
+        raise ValueError(f"{who}: priority must be 'key', 'strength' or 'uniform', got {priority!r}")
+    alpha = float(alpha)
+    if not (0.0 <= alpha <= REPLAY_MAX_ALPHA):
+        raise ValueError(f"{who}: alpha must be in [0, {REPLAY_MAX_ALPHA:g}], got {alpha}")
+    t = replay_scope_tags(tags)
+    cond, bounds = 0, []
+    for bit, v, name in ((1, newer_than, "newer_than"), (2, older_than, "older_than"), (4, min_strength, "min_strength")):
+        v32 = 0.0
+        if v is not None:
+            v32 = float(np.float32(v))
+            if v32 != v32:
+                raise ValueError(f"{who}: {name} must be a number")
+            cond |= bit
+        bounds.append(v32)
+    seed, draw = int(seed), int(draw)
+    if not (0 <= seed < (1 << 64)) or not (0 <= draw < (1 << 64)):
+        raise ValueError(f"{who}: seed and draw must be in [0, 2^64)")
+    return (REPLAY_PRIORITIES[priority], alpha, t.ctypes.data if t.size else None, t.size, cond, *bounds, seed, draw), t
+
+
+def bank_replay_keys(meta, count: int, now: float, *, priority: str = "key", alpha: float = 1.0, tags=None,
+                     newer_than: Optional[float] = None, older_than: Optional[float] = None,
+                     min_strength: Optional[float] = None, seed: int = 0, draw: int = 0,
+                     return_uniforms: bool = False):
+    """fp32 [count]: the draw key ``d = alpha * lw - log(-log(u))`` of every row of [0, count) for ``(seed, draw)``,
+    ``-inf`` for a row that is not eligible (the rule: ``include/aura_hip.h``, "Replay") -- the read-only half of
+    ``bank_replay``, whose sample is the top ``n`` of these by ``(d descending, row ascending)``.
+    ``return_uniforms``: also int32 [count], the 23-bit integers ``x >> 9`` with ``u = (that + 0.5) * 2^-23``."""
+    _check_meta(meta, count, "bank_replay_keys")
+    args, keep = _replay_args("bank_replay_keys", priority, alpha, tags, newer_than, older_than, min_strength, seed, draw)
+    out = torch.empty(count, dtype=torch.float32, device=meta.device)
+    out_u = torch.empty(count, dtype=torch.int32, device=meta.device) if return_uniforms else None
+    check(lib().aura_bank_replay_keys(_p(meta), count, now, *args, _p(out), _p(out_u), _stream()),
+          "aura_bank_replay_keys")
+    del keep
+    return (out, out_u) if return_uniforms else out
+
+
+def bank_replay(meta, count: int, now: float, n: int, *, priority: str = "key", alpha: float = 1.0, tags=None,
+                newer_than: Optional[float] = None, older_than: Optional[float] = None,
+                min_strength: Optional[float] = None, seed: int = 0,
+                draw: int = 0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """A seeded draw of ``n`` eligible rows of [0, count) without replacement, the likelier the larger
+    ``exp(alpha * lw)`` -> ``(rows int32 [n], keys fp32 [n], eligible int64 scalar)``, all on the device: the first
+    ``min(n, eligible)`` eligible rows by ``(d descending, row ascending)`` in that order, then ``-1`` / ``-inf``.
+    ``priority``: ``'key'`` (``lw`` = log of the retention key, strength x recency), ``'strength'`` or ``'uniform'``;
+    ``tags``: None (any), an int or several (a union; 0 = untagged); the other scope conditions as in
+    ``knn_search_scoped``.  The key pass and the radix selection run in the library; the n entries are then ordered
+    by one ``torch.sort`` of their composites.  No host sync: the padding is written on the device."""
+    _check_meta(meta, count, "bank_replay")
+    n = int(n)
+    if not (1 <= n <= count):
+        raise ValueError(f"bank_replay: need 1 <= n <= count (n={n}, count={count})")
+    args, keep = _replay_args("bank_replay", priority, alpha, tags, newer_than, older_than, min_strength, seed, draw)
+    L = lib()
+    nbytes = L.aura_bank_replay_workspace_bytes(count, n)
+    if nbytes < 0:
+        raise ValueError("bank_replay: unsupported size")
+    base = _workspace(meta.device, nbytes)
+    rows = torch.empty(n, dtype=torch.int32, device=meta.device)
+    keys = torch.empty(n, dtype=torch.float32, device=meta.device)
+    eligible = torch.empty(1, dtype=torch.int64, device=meta.device)
+    check(L.aura_bank_replay(_p(meta), count, now, *args, n, _p(rows), _p(keys), _p(eligible), base, nbytes, _stream()),
+          "aura_bank_replay")
+    del keep
+    if n > 1:
+        # (the sort reads the workspace before any later call on this stream can overwrite it)
+        order = torch.sort(_workspace_view(meta.device, 8 * n).view(torch.int64)).indices
+        rows, keys = rows[order], keys[order]
+    return rows, keys, eligible[0]
+
+
 CONSOLIDATE_MAX_BATCH = 1024
 CONSOLIDATE_MAX_IMAGE_DIM = 768
 

@@ -368,6 +368,66 @@ int aura_bank_select_weakest_masked(const float* meta, int64_t count, float now,
                                     const uint32_t* bitmap, int64_t* out_slots, float* out_keys, void* workspace,
                                     int64_t workspace_bytes, void* stream);
 
+/* Replay: a seeded draw of held memories by priority, without replacement (csrc/aura_replay.hip).  [build-side] the
+ * reference samples a Python list of CPU tensors (hippocampal_trainer.py:43-66, torch.randperm); its bank cannot be
+ * sampled.
+ *
+ * THE RULE.  For a call (count, now, priority, alpha, scope, seed, draw, n), rows r < count, all fp32, unfused:
+ *   1. random word    x_r = word 0 of Philox4x32-10 with counter (r & 0xffffffff, r >> 32, draw & 0xffffffff, draw >> 32)
+ *                     and key (seed & 0xffffffff, seed >> 32); multipliers 0xD2511F53, 0xCD9E8D57, key increments
+ *                     0x9E3779B9, 0xBB67AE85 (Random123; counter 0, key 0 gives 6627e8d5).
+ *   2. uniform        u_r = ((x_r >> 9) + 0.5) * 2^-23: a 24-bit odd numerator over 2^24, exact in fp32, inside
+ *                     [2^-24, 1 - 2^-24]: never 0 or 1.
+ *   3. log-priority   lw_r = logf(meta[r][0]) + a with a = -(now - meta[r][1]) / 3600   (AURA_REPLAY_KEY: the log of the
+ *                            retention key; a is the argument aura_bank_retention_keys hands to expf.  In the log domain
+ *                            on purpose: expf underflows for rows older than about four days, which would never be drawn)
+ *                          = logf(meta[r][0])                                          (AURA_REPLAY_STRENGTH)
+ *                          = 0                                                         (AURA_REPLAY_UNIFORM)
+ *   4. eligible       r is in scope and lw_r is finite (KEY, STRENGTH: 0 < strength < inf; KEY: a timestamp that is not
+ *                     NaN).  Does not depend on alpha.  In scope iff ALL of
+ *                       n_tags == 0 (any tag)  or  the row's tag (column 3, as aura_knn_search_scoped reads it: a value
+ *                                                   outside (-1, 2^24) is no tag) is one of tags[0 .. n_tags), 0 = untagged
+ *                       conditions & 1 == 0  or  meta[r][1] >= newer_than
+ *                       conditions & 2 == 0  or  meta[r][1] <= older_than
+ *                       conditions & 4 == 0  or  meta[r][0] >= min_strength
+ *   5. draw key       d_r = alpha * lw_r - logf(-logf(u_r)), 0 <= alpha <= 16; a zero is written as +0.
+ *   6. sample         the first n' = min(n, #eligible) eligible rows by (d descending, row ascending), in that order;
+ *                     then rows -1 and keys -inf up to n.
+ * This is the exponential-race form of successive sampling (Gumbel top-n).  With p = exp(alpha lw):
+ *   - the first row is r with probability p_r / sum p; each later row is drawn the same way from what is left;
+ *   - the first m rows of a sample of n are the sample of m;
+ *   - the sample of a scope is the full-bank order filtered to that scope;
+ *   - the key of a (draw, row) pair does not depend on what else is in the call, on n, or on the launch geometry.
+ *
+ * tags: HOST int32 [n_tags], 0 <= n_tags <= AURA_REPLAY_MAX_TAGS, each in [0, 2^24), strictly ascending (they travel in
+ *   the kernel arguments; the call reads them before it returns).  meta: 16-byte aligned.
+ * aura_bank_replay_keys: out_d[r] = d_r for r < count, -inf for an ineligible row; out_u (may be NULL) [count] receives
+ *   the 23-bit integers x_r >> 9.  One pass, reads 16 B per row.  count == 0 launches nothing.
+ * aura_bank_replay: out_rows (int32 [n]) / out_d (fp32 [n]) receive the sample's n' rows and keys in the compaction's
+ *   arrival order, the other n - n' entries the padding (written on the device: the host never learns n'), and the first
+ *   n int64 of the workspace the composites  ~ordered_u32(d) << 32 | row  with the top bit flipped, INT64_MAX for the
+ *   padding (ascending as signed integers = the sample's order): sorting those n values orders the sample
+ *   (ops.bank_replay does).  out_eligible (int64 [1]) = #eligible.  The key pass is pass 0 of the radix selection of
+ *   aura_bank_select_weakest (16 B per row once, then 4 B per row per pass; the same digit passes and compaction).
+ *   1 <= n <= count; workspace: *_workspace_bytes(count, n) bytes, 256-byte aligned.  count == 0: any n >= 1, writes
+ *   the padding with fills and launches nothing (workspace size 0).
+ * AURA_E_INVAL, nothing launched: n < 1 or n > count; alpha outside [0, 16] or NaN; an unknown priority; n_tags outside
+ *   [0, 64], a tag outside [0, 2^24) or tags not strictly ascending; conditions with unknown bits; a null array; a
+ *   workspace that is too small.  AURA_E_ALIGN: meta not 16-byte, workspace not 256-byte, an output not aligned to its
+ *   element. */
+#define AURA_REPLAY_KEY 0
+#define AURA_REPLAY_STRENGTH 1
+#define AURA_REPLAY_UNIFORM 2
+#define AURA_REPLAY_MAX_TAGS 64
+int aura_bank_replay_keys(const float* meta, int64_t count, float now, int priority, float alpha, const int32_t* tags,
+                          int64_t n_tags, int conditions, float newer_than, float older_than, float min_strength,
+                          uint64_t seed, uint64_t draw, float* out_d, uint32_t* out_u, void* stream);
+int64_t aura_bank_replay_workspace_bytes(int64_t count, int64_t n);
+int aura_bank_replay(const float* meta, int64_t count, float now, int priority, float alpha, const int32_t* tags,
+                     int64_t n_tags, int conditions, float newer_than, float older_than, float min_strength,
+                     uint64_t seed, uint64_t draw, int64_t n, int32_t* out_rows, float* out_d, int64_t* out_eligible,
+                     void* workspace, int64_t workspace_bytes, void* stream);
+
 /* Workspace size (bytes) aura_knn_search needs for (N, nq, k). */
 int64_t aura_knn_workspace_bytes(int64_t N, int64_t nq, int k);
 
