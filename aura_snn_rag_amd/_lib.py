@@ -60,6 +60,7 @@ SIGNATURES = {
     "aura_bank_find_repeats_workspace_bytes": (I64, [I64]),
     "aura_bank_find_repeats": (I, [P, P, I64, I64, P, P, I64, P, P, I64, F, P, P, P, P, P, I64, P]),
     "aura_bank_find_repeats_scoped": (I, [P, P, I64, I64, P, P, I64, P, P, I64, F, P, P, P, P, P, I64, P, P, P]),
+    "aura_bank_blend": (I, [P, P, I64, I64, I64, P, I64, I64, P, P, F, P, P, P, I64, P, P, P, I64, P]),
     "aura_bank_touch": (I, [P, I64, P, I64, F, P]),
     "aura_bank_compact_round_rows": (I64, []),
     "aura_bank_compact_workspace_bytes": (I64, [I64, I64, I]),

@@ -125,12 +125,14 @@ class ConsolidationReport:
     """What a consolidating write did with its ``n`` rows (host tensors and lists).  ``merged[i]``: row i repeated a
     memory and was not stored; ``ids[i]``: the id of the memory row i became (its own id if it was stored, else the id
     of the memory it repeats); ``rows[i]``: the slot ``s`` that holds that memory when the call returns, with
-    ``id_of_row(s) == ids[i]``, or -1 if this same call overwrote it again."""
+    ``id_of_row(s) == ids[i]``, or -1 if this same call overwrote it again.  ``n_blended``: how many memories' features
+    moved (a blending write: once per chunk for every memory that rows of the chunk repeat; 0 without blending)."""
     merged: torch.Tensor
     rows: torch.Tensor
     ids: List[Optional[str]]
     n_stored: int
     n_merged: int
+    n_blended: int = 0
 
 
 @dataclass
@@ -145,11 +147,13 @@ class CompactionReport:
 class BankConsolidationReport:
     """What ``consolidate`` did with the ``n_before`` held rows: ``n_kept`` remain, ``n_merged`` repeated a kept memory
     and are gone; ``old_to_new`` (host int64 [n_before]) is the row every memory has now -- for a merged row the row of
-    the memory it merged into."""
+    the memory it merged into.  ``n_blended``: how many memories' features moved (``consolidate(blend=...)``: once per
+    slab for every memory that rows of the slab repeat; 0 without blending)."""
     n_before: int
     n_kept: int
     n_merged: int
     old_to_new: np.ndarray
+    n_blended: int = 0
 
 
 @dataclass
@@ -187,13 +191,17 @@ class HippocampalFormation(nn.Module):
                  merge_cap: float = 1.0,
                  merge_within_tags: bool = False,
                  tag_quota=None,
-                 replay_seed: int = 0):
+                 replay_seed: int = 0,
+                 merge_blend: Optional[float] = None):
         super().__init__()
         # consolidating writes (create_episodic_memories): None = every row is stored, today's behaviour
         self._check_merge(merge_similarity, merge_reinforce, merge_cap)
         self.merge_similarity = merge_similarity
         self.merge_reinforce = merge_reinforce
         self.merge_cap = merge_cap
+        # blending merges (consolidating writes and consolidate()): None = the first observation stands, today's behaviour
+        self._check_blend(merge_blend, merge_similarity)
+        self.merge_blend = merge_blend
         # consolidation within tags (consolidating writes and consolidate()): False = scope-blind, today's behaviour
         self.merge_within_tags = bool(merge_within_tags)
         self.spatial_dims = spatial_dimensions
@@ -916,17 +924,19 @@ class HippocampalFormation(nn.Module):
     def create_episodic_memory(self, memory_id: str, event_id: str, features: torch.Tensor,
                                associated_experts: List[str] = None,
                                merge_similarity=_INSTANCE_DEFAULT, tag: Optional[int] = None,
-                               merge_within_tags=_INSTANCE_DEFAULT) -> Optional[ConsolidationReport]:
+                               merge_within_tags=_INSTANCE_DEFAULT,
+                               merge_blend=_INSTANCE_DEFAULT) -> Optional[ConsolidationReport]:
         """Store one memory (reference ``:195-243``).  ``event_id`` / ``associated_experts`` are
-        accepted and unused, as in the reference.  ``merge_similarity``, ``tag`` and ``merge_within_tags``: as
-        ``create_episodic_memories``."""
+        accepted and unused, as in the reference.  ``merge_similarity``, ``tag``, ``merge_within_tags`` and
+        ``merge_blend``: as ``create_episodic_memories``."""
         return self.create_episodic_memories([memory_id], self._features_to_device(features, rows=1),
                                              merge_similarity=merge_similarity, tags=tag,
-                                             merge_within_tags=merge_within_tags)
+                                             merge_within_tags=merge_within_tags, merge_blend=merge_blend)
 
     def create_episodic_memories(self, memory_ids: Sequence[str], features: torch.Tensor,
                                  merge_similarity=_INSTANCE_DEFAULT, tags=None,
-                                 merge_within_tags=_INSTANCE_DEFAULT) -> Optional[ConsolidationReport]:
+                                 merge_within_tags=_INSTANCE_DEFAULT,
+                                 merge_blend=_INSTANCE_DEFAULT) -> Optional[ConsolidationReport]:
         """Batched one-shot write: identical to calling ``create_episodic_memory`` once per row,
         including the rebuild every ``centroids_update_interval`` inserts (``:242-243``).
 
@@ -939,9 +949,22 @@ class HippocampalFormation(nn.Module):
         host read), then ``reinforce`` + ``touch`` of the distinct stored targets -- BEFORE the write, so that under
         ``overflow='weakest'`` a memory that has just been repeated is not the one evicted -- then the kept rows go
         through the unchanged write path (every overflow policy applies; the rebuild cadence counts kept rows only).
-        Returns a ``ConsolidationReport``.  The first observation stands: the repeat's features are not blended into
-        the stored row.  ``bulk_write`` and ``write_at`` (the seeding path and the sharded bank's building block) do
-        not consolidate, and ``ShardedHippocampus`` has no cross-rank search.
+        Returns a ``ConsolidationReport``.  Without ``merge_blend`` the first observation stands: the repeat's features
+        are not blended into the stored row.  ``bulk_write`` and ``write_at`` (the seeding path and the sharded bank's
+        building block) do not consolidate, and ``ShardedHippocampus`` has no cross-rank search.
+
+        ``merge_blend`` (default: the value the bank was constructed with; None there: off, nothing more is launched):
+        a rate ``beta`` in ``(0, 1]``; needs a merge threshold (``ValueError`` without one).  A memory that rows of a
+        chunk repeat moves toward them: ``g = g + beta * (f_i - g)`` over its repeats in ascending batch order, in fp32
+        (the rule: ``include/aura_hip.h``, "Blending merges"); an in-batch leader is blended the same way before it is
+        stored.  Per chunk the order is search (the one host read), blend (one launch, ``ops.bank_blend``, grouping on
+        the device: no further read), reinforce, touch, write: the kept rows written are the blended ones, and the
+        caller's tensor is never written.  The launch keeps ``1/||row||``, the bf16 shadow with its residuals and the
+        list-sorted image of every moved row current.  All decisions of a chunk are those the search made against the
+        bank as it stood BEFORE the chunk's blend: a blended memory that drifts within the threshold of another held
+        memory merges with it only at the next ``consolidate()``.  Strength, timestamp, tag, ids and the stored
+        centroid id are untouched by the blend; the centroid means follow at the next ``rebuild_centroids``, as after
+        ``forget``.
 
         ``tags`` (default None: nothing changes and nothing more is launched): an int for every row, or a host
         sequence / int array of one int per row, each in ``[0, 2^24)``.  The rows go through the unchanged write path
@@ -961,6 +984,11 @@ class HippocampalFormation(nn.Module):
         within = self.merge_within_tags if merge_within_tags is _INSTANCE_DEFAULT else bool(merge_within_tags)
         if tau is not None:
             self._check_merge(tau, self.merge_reinforce, self.merge_cap)
+        if merge_blend is _INSTANCE_DEFAULT:
+            beta = self.merge_blend if tau is not None else None      # (a write with merging switched off blends nothing)
+        else:
+            beta = merge_blend
+            self._check_blend(beta, tau)
         feats = self._features_to_device(features)
         n = len(memory_ids)
         if feats.shape[0] != n:
@@ -973,9 +1001,10 @@ class HippocampalFormation(nn.Module):
         if tau is None:
             self._write_batch(memory_ids, feats, tags)
             return None
+        kw = {} if beta is None else dict(blend=float(beta))
         if not within:
-            return self._write_consolidated(memory_ids, feats, float(tau))
-        return self._write_consolidated(memory_ids, feats, float(tau), tags=tags, within_tags=True)
+            return self._write_consolidated(memory_ids, feats, float(tau), **kw)
+        return self._write_consolidated(memory_ids, feats, float(tau), tags=tags, within_tags=True, **kw)
 
     def _write_batch(self, memory_ids: Sequence[str], feats: torch.Tensor, tags: Optional[np.ndarray] = None) -> None:
         n = len(memory_ids)
@@ -1025,6 +1054,20 @@ class HippocampalFormation(nn.Module):
         if float(cap) != float(cap):
             raise ValueError("merge_cap must be a number")
 
+    @staticmethod
+    def _check_blend(beta, similarity) -> None:
+        if beta is None:
+            return
+        try:
+            ok = not isinstance(beta, bool) and 0.0 < float(beta) <= 1.0
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError(f"merge_blend must be None or a rate in (0, 1], got {beta!r}")
+        if similarity is None:
+            raise ValueError("merge_blend needs a merge threshold: blending moves a memory toward the rows that "
+                             "merge_similarity decides repeat it")
+
     def find_repeats(self, features: torch.Tensor, threshold: float, now: Optional[float] = None, *,
                      tags=None, _use_lists: bool = True) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """Which of the (at most ``ops.CONSOLIDATE_MAX_BATCH``) rows ``features`` repeat a held memory or an earlier
@@ -1046,6 +1089,14 @@ class HippocampalFormation(nn.Module):
         if threshold is None:
             raise ValueError("find_repeats needs a threshold in (0, 1]")
         self._check_merge(threshold, 0.0, 1.0)
+        packed, _ = self._find_repeats_packed(features, threshold, tags, _use_lists)
+        n = (packed.numel() - 2) // 3
+        return packed[:n], packed[n:2 * n], packed[2 * n:3 * n].view(torch.float32)
+
+    def _find_repeats_packed(self, features, threshold: float, tags, _use_lists: bool) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``find_repeats``' search: ``(packed on the host, the same int32 [3 n + 2] where the library left it)`` --
+        stored targets, leaders, cosine bits, the two flags (``ops.find_repeats``).  The device copy is what a blend
+        groups by (``ops.bank_blend``)."""
         f = self._features_to_device(features)
         n = f.shape[0]
         if n > ops.CONSOLIDATE_MAX_BATCH:
@@ -1074,11 +1125,12 @@ class HippocampalFormation(nn.Module):
                 else:
                     kw = dict(image=shadow, rho=self._rho)
             if t_dev is None:
-                packed = ops.find_repeats(self.memory_features, self._inv_norm, self.memory_count, f, float(threshold),
-                                          **kw)[3].cpu()                   # THE host read
+                packed_dev = ops.find_repeats(self.memory_features, self._inv_norm, self.memory_count, f,
+                                              float(threshold), **kw)[3]
             else:
-                packed = ops.find_repeats_scoped(self.memory_features, self._inv_norm, self.memory_metadata,
-                                                 self.memory_count, f, t_dev, float(threshold), **kw)[3].cpu()
+                packed_dev = ops.find_repeats_scoped(self.memory_features, self._inv_norm, self.memory_metadata,
+                                                     self.memory_count, f, t_dev, float(threshold), **kw)[3]
+            packed = packed_dev.cpu()                  # THE host read
             overflow, stale = int(packed[3 * n]), int(packed[3 * n + 1])
             if ivf is not None and stale:
                 ivf.valid = False                      # a write outgrew a list's slack: re-pack and once more;
@@ -1089,7 +1141,41 @@ class HippocampalFormation(nn.Module):
                 mode = 'fp32'                          # a survivor list overflowed: the dense scan cannot
                 continue
             break
-        return packed[:n], packed[n:2 * n], packed[2 * n:3 * n].view(torch.float32)
+        return packed, packed_dev
+
+    def _blend_groups(self, packed_dev: torch.Tensor, stored: np.ndarray, leader: np.ndarray, beta: float,
+                      feats: Optional[torch.Tensor] = None, row0: int = -1) -> Tuple[Optional[torch.Tensor], int]:
+        """One blend launch for the batch a search has just decided (``packed_dev``: its device result; ``stored`` /
+        ``leader``: the host copies, only counted here).  ``row0 < 0``: the batch is ``feats``; returns the batch as it
+        will be stored -- a copy with the blended leaders, ``feats`` itself where no in-batch leader has a repeat -- and
+        the number of memories that moved.  ``row0 >= 0``: the batch is bank rows ``[row0, row0 + n)``, blended in
+        place.  The derived state the launch keeps current: 1/||row||, the row-ordered shadow below its watermark, the
+        list-sorted image while it is valid, rho; the cached score constants are dropped (rho changed)."""
+        n = stored.size
+        in_batch = (stored < 0) & (leader >= 0)
+        n_keys = int(np.unique(stored[stored >= 0]).size + np.unique(leader[in_batch]).size)
+        if n_keys == 0:
+            return feats, 0
+        out = None
+        if row0 < 0:
+            # the caller's tensor is never written: blended leaders go into a copy (needed only when there are any;
+            # the op wants a distinct buffer either way, and a chunk is a few MB at most)
+            out = feats.clone()
+        kw = {}
+        if self._shadow_travels():
+            kw.update(shadow=self._shadow, shadow_upto=self._shadow_valid_upto)
+        st = self._ivf
+        if row0 < 0 and st is not None and st.valid and self._rho is not None and \
+                st.sorted_bf16.device == self.memory_features.device:
+            kw.update(sorted_bf16=st.sorted_bf16, sorted_rows=st.sorted_rows, pos_of_row=st.pos_of_row,
+                      n_sorted=st.n_sorted)
+        if kw:
+            kw["rho"] = self._rho
+        ops.bank_blend(self.memory_features, self._inv_norm, self.memory_count, packed_dev[:n], packed_dev[n:2 * n],
+                       beta, feats=feats if row0 < 0 else None, out=out, feats_row0=row0, **kw)
+        if st is not None:
+            st.rowc_live = False
+        return (out if bool(in_batch.any()) else feats), n_keys
 
     def _search_tags(self, tags, n: int) -> torch.Tensor:
         """``find_repeats(tags=...)`` as int32 [n] on the bank's device.  Nothing is refused for its value: a tag
@@ -1134,10 +1220,13 @@ class HippocampalFormation(nn.Module):
             self._ivf.rowc_live = False                 # timestamps changed under the cached score constants
 
     def _write_consolidated(self, memory_ids: Sequence[str], feats: torch.Tensor, tau: float,
-                            tags: Optional[np.ndarray] = None, within_tags: bool = False) -> ConsolidationReport:
+                            tags: Optional[np.ndarray] = None, within_tags: bool = False,
+                            blend: Optional[float] = None) -> ConsolidationReport:
         """``within_tags``: every chunk is searched with its rows' tags (``tags`` int32 [n], checked; None: all 0,
-        "untagged") and its kept rows are written with them."""
+        "untagged") and its kept rows are written with them.  ``blend``: the rate of a blending write (None: off, the
+        launches of a plain consolidating write); the blend follows whatever the search decided, tags included."""
         n = len(memory_ids)
+        n_blended = 0
         merged = torch.zeros(n, dtype=torch.bool)
         mem_ids: List[Optional[str]] = [None] * n       # the memory every row became
         slot = np.full(n, -1, dtype=np.int64)           # where that memory was when its chunk was done
@@ -1146,12 +1235,20 @@ class HippocampalFormation(nn.Module):
             hi = min(n, lo + step)
             f = feats[lo:hi]
             now = time.time()
-            if within_tags:
+            packed_dev = None
+            if blend is not None:
+                chunk_tags = None if not within_tags else (0 if tags is None else tags[lo:hi])
+                packed, packed_dev = self._find_repeats_packed(f, tau, chunk_tags, True)
+                stored, leader = packed[:hi - lo], packed[hi - lo:2 * (hi - lo)]
+            elif within_tags:
                 stored, leader, _ = self.find_repeats(f, tau, now=now, tags=0 if tags is None else tags[lo:hi])
             else:
                 stored, leader, _ = self.find_repeats(f, tau, now=now)
             stored, leader = stored.numpy().astype(np.int64), leader.numpy().astype(np.int64)
             kept = np.nonzero((stored < 0) & (leader < 0))[0]
+            if packed_dev is not None:                                   # blend BEFORE reinforce, touch and the write:
+                f, moved = self._blend_groups(packed_dev, stored, leader, blend, feats=f)   # f: the rows as stored
+                n_blended += moved
             for i in np.nonzero(stored >= 0)[0].tolist():               # ids of the targets as they are held NOW
                 mem_ids[lo + i], slot[lo + i] = self.id_of_row(int(stored[i])), stored[i]
             targets = np.unique(stored[stored >= 0])
@@ -1177,7 +1274,8 @@ class HippocampalFormation(nn.Module):
                            dtype=bool, count=n)
         rows = torch.from_numpy(np.where(live, slot, -1))
         n_merged = int(merged.sum())
-        return ConsolidationReport(merged=merged, rows=rows, ids=mem_ids, n_stored=n - n_merged, n_merged=n_merged)
+        return ConsolidationReport(merged=merged, rows=rows, ids=mem_ids, n_stored=n - n_merged, n_merged=n_merged,
+                                   n_blended=n_blended)
 
     # ------------------------------------------------------------------ forgetting, pruning, consolidating held rows
     def _ring_start(self) -> int:
@@ -1347,7 +1445,7 @@ class HippocampalFormation(nn.Module):
         return self.forget(rows=torch.nonzero(weak).flatten())
 
     def consolidate(self, similarity: Optional[float] = None, rebuild: bool = True,
-                    within_tags: Optional[bool] = None) -> BankConsolidationReport:
+                    within_tags: Optional[bool] = None, blend: Optional[float] = None) -> BankConsolidationReport:
         """Merge the near-copies the bank already holds (rows from ``bulk_write``, ``write_at``, a checkpoint, or
         written before ``merge_similarity`` was set).  The rule: the bank becomes what writing its rows, oldest first,
         into an empty bank with ``create_episodic_memories(merge_similarity=similarity)`` in chunks of
@@ -1361,8 +1459,8 @@ class HippocampalFormation(nn.Module):
         is kept; the centroid index is not consulted -- and ``aura_bank_compact`` moves the slab's kept rows down behind
         the prefix.  One host read per slab, as in the write path.  A kept memory takes the largest strength and the
         latest timestamp among itself and the rows merged into it; the distinct STORED targets of a slab are then
-        reinforced once by ``merge_reinforce`` up to ``merge_cap``, as a consolidating write does per chunk.  The kept
-        row's features stand (nothing is blended).  With ``rebuild`` the pass ends in ``rebuild_centroids()`` when the
+        reinforced once by ``merge_reinforce`` up to ``merge_cap``, as a consolidating write does per chunk.  Without
+        ``blend`` the kept row's features stand.  With ``rebuild`` the pass ends in ``rebuild_centroids()`` when the
         index is in use and more than ``centroids_k`` rows remain; otherwise the inverted lists are invalidated and
         ``centroid_counts`` corrected as ``forget`` does (the centroid means stay).  If a slab fails, the undecided
         remainder is moved down unchanged and the host maps are committed before the error is raised again: the bank
@@ -1374,13 +1472,25 @@ class HippocampalFormation(nn.Module):
         nothing more is read back -- so a row merges only into a kept row of ITS tag (0, "untagged", is a scope like any
         other): the bank becomes what writing its rows oldest first, each with its tag, through
         ``create_episodic_memories(..., tags=..., merge_within_tags=True)`` would have left.  Every kept row keeps its
-        own tag; strength and timestamp take the maximum as above."""
+        own tag; strength and timestamp take the maximum as above.
+
+        ``blend`` (None: ``self.merge_blend``, off unless the bank was built otherwise): a rate in ``(0, 1]``.  Per slab,
+        after the search and before the metadata maxima, the reinforcement and the move, one launch
+        (``ops.bank_blend`` on the slab in place) moves every kept memory toward the slab rows that repeat it,
+        ``g = g + beta * (f_i - g)`` in ascending row order (the rule: ``include/aura_hip.h``, "Blending merges").  The
+        equivalence above keeps holding, bit for bit in the features: the bank becomes what writing its rows oldest
+        first through BLENDED consolidating writes in chunks of 1024 would have left.  As there, a slab's decisions are
+        those made before its blend, and a memory that drifts within ``similarity`` of another kept memory merges only
+        at the next ``consolidate()``."""
         tau = self.merge_similarity if similarity is None else similarity
         within = self.merge_within_tags if within_tags is None else bool(within_tags)
         if tau is None:
             raise ValueError("consolidate needs a similarity in (0, 1] (none given and the bank has no merge_similarity)")
         self._check_merge(tau, self.merge_reinforce, self.merge_cap)
         tau = float(tau)
+        beta = self.merge_blend if blend is None else blend
+        self._check_blend(beta, tau)
+        n_blended = 0
         n_before = self.memory_count
         first = None
         if self._ring_start():
@@ -1400,12 +1510,19 @@ class HippocampalFormation(nn.Module):
             while lo < count:
                 hi = min(count, lo + ops.CONSOLIDATE_MAX_BATCH)   # a slab: what one find_repeats call decides
                 self.memory_count = n_kept                  # the held set of this slab: the decided prefix
-                if within:
+                packed_dev = None
+                if beta is not None:
+                    slab_tags = self.memory_metadata[lo:hi, 3].to(torch.int32) if within else None
+                    packed, packed_dev = self._find_repeats_packed(self.memory_features[lo:hi], tau, slab_tags, False)
+                    stored, leader = packed[:hi - lo], packed[hi - lo:2 * (hi - lo)]
+                elif within:
                     stored, leader, _ = self.find_repeats(self.memory_features[lo:hi], tau, _use_lists=False,
                                                           tags=self.memory_metadata[lo:hi, 3].to(torch.int32))
                 else:
                     stored, leader, _ = self.find_repeats(self.memory_features[lo:hi], tau, _use_lists=False)
                 stored, leader = stored.numpy().astype(np.int64), leader.numpy().astype(np.int64)
+                if packed_dev is not None:                  # the slab in place; held targets lie below it
+                    n_blended += self._blend_groups(packed_dev, stored, leader, float(beta), row0=lo)[1]
                 kept = (stored < 0) & (leader < 0)
                 kept_local = np.nonzero(kept)[0]
                 merged_local = np.nonzero(~kept)[0]
@@ -1447,7 +1564,8 @@ class HippocampalFormation(nn.Module):
             self.rebuild_centroids()
         if first is not None:
             old_to_new = old_to_new[first]                  # (putting the ring in order removed nothing)
-        return BankConsolidationReport(n_before=n_before, n_kept=n_kept, n_merged=count - n_kept, old_to_new=old_to_new)
+        return BankConsolidationReport(n_before=n_before, n_kept=n_kept, n_merged=count - n_kept, old_to_new=old_to_new,
+                                       n_blended=n_blended)
 
     # ------------------------------------------------------------------ recall
     def _candidate_mode(self) -> bool:

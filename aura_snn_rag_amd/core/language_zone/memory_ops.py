@@ -58,7 +58,8 @@ def retrieve_memories(hippocampus, query: torch.Tensor, k: int = 5, dtype=None,
 
 
 def store_memory(hippocampus, hidden_states: torch.Tensor, event_tag: str = "layer",
-                 merge_similarity: Optional[float] = None, tag=None, merge_within_tags: Optional[bool] = None):
+                 merge_similarity: Optional[float] = None, tag=None, merge_within_tags: Optional[bool] = None,
+                 merge_blend: Optional[float] = None):
     """Mean-pool each batch item and store it (``memory_augmented_layer.py:132-153``).  ``merge_similarity`` (default
     off): a consolidating write -- a pooled row that repeats a held memory at that cosine strengthens it instead of
     taking a slot (``HippocampalFormation.create_episodic_memories(merge_similarity=...)``, whose report is returned);
@@ -66,7 +67,9 @@ def store_memory(hippocampus, hidden_states: torch.Tensor, event_tag: str = "lay
     the stored memories carry it (``HippocampalFormation.create_episodic_memories(tags=...)``) and
     ``retrieve_memories(tags=...)`` recalls within it; together with a consolidating write only when the consolidation
     stays within tags.  ``merge_within_tags`` (default None: what the bank was constructed with): a pooled row then
-    merges only into a memory of its own tag (``create_episodic_memories(merge_within_tags=...)``)."""
+    merges only into a memory of its own tag (``create_episodic_memories(merge_within_tags=...)``).  ``merge_blend``
+    (default None: what the bank was constructed with): the rate at which a repeated memory moves toward the pooled rows
+    that repeat it (``create_episodic_memories(merge_blend=...)``)."""
     if hippocampus is None:
         return None
     feats = hidden_states.detach().float().mean(dim=1)                      # [B, D]
@@ -74,6 +77,8 @@ def store_memory(hippocampus, hidden_states: torch.Tensor, event_tag: str = "lay
     kw = {} if tag is None else dict(tags=tag)
     if merge_within_tags is not None:
         kw["merge_within_tags"] = merge_within_tags
+    if merge_blend is not None:
+        kw["merge_blend"] = merge_blend
     if merge_similarity is None:
         return hippocampus.create_episodic_memories(ids, feats, **kw)
     return hippocampus.create_episodic_memories(ids, feats, merge_similarity=merge_similarity, **kw)
@@ -140,9 +145,10 @@ class MemoryInjection(nn.Module):
                                  min_strength=min_strength)
 
     def store_memory(self, hidden_states: torch.Tensor, merge_similarity: Optional[float] = None, tag=None,
-                     merge_within_tags: Optional[bool] = None):
+                     merge_within_tags: Optional[bool] = None, merge_blend: Optional[float] = None):
         return store_memory(self.hippocampus, hidden_states, event_tag=f"layer_{id(self)}",
-                            merge_similarity=merge_similarity, tag=tag, merge_within_tags=merge_within_tags)
+                            merge_similarity=merge_similarity, tag=tag, merge_within_tags=merge_within_tags,
+                            merge_blend=merge_blend)
 
     def inject_memories(self, hidden_states, memory_features, memory_scores):
         if self.memory_injection == "cross_attention":
@@ -152,12 +158,15 @@ class MemoryInjection(nn.Module):
             return inject_concat(hidden_states, memory_features, memory_scores)
         return inject_gate(hidden_states, memory_features, memory_scores, self.memory_proj, self.memory_gate)
 
-    def consolidate_memory(self, similarity: Optional[float] = None, within_tags: Optional[bool] = None):
+    def consolidate_memory(self, similarity: Optional[float] = None, within_tags: Optional[bool] = None,
+                           blend: Optional[float] = None):
         """Merge the near-copies the bank holds (``HippocampalFormation.consolidate``); ``within_tags`` (None: the
-        bank's default): only among memories of one tag."""
-        if within_tags is None:
-            return self.hippocampus.consolidate(similarity=similarity)
-        return self.hippocampus.consolidate(similarity=similarity, within_tags=within_tags)
+        bank's default): only among memories of one tag; ``blend`` (None: the bank's default): the rate at which a
+        kept memory moves toward the rows merged into it."""
+        kw = {} if within_tags is None else dict(within_tags=within_tags)
+        if blend is not None:
+            kw["blend"] = blend
+        return self.hippocampus.consolidate(similarity=similarity, **kw)
 
     def replay_memories(self, n: int, **kw):
         """``(features [n, D], rows int32 [n])``: ``n`` held memories drawn by priority for a sleep phase
@@ -189,16 +198,20 @@ class BatchedMemoryMixin:
                                  min_strength=min_strength)
 
     def store_memory(self, hidden_states: torch.Tensor, merge_similarity: Optional[float] = None, tag=None,
-                     merge_within_tags: Optional[bool] = None):
+                     merge_within_tags: Optional[bool] = None, merge_blend: Optional[float] = None):
         return store_memory(self.hippocampus, hidden_states, event_tag=f"layer_{id(self)}",
-                            merge_similarity=merge_similarity, tag=tag, merge_within_tags=merge_within_tags)
+                            merge_similarity=merge_similarity, tag=tag, merge_within_tags=merge_within_tags,
+                            merge_blend=merge_blend)
 
-    def consolidate_memory(self, similarity: Optional[float] = None, within_tags: Optional[bool] = None):
+    def consolidate_memory(self, similarity: Optional[float] = None, within_tags: Optional[bool] = None,
+                           blend: Optional[float] = None):
         """Merge the near-copies the bank holds (``HippocampalFormation.consolidate``); ``within_tags`` (None: the
-        bank's default): only among memories of one tag."""
-        if within_tags is None:
-            return self.hippocampus.consolidate(similarity=similarity)
-        return self.hippocampus.consolidate(similarity=similarity, within_tags=within_tags)
+        bank's default): only among memories of one tag; ``blend`` (None: the bank's default): the rate at which a
+        kept memory moves toward the rows merged into it."""
+        kw = {} if within_tags is None else dict(within_tags=within_tags)
+        if blend is not None:
+            kw["blend"] = blend
+        return self.hippocampus.consolidate(similarity=similarity, **kw)
 
     def replay_memories(self, n: int, **kw):
         """``(features [n, D], rows int32 [n])``: ``n`` held memories drawn by priority for a sleep phase

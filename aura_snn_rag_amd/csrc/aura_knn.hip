@@ -81,20 +81,7 @@ __global__ __launch_bounds__(256) void row_inv_norm_kernel(const float* __restri
 // per-lane fmaf chain, same butterfly), so a bank's cached norms do not depend on whether they were
 // produced by a write or recomputed after a state_dict load: recall is bit-identical either way.
 // ------------------------------------------------------------------------------------------
-__device__ __forceinline__ float wave_row_sumsq(const float* __restrict__ p, int64_t D, int lane, bool vec4) {
-    float s = 0.0f;
-    if (vec4) {
-        for (int64_t i = lane * 4; i < D; i += 256) {
-            const float4 v = *reinterpret_cast<const float4*>(p + i);
-            s = fmaf(v.x, v.x, s); s = fmaf(v.y, v.y, s); s = fmaf(v.z, v.z, s); s = fmaf(v.w, v.w, s);
-        }
-    } else {
-        for (int64_t i = lane; i < D; i += 64) s = fmaf(p[i], p[i], s);
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
-    return s;
-}
+#include "aura_row.inl"      // wave_row_sumsq
 
 // Without centroid maintenance: independent rows, one wave per row.
 __global__ __launch_bounds__(256) void bank_write_kernel(float* bank, float* loc, float* meta,

@@ -770,6 +770,82 @@ def _find_repeats(bank, inv_norm, count, feats, tau, image, image_rows, n_image,
     return stored, leader, cos, packed
 
 
+def bank_blend(bank, inv_norm, count: int, stored_target, batch_leader, beta: float, feats=None, out=None,
+               feats_row0: int = -1, shadow=None, rho=None, shadow_upto: int = 0, sorted_bf16=None, sorted_rows=None,
+               pos_of_row=None, n_sorted: Optional[int] = None) -> None:
+    """Blending merges (the rule: ``include/aura_hip.h``, "Blending merges"): every memory that rows of the batch
+    repeat moves toward them, ``g = g + beta * (f_i - g)`` over its members in ascending batch order, in one launch.
+    ``stored_target`` / ``batch_leader``: int32 [n] on the bank's device, as ONE ``find_repeats`` call against
+    ``bank[:count]`` left them (grouping happens on the device; nothing is read back).  ``feats_row0 == -1``: the batch
+    is ``feats`` [n, D]; a blended in-batch leader goes to ``out`` [n, D], which the caller has filled with a copy of
+    ``feats`` (``feats`` is never written).  ``feats_row0 >= count``: the batch is bank rows
+    ``[feats_row0, feats_row0 + n)`` and a blended leader is written in place.  For every BANK row that moves the launch
+    also refreshes ``inv_norm`` (``bank_row_norms``' bits), with ``shadow`` + ``rho`` the row's bf16 shadow and residual
+    if it lies below ``shadow_upto`` (``bank_shadow_update``'s bits), and with ``sorted_bf16`` + ``sorted_rows`` +
+    ``pos_of_row`` (+ ``rho``) its entry of the list-sorted image, in place.  ``rho`` goes with a shadow or an image,
+    and only with one; the image's three tensors go together.  Entries out of range are ignored.  No host sync."""
+    _need(bank, "bank", torch.float32); _need(inv_norm, "inv_norm", torch.float32)
+    _need(stored_target, "stored_target", torch.int32); _need(batch_leader, "batch_leader", torch.int32)
+    beta = float(beta)
+    if not (0.0 < beta <= 1.0):
+        raise ValueError(f"bank_blend: beta must be in (0, 1], got {beta}")
+    if bank.dim() != 2 or not (0 <= count <= bank.shape[0]) or inv_norm.numel() != bank.shape[0]:
+        raise ValueError("bank_blend: bank must be [rows, D] with count <= rows and one inv_norm per row")
+    M, D = bank.shape
+    if not (1 <= D <= 4096) or M > 0x7fffffff:
+        raise ValueError(f"bank_blend: D={D} must be in [1, 4096] and the bank below 2^31 rows")
+    n = stored_target.numel()
+    if stored_target.dim() != 1 or batch_leader.shape != stored_target.shape or n > CONSOLIDATE_MAX_BATCH:
+        raise ValueError(f"bank_blend: stored_target and batch_leader must be int32 [n], n <= {CONSOLIDATE_MAX_BATCH}")
+    feats_row0 = int(feats_row0)
+    if feats_row0 == -1:
+        if feats is None or out is None:
+            raise ValueError("bank_blend: feats and out are required unless the batch is a slab of the bank")
+        _need(feats, "feats", torch.float32); _need(out, "out", torch.float32)
+        if feats.shape != (n, D) or out.shape != (n, D):
+            raise ValueError(f"bank_blend: feats and out must be [{n}, {D}]")
+        if out.data_ptr() == feats.data_ptr() and n:
+            raise ValueError("bank_blend: out must be a copy of feats, not feats itself")
+    else:
+        if feats is not None or out is not None:
+            raise ValueError("bank_blend: a slab of the bank (feats_row0 >= 0) takes no feats / out")
+        if not (count <= feats_row0 and feats_row0 + n <= M):
+            raise ValueError(f"bank_blend: the slab [{feats_row0}, {feats_row0 + n}) must lie in [count={count}, {M}]")
+    has_image = sorted_bf16 is not None
+    if (sorted_rows is not None) != has_image or (pos_of_row is not None) != has_image:
+        raise ValueError("bank_blend: sorted_bf16, sorted_rows and pos_of_row go together")
+    if (rho is not None) != (shadow is not None or has_image):
+        raise ValueError("bank_blend: rho goes with a shadow or a list-sorted image, and only with one")
+    if rho is not None:
+        _need(rho, "rho", torch.float32)
+        if rho.numel() != M or D % 8:
+            raise ValueError("bank_blend: a shadow or image needs D % 8 == 0 and one rho per bank row")
+    if shadow is not None:
+        _need(shadow, "shadow", torch.bfloat16)
+        shadow_upto = int(shadow_upto)
+        if shadow.shape != bank.shape or not (0 <= shadow_upto <= M):
+            raise ValueError("bank_blend: the shadow is [rows, D] bf16 and shadow_upto lies in [0, rows]")
+    else:
+        shadow_upto = 0
+    ns = 0
+    if has_image:
+        _need(sorted_bf16, "sorted_bf16", torch.bfloat16); _need(sorted_rows, "sorted_rows", torch.int32)
+        _need(pos_of_row, "pos_of_row", torch.int32)
+        ns = sorted_rows.numel() if n_sorted is None else int(n_sorted)
+        if sorted_bf16.dim() != 2 or sorted_bf16.shape[1] != D or pos_of_row.numel() != M or \
+                not (0 <= ns <= min(sorted_rows.numel(), sorted_bf16.shape[0])):
+            raise ValueError("bank_blend: the image is [>= n_sorted, D] bf16 with sorted_rows [>= n_sorted] and "
+                             "pos_of_row [rows]")
+    for t in (inv_norm, stored_target, batch_leader, feats, out, shadow, rho, sorted_bf16, sorted_rows, pos_of_row):
+        if t is not None and t.device != bank.device:
+            raise ValueError("bank_blend: tensors are on different devices")
+    if n == 0:
+        return
+    check(lib().aura_bank_blend(_p(bank), _p(inv_norm), count, M, D, _p(feats), feats_row0, n, _p(stored_target),
+                                _p(batch_leader), beta, _p(out), _p(shadow), _p(rho), shadow_upto, _p(sorted_bf16),
+                                _p(sorted_rows), _p(pos_of_row), ns, _stream()), "aura_bank_blend")
+
+
 def bank_touch(meta, count: int, rows, now: float) -> None:
     """``meta[r][1] = now`` for every row id of ``rows`` (int32, any shape) inside [0, count); others are ignored."""
     _check_meta(meta, count, "bank_touch")

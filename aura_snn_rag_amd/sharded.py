@@ -114,6 +114,7 @@ class ShardedHippocampus:
         self.local = local
         self._refuse_quota()
         self._refuse_weakest()
+        self._refuse_blend(getattr(local, 'merge_blend', None))
         self.ops = _ops if ops_module is None else ops_module
         self.group = group
         self.R = int(local.max_memories)
@@ -175,6 +176,15 @@ class ShardedHippocampus:
                              "weakest rows would need a selection across them; set quotas on a single "
                              "HippocampalFormation")
 
+    @staticmethod
+    def _refuse_blend(beta) -> None:
+        """Blending merges are a single-bank feature: raised from the argument alone, on every rank alike and before
+        any collective."""
+        if beta is not None:
+            raise ValueError("ShardedHippocampus does not blend (merge_blend): a sharded write stores every row -- it has "
+                             "no cross-rank near-copy search for a blend to follow; blend on a single "
+                             "HippocampalFormation")
+
     def set_tag_quota(self, tag, quota) -> None:
         """Refused (``ValueError``): quotas are not available on a row-sharded bank."""
         raise ValueError("ShardedHippocampus does not support tag_quota: a tag's rows would span the shards, and its "
@@ -192,13 +202,15 @@ class ShardedHippocampus:
                              f"sizes); tag and recall on a single HippocampalFormation")
 
     # ------------------------------------------------------------------ write
-    def write(self, memory_ids, features, tags=None) -> None:
+    def write(self, memory_ids, features, tags=None, merge_blend=None) -> None:
         """Collective batched write: identical to ``HippocampalFormation.create_episodic_memories`` on one
         bank of ``total_rows`` rows, including the rebuild every ``centroids_update_interval`` inserts
         (``overflow='reference'`` or ``'fifo'``; ``'weakest'`` raises ``ValueError``).  ``tags`` is refused
-        (``ValueError``): cross-rank scopes are not implemented."""
+        (``ValueError``): cross-rank scopes are not implemented; so is ``merge_blend`` (a sharded write does not
+        consolidate, so there is nothing to blend into)."""
         import numpy as np
         self._refuse_scope("write", tags=tags)
+        self._refuse_blend(merge_blend)
         self._refuse_weakest()
         loc = self.local
         feats = loc._features_to_device(features)

@@ -230,6 +230,52 @@ int aura_bank_find_repeats_scoped(const float* bank, const float* inv_norm, int6
                                   int32_t* batch_leader, float* cos_out, int32_t* overflow_out, void* workspace,
                                   int64_t workspace_bytes, void* stream, const float* meta, const int32_t* batch_tags);
 
+/* Blending merges: a repeated memory moves toward the rows that repeat it (csrc/aura_blend.hip).  [build-side] the
+ * reference's centroid index keeps an online running mean of what it absorbs (hippocampal.py:226-228); its bank stores
+ * every row.
+ *
+ * THE RULE.  Inputs: the stored_target / batch_leader of ONE aura_bank_find_repeats[_scoped] call for a batch
+ * f_0 .. f_{n-1} (n <= 1024) against the N held rows, and a rate beta in (0, 1], fp32.
+ *   Group key of batch row i.  stored_target[i] = r >= 0: held row r.  Else batch_leader[i] = j >= 0: batch row j.
+ *     Else row i is kept and is a member of nothing.
+ *   Members are never keys (a row with a stored target or a leader is not stored); they are read unblended.
+ *   Held key r.  g = bank[r]; for its members in ASCENDING i:  g = g + beta * (f_i - g), per component in fp32 with
+ *     three roundings -- the difference, the product, the sum; never fused (-ffp-contract=off and the pragma of
+ *     aura_common.inl).  Then bank[r] = g.  The order matters: the update does not commute for beta != 1/2.
+ *   Batch key j.  The same chain from g = f_j; the result replaces row j of the batch as it will be stored.
+ *   Decisions.  Every decision of the call is the one find_repeats made against the bank as it stood BEFORE the blend:
+ *     a blended memory that drifts within tau of another held memory merges with it only at the next consolidate().
+ *   Metadata.  Strength, timestamp, tag, centroid id, ids and centroid_counts are not touched; reinforcing, touching
+ *     and the maxima of consolidate() stay what they are.  The stored centroid id and the centroid means stay until the
+ *     next centroid rebuild, as after a compaction.
+ *
+ * aura_bank_blend applies the rule in one launch and keeps the derived state of every BANK row it moves current:
+ *   bank[r]; inv_norm[r] with aura_bank_row_norms' arithmetic, bit for bit; when shadow_bf16 is given and
+ *   r < shadow_upto, shadow_bf16[r] and rho[r] with aura_bank_shadow_update's arithmetic; when the list-sorted image is
+ *   given and pos_of_row[r] = p with 0 <= p < n_sorted and sorted_rows[p] == r, the same bf16 bits into sorted_bf16[p]
+ *   (and rho[r]), in place -- the centroid id has not changed, so the lists gain no hole and use no slack.  A cached
+ *   table of aura_ivf2_row_constants is stale afterwards (rho changed).
+ * The batch.  feats_row0 == -1: feats [n][D]; blended batch keys go to out_feats [n][D], which the caller has filled
+ *   with a copy of feats (only blended rows are written; feats itself never is); the write that stores them derives
+ *   their norms and shadows as for any row.  feats_row0 >= 0: the batch IS bank rows [feats_row0, feats_row0 + n)
+ *   (feats / out_feats are ignored); held targets lie below it (N <= feats_row0) and a blended batch key is written
+ *   in place with the derived state above.
+ * Grouping is done on the device from the two arrays (device int32 [n]); nothing is read back.  Every id is checked
+ *   before it becomes an address: a stored target outside [0, N), and a leader outside [0, i) or one that is not
+ *   itself a kept row, are ignored (the row is a member of nothing).  Sets no flag, needs no workspace, cannot overflow.
+ * 1 <= D <= 4096; n == 0 launches nothing.  16-byte accesses when D % 4 == 0 and bank is 16-byte aligned (the
+ *   condition of aura_bank_row_norms, so that the norm associates alike), 4-byte ones otherwise.
+ * AURA_E_INVAL: n outside [0, 1024], D outside [1, 4096], rows < N or rows >= 2^31, beta outside (0, 1] or NaN,
+ *   feats_row0 < -1 or a slab outside [N, rows], a null array that is needed, rho given without shadow_bf16 or the
+ *   image (or the reverse), the image's three arrays not all given, an image or shadow with D % 8 != 0, shadow_upto
+ *   outside [0, rows].  AURA_E_ALIGN: a shadow or image that is not 16-byte aligned or comes with an unaligned bank;
+ *   an aligned bank with D % 4 == 0 whose feats / out_feats are not 16-byte aligned. */
+int aura_bank_blend(float* bank, float* inv_norm, int64_t N, int64_t rows, int64_t D, const float* feats,
+                    int64_t feats_row0, int64_t n, const int32_t* stored_target, const int32_t* batch_leader,
+                    float beta, float* out_feats, uint16_t* shadow_bf16, float* rho, int64_t shadow_upto,
+                    uint16_t* sorted_bf16, const int32_t* sorted_rows, const int32_t* pos_of_row, int64_t n_sorted,
+                    void* stream);
+
 /* In-place compaction of the bank (csrc/aura_compact.hip): the primitive under forgetting, pruning and the
  * consolidation of held rows.  [build-side] no upstream counterpart (the reference's pruning ends in `pass`).
  * For every i < n, row src[i] of every array moves to row dst0 + i.  The arrays: bank [rows][D], loc [rows][S],

@@ -32,6 +32,14 @@ warm-up, the things compared taken in alternating order inside each round (tools
   The bar: the scoped search costs what the unscoped one costs -- its median may not exceed the largest window of the
   unscoped call in the same run (the margin is the unscoped call's own spread, nothing else).
 
+  blending merges ("blending"): merging writes with ``merge_blend = 0.5`` next to the same writes without,
+  a stream whose rows are half noisy copies of held rows, batches of 256 and of 1024 rows, alternated in one process on
+  the same bank, the unblended call taken TWICE (a, b) as above; then ``consolidate(blend=0.5)`` next to
+  ``consolidate()`` on fresh banks of ``--consolidate-rows`` bulk-written rows, a fifth of them noisy copies (a pass
+  consumes its bank, so every measurement builds one; only the pass is timed).  The bar, both times: the blended median
+  may not exceed the largest unblended window of the same run.  ``--only blend`` measures this section alone and
+  replaces it in an existing ``--out`` file, leaving the other sections as they were recorded.
+
 ``--only trace``: find_repeats alone, both batch sizes, for ``rocprofv3 --kernel-trace --stats -- python
 tools/consolidate_bench.py --only trace`` in a run of its own."""
 import argparse
@@ -39,6 +47,7 @@ import json
 import os
 import statistics
 import sys
+import time
 
 import torch
 
@@ -54,7 +63,8 @@ WINDOW_S = 0.3
 TAU = 0.9
 BATCHES = (256, 1024)
 WRITE_BATCH = 256
-HEADROOM = 1 << 16
+HEADROOM = 1 << 17
+BETA = 0.5
 BAR = 1.10
 N_TAGS = 64
 
@@ -96,12 +106,99 @@ def tags_for(hf, src, g):
     return torch.where(src >= 0, held, fresh).contiguous()
 
 
+def blend_section(hf, g, consolidate_rows, D, dev):
+    """Blended next to unblended merging writes on ``hf``, then consolidate(blend=) next to consolidate()."""
+    from aura_snn_rag_amd.core.hippocampal import HippocampalFormation
+    res = {"beta": BETA, "repeat_share": 0.5, "writes": [], "batches_per_window": 5}
+    serial = [0]
+    per_writer = 3 + 5 * WINDOWS
+
+    def writer(n, beta):
+        todo = []
+        for _ in range(per_writer):
+            todo.append(([f"b{serial[0]}-{i}" for i in range(n)], make_batch(hf, n, n // 2, g)))
+            serial[0] += 1
+
+        def fn():
+            ids, f = todo.pop()
+            if beta is None:
+                hf.create_episodic_memories(ids, f, merge_similarity=TAU)
+            else:
+                hf.create_episodic_memories(ids, f, merge_similarity=TAU, merge_blend=beta)
+        return fn
+
+    def compare(ms, n=None):
+        un = ms["unblended_a"] + ms["unblended_b"]
+        med_un, med_bl = statistics.median(un), statistics.median(ms["blended"])
+        r = {**{k: summary(v) for k, v in ms.items()}, "unblended_median_ms": med_un, "unblended_min_ms": min(un),
+             "unblended_max_ms": max(un), "unblended_spread": (max(un) - min(un)) / med_un, "blended_median_ms": med_bl,
+             "blended_over_unblended": med_bl / med_un, "bar_met": med_bl <= max(un)}
+        if n is not None:
+            r["n"] = n
+            r["blended_rows_per_s"] = n / (med_bl * 1e-3 / 5)
+            r["unblended_rows_per_s"] = n / (med_un * 1e-3 / 5)
+        return r
+    for n in BATCHES:
+        fns = {"unblended_a": writer(n, None), "blended": writer(n, BETA), "unblended_b": writer(n, None)}
+        ms = {name: [] for name in fns}
+        for fn in fns.values():
+            for _ in range(3):
+                fn()
+        names = list(fns)
+        for rnd in range(WINDOWS):
+            for name in (names if rnd % 2 == 0 else names[::-1]):
+                ms[name].append(wall_window(fns[name], 5) * 5)          # ms per window of 5 batches
+        r = compare(ms, n)
+        print(r, flush=True)
+        res["writes"].append(r)
+    res["bank_rows_at_the_end"] = hf.memory_count
+    # ---- consolidate(blend=) next to consolidate(): fresh banks of the same rows
+    gc = torch.Generator(device=dev).manual_seed(5)
+    base = torch.randn(consolidate_rows - consolidate_rows // 5, D, generator=gc, device=dev)
+    pick = torch.randint(0, base.shape[0], (consolidate_rows // 5,), generator=gc, device=dev)
+    rows = torch.cat([base, base[pick] + 0.05 * torch.randn(pick.numel(), D, generator=gc, device=dev)])
+    rows = rows[torch.randperm(rows.shape[0], generator=gc, device=dev)].contiguous()
+    kept = {}
+
+    def one_pass(beta):
+        bank = HippocampalFormation(feature_dim=D, max_memories=rows.shape[0], n_place_cells=8, n_time_cells=4,
+                                    n_grid_cells=4, device="cuda", use_centroid_index=False)
+        bank.bulk_write(rows, rebuild=False)
+        bank._ensure_shadow()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        rep = bank.consolidate(TAU) if beta is None else bank.consolidate(TAU, blend=beta)
+        torch.cuda.synchronize()
+        kept[beta] = (rep.n_kept, rep.n_merged, rep.n_blended)
+        return 1e3 * (time.perf_counter() - t0)
+    one_pass(None), one_pass(BETA)                                       # warm-up
+    ms = {"unblended_a": [], "blended": [], "unblended_b": []}
+    order = [("unblended_a", None), ("blended", BETA), ("unblended_b", None)]
+    for rnd in range(WINDOWS):
+        for name, beta in (order if rnd % 2 == 0 else order[::-1]):
+            ms[name].append(one_pass(beta))
+    r = compare(ms)
+    r.update(rows=int(rows.shape[0]), kept_merged_blended_unblended=kept[None], kept_merged_blended_blended=kept[BETA])
+    print(r, flush=True)
+    res["consolidate"] = r
+    return res
+
+
+def report_blend(res):
+    for r in res["writes"] + [res["consolidate"]]:
+        if not r["bar_met"]:
+            what = f"merging writes, n = {r['n']}" if "n" in r else "consolidate"
+            print(f"blending, {what}: the blended median {r['blended_median_ms']:.4f} ms lies above every unblended "
+                  f"window (max {r['unblended_max_ms']:.4f} ms): the bar is MISSED")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=1_000_000)
     ap.add_argument("--dim", type=int, default=768)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "consolidate_bench.json"))
-    ap.add_argument("--only", choices=("trace",), default=None)
+    ap.add_argument("--only", choices=("trace", "blend"), default=None)
+    ap.add_argument("--consolidate-rows", type=int, default=100_000)
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("consolidate_bench.py measures on the GPU; none found (nothing is measured on the CPU)")
@@ -127,6 +224,18 @@ def main():
             for _ in range(30):
                 hf.find_repeats(batches[n], TAU)
         torch.cuda.synchronize()
+        return
+    if a.only == "blend":
+        out = {}
+        if os.path.exists(a.out):
+            with open(a.out) as fh:
+                out = json.load(fh)
+        out["blend"] = dict(blend_section(hf, g, a.consolidate_rows, D, dev), device=torch.cuda.get_device_name(0),
+                            rows=a.rows, dim=D, tau=TAU, windows=WINDOWS)
+        with open(a.out, "w") as fh:
+            json.dump(out, fh, indent=1)
+        print("wrote", a.out)
+        report_blend(out["blend"])
         return
     out = {"device": torch.cuda.get_device_name(0), "rows": a.rows, "dim": D, "index": True, "tau": TAU,
            "windows": WINDOWS, "window_s_at_least": WINDOW_S, "copy_bytes_per_s_assumed": COPY_BYTES_PER_S,
@@ -241,6 +350,7 @@ def main():
         out["write_rate"][f"merge_tagged_over_merge_{share}"] = (out["write_rate"][f"merge_tagged_{share}"]["median_ms"] /
                                                                  out["write_rate"][f"merge_{share}"]["median_ms"])
     print(out["write_rate"], flush=True)
+    out["blend"] = blend_section(hf, g, a.consolidate_rows, D, dev)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as fh:
         json.dump(out, fh, indent=1)
@@ -252,6 +362,7 @@ def main():
             if not r[key]["bar_met"]:
                 print(f"within tags, n = {r['n']}, {key}: the scoped median {r[key]['scoped_median_ms']:.4f} ms lies above "
                       f"every unscoped window (max {r[key]['unscoped_max_ms']:.4f} ms): the bar is MISSED")
+    report_blend(out["blend"])
     missed = [r["n"] for r in out["find_repeats"] if not r["bar_met"]]
     if missed:
         raise SystemExit(f"find_repeats takes more than {BAR} x recall_batch(k=1, use_candidates=False) at n = {missed}")
