@@ -22,6 +22,7 @@ ERRORS = {-1: "AURA_E_INVAL (bad argument)", -2: "AURA_E_LAUNCH (HIP launch erro
 
 DTYPE_F32, DTYPE_BF16 = 0, 1
 GIF_TIME_INVARIANT, GIF_MEAN_OUT = 1, 2
+STDP_PRE_TIME_INVARIANT, STDP_NO_APPLY = 1, 2
 KNN_FORCE_DENSE = 1
 KNN_FP32_SCAN = 2
 KNN_FLAG_LISTS_STALE = 128     # bit of the overflow flag: the inverted lists dropped a row (re-pack and repeat)
@@ -116,6 +117,8 @@ SIGNATURES = {
     "aura_signal_flag": (I, [P, P, U32, P]),
     "aura_knn_search_ivf2_signal": (I, [P, P, P, P, P, P, P, P, P, P, I64, I64, P, F, I64, I64, I, P, I, P, I32, P, P, P,
                                         I64, P, P, U32, P]),
+    "aura_stdp_workspace_bytes": (I64, [I64, I64, I64, I64]),
+    "aura_stdp_update": (I, [P, P, P, P, P, P, P, P, F, F, F, F, F, F, F, I64, I64, I64, I64, I, I, P, I64, P]),
     "aura_profile_begin": (I, [I]),
     "aura_debug_cs_flags": (I, [I]),
     "aura_debug_clock_mhz": (I, [P, I, P]),

@@ -30,15 +30,16 @@ from .synapsis import Synapsis
 
 class SNNFFN(nn.Module):
     def __init__(self, input_dim: int, hidden_dim: int, output_dim: Optional[int] = None,
-                 num_timesteps: int = 4, L: int = 8, dropout: float = 0.1):
+                 num_timesteps: int = 4, L: int = 8, dropout: float = 0.1, plasticity: bool = False):
         super().__init__()
         self.input_dim = input_dim
         self.hidden_dim = hidden_dim
         self.output_dim = output_dim or input_dim
         self.num_timesteps = num_timesteps
-        self.syn1 = Synapsis(input_dim, hidden_dim)
+        self.plasticity = plasticity                       # both synapses learn by timestep STDP (stdp_step)
+        self.syn1 = Synapsis(input_dim, hidden_dim, enable_plasticity=plasticity)
         self.neuron1 = GIFNeuron(hidden_dim, hidden_dim, L=L)
-        self.syn2 = Synapsis(hidden_dim, self.output_dim)
+        self.syn2 = Synapsis(hidden_dim, self.output_dim, enable_plasticity=plasticity)
         self.neuron2 = GIFNeuron(self.output_dim, self.output_dim, L=L)
         self.dropout = nn.Dropout(dropout)
 
@@ -71,6 +72,39 @@ class SNNFFN(nn.Module):
             out, _ = run_gif_loop(c2, None, decay=n2.decay, L=n2.L, alpha=n2.alpha,
                                   threshold=n2.threshold, T=T, mean_out=True)
         return self.dropout(out.reshape(B, S, self.output_dim))
+
+    def stdp_step(self, x: torch.Tensor, state=None):
+        """One online-learning step (fp32 modules, ``plasticity=True``): the no-grad forward with the spikes of both
+        layers written, then timestep STDP (``Synapsis.stdp_update``) of ``syn2`` from ``(spikes1, spikes2)`` and of
+        ``syn1`` from ``(x, spikes1)`` -- ``x`` is the same at every step, so it is read once per row.  The forward
+        sees the weights as they were before the step.  ``state``: the ``(state1, state2)`` of the previous step on the
+        same rows, or ``None``.  Returns ``(out, (state1, state2))`` with ``out`` [B, S, output_dim] the mean over T of
+        layer 2's spikes (no dropout: this is not the training forward)."""
+        _check_input(x, "SNNFFN.stdp_step")
+        if not self.plasticity:
+            raise RuntimeError("SNNFFN.stdp_step: build the module with plasticity=True")
+        if x.dtype != torch.float32 or self.syn1.weight.dtype != torch.float32:
+            raise TypeError("SNNFFN.stdp_step runs on fp32 modules and inputs only")
+        B, S, _ = x.shape
+        T = self.num_timesteps
+        rows = B * S
+        n1, n2 = self.neuron1, self.neuron2
+        state1, state2 = (None, None) if state is None else state
+        with torch.no_grad():
+            x1 = x.detach().reshape(rows, self.input_dim).contiguous()
+            h1 = torch.nn.functional.linear(x1, self.syn1.weight, self.syn1.bias)
+            c1 = n1.currents(h1)                                   # [rows, H]
+            spikes1, _ = run_gif_loop(c1, None, decay=n1.decay, L=n1.L, alpha=n1.alpha,
+                                      threshold=n1.threshold, T=T, time_invariant=True)
+            h2 = torch.nn.functional.linear(spikes1.reshape(rows * T, self.hidden_dim), self.syn2.weight,
+                                            self.syn2.bias)
+            c2 = n2.currents(h2).reshape(rows, T, self.output_dim)
+            spikes2, _ = run_gif_loop(c2, None, decay=n2.decay, L=n2.L, alpha=n2.alpha,
+                                      threshold=n2.threshold, T=T)
+            state2, _ = self.syn2.stdp_update(spikes1, spikes2, state2)
+            state1, _ = self.syn1.stdp_update(x1, spikes1, state1)
+            out = spikes2.mean(dim=1).reshape(B, S, self.output_dim)
+        return out, (state1, state2)
 
 
 class HybridFFN(nn.Module):

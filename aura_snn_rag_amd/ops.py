@@ -141,6 +141,87 @@ def gif_run(h, out, v, theta, decay: float, L: int, alpha: float, threshold: flo
 
 
 # ---------------------------------------------------------------------------------------
+# timestep STDP (the rule: include/aura_hip.h, "STDP")
+# ---------------------------------------------------------------------------------------
+
+def _stdp_shapes(pre, post, x_trace, y_trace, weight, dw_out, pre_time_invariant: bool):
+    """Shape, dtype and contiguity checks of ``stdp_update`` (``ValueError``): ``(B, T, I, O)``.  Touches no device."""
+    named = (("pre", pre), ("post", post), ("x_trace", x_trace), ("y_trace", y_trace), ("weight", weight),
+             ("dw_out", dw_out))
+    for n, t in named:
+        if t is not None and not isinstance(t, torch.Tensor):
+            raise TypeError(f"stdp_update: {n} must be a torch.Tensor, got {type(t)}")
+    if pre is None or post is None:
+        raise ValueError("stdp_update: pre and post are required")
+    if post.dim() != 3:
+        raise ValueError(f"stdp_update: post must be [B, T, O], got {tuple(post.shape)}")
+    if pre.dim() != (2 if pre_time_invariant else 3):
+        raise ValueError(f"stdp_update: pre must be {'[B, I]' if pre_time_invariant else '[B, T, I]'}, "
+                         f"got {tuple(pre.shape)}")
+    B, T, O = post.shape
+    I = pre.shape[-1]
+    if pre.shape[0] != B or (not pre_time_invariant and pre.shape[1] != T):
+        raise ValueError(f"stdp_update: pre {tuple(pre.shape)} and post {tuple(post.shape)} disagree in B or T")
+    if B < 1 or T < 1:
+        raise ValueError("stdp_update: B and T must be at least 1")
+    if pre.dtype != post.dtype or pre.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"stdp_update: pre and post share one dtype, fp32 or bf16; got {pre.dtype} and {post.dtype}")
+    if I < 4 or O < 4 or I % 4 or O % 4:
+        raise ValueError(f"stdp_update: I={I} and O={O} must be multiples of 4")
+    for n, t, shape in (("x_trace", x_trace, (B, I)), ("y_trace", y_trace, (B, O)), ("weight", weight, (O, I)),
+                        ("dw_out", dw_out, (O, I))):
+        if t is None:
+            continue
+        if t.dtype != torch.float32:
+            raise ValueError(f"stdp_update: {n} must be fp32, got {t.dtype}")
+        if tuple(t.shape) != shape:
+            raise ValueError(f"stdp_update: {n} must be {shape}, got {tuple(t.shape)}")
+    if weight is None and dw_out is None:
+        raise ValueError("stdp_update: give weight (applied in place), dw_out (dW only), or both")
+    for n, t in named:
+        if t is not None and not t.is_contiguous():
+            raise ValueError(f"stdp_update: {n} must be contiguous")
+    return B, T, I, O
+
+
+def stdp_update(pre, post, x_trace, y_trace, weight=None, dw_out=None, *, lambda_pre: float, lambda_post: float,
+                a_plus: float, a_minus: float, lr: float, w_min: float, w_max: float,
+                pre_time_invariant: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Timestep STDP of one dense synapse in one fused launch plus a small reduction (the rule: ``include/aura_hip.h``,
+    "STDP").  ``pre`` [B, T, I] (or [B, I] with ``pre_time_invariant``: the same value at every step) and ``post``
+    [B, T, O] share one dtype, fp32 or bf16; neither is written.  ``x_trace`` [B, I] / ``y_trace`` [B, O] fp32 are the
+    incoming traces (``None``: zero) and are not written either: the traces after the last step are RETURNED as new
+    tensors ``(x, y)``.  ``weight`` [O, I] fp32 is updated in place, ``clamp(W + lr dW, w_min, w_max)``; ``dw_out``
+    [O, I] fp32 receives dW (with ``weight`` given: the dW that was applied; alone: nothing is applied).  The result is
+    a function of the arguments alone: the same call gives the same bits.  No host sync."""
+    B, T, I, O = _stdp_shapes(pre, post, x_trace, y_trace, weight, dw_out, pre_time_invariant)
+    if weight is not None and not (float(w_min) <= float(w_max)):
+        raise ValueError(f"stdp_update: w_min={w_min} must not exceed w_max={w_max}")
+    _need(pre, "pre"); _need(post, "post")
+    for n, t in (("x_trace", x_trace), ("y_trace", y_trace), ("weight", weight), ("dw_out", dw_out)):
+        if t is not None:
+            _need(t, n, torch.float32)
+            if t.device != pre.device:
+                raise ValueError("stdp_update: tensors are on different devices")
+    if post.device != pre.device:
+        raise ValueError("stdp_update: tensors are on different devices")
+    L = lib()
+    nbytes = int(L.aura_stdp_workspace_bytes(B, T, I, O))
+    if nbytes < 0:
+        raise ValueError(f"stdp_update: unsupported shape B={B} T={T} I={I} O={O}")
+    x_new = torch.empty(B, I, dtype=torch.float32, device=pre.device)
+    y_new = torch.empty(B, O, dtype=torch.float32, device=pre.device)
+    flags = (_lib.STDP_PRE_TIME_INVARIANT if pre_time_invariant else 0) | (_lib.STDP_NO_APPLY if weight is None else 0)
+    ws = _workspace(pre.device, nbytes)
+    check(L.aura_stdp_update(_p(pre), _p(post), _p(x_trace), _p(y_trace), _p(x_new), _p(y_new), _p(weight),
+                             _p(dw_out), float(lambda_pre), float(lambda_post), float(a_plus), float(a_minus),
+                             float(lr), float(w_min), float(w_max), B, T, I, O,
+                             _lib.DTYPE_F32 if pre.dtype == torch.float32 else _lib.DTYPE_BF16, flags, ws, nbytes,
+                             _stream()), "aura_stdp_update")
+    return x_new, y_new
+
+
+# ---------------------------------------------------------------------------------------
 # surrogate-gradient training path + prosody-modulated GIF (fp32 and bf16)
 # ---------------------------------------------------------------------------------------
 

@@ -841,6 +841,53 @@ int aura_addition_linear_backward(const float* x, const float* weight_patterns, 
                                   float* g_x, float* g_w, int64_t B, int64_t in_features,
                                   int64_t out_features, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * STDP
+ * ------------------------------------------------------------------------------------- */
+
+/* Timestep spike-timing-dependent plasticity of one dense synapse W [O][I] (csrc/aura_stdp.hip).  [build-side] the
+ * reference's Synapsis keeps a rate rule on time-mean activity (src/core/language_zone/synapsis.py: "Full STDP would
+ * require timestep-by-timestep update"); this is that update.
+ * For batch row b and step t = 0 .. T-1, with presynaptic value pre[b,t,i], postsynaptic spike post[b,t,o] and the
+ * carried traces x[b,i], y[b,o] (fp32; zero when no incoming trace is given):
+ *     x[b,t,i]  = fl( fl(lambda_pre  * x[b,t-1,i]) + pre[b,t,i] )   fp32, two roundings, never fused
+ *     y-[b,t,o] = fl(lambda_post * y[b,t-1,o])                      y at step t before the step's own spike: post
+ *                                                                   activity strictly before t, decayed to t
+ *     y[b,t,o]  = fl( y-[b,t,o] + post[b,t,o] )
+ *     dW[o,i]   = (1/B) sum_b sum_t ( a_plus * post[b,t,o] * x[b,t,i]  -  a_minus * y-[b,t,o] * pre[b,t,i] )
+ *     W'[o,i]   = clamp( W[o,i] + lr * dW[o,i], w_min, w_max )
+ * A post spike is potentiated by the pre trace INCLUDING the same step (the synapse transmitted at t); a pre spike is
+ * depressed by the post trace BEFORE the step's own spike: simultaneous spikes are potentiation only, and one pre spike
+ * d steps after (before) one post spike gives -a_minus lambda_post^d / B (+a_plus lambda_pre^d / B).  pre / post may be 0/1
+ * spikes, the GIF loops' levels 0 .. L or any real value.  The traces are exact fp32 recursions: every evaluation gives
+ * the bits of the two-rounding form above.  dW is accumulated in fp32 by v_mfma_f32_32x32x2_f32 (bitwise a k-ordered
+ * fmaf chain) over the operands a_plus * post and -a_minus * y- (one rounding each), x and pre; the batch rows are
+ * split over workgroups, the splits are added in ascending order and the sum is divided by B.  The order is a function
+ * of (B, T, I, O) alone: no float atomics, no dependence on the device; the same call gives the same bits every time.
+ * Against the fp64 sum of the same fp32 traces, with S[o,i] = (1/B) sum_b sum_t (|a_plus post x| + |a_minus y- pre|):
+ *     |dW - dW_64| <= (2 B T + 8) 2^-24 S      (and dW == 0 exactly where S == 0).
+ *
+ * pre  [B][T][I], or [B][I] with AURA_STDP_PRE_TIME_INVARIANT (the same value at every step);  post [B][T][O];
+ *   both of `dtype` (AURA_DTYPE_F32 or AURA_DTYPE_BF16; bf16 is widened exactly).  Inputs are never written.
+ * x_in [B][I], y_in [B][O]: the incoming traces, NULL = zero.  x_out, y_out: the traces after step T-1, NULL = not
+ *   wanted; each element is written once.  An incoming trace must not be the array that is written.
+ * W [O][I] fp32 is updated in place; with dw_out [O][I] also given, the dW that was applied is written there.  With
+ *   AURA_STDP_NO_APPLY only dw_out is written (W is ignored and may be NULL; lr and the bounds are unused), with the
+ *   bits an applying call writes.
+ * workspace: *_workspace_bytes(B, T, I, O) = align256(splits * O * I * 4) bytes, 256-byte aligned (negative for an
+ *   unsupported shape); splits = clamp(1024 / (ceil(I/128) ceil(O/128)), 1, min(B, 64)).  Two launches on `stream`.
+ * AURA_E_INVAL: B < 1, T < 1, I or O not a positive multiple of 4 (either dtype), O * I > 2^40, another dtype or
+ *   flag, a null pre / post / workspace, a null W when applying or a null dw_out when not, w_min > w_max or a NaN
+ *   bound when applying, x_in == x_out or y_in == y_out, a workspace that is too small.  AURA_E_ALIGN: workspace not
+ *   256-byte, pre / post / W / dw_out not 16-byte, a trace not 4-byte aligned. */
+#define AURA_STDP_PRE_TIME_INVARIANT 1
+#define AURA_STDP_NO_APPLY 2
+int64_t aura_stdp_workspace_bytes(int64_t B, int64_t T, int64_t I, int64_t O);
+int aura_stdp_update(const void* pre, const void* post, const float* x_in, const float* y_in, float* x_out,
+                     float* y_out, float* W, float* dw_out, float lambda_pre, float lambda_post, float a_plus,
+                     float a_minus, float lr, float w_min, float w_max, int64_t B, int64_t T, int64_t I, int64_t O,
+                     int dtype, int flags, void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
