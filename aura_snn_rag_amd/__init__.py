@@ -5,6 +5,7 @@ episodic-retrieval hot path, behind the reference's own module API.
     from aura_snn_rag_amd.base.neuron import IzhikevichNeuron, AdExNeuron, VectorizedLIFNeuron
     from aura_snn_rag_amd.core.language_zone.gif_neuron import GIFNeuron
     from aura_snn_rag_amd.core.language_zone.snn_ffn import SNNFFN, HybridFFN
+    from aura_snn_rag_amd import PlaceCellSemanticEncoder, PlaceCode
 
 All arithmetic on the path runs in ``lib/libaura_hip.so`` (hand-written HIP, C ABI in
 ``include/aura_hip.h``); there is no CPU or eager-PyTorch fallback.
@@ -12,3 +13,14 @@ All arithmetic on the path runs in ``lib/libaura_hip.so`` (hand-written HIP, C A
 from ._lib import AuraHipError, AuraHipUnavailable, load as load_library  # noqa: F401
 
 __version__ = "0.1.0"
+
+_LAZY = {"PlaceCellSemanticEncoder": "core.language_zone.place_cell_encoder",
+         "PlaceCode": "core.language_zone.place_cell_encoder"}
+
+
+def __getattr__(name):
+    # the modules import torch; the package itself (and the ctypes loader) does not
+    if name in _LAZY:
+        import importlib
+        return getattr(importlib.import_module("." + _LAZY[name], __name__), name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

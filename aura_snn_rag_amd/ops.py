@@ -222,6 +222,159 @@ def stdp_update(pre, post, x_trace, y_trace, weight=None, dw_out=None, *, lambda
 
 
 # ---------------------------------------------------------------------------------------
+# place-cell code (the rule: include/aura_hip.h, "Place code")
+# ---------------------------------------------------------------------------------------
+
+PLACE_MAX_K, PLACE_MAX_CELLS = 256, 8192
+
+
+def _place_fp32(who: str, named) -> None:
+    for n, t in named:
+        if t is None:
+            continue
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{who}: {n} must be a torch.Tensor, got {type(t)}")
+        if t.dtype != torch.float32:
+            raise TypeError(f"{who}: {n} is {t.dtype}; the place code runs in fp32 only (fp32 is the limit: "
+                            f"bf16 and fp16 are not supported)")
+        if not t.is_contiguous():
+            raise ValueError(f"{who}: {n} must be contiguous")
+
+
+def _place_limits(who: str, N: int, P: int, D: int, k) -> int:
+    if isinstance(k, bool) or not isinstance(k, int):
+        raise TypeError(f"{who}: k must be an int, got {type(k)}")
+    if P > PLACE_MAX_CELLS:
+        raise ValueError(f"{who}: P={P} cells exceed the limit of {PLACE_MAX_CELLS}")
+    if not 1 <= k <= min(P, PLACE_MAX_K):
+        raise ValueError(f"{who}: k={k} must be in [1, min(P, {PLACE_MAX_K})] with P={P}")
+    if D < 1:
+        raise ValueError(f"{who}: D={D} must be at least 1")
+    if N > 0x7fffffff:
+        raise ValueError(f"{who}: N={N} rows exceed 2^31 - 1")
+    return k
+
+
+def _place_shapes(z, e, w2t, b2, k) -> Tuple[int, int, int, int]:
+    """Type, shape and limit checks of ``place_code``: ``(N, P, D, k)``.  Touches no device."""
+    _place_fp32("place_code", (("z", z), ("e", e), ("w2t", w2t), ("b2", b2)))
+    for n, t in (("z", z), ("e", e), ("w2t", w2t), ("b2", b2)):
+        if t is None:
+            raise ValueError(f"place_code: {n} is required")
+    if z.dim() != 2 or e.dim() != 2 or w2t.dim() != 2 or b2.dim() != 1:
+        raise ValueError(f"place_code: z [N, P], e [N, D], w2t [P, D], b2 [D]; got {tuple(z.shape)}, "
+                         f"{tuple(e.shape)}, {tuple(w2t.shape)}, {tuple(b2.shape)}")
+    N, P = z.shape
+    D = e.shape[1]
+    if e.shape[0] != N or tuple(w2t.shape) != (P, D) or b2.shape[0] != D:
+        raise ValueError(f"place_code: z {tuple(z.shape)}, e {tuple(e.shape)}, w2t {tuple(w2t.shape)} and b2 "
+                         f"{tuple(b2.shape)} disagree")
+    return N, P, D, _place_limits("place_code", N, P, D, k)
+
+
+def place_code(z, e, w2t, b2, k: int, dense: bool = True):
+    """The sparse place-cell code in one launch (the rule: ``include/aura_hip.h``, "Place code").  ``z`` [N, P] logits,
+    ``e`` [N, D] embeddings, ``w2t`` [P, D] the transpose of ``place_to_semantic.weight``, ``b2`` [D]; fp32, contiguous.
+    Returns ``(out [N, D], idx [N, k] int32, act [N, k], dense [N, P] or None)``: the exact top ``k`` cells of every row
+    (ties to the lower cell, NaN first) in ascending cell index, their sigmoid, ``e + 0.1 (act @ w2t[idx] + b2)`` and,
+    with ``dense``, the code scattered into zeros.  A row's bits depend on that row alone.  No host sync."""
+    N, P, D, k = _place_shapes(z, e, w2t, b2, k)
+    for n, t in (("z", z), ("e", e), ("w2t", w2t), ("b2", b2)):
+        _need(t, n, torch.float32)
+        if t.device != z.device:
+            raise ValueError("place_code: tensors are on different devices")
+    dev = z.device
+    out = torch.empty(N, D, dtype=torch.float32, device=dev)
+    idx = torch.empty(N, k, dtype=torch.int32, device=dev)
+    act = torch.empty(N, k, dtype=torch.float32, device=dev)
+    code = torch.empty(N, P, dtype=torch.float32, device=dev) if dense else None
+    check(lib().aura_place_code(_p(z), _p(e), _p(w2t), _p(b2), N, P, D, k, _p(idx), _p(act), _p(out), _p(code),
+                                _stream()), "aura_place_code")
+    return out, idx, act, code
+
+
+def _place_backward_shapes(g_out, g_dense, idx, act, w2t) -> Tuple[int, int, int, int]:
+    _place_fp32("place_code_backward", (("g_out", g_out), ("g_dense", g_dense), ("act", act), ("w2t", w2t)))
+    for n, t in (("g_out", g_out), ("idx", idx), ("act", act), ("w2t", w2t)):
+        if t is None:
+            raise ValueError(f"place_code_backward: {n} is required")
+    if not isinstance(idx, torch.Tensor) or idx.dtype != torch.int32:
+        raise TypeError("place_code_backward: idx must be an int32 tensor")
+    if not idx.is_contiguous():
+        raise ValueError("place_code_backward: idx must be contiguous")
+    if g_out.dim() != 2 or idx.dim() != 2 or w2t.dim() != 2:
+        raise ValueError("place_code_backward: g_out [N, D], idx [N, k], act [N, k], w2t [P, D]")
+    N, D = g_out.shape
+    P = w2t.shape[0]
+    k = idx.shape[1]
+    if idx.shape[0] != N or act.shape != idx.shape or w2t.shape[1] != D:
+        raise ValueError(f"place_code_backward: g_out {tuple(g_out.shape)}, idx {tuple(idx.shape)}, act "
+                         f"{tuple(act.shape)} and w2t {tuple(w2t.shape)} disagree")
+    if g_dense is not None and tuple(g_dense.shape) != (N, P):
+        raise ValueError(f"place_code_backward: g_dense must be {(N, P)}, got {tuple(g_dense.shape)}")
+    return N, P, D, _place_limits("place_code_backward", N, P, D, int(k))
+
+
+def place_code_backward(g_out, g_dense, idx, act, w2t) -> torch.Tensor:
+    """The logit gradient of ``place_code`` in one launch: ``g_z`` [N, P], ``(0.1 <g_out[n], w2t[j]> + g_dense[n, j])
+    act (1 - act)`` at the winners and +0.0 elsewhere.  ``g_dense`` may be ``None``; ``idx`` / ``act`` are what the
+    forward returned.  The dot products have a fixed order: the same call gives the same bits."""
+    N, P, D, k = _place_backward_shapes(g_out, g_dense, idx, act, w2t)
+    for n, t in (("g_out", g_out), ("g_dense", g_dense), ("idx", idx), ("act", act), ("w2t", w2t)):
+        if t is not None:
+            _need(t, n)
+            if t.device != g_out.device:
+                raise ValueError("place_code_backward: tensors are on different devices")
+    g_z = torch.empty(N, P, dtype=torch.float32, device=g_out.device)
+    check(lib().aura_place_code_backward(_p(g_out), _p(g_dense), _p(idx), _p(act), _p(w2t), N, P, D, k, _p(g_z),
+                                         _stream()), "aura_place_code_backward")
+    return g_z
+
+
+class PlaceCodeFunction(torch.autograd.Function):
+    """``(z, e, w2t, b2) -> (out, idx, act, dense or None)`` with gradients for all four inputs.  ``g_z`` is the mirror
+    launch; ``g_e = g_out``, ``g_b2 = 0.1 sum_n g_out`` and ``g_w2t = 0.1 dense^T g_out`` are library calls (the last a
+    GEMM over the dense code, rebuilt from idx / act when the forward did not write it).  ``idx`` carries no gradient;
+    a gradient that reaches ``act`` is folded into the winners' cells like one that reaches ``dense``.  ``weight``
+    [D, P]: the parameter that a detached ``w2t`` is the transpose of; its gradient is then ``0.1 g_out^T dense`` and
+    ``w2t`` gets none (the module's cached transpose)."""
+
+    @staticmethod
+    def forward(ctx, z, e, w2t, b2, k: int, want_dense: bool, weight=None):
+        out, idx, act, code = place_code(z, e, w2t, b2, k, dense=want_dense)
+        ctx.save_for_backward(idx, act, w2t, code)
+        ctx.n_cells = z.shape[1]
+        ctx.mark_non_differentiable(idx)
+        return out, idx, act, code
+
+    @staticmethod
+    def backward(ctx, g_out, _g_idx, g_act, g_code):
+        idx, act, w2t, code = ctx.saved_tensors
+        N, k = idx.shape
+        P = ctx.n_cells
+        if g_out is None:
+            g_out = torch.zeros(N, w2t.shape[1], dtype=torch.float32, device=idx.device)
+        g_out = g_out.contiguous()
+        if g_act is not None:
+            spread = torch.zeros(N, P, dtype=torch.float32, device=idx.device).scatter_(1, idx.long(), g_act)
+            g_code = spread if g_code is None else g_code + spread
+        g_z = g_e = g_w2t = g_b2 = g_weight = None
+        if ctx.needs_input_grad[0]:
+            g_z = place_code_backward(g_out, None if g_code is None else g_code.contiguous(), idx, act, w2t)
+        if ctx.needs_input_grad[1]:
+            g_e = g_out
+        if (ctx.needs_input_grad[2] or ctx.needs_input_grad[6]) and code is None:
+            code = torch.zeros(N, P, dtype=torch.float32, device=idx.device).scatter_(1, idx.long(), act)
+        if ctx.needs_input_grad[2]:
+            g_w2t = 0.1 * (code.t() @ g_out)
+        if ctx.needs_input_grad[6]:
+            g_weight = 0.1 * (g_out.t() @ code)
+        if ctx.needs_input_grad[3]:
+            g_b2 = 0.1 * g_out.sum(0)
+        return g_z, g_e, g_w2t, g_b2, None, None, g_weight
+
+
+# ---------------------------------------------------------------------------------------
 # surrogate-gradient training path + prosody-modulated GIF (fp32 and bf16)
 # ---------------------------------------------------------------------------------------
 

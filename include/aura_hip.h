@@ -888,6 +888,50 @@ int aura_stdp_update(const void* pre, const void* post, const float* x_in, const
                      float a_minus, float lr, float w_min, float w_max, int64_t B, int64_t T, int64_t I, int64_t O,
                      int dtype, int flags, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Place code
+ * ------------------------------------------------------------------------------------- */
+
+/* The sparse place-cell code of PlaceCellSemanticEncoder.forward (src/core/language_zone/place_cell_encoder.py:
+ * topk, sigmoid, scatter, Linear(P -> D), residual) in one launch, from the logits (csrc/aura_place.hip).  All fp32:
+ * z [N][P] the logits, e [N][D] the token embeddings, W2t [P][D] the TRANSPOSE of place_to_semantic.weight, b2 [D].
+ *   winners  the k winners of row n are its exact top k under this order: the larger value first; -0.0 and +0.0 are
+ *            equal; a NaN (either sign) ranks above +inf, as in torch.topk, and all NaNs are equal; equal values go
+ *            to the LOWER cell index (torch.topk leaves this open).  They are emitted in ASCENDING cell index:
+ *            idx [N][k] int32, act [N][k].
+ *   act      = 1 / (1 + expf(-z)), accurate expf (1 ulp), one add, one correctly rounded division.
+ *   out      acc = 0;  for the winners j in ascending cell index: acc = fmaf(act_j, W2t[j][d], acc);
+ *            r = acc + b2[d];  out[n][d] = e[n][d] + fl(0.1f * r)       (the product rounded before the add).
+ *   dense    [N][P] or NULL (not wanted): +0.0 everywhere except act at the winners; every element is written.
+ * A row's result depends on nothing else in the call: its bits are the same computed alone or in any batch, whatever
+ * the launch geometry.  One wave owns a row: the selection is a 32-step bisection on the monotone key of the float
+ * bits with the row in registers (counts by ballot), the compaction a running ballot prefix in cell order.  No atomics.
+ * Against the fp64 evaluation of the same fp32 inputs with the same winners, mag = sum_j |act_j W2t[j][d]| + |b2[d]|:
+ *     |act - act_64| <= 2^-22,     |out - out_64| <= 0.1 (k + 2) 2^-24 mag + 2^-23 |out_64|.
+ * AURA_E_INVAL: N < 0 or N > 2^31 - 1, k < 1, k > min(P, 256), P > 8192, D < 1, D > 2^31 - 1, a null pointer other
+ *   than dense.  AURA_E_ALIGN: a pointer not 4-byte aligned.  N == 0 launches nothing.  Rows move as float4 when
+ *   D % 4 == 0 and e, W2t, b2 and out are 16-byte aligned, else one float at a time (the same bits). */
+int aura_place_code(const float* z, const float* e, const float* W2t, const float* b2, int64_t N, int64_t P, int64_t D,
+                    int64_t k, int32_t* idx, float* act, float* out, float* dense_or_null, void* stream);
+
+/* The mirror launch: the gradient of the logits from that of out and (optionally) of the dense code.  Per row n and
+ * winner j = idx[n][r], r = 0 .. k-1:
+ *     dot     = <g_out[n], W2t[j]> in fp32: lane l of the row's wave owns the elements d with (d / 4) % 64 == l
+ *               (d % 64 == l when the rows do not move as float4) and chains them in ascending d with fmaf from 0
+ *               within each tile of 1024 (256) elements; a tile's 64 lane sums are added by the xor butterfly 32, 16,
+ *               8, 4, 2, 1; the tiles' sums are added in ascending order.  The order is a function of D (and of the
+ *               float4 condition below) alone.
+ *     g_act   = fl(0.1f * dot)  (+ g_dense[n][j] when g_dense is given)
+ *     g_z[n][j] = fl(fl(g_act * act) * fl(1 - act)),  act = act[n][r]
+ * and g_z[n][c] = +0.0 at every other cell: the whole row is written.  idx must hold, per row, k ascending cells in
+ * [0, P) (what aura_place_code wrote); a cell outside that range is clamped into it for the reads.  The remaining
+ * gradients (g_e = g_out, g_b2 = 0.1 sum_n g_out, g_W2 = 0.1 g_out^T dense) are the caller's library calls.
+ * Against fp64 on the same inputs, at a winner:
+ *     |g_z - g_z64| <= (D + 3) 2^-24 * 0.1 * sum_d |g_out[n][d] W2t[j][d]| * 0.25 + 2^-23 |g_z64|   (g_dense NULL).
+ * Errors as aura_place_code; float4 when D % 4 == 0 and g_out and W2t are 16-byte aligned.  One launch on `stream`. */
+int aura_place_code_backward(const float* g_out, const float* g_dense_or_null, const int32_t* idx, const float* act,
+                             const float* W2t, int64_t N, int64_t P, int64_t D, int64_t k, float* g_z, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
