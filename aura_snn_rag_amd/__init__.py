@@ -6,6 +6,7 @@ episodic-retrieval hot path, behind the reference's own module API.
     from aura_snn_rag_amd.core.language_zone.gif_neuron import GIFNeuron
     from aura_snn_rag_amd.core.language_zone.snn_ffn import SNNFFN, HybridFFN
     from aura_snn_rag_amd import PlaceCellSemanticEncoder, PlaceCode
+    from aura_snn_rag_amd import ThetaGammaPositionalEncoding, embed_tokens
 
 All arithmetic on the path runs in ``lib/libaura_hip.so`` (hand-written HIP, C ABI in
 ``include/aura_hip.h``); there is no CPU or eager-PyTorch fallback.
@@ -15,7 +16,9 @@ from ._lib import AuraHipError, AuraHipUnavailable, load as load_library  # noqa
 __version__ = "0.1.0"
 
 _LAZY = {"PlaceCellSemanticEncoder": "core.language_zone.place_cell_encoder",
-         "PlaceCode": "core.language_zone.place_cell_encoder"}
+         "PlaceCode": "core.language_zone.place_cell_encoder",
+         "ThetaGammaPositionalEncoding": "core.language_zone.theta_gamma_encoding",
+         "embed_tokens": "core.language_zone.theta_gamma_encoding"}
 
 
 def __getattr__(name):

@@ -121,6 +121,10 @@ SIGNATURES = {
     "aura_stdp_update": (I, [P, P, P, P, P, P, P, P, F, F, F, F, F, F, F, I64, I64, I64, I64, I, I, P, I64, P]),
     "aura_place_code": (I, [P, P, P, P, I64, I64, I64, I64, P, P, P, P, P]),
     "aura_place_code_backward": (I, [P, P, P, P, P, I64, I64, I64, I64, P, P]),
+    "aura_theta_gamma_table": (I, [P, I64, I64, I64, P, P, P, I64, F, P, P, P, P, P]),
+    "aura_theta_gamma_norm": (I, [P, P, P, P, F, I64, I64, I64, I64, P, P, P, P]),
+    "aura_theta_gamma_groups": (I64, [I64]),
+    "aura_theta_gamma_norm_backward": (I, [P, P, P, P, P, P, P, P, P, I64, I64, I64, I64, P, P, P, P]),
     "aura_profile_begin": (I, [I]),
     "aura_debug_cs_flags": (I, [I]),
     "aura_debug_clock_mhz": (I, [P, I, P]),

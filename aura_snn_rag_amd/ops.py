@@ -228,14 +228,14 @@ def stdp_update(pre, post, x_trace, y_trace, weight=None, dw_out=None, *, lambda
 PLACE_MAX_K, PLACE_MAX_CELLS = 256, 8192
 
 
-def _place_fp32(who: str, named) -> None:
+def _place_fp32(who: str, named, what: str = "the place code runs") -> None:
     for n, t in named:
         if t is None:
             continue
         if not isinstance(t, torch.Tensor):
             raise TypeError(f"{who}: {n} must be a torch.Tensor, got {type(t)}")
         if t.dtype != torch.float32:
-            raise TypeError(f"{who}: {n} is {t.dtype}; the place code runs in fp32 only (fp32 is the limit: "
+            raise TypeError(f"{who}: {n} is {t.dtype}; {what} in fp32 only (fp32 is the limit: "
                             f"bf16 and fp16 are not supported)")
         if not t.is_contiguous():
             raise ValueError(f"{who}: {n} must be contiguous")
@@ -372,6 +372,234 @@ class PlaceCodeFunction(torch.autograd.Function):
         if ctx.needs_input_grad[3]:
             g_b2 = 0.1 * g_out.sum(0)
         return g_z, g_e, g_w2t, g_b2, None, None, g_weight
+
+
+# ---------------------------------------------------------------------------------------
+# theta-gamma positions (the rule: include/aura_hip.h, "Theta-gamma")
+# ---------------------------------------------------------------------------------------
+
+THETA_MAX_D = 2048
+
+
+def _theta_fp32(who: str, named) -> None:
+    _place_fp32(who, named, "the theta-gamma kernels run")
+
+
+def _theta_required(who: str, named) -> None:
+    for n, t in named:
+        if t is None:
+            raise ValueError(f"{who}: {n} is required")
+
+
+def _theta_device(who: str, named, wide=()) -> torch.device:
+    """Every tensor on one HIP device; the ``wide`` ones ([.., D] rows, which move as float4 when D % 4 == 0) 16-byte
+    aligned.  After the shape checks."""
+    dev = None
+    for n, t in named:
+        if t is None:
+            continue
+        _need(t, f"{who}: {n}")
+        dev = t.device if dev is None else dev
+        if t.device != dev:
+            raise ValueError(f"{who}: tensors are on different devices")
+        if n in wide and t.shape[-1] % 4 == 0 and t.data_ptr() % 16:
+            raise ValueError(f"{who}: {n} is not 16-byte aligned (a view into the middle of a buffer?)")
+    return dev
+
+
+def theta_gamma_ratio(theta_freq: float, gamma_freq: float) -> float:
+    """The rule's ``ratio``: ``fp32(double(gamma_freq) / double(theta_freq))``."""
+    theta_freq, gamma_freq = float(theta_freq), float(gamma_freq)
+    if not (theta_freq == theta_freq and gamma_freq == gamma_freq) or theta_freq == 0.0:
+        raise ValueError(f"theta_gamma: theta_freq={theta_freq} and gamma_freq={gamma_freq} give no frequency ratio")
+    return float(np.float32(gamma_freq / theta_freq))
+
+
+def _theta_table_shapes(theta_off, gamma_off, amp, max_seq_len, positions, start, rows) -> Tuple[int, int]:
+    """Type, shape and limit checks of ``theta_gamma_table``: ``(R, D)``.  Touches no device."""
+    who = "theta_gamma_table"
+    named = (("theta_off", theta_off), ("gamma_off", gamma_off), ("amp", amp))
+    _theta_required(who, named)
+    _theta_fp32(who, named + (("positions", positions),))
+    if theta_off.dim() != 1 or gamma_off.shape != theta_off.shape or amp.shape != theta_off.shape:
+        raise ValueError(f"{who}: theta_off, gamma_off and amp are [D]; got {tuple(theta_off.shape)}, "
+                         f"{tuple(gamma_off.shape)}, {tuple(amp.shape)}")
+    D = theta_off.shape[0]
+    if not 1 <= D <= THETA_MAX_D:
+        raise ValueError(f"{who}: D={D} must be in [1, {THETA_MAX_D}]")
+    if isinstance(max_seq_len, bool) or not isinstance(max_seq_len, int) or max_seq_len < 1:
+        raise ValueError(f"{who}: max_seq_len={max_seq_len!r} must be an int of at least 1")
+    if positions is not None:
+        if rows is not None or start != 0:
+            raise ValueError(f"{who}: give positions, or start and rows, not both")
+        if positions.dim() != 1:
+            raise ValueError(f"{who}: positions is [R] fp32, got {tuple(positions.shape)}")
+        R = positions.shape[0]
+    else:
+        if rows is None:
+            raise ValueError(f"{who}: give positions, or start and rows")
+        for n, v in (("start", start), ("rows", rows)):
+            if isinstance(v, bool) or not isinstance(v, int):
+                raise TypeError(f"{who}: {n} must be an int, got {type(v)}")
+        if rows < 0 or not -2 ** 62 <= start <= 2 ** 62:
+            raise ValueError(f"{who}: rows={rows} must not be negative (start={start})")
+        R = rows
+    if R > 0x7fffffff:
+        raise ValueError(f"{who}: R={R} rows exceed 2^31 - 1")
+    return R, D
+
+
+def theta_gamma_table(theta_off, gamma_off, amp, max_seq_len: int, ratio: float, positions=None, start: int = 0,
+                      rows: Optional[int] = None, derivatives: bool = False, pe: bool = True):
+    """The phase-code table in one launch (the rule: ``include/aura_hip.h``, "Theta-gamma"): ``pe`` [R, D] for the fp32
+    ``positions`` [R], or for ``start, start + 1, ..`` (``rows`` of them, formed in the kernel) when ``positions`` is
+    ``None``.  With ``derivatives`` returns ``(pe, d_theta, d_gamma, d_amp)``, each [R, D]; ``pe=False`` leaves the
+    first ``None`` and unwritten.  The only place the sines and cosines are evaluated.  No host sync."""
+    R, D = _theta_table_shapes(theta_off, gamma_off, amp, max_seq_len, positions, start, rows)
+    if not (derivatives or pe):
+        raise ValueError("theta_gamma_table: nothing to compute")
+    ratio = float(ratio)
+    dev = _theta_device("theta_gamma_table", (("theta_off", theta_off), ("gamma_off", gamma_off), ("amp", amp),
+                                              ("positions", positions)))
+    new = lambda: torch.empty(R, D, dtype=torch.float32, device=dev)
+    out = new() if pe else None
+    d = (new(), new(), new()) if derivatives else (None, None, None)
+    check(lib().aura_theta_gamma_table(_p(positions), start, R, D, _p(theta_off), _p(gamma_off), _p(amp), max_seq_len,
+                                       ratio, _p(out), _p(d[0]), _p(d[1]), _p(d[2]), _stream()),
+          "aura_theta_gamma_table")
+    return (out, *d) if derivatives else out
+
+
+def _theta_norm_shapes(who: str, x, table, w, b, seq_len, eps=1e-5) -> Tuple[int, int, int, int]:
+    """``(N, S, R, D)`` of a fused call.  Touches no device."""
+    named = (("x", x), ("table", table), ("w", w)) + ((("b", b),) if who == "theta_gamma_norm" else ())
+    _theta_required(who, named)
+    _theta_fp32(who, named)
+    if x.dim() != 2 or table.dim() != 2 or w.dim() != 1 or (b is not None and b.dim() != 1):
+        raise ValueError(f"{who}: x [N, D], table [R, D], w [D], b [D]; got {tuple(x.shape)}, {tuple(table.shape)}, "
+                         f"{tuple(w.shape)}" + ("" if b is None else f", {tuple(b.shape)}"))
+    N, D = x.shape
+    R = table.shape[0]
+    if table.shape[1] != D or w.shape[0] != D or (b is not None and b.shape[0] != D):
+        raise ValueError(f"{who}: x {tuple(x.shape)}, table {tuple(table.shape)}, w {tuple(w.shape)}"
+                         + ("" if b is None else f", b {tuple(b.shape)}") + " disagree in D")
+    if not 1 <= D <= THETA_MAX_D:
+        raise ValueError(f"{who}: D={D} must be in [1, {THETA_MAX_D}]")
+    if N > 0x7fffffff:
+        raise ValueError(f"{who}: N={N} tokens exceed 2^31 - 1")
+    if isinstance(seq_len, bool) or not isinstance(seq_len, int) or seq_len < 1:
+        raise ValueError(f"{who}: seq_len={seq_len!r} must be an int of at least 1")
+    if not (R == N or (R == seq_len and N % seq_len == 0)):
+        raise ValueError(f"{who}: a table of {R} rows fits neither the {N} tokens (one row each) nor sequences of "
+                         f"seq_len={seq_len} (shared rows, N a multiple of it)")
+    if not isinstance(eps, float) or not eps >= 0.0:
+        raise ValueError(f"{who}: eps={eps!r} must be a float that is not negative")
+    return N, seq_len, R, D
+
+
+def theta_gamma_norm(x, table, w, b, seq_len: int, eps: float = 1e-5):
+    """``LayerNorm(x + pe)`` in one launch: ``x`` [N, D] the tokens of sequences of ``seq_len``, ``table`` [R, D] from
+    ``theta_gamma_table`` with R = ``seq_len`` (token n reads row ``n % seq_len``) or R = N (row n), ``w`` / ``b`` [D]
+    the norm's weight and bias.  Returns ``(y [N, D], mean [N], rstd [N])``; ``x + pe`` is never written.  A token's
+    bits are the same alone and in any batch.  No host sync."""
+    N, S, R, D = _theta_norm_shapes("theta_gamma_norm", x, table, w, b, seq_len, eps)
+    dev = _theta_device("theta_gamma_norm", (("x", x), ("table", table), ("w", w), ("b", b)),
+                        wide=("x", "table", "w", "b"))
+    y = torch.empty(N, D, dtype=torch.float32, device=dev)
+    mean = torch.empty(N, dtype=torch.float32, device=dev)
+    rstd = torch.empty(N, dtype=torch.float32, device=dev)
+    check(lib().aura_theta_gamma_norm(_p(x), _p(table), _p(w), _p(b), eps, N, S, R, D, _p(y), _p(mean), _p(rstd),
+                                      _stream()), "aura_theta_gamma_norm")
+    return y, mean, rstd
+
+
+def theta_gamma_groups(N: int) -> int:
+    """How many partial rows the backward adds per column: ``clamp(ceil(N / 16), 1, 1024)`` (the header's G)."""
+    return max(1, min(1024, -(-int(N) // 16)))
+
+
+def _theta_backward_shapes(g_y, x, table, derivs, mean, rstd, w, seq_len) -> Tuple[int, int, int, int]:
+    who = "theta_gamma_norm_backward"
+    N, S, R, D = _theta_norm_shapes(who, x, table, w, None, seq_len)
+    named = (("g_y", g_y), ("mean", mean), ("rstd", rstd))
+    _theta_required(who, named)
+    _theta_fp32(who, named)
+    if tuple(g_y.shape) != (N, D):
+        raise ValueError(f"{who}: g_y must be {(N, D)}, got {tuple(g_y.shape)}")
+    if tuple(mean.shape) != (N,) or tuple(rstd.shape) != (N,):
+        raise ValueError(f"{who}: mean and rstd must be {(N,)}, got {tuple(mean.shape)} and {tuple(rstd.shape)}")
+    if derivs is not None:
+        if not isinstance(derivs, (tuple, list)) or len(derivs) != 3:
+            raise ValueError(f"{who}: derivatives is (d_theta, d_gamma, d_amp) or None")
+        named = tuple(zip(("d_theta", "d_gamma", "d_amp"), derivs))
+        _theta_required(who, named)
+        _theta_fp32(who, named)
+        for n, t in named:
+            if tuple(t.shape) != (R, D):
+                raise ValueError(f"{who}: {n} must be {(R, D)} like the table, got {tuple(t.shape)}")
+    return N, S, R, D
+
+
+def theta_gamma_norm_backward(g_y, x, table, derivatives, mean, rstd, w, seq_len: int, column_sums: bool = True):
+    """The backward of ``theta_gamma_norm``: ``(g_x [N, D], grads)``.  ``derivatives`` is ``(d_theta, d_gamma, d_amp)``
+    from ``theta_gamma_table(.., derivatives=True)`` or ``None``; ``mean`` / ``rstd`` are what the forward returned.
+    ``grads`` is [5, D] -- ``g_w, g_b, g_theta, g_gamma, g_amp`` -- with the derivatives, [2, D] without them, and
+    ``None`` with ``column_sums=False`` (one launch instead of two; not with derivatives).  Every sum has a fixed order:
+    the same call gives the same bits."""
+    N, S, R, D = _theta_backward_shapes(g_y, x, table, derivatives, mean, rstd, w, seq_len)
+    if derivatives is not None and not column_sums:
+        raise ValueError("theta_gamma_norm_backward: derivative tables are read for the column sums only")
+    d = tuple(derivatives) if derivatives is not None else (None, None, None)
+    dev = _theta_device("theta_gamma_norm_backward", (("g_y", g_y), ("x", x), ("table", table), ("d_theta", d[0]),
+                                                      ("d_gamma", d[1]), ("d_amp", d[2]), ("mean", mean),
+                                                      ("rstd", rstd), ("w", w)),
+                        wide=("g_y", "x", "table", "d_theta", "d_gamma", "d_amp", "w"))
+    g_x = torch.empty(N, D, dtype=torch.float32, device=dev)
+    partials = grads = None
+    if column_sums:
+        partials = torch.empty(theta_gamma_groups(N), 5, D, dtype=torch.float32, device=dev)
+        grads = torch.zeros(5, D, dtype=torch.float32, device=dev)      # N == 0 launches nothing: the sums are zero
+    check(lib().aura_theta_gamma_norm_backward(_p(g_y), _p(x), _p(table), _p(d[0]), _p(d[1]), _p(d[2]), _p(mean),
+                                               _p(rstd), _p(w), N, S, R, D, _p(g_x), _p(partials), _p(grads),
+                                               _stream()), "aura_theta_gamma_norm_backward")
+    if grads is not None and derivatives is None:
+        grads = grads[:2]
+    return g_x, grads
+
+
+class ThetaGammaNormFunction(torch.autograd.Function):
+    """``(x, table, theta_off, gamma_off, amp, w, b) -> LayerNorm(x + pe)`` with gradients for all but ``table``, which
+    is the detached ``theta_gamma_table`` of the three parameters at ``geometry = (positions or None, start,
+    max_seq_len, ratio)``.  Saves ``x``, the table, ``mean`` and ``rstd`` (never ``x + pe``); the derivative tables are
+    built in backward by a second table call, and only when one of the three parameters wants a gradient.  Without any
+    parameter gradient the backward is one launch."""
+
+    @staticmethod
+    def forward(ctx, x, table, theta_off, gamma_off, amp, w, b, seq_len: int, eps: float, geometry):
+        y, mean, rstd = theta_gamma_norm(x, table, w, b, seq_len, eps)
+        positions = geometry[0]
+        ctx.save_for_backward(x, table, mean, rstd, theta_off, gamma_off, amp, w, positions)
+        ctx.seq_len, ctx.geometry = seq_len, geometry[1:]
+        return y
+
+    @staticmethod
+    def backward(ctx, g_y):
+        x, table, mean, rstd, theta_off, gamma_off, amp, w, positions = ctx.saved_tensors
+        start, max_seq_len, ratio = ctx.geometry
+        need = ctx.needs_input_grad
+        phase, affine = any(need[2:5]), any(need[5:7])
+        if not (need[0] or phase or affine):
+            return (None,) * 10
+        derivs = None
+        if phase:
+            rows = None if positions is not None else table.shape[0]
+            derivs = theta_gamma_table(theta_off, gamma_off, amp, max_seq_len, ratio, positions=positions, start=start,
+                                       rows=rows, derivatives=True, pe=False)[1:]
+        g_x, grads = theta_gamma_norm_backward(g_y.contiguous(), x, table, derivs, mean, rstd, w, ctx.seq_len,
+                                               column_sums=phase or affine)
+        pick = lambda i, k: grads[k] if need[i] else None
+        return (g_x if need[0] else None, None, *(pick(2 + k, 2 + k) if phase else None for k in range(3)),
+                pick(5, 0) if affine else None, pick(6, 1) if affine else None, None, None, None)
 
 
 # ---------------------------------------------------------------------------------------

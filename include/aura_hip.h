@@ -932,6 +932,76 @@ int aura_place_code(const float* z, const float* e, const float* W2t, const floa
 int aura_place_code_backward(const float* g_out, const float* g_dense_or_null, const int32_t* idx, const float* act,
                              const float* W2t, int64_t N, int64_t P, int64_t D, int64_t k, float* g_z, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Theta-gamma
+ * ------------------------------------------------------------------------------------- */
+
+/* The positional phase code of ThetaGammaPositionalEncoding (src/core/language_zone/theta_gamma_encoding.py) and the
+ * two lines that consume it in both models' forward, h = semantic + pos and LayerNorm(h) (hippocampal_transformer.py:
+ * 95-101, snn_rag_transformer.py:132-135), csrc/aura_theta.hip.  All fp32, every operation rounded on its own (no fused
+ * multiply-add), fl() = round to nearest even.  For a token at position p (an fp32 number) and column d:
+ *     denom = float(max(max_seq_len - 1, 1))            the module's max_seq_len, not the length of the call
+ *     phi   = fl(fl(p / denom) * TWO_PI)                a correctly rounded division; TWO_PI = fp32(2 pi)
+ *     a     = fl(phi + theta_off[d])
+ *     g     = fl(fl(phi * ratio) + gamma_off[d])        ratio = fp32(double(gamma_freq) / double(theta_freq))
+ *     A     = fl(fl(cos a + 1) * 0.5)
+ *     q     = fl(sin a + fl(0.5 * fl(A * sin g)))
+ *     pe    = fl(q * amp[d])
+ * with the accurate sinf / cosf (full range reduction: a phase is about 32 rad at the end of max_seq_len with 8 Hz /
+ * 40 Hz and thousands of radians in generation beyond it).  The derivatives of pe, from the same a, g, A:
+ *     d_amp = q,   d_theta = fl(amp * fl(cos a - fl(fl(0.25 sin a) * sin g))),   d_gamma = fl(amp * fl(fl(0.5 A) * cos g)).
+ * Against fp64 on the same fp32 a and g, with E = 2^-21 (4 ulp of a sine):
+ *     |pe - pe_64| <= |amp| (1.75 E + 9 * 2^-24) + 2^-24 |pe_64|, and the same form for d_theta, d_gamma (d_amp: amp = 1).
+ *
+ * positions [R] fp32 or NULL: position r is float(start + r).  pe and the three derivative tables are [R][D]; pe may be
+ * NULL when the derivatives are given, the derivatives are given all three or not at all.  One launch; sines and
+ * cosines are evaluated here only, R * D times.
+ * AURA_E_INVAL: R < 0 or R > 2^31 - 1, D < 1 or D > 2048, max_seq_len < 1, a null parameter vector, nothing to write.
+ * AURA_E_ALIGN: a pointer not 4-byte aligned.  R == 0 launches nothing. */
+int aura_theta_gamma_table(const float* positions_or_null, int64_t start, int64_t R, int64_t D, const float* theta_off,
+                           const float* gamma_off, const float* amp, int64_t max_seq_len, float ratio,
+                           float* pe_or_null, float* d_theta_or_null, float* d_gamma_or_null, float* d_amp_or_null,
+                           void* stream);
+
+/* y = LayerNorm(x + pe) in one launch; h is never written.  x [N][D] the tokens of B sequences of S (N = B S), table
+ * [R][D]: token n reads row n % S when R == S (shared positions) and row n when R == N.  Per token:
+ *     h    = fl(x + pe)
+ *     mu   = sum_d h / D,   var = sum_d fl(fl(h - mu)^2) / D        (two passes over registers, biased)
+ *     rstd = 1 / sqrt(var + eps)                                     (sqrt and division correctly rounded)
+ *     n    = fl(fl(h - mu) * rstd),   y = fl(fl(n * w[d]) + b[d])
+ * A row sum: one wave owns the token; lane l owns the units u with u % 64 == l, a unit being four consecutive columns
+ * when D % 4 == 0 and one column otherwise; the lane adds its elements in ascending d from 0, the 64 lane sums are added
+ * by the xor butterfly 32, 16, 8, 4, 2, 1, the total is divided by float(D).  The order is a function of D alone: a
+ * token's bits are the same alone, in any batch and at any grid.  No atomics.  Writes y [N][D], mean [N] = mu, rstd [N].
+ * With T_D = ceil(units / 64) * (4 or 1) + 7 and A = mean_d |h|, against fp64 on the fp32 h:
+ *     |n - n_64| <= (T_D + 8) 2^-24 (A rstd + 2 |n|),    |y - y_64| <= |w| (that) + 2^-23 |y_64|.
+ * AURA_E_INVAL: N < 0 or N > 2^31 - 1, D < 1 or D > 2048, S < 1, R neither N nor (S with N % S == 0), a null pointer.
+ * AURA_E_ALIGN: a pointer not 4-byte aligned, or, when D % 4 == 0, x, table, w, b or y not 16-byte aligned.
+ * N == 0 launches nothing. */
+int aura_theta_gamma_norm(const float* x, const float* table, const float* w, const float* b, float eps, int64_t N,
+                          int64_t S, int64_t R, int64_t D, float* y, float* mean, float* rstd, void* stream);
+
+/* The backward.  Per token, h and n re-formed from x, the table row, mean and rstd with the forward's roundings;
+ * wg = fl(w g_y), c1 = sum_d wg / D, c2 = sum_d fl(wg n) / D (row sums as above),
+ *     g_h = fl(rstd * fl(fl(wg - c1) - fl(n c2))),      g_x = g_h                           written for every token.
+ * Column sums over the tokens, wanted when partials / grads are given: grads [5][D] =
+ *     g_w = sum g_y n,  g_b = sum g_y,  g_theta = sum g_h d_theta[row],  g_gamma = sum g_h d_gamma[row],
+ *     g_amp = sum g_h d_amp[row]
+ * (each product rounded, then added).  Without the derivative tables only the first two rows of grads are written.
+ * The order of a token sum: G = aura_theta_gamma_groups(N) = clamp(ceil(N / 16), 1, 1024) workgroups of four waves;
+ * wave v of group g adds the tokens [c (4 g + v), c (4 g + v + 1)), c = ceil(N / 4 G), in ascending order from 0; a
+ * group adds its waves as ((0 + 1) + 2) + 3 and writes partials [g][5][D]; the finish launch cuts the groups into
+ * eight runs of ceil(G / 8), adds each run in ascending g from 0 and the eight results in order.  A function of (N, D)
+ * alone; no atomics; the same call gives the same bits.  T_N = c + 3 + ceil(G / 8) + 7 + 1.
+ * partials: G * 5 * D floats of workspace (16-byte aligned when D % 4 == 0), written before they are read.
+ * Errors as aura_theta_gamma_norm; AURA_E_INVAL also for one or two of the three derivative tables, partials without
+ * grads or grads without partials, derivative tables without partials.  Two launches on `stream` (one without grads). */
+int64_t aura_theta_gamma_groups(int64_t N);
+int aura_theta_gamma_norm_backward(const float* g_y, const float* x, const float* table, const float* d_theta_or_null,
+                                   const float* d_gamma_or_null, const float* d_amp_or_null, const float* mean,
+                                   const float* rstd, const float* w, int64_t N, int64_t S, int64_t R, int64_t D,
+                                   float* g_x, float* partials_or_null, float* grads_or_null, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
