@@ -7,6 +7,7 @@ episodic-retrieval hot path, behind the reference's own module API.
     from aura_snn_rag_amd.core.language_zone.snn_ffn import SNNFFN, HybridFFN
     from aura_snn_rag_amd import PlaceCellSemanticEncoder, PlaceCode
     from aura_snn_rag_amd import ThetaGammaPositionalEncoding, embed_tokens
+    from aura_snn_rag_amd import ProsodyAttentionBridge, MultiChannelSpikingAttention, prosody_channels_from_text
 
 All arithmetic on the path runs in ``lib/libaura_hip.so`` (hand-written HIP, C ABI in
 ``include/aura_hip.h``); there is no CPU or eager-PyTorch fallback.
@@ -18,7 +19,10 @@ __version__ = "0.1.0"
 _LAZY = {"PlaceCellSemanticEncoder": "core.language_zone.place_cell_encoder",
          "PlaceCode": "core.language_zone.place_cell_encoder",
          "ThetaGammaPositionalEncoding": "core.language_zone.theta_gamma_encoding",
-         "embed_tokens": "core.language_zone.theta_gamma_encoding"}
+         "embed_tokens": "core.language_zone.theta_gamma_encoding",
+         "MultiChannelSpikingAttention": "core.language_zone.prosody_attention",
+         "ProsodyAttentionBridge": "core.language_zone.prosody_attention",
+         "prosody_channels_from_text": "core.language_zone.prosody_attention"}
 
 
 def __getattr__(name):

@@ -603,6 +603,148 @@ class ThetaGammaNormFunction(torch.autograd.Function):
 
 
 # ---------------------------------------------------------------------------------------
+# prosody attention (the rule: include/aura_hip.h, "Prosody attention")
+# ---------------------------------------------------------------------------------------
+
+PROSODY_MAX_S, PROSODY_MAX_K, PROSODY_MAX_SMOOTHING, PROSODY_MAX_ID = 8192, 256, 64, 1 << 24
+
+
+class ProsodyAttention:
+    """What ``prosody_attention`` returns: ``gains`` and ``salience`` [B, S], ``mu`` [B], ``winners`` [B, k] int32 in
+    rank order (-1 beyond ``min(k, len)``), ``state`` [B, 3] (the membranes after the last live step), and, when asked
+    for, ``spikes`` and ``channels`` [3, B, S] (amp, pitch, boundary), else ``None``."""
+    __slots__ = ("gains", "salience", "mu", "winners", "state", "spikes", "channels")
+
+    def __init__(self, gains, salience, mu, winners, state, spikes=None, channels=None):
+        self.gains, self.salience, self.mu, self.winners, self.state = gains, salience, mu, winners, state
+        self.spikes, self.channels = spikes, channels
+
+
+def _prosody_ids(who: str, ids) -> Tuple[int, int]:
+    if not isinstance(ids, torch.Tensor):
+        raise TypeError(f"{who}: ids must be a torch.Tensor, got {type(ids)}")
+    if ids.dtype not in (torch.int64, torch.int32):
+        raise TypeError(f"{who}: ids is {ids.dtype}; token ids are int64 or int32")
+    if ids.dim() != 2:
+        raise ValueError(f"{who}: ids is [B, S], got {tuple(ids.shape)}")
+    if not ids.is_contiguous():
+        raise ValueError(f"{who}: ids must be contiguous")
+    return ids.shape[0], ids.shape[1]
+
+
+def _prosody_shapes(ids, channels, k, decay, weights, gain_up, min_gain, max_gain, smoothing, lengths,
+                    state) -> Tuple[int, int, int, int]:
+    """Type, shape and limit checks of ``prosody_attention``: ``(B, S, k, m)``.  Touches no device and reads no
+    value."""
+    who = "prosody_attention"
+    if (ids is None) == (channels is None):
+        raise ValueError(f"{who}: give token ids or the three channels, not both and not neither")
+    if ids is not None:
+        B, S = _prosody_ids(who, ids)
+    else:
+        if not isinstance(channels, (tuple, list)) or len(channels) != 3:
+            raise TypeError(f"{who}: channels is the triple (amp, pitch, boundary)")
+        named = tuple(zip(("amp", "pitch", "boundary"), channels))
+        _theta_required(who, named)
+        _place_fp32(who, named, "prosody attention runs")
+        if channels[0].dim() != 2 or any(c.shape != channels[0].shape for c in channels):
+            raise ValueError(f"{who}: amp, pitch and boundary are [B, S] alike, got "
+                             + ", ".join(str(tuple(c.shape)) for c in channels))
+        B, S = channels[0].shape
+    if not 1 <= S <= PROSODY_MAX_S:
+        raise ValueError(f"{who}: S={S} must be in [1, {PROSODY_MAX_S}]")
+    if B > 0x7fffffff:
+        raise ValueError(f"{who}: B={B} rows exceed 2^31 - 1")
+    for n, v in (("k", k), ("smoothing", smoothing)):
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise TypeError(f"{who}: {n} must be an int, got {type(v)}")
+    if not 1 <= k <= min(S, PROSODY_MAX_K):
+        raise ValueError(f"{who}: k={k} must be in [1, min(S, {PROSODY_MAX_K})] with S={S}")
+    if not 0 <= smoothing <= PROSODY_MAX_SMOOTHING:
+        raise ValueError(f"{who}: smoothing={smoothing} must be in [0, {PROSODY_MAX_SMOOTHING}]")
+    for n, t in (("decay", decay), ("weights", weights)):
+        _theta_required(who, ((n, t),))
+        _place_fp32(who, ((n, t),), "prosody attention runs")
+        if tuple(t.shape) != (3,):
+            raise ValueError(f"{who}: {n} is [3] (amp, pitch, boundary), got {tuple(t.shape)}")
+    for n, v in (("gain_up", gain_up), ("min_gain", min_gain), ("max_gain", max_gain)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or v != v or abs(v) == float("inf"):
+            raise ValueError(f"{who}: {n}={v!r} must be a finite number")
+    if lengths is not None:
+        if not isinstance(lengths, torch.Tensor) or lengths.dtype != torch.int32:
+            raise TypeError(f"{who}: lengths must be an int32 tensor")
+        if tuple(lengths.shape) != (B,):
+            raise ValueError(f"{who}: lengths is [{B}], got {tuple(lengths.shape)}")
+        if not lengths.is_contiguous():
+            raise ValueError(f"{who}: lengths must be contiguous")
+    if state is not None:
+        _place_fp32(who, (("state", state),), "prosody attention runs")
+        if tuple(state.shape) != (B, 3):
+            raise ValueError(f"{who}: state is [{B}, 3], got {tuple(state.shape)}")
+    return B, S, k, max(1, smoothing)
+
+
+def _prosody_values(who: str, ids, lengths, S: int) -> None:
+    """The checks that read values (a host sync on a device tensor): ids in [0, 2^24), lengths in [0, S]."""
+    if ids is not None and ids.numel():
+        lo, hi = int(ids.min()), int(ids.max())
+        if lo < 0 or hi >= PROSODY_MAX_ID:
+            raise ValueError(f"{who}: token ids must be in [0, 2^24) (fp32 holds them exactly); got {lo} .. {hi}")
+    if lengths is not None and lengths.numel():
+        lo, hi = int(lengths.min()), int(lengths.max())
+        if lo < 0 or hi > S:
+            raise ValueError(f"{who}: lengths must be in [0, S={S}]; got {lo} .. {hi}")
+
+
+def prosody_attention(ids=None, channels=None, *, k: int, decay, weights, gain_up: float = 1.8,
+                      min_gain: float = 0.5, max_gain: float = 2.5, smoothing: int = 0, normalize: bool = True,
+                      lengths=None, state=None, want_spikes: bool = False, want_channels: bool = False,
+                      validate: bool = True) -> ProsodyAttention:
+    """Attention gains from token ids (or from three given prosody channels) in one launch (the rule:
+    ``include/aura_hip.h``, "Prosody attention").  ``ids`` [B, S] int64 / int32 in [0, 2^24), or ``channels`` = (amp,
+    pitch, boundary), each [B, S] fp32; ``decay`` and ``weights`` [3] fp32 on the device; ``lengths`` [B] int32 (rows
+    end there: beyond it spikes and salience are 0 and gains are ``mu``); ``state`` [B, 3] the membranes to start from.
+    Forward only.  ``validate`` reads the range of ``ids`` and ``lengths`` before the launch, which waits for the device;
+    the kernel itself is safe for any value (an id beyond 2^24 merely loses its low bits, a length is clamped), so a
+    caller who knows its vocabulary can switch it off and keep the call asynchronous."""
+    who = "prosody_attention"
+    B, S, k, m = _prosody_shapes(ids, channels, k, decay, weights, gain_up, min_gain, max_gain, smoothing, lengths,
+                                 state)
+    named = ((("ids", ids),) if ids is not None else tuple(zip(("amp", "pitch", "boundary"), channels))) + (
+        ("decay", decay), ("weights", weights), ("lengths", lengths), ("state", state))
+    if validate:
+        _prosody_values(who, ids, lengths, S)
+    dev = _theta_device(who, named)
+    f32 = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+    out = ProsodyAttention(f32(B, S), f32(B, S), f32(B), torch.empty(B, k, dtype=torch.int32, device=dev), f32(B, 3),
+                           f32(3, B, S) if want_spikes else None, f32(3, B, S) if want_channels else None)
+    ch = (None, None, None) if ids is not None else channels
+    check(lib().aura_prosody_attention(_p(ids), 0 if ids is None else ids.element_size(), _p(ch[0]), _p(ch[1]),
+                                       _p(ch[2]), _p(lengths), _p(state), _p(decay), _p(weights), float(gain_up),
+                                       float(min_gain), float(max_gain), m, int(bool(normalize)), B, S, k,
+                                       _p(out.gains), _p(out.salience), _p(out.mu), _p(out.winners), _p(out.state),
+                                       _p(out.spikes), _p(out.channels), _stream()), "aura_prosody_attention")
+    return out
+
+
+def prosody_channels(ids, validate: bool = True) -> torch.Tensor:
+    """The three prosody channels of token ids, [3, B, S] fp32 (amp, pitch, boundary): the same launch as
+    ``prosody_attention`` with only the channels requested."""
+    who = "prosody_channels"
+    B, S = _prosody_ids(who, ids)
+    if not 1 <= S <= PROSODY_MAX_S:
+        raise ValueError(f"{who}: S={S} must be in [1, {PROSODY_MAX_S}]")
+    if validate:
+        _prosody_values(who, ids, None, S)
+    _need(ids, f"{who}: ids")
+    out = torch.empty(3, B, S, dtype=torch.float32, device=ids.device)
+    check(lib().aura_prosody_attention(_p(ids), ids.element_size(), None, None, None, None, None, None, None, 0.0, 0.0,
+                                       0.0, 1, 0, B, S, 1, None, None, None, None, None, None, _p(out), _stream()),
+          "aura_prosody_attention")
+    return out
+
+
+# ---------------------------------------------------------------------------------------
 # surrogate-gradient training path + prosody-modulated GIF (fp32 and bf16)
 # ---------------------------------------------------------------------------------------
 

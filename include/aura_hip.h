@@ -1002,6 +1002,53 @@ int aura_theta_gamma_norm_backward(const float* g_y, const float* x, const float
                                    const float* rstd, const float* w, int64_t N, int64_t S, int64_t R, int64_t D,
                                    float* g_x, float* partials_or_null, float* grads_or_null, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Prosody attention
+ * ------------------------------------------------------------------------------------- */
+
+/* The attention gains that ProsodyModulatedGIF consumes, from token ids (or from three given prosody channels) in one
+ * launch: prosody_channels_from_text, MultiChannelSpikingAttention.forward (src/core/language_zone/
+ * multi_channel_attention.py) and the gain line of ProsodyAttentionBridge.forward (prosody_attention.py), csrc/
+ * aura_prosody.hip.  Forward only: the spikes are a comparison, so the reference carries no gradient either.  All fp32,
+ * every operation rounded on its own (no fused multiply-add), fl() = round to nearest even.  Per row b of B, with
+ * len = clamp(lengths[b], 0, S) (S without lengths):
+ *   channels  from ids (int64 or int32, 0 <= id < 2^24 so that float(id) is exact), with the accurate sinf / cosf (full
+ *             range reduction: the phases reach 2e4 rad for a 65 536-word vocabulary):
+ *                 amp = |sin(fl(float(id) * 0.1f))|,  pitch = |cos(fl(float(id) * 0.05f))|,
+ *                 boundary = sin(fl(float(id) * 0.3f)) > 0.8f ? 1 : 0;
+ *             or the three arrays amp, pitch, boundary [B][S] as given (ids NULL).
+ *   LIF       per channel c with decay d = decay[c], from v = v0[b][c] (0 without v0), for t = 0 .. len - 1:
+ *                 v = fl(fl(d * v) + x_t);   s_t = (v >= 1.0f);   v = fl(v - s_t)
+ *             at most one spike per step; NaN and inf follow the IEEE comparison and subtraction.  v after step
+ *             len - 1 is v_out[b][c] (v0 itself when len == 0).
+ *   salience  sal_t = fl(fl(fl(w0 s_amp) + fl(w1 s_pitch)) + fl(w2 s_bound)),  w = weights[0 .. 2].
+ *   smoothing m > 1: kw = fl(1.0f / m);  out_t = fl(kw sal[t - m/2]) + fl(kw sal[t - m/2 + 1]) + .. (m terms, added left
+ *             to right from the first, sal = 0 outside [0, len)): the reference's conv1d(padding = m // 2)[:S].
+ *   normalize sal_t = sal_t / fl(max_{t < len} sal + 1e-6f), a correctly rounded division.
+ *   winners   the exact top k_eff = min(k, len) of sal[0 .. len): the larger value first, -0.0 and +0.0 equal, equal
+ *             values to the LOWER position (torch.topk leaves this open), emitted in RANK order as int32 [B][k], the
+ *             rest -1.  avg = fl(sum of the winners' values, added in rank order from the first, / float(k_eff)); 0 when
+ *             len == 0.
+ *   gains     mu = fl(min_gain + fl(fl(max_gain - min_gain) * tanhf(fl(gain_up * avg)))),  gains_t = fl(mu * fl(1 + sal_t)).
+ *   t >= len  spikes 0, sal = 0, gains = mu.
+ * decay and weights are [3] fp32 in device memory (the module's buffers) and must be finite: a NaN salience is ranked
+ * as in the place code (above +inf) but is skipped by the maximum.  A row's result depends on nothing else in the
+ * call: its bits are the same alone or in any batch, whatever the launch geometry.  No atomics.
+ * Outputs: gains, salience [B][S], mu [B], winners [B][k], v_out [B][3]; spikes [3][B][S] and channels [3][B][S] when
+ * their pointers are given.  With all five of the first group NULL and channels given, only the channels are computed
+ * (ids required in practice; lengths, v0 and spikes must then be NULL, k and smoothing are ignored).
+ * Against fp64 on the same fp32 phase, amp and pitch are within 2^-21 (4 ulp of a sine); tanhf is within 5 * 2^-23.
+ * AURA_E_INVAL: B < 0 or B > 2^31 - 1, S < 1 or S > 8192, k < 1 or k > min(S, 256), smoothing < 1 or > 64, ids together
+ *   with a channel array or neither, fewer than three channel arrays, id_bytes not 8 / 4 (ids) or 0 (channels), some but
+ *   not all of the five outputs, a null decay or weights.  AURA_E_ALIGN: ids not aligned to id_bytes, any other pointer
+ *   not 4-byte aligned.  B == 0 launches nothing.  One launch on `stream`. */
+int aura_prosody_attention(const void* ids_or_null, int id_bytes, const float* amp, const float* pitch,
+                           const float* boundary, const int32_t* lengths_or_null, const float* v0_or_null,
+                           const float* decay, const float* weights, float gain_up, float min_gain, float max_gain,
+                           int smoothing, int normalize, int64_t B, int64_t S, int64_t k, float* gains, float* salience,
+                           float* mu, int32_t* winners, float* v_out, float* spikes_or_null, float* channels_or_null,
+                           void* stream);
+
 #ifdef __cplusplus
 }
 #endif
