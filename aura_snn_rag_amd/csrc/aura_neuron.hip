@@ -282,7 +282,7 @@ struct Io<uint16_t, 1> {
 // ------------------------------------------------------------------------------------------
 constexpr int RTC_UNROLL = 4;
 
-template <class Model, typename T, int VEC, bool TIME_INV, bool MEAN_OUT, bool BF16_MEAN>
+template <class Model, typename T, int VEC, bool TIME_INV, bool MEAN_OUT>
 __global__ __launch_bounds__(256) void seq_rtc_kernel(Model m, const T* __restrict__ x,
                                                       T* __restrict__ out, T* st0, T* st1,
                                                       int64_t R, int64_t Tn, int64_t C) {
@@ -343,12 +343,14 @@ __global__ __launch_bounds__(256) void seq_rtc_kernel(Model m, const T* __restri
             }
         }
         if (MEAN_OUT) {
-            // spikes.mean(dim=1): sum (exact: small integers) then a true division by T
-            // (snn_ffn.py:81); in bf16 the sum is rounded to bf16 before the division.
+            // spikes.mean(dim=1) (snn_ffn.py:81) is RNE_dtype(fp32 sum / T): the fp32 sum (exact: small
+            // integers), a true fp32 division by T -- not a multiplication by 1/T -- and ONE rounding, by the
+            // store.  The sum is not rounded to bf16 first: past 256 that gives another mean.  Checked against
+            // torch 2.10 on the CPU (tests/test_host_neuron_rules.py); an older torch may have differed.
             float mean[VEC];
             const float tf = static_cast<float>(Tn);
 #pragma unroll
-            for (int e = 0; e < VEC; ++e) mean[e] = (BF16_MEAN ? round_bf16(acc[e]) : acc[e]) / tf;
+            for (int e = 0; e < VEC; ++e) mean[e] = acc[e] / tf;
             Io<T, VEC>::store(op, mean);
         }
 #pragma unroll
@@ -611,11 +613,11 @@ int launch_rtc_f32(const Model& m, const float* x, float* out, float* st0, float
     const bool vec = (C % 4 == 0) && aligned16(x) && aligned16(out) && aligned16(st0) &&
                      (Model::NS == 1 || aligned16(st1));
     if (vec)
-        hipLaunchKernelGGL((seq_rtc_kernel<Model, float, 4, false, false, false>),
+        hipLaunchKernelGGL((seq_rtc_kernel<Model, float, 4, false, false>),
                            dim3(rtc_grid(R * (C / 4))), dim3(256), 0, s, m, x, out, st0, st1, R, T,
                            C);
     else
-        hipLaunchKernelGGL((seq_rtc_kernel<Model, float, 1, false, false, false>),
+        hipLaunchKernelGGL((seq_rtc_kernel<Model, float, 1, false, false>),
                            dim3(rtc_grid(R * C)), dim3(256), 0, s, m, x, out, st0, st1, R, T, C);
     return aura_check_launch();
 }
@@ -630,7 +632,7 @@ int launch_gif(const GifModel<BF16, POW2L>& m, const void* h, void* out, void* v
     const dim3 g(rtc_grid(rows * (H / VEC))), b(256);
     const bool ti = flags & AURA_GIF_TIME_INVARIANT, mo = flags & AURA_GIF_MEAN_OUT;
 #define AURA_GIF_LAUNCH(TI, MO)                                                                  \
-    hipLaunchKernelGGL((seq_rtc_kernel<GifModel<BF16, POW2L>, T, VEC, TI, MO, BF16>), g, b, 0, s, m, hp, \
+    hipLaunchKernelGGL((seq_rtc_kernel<GifModel<BF16, POW2L>, T, VEC, TI, MO>), g, b, 0, s, m, hp, \
                        op, vp, tp, rows, Tn, H)
     if (ti && mo) AURA_GIF_LAUNCH(true, true);
     else if (ti) AURA_GIF_LAUNCH(true, false);

@@ -79,7 +79,9 @@ int aura_lif_run(const float* x, float* spikes, float* mem, const float* beta,
  * In bf16 every op rounds to bf16, as the reference does (state dtype follows the input,
  * gif_neuron.py:46-47).  Replaces GIFNeuron.forward's loop,
  * src/core/language_zone/gif_neuron.py:54-69 (+ MultiBitSurrogate.forward :11-13) and the
- * spikes.mean(dim=1) readout of SNNFFN.forward, snn_ffn.py:81. */
+ * spikes.mean(dim=1) readout of SNNFFN.forward, snn_ffn.py:81.  The mean is
+ * RNE_dtype(fp32 sum / T): the spike counts summed in fp32, divided by T in fp32, rounded once
+ * to the output dtype (checked against torch 2.10 on the CPU; an older torch may have differed). */
 int aura_gif_run(const void* h, void* out, void* v, void* theta, float decay, int L, float alpha,
                  float threshold, int64_t rows, int64_t T, int64_t H, int dtype, int flags,
                  void* stream);
