@@ -8,6 +8,7 @@ episodic-retrieval hot path, behind the reference's own module API.
     from aura_snn_rag_amd import PlaceCellSemanticEncoder, PlaceCode
     from aura_snn_rag_amd import ThetaGammaPositionalEncoding, embed_tokens
     from aura_snn_rag_amd import ProsodyAttentionBridge, MultiChannelSpikingAttention, prosody_channels_from_text
+    from aura_snn_rag_amd import HippocampalProsodyAttention, HippocampalTransformerLayer, AttentionCache
 
 All arithmetic on the path runs in ``lib/libaura_hip.so`` (hand-written HIP, C ABI in
 ``include/aura_hip.h``); there is no CPU or eager-PyTorch fallback.
@@ -22,7 +23,10 @@ _LAZY = {"PlaceCellSemanticEncoder": "core.language_zone.place_cell_encoder",
          "embed_tokens": "core.language_zone.theta_gamma_encoding",
          "MultiChannelSpikingAttention": "core.language_zone.prosody_attention",
          "ProsodyAttentionBridge": "core.language_zone.prosody_attention",
-         "prosody_channels_from_text": "core.language_zone.prosody_attention"}
+         "prosody_channels_from_text": "core.language_zone.prosody_attention",
+         "HippocampalProsodyAttention": "core.language_zone.hippocampal_attention",
+         "AttentionCache": "core.language_zone.hippocampal_attention",
+         "HippocampalTransformerLayer": "core.language_zone.hippocampal_layer"}
 
 
 def __getattr__(name):

@@ -126,6 +126,8 @@ SIGNATURES = {
     "aura_theta_gamma_groups": (I64, [I64]),
     "aura_theta_gamma_norm_backward": (I, [P, P, P, P, P, P, P, P, P, I64, I64, I64, I64, P, P, P, P]),
     "aura_prosody_attention": (I, [P, I, P, P, P, P, P, P, P, F, F, F, I, I, I64, I64, I64, P, P, P, P, P, P, P, P]),
+    "aura_attn_decode_workspace_bytes": (I64, [I64, I64, I64, I64]),
+    "aura_attn_decode_step": (I, [P, P, P, P, P, P, P, P, P, P, P, P, I64, I64, I64, I64, I64, I, P, I64, P, P, P]),
     "aura_profile_begin": (I, [I]),
     "aura_debug_cs_flags": (I, [I]),
     "aura_debug_clock_mhz": (I, [P, I, P]),

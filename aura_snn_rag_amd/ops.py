@@ -745,6 +745,111 @@ def prosody_channels(ids, validate: bool = True) -> torch.Tensor:
 
 
 # ---------------------------------------------------------------------------------------
+# decode attention (the rule: include/aura_hip.h, "Decode attention")
+# ---------------------------------------------------------------------------------------
+
+DECODE_CHUNK, DECODE_MAX_D, DECODE_MAX_HEAD, DECODE_MAX_CAP = 256, 2048, 128, 32768
+
+
+def attn_decode_chunks(capacity: int) -> int:
+    """The chunk count that serves every length of a cache of ``capacity`` positions: ``ceil(capacity / 256)``."""
+    return -(-int(capacity) // DECODE_CHUNK)
+
+
+def attn_decode_workspace_floats(B: int, H: int, dh: int, n_chunks: int) -> int:
+    """Floats of partials workspace of a step: per (b, h) a header of 4 and ``n_chunks`` chunks of ``4 + dh``."""
+    return max(4, B * H * (4 + n_chunks * (4 + dh)))
+
+
+def _attn_decode_shapes(q, k_new, v_new, x, prosody, Wp, bp, wm, bm, lengths, k_cache, v_cache, workspace,
+                        n_chunks) -> Tuple[int, int, int, int, int]:
+    """Type, shape and limit checks of ``attn_decode_step``: ``(B, H, dh, cap, n_chunks)``.  Touches no device."""
+    who = "attn_decode_step"
+    _theta_required(who, (("q", q), ("k_new", k_new), ("v_new", v_new), ("lengths", lengths), ("k_cache", k_cache),
+                          ("v_cache", v_cache), ("workspace", workspace)))
+    _place_fp32(who, (("q", q), ("k_new", k_new), ("v_new", v_new), ("x", x), ("prosody", prosody), ("Wp", Wp),
+                      ("bp", bp), ("wm", wm), ("bm", bm), ("k_cache", k_cache), ("v_cache", v_cache),
+                      ("workspace", workspace)), "the decode step runs")
+    if not isinstance(lengths, torch.Tensor):
+        raise TypeError(f"{who}: lengths must be a torch.Tensor, got {type(lengths)}")
+    if lengths.dtype != torch.int32:
+        raise TypeError(f"{who}: lengths is {lengths.dtype}; the kernel reads and advances int32 lengths")
+    if not lengths.is_contiguous():
+        raise ValueError(f"{who}: lengths must be contiguous")
+    if k_cache.dim() != 4 or v_cache.shape != k_cache.shape:
+        raise ValueError(f"{who}: k_cache and v_cache are [B, H, cap, dh]; got {tuple(k_cache.shape)}, "
+                         f"{tuple(v_cache.shape)}")
+    B, H, cap, dh = k_cache.shape
+    D = H * dh
+    if H < 1 or dh % 4 != 0 or not 4 <= dh <= DECODE_MAX_HEAD:
+        raise ValueError(f"{who}: dh={dh} must be a multiple of 4 in [4, {DECODE_MAX_HEAD}] (H={H})")
+    if D > DECODE_MAX_D:
+        raise ValueError(f"{who}: D = H dh = {D} exceeds {DECODE_MAX_D}")
+    if not 1 <= cap <= DECODE_MAX_CAP:
+        raise ValueError(f"{who}: cap={cap} must be in [1, {DECODE_MAX_CAP}]")
+    for n, t in (("q", q), ("k_new", k_new), ("v_new", v_new)):
+        if tuple(t.shape) != (B, D):
+            raise ValueError(f"{who}: {n} is [B, D] = ({B}, {D}), got {tuple(t.shape)}")
+    if tuple(lengths.shape) != (B,):
+        raise ValueError(f"{who}: lengths is [B] = ({B},), got {tuple(lengths.shape)}")
+    if prosody is not None:
+        if tuple(prosody.shape) != (B, 4):
+            raise ValueError(f"{who}: prosody is [B, 4] = ({B}, 4), got {tuple(prosody.shape)}")
+        _theta_required(who, (("Wp (with prosody)", Wp), ("bp (with prosody)", bp)))
+        if tuple(Wp.shape) != (H, 4) or tuple(bp.shape) != (H,):
+            raise ValueError(f"{who}: Wp is [H, 4] and bp [H] with H={H}; got {tuple(Wp.shape)}, {tuple(bp.shape)}")
+    if (wm is None) != (bm is None):
+        raise ValueError(f"{who}: wm and bm are the memory gate's weight and bias: give both or neither")
+    if wm is not None:
+        _theta_required(who, (("x (with wm)", x),))
+        if wm.numel() != D or bm.numel() != 1:
+            raise ValueError(f"{who}: wm holds D={D} weights and bm one bias; got {tuple(wm.shape)}, {tuple(bm.shape)}")
+        if tuple(x.shape) != (B, D):
+            raise ValueError(f"{who}: x is [B, D] = ({B}, {D}), got {tuple(x.shape)}")
+    if n_chunks is None:
+        n_chunks = attn_decode_chunks(cap)
+    if isinstance(n_chunks, bool) or not isinstance(n_chunks, int):
+        raise TypeError(f"{who}: n_chunks must be an int, got {type(n_chunks)}")
+    if n_chunks < 1 or n_chunks * DECODE_CHUNK > cap + DECODE_CHUNK - 1:
+        raise ValueError(f"{who}: n_chunks={n_chunks} must be in [1, ceil(cap / {DECODE_CHUNK})] with cap={cap}")
+    if B * H * n_chunks > 0x7fffffff:
+        raise ValueError(f"{who}: B H n_chunks = {B * H * n_chunks} waves exceed 2^31 - 1")
+    need = attn_decode_workspace_floats(B, H, dh, n_chunks)
+    if workspace.numel() < need:
+        raise ValueError(f"{who}: workspace holds {workspace.numel()} floats, the step needs {need}")
+    return B, H, dh, cap, n_chunks
+
+
+def attn_decode_step(q, k_new, v_new, x, prosody, Wp, bp, wm, bm, lengths, k_cache, v_cache, workspace,
+                     n_chunks: Optional[int] = None, advance: bool = True, return_scale: bool = False):
+    """One cached decoding step of HippocampalProsodyAttention in two launches (the rule: ``include/aura_hip.h``,
+    "Decode attention"): scales the new query row ``q`` [B, D] by the prosody and memory gates (``prosody`` [B, 4] with
+    ``Wp`` [H, 4], ``bp`` [H]; ``wm`` [D], ``bm`` [1] with the normed hidden row ``x`` [B, D]; either may be ``None``),
+    appends ``k_new`` / ``v_new`` at position ``lengths[b]`` of ``k_cache`` / ``v_cache`` [B, H, cap, dh], attends over
+    positions ``0 .. lengths[b]`` and returns ``ctx`` [B, D] in the layout ``o_proj`` reads.  Rows with a length outside
+    ``[0, cap)`` are inactive: zeros, nothing written.  ``advance`` adds one to the active rows' int32 ``lengths`` on the
+    device.  ``workspace``: ``attn_decode_workspace_floats`` fp32, owned by the caller.  ``return_scale`` also returns
+    the scale ``s`` [B, H].  A row's bits do not depend on the batch, ``cap`` or ``n_chunks``.  No host sync."""
+    B, H, dh, cap, n_chunks = _attn_decode_shapes(q, k_new, v_new, x, prosody, Wp, bp, wm, bm, lengths, k_cache,
+                                                   v_cache, workspace, n_chunks)
+    if prosody is None:
+        Wp = bp = None
+    if wm is None:
+        x = None
+    dev = _theta_device("attn_decode_step", (("q", q), ("k_new", k_new), ("v_new", v_new), ("x", x), ("prosody", prosody),
+                                             ("Wp", Wp), ("bp", bp), ("wm", wm), ("bm", bm), ("lengths", lengths),
+                                             ("k_cache", k_cache), ("v_cache", v_cache), ("workspace", workspace)),
+                        wide=("q", "k_new", "v_new", "x", "wm", "k_cache", "v_cache", "workspace"))
+    ctx = torch.empty(B, H * dh, dtype=torch.float32, device=dev)
+    scale = torch.empty(B, H, dtype=torch.float32, device=dev) if return_scale else None
+    check(lib().aura_attn_decode_step(_p(q), _p(k_new), _p(v_new), _p(x), _p(prosody), _p(Wp), _p(bp), _p(wm), _p(bm),
+                                      _p(lengths), _p(k_cache), _p(v_cache), B, H, dh, cap, n_chunks, int(bool(advance)),
+                                      _p(workspace), workspace.numel() * 4, _p(ctx), _p(scale), _stream()),
+          "aura_attn_decode_step")
+    return (ctx, scale) if return_scale else ctx
+
+
+# ---------------------------------------------------------------------------------------
 # surrogate-gradient training path + prosody-modulated GIF (fp32 and bf16)
 # ---------------------------------------------------------------------------------------
 

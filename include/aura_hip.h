@@ -1051,6 +1051,70 @@ int aura_prosody_attention(const void* ids_or_null, int id_bytes, const float* a
                            float* mu, int32_t* winners, float* v_out, float* spikes_or_null, float* channels_or_null,
                            void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Decode attention
+ * ------------------------------------------------------------------------------------- */
+
+/* One cached decoding step of HippocampalProsodyAttention (src/core/language_zone/hippocampal_attention.py): the query
+ * modulation of lines 46-75, the append of the new key and value to a K/V cache, and the attention of the one new query
+ * row over the positions 0 .. L, csrc/aura_decode.hip.  The module's causal forward at position L is this function of
+ * the rows 0 .. L, so stepping is the same function as the forward, not an approximation.  All fp32, every operation
+ * rounded on its own (no fused multiply-add), fl() = round to nearest even, expf / tanhf the accurate device functions.
+ *
+ * q, k_new, v_new, x [B][D], D = H dh: the three projections of the new token and the normed hidden row they were taken
+ * from (x is read only with wm).  prosody [B][4] or NULL; Wp [H][4], bp [H] the prosody gate (read only with prosody);
+ * wm [D], bm [1] the memory gate, both or neither (NULL: use_memory=False).  lengths int32 [B]; Kc, Vc [B][H][cap][dh].
+ * Per row b and head h, L = lengths[b]:
+ *   inactive  L < 0 or L >= min(cap, 256 n_chunks): nothing is written to either cache, ctx[b] = 0, scale[b][h] = 0,
+ *             lengths[b] stays.  lengths[b] = -1 retires a sequence; a full cache is harmless on the device.
+ *   scale     sig(a) = fl(1 / fl(1 + expf(-a)));  p = prosody[b]
+ *                 g  = fl(fl(fl(fl(fl(Wp[h][0] p0) + fl(Wp[h][1] p1)) + fl(Wp[h][2] p2)) + fl(Wp[h][3] p3)) + bp[h])
+ *                 sp = fl(fl(fl(1 + sig(g)) * fl(1 + fl(0.2 tanhf(p0)))) * fl(1 + fl(0.05 tanhf(p1))))     (1 without prosody)
+ *                 sm = fl(1 + fl(0.5 sig(fl(dot_D(wm, x[b]) + bm[0]))))                                    (1 without wm)
+ *                 s  = fl(sp * sm),   q' = fl(q * s)
+ *             dot_D: lane l of a wave owns the units u = l, l + 64, .. of D / 4 (a unit is four consecutive columns) and
+ *             adds fl(wm[d] x[d]) in ascending d from 0; the 64 lane sums are added by the xor butterfly 32, 16, 8, 4, 2, 1.
+ *             A function of D alone.
+ *   append    Kc[b][h][L] = k_new[b][h dh ..], Vc[b][h][L] = v_new[b][h dh ..], bit copies.  Position L's key and value
+ *             are taken from k_new / v_new by whoever needs them, never read back from the cache.
+ *   scores    z_t = fl(dot_dh(q', K_t) * isq), isq = fl(1 / sqrtf(float(dh))), t = 0 .. L.  dot_dh: G = dh / 4 units, GP the
+ *             power of two >= G; unit j gives fl(fl(fl(q0 k0 + q1 k1) + q2 k2) + q3 k3) (each product rounded), the GP
+ *             values (0 for j >= G) are added by the xor butterfly GP/2, .., 1.
+ *   chunks    chunk c is the positions [256 c, 256 c + 256), cut by position alone.  A chunk is reduced by R = 64 / GP
+ *             slots; slot r takes the positions 256 c + r + R i, i = 0, 1, .., four at a time (a block; the positions
+ *             past L are left out), from (m, l, acc) = (-inf, 0, 0):
+ *                 m' = max(m, z of the block);  al = (m == m') ? 1 : expf(m - m');  l = fl(l al);  acc = fl(acc al);
+ *                 then for each position of the block in order: p = expf(z - m'); l = fl(l + p); acc = fl(acc + fl(p V_t)).
+ *             The slots are merged by the xor butterfly GP, 2 GP, .., 32 with
+ *                 M = max(m_a, m_b);  e_x = (m_x == -inf) ? 0 : expf(m_x - M);  l = fl(fl(l_a e_a) + fl(l_b e_b))  (acc alike),
+ *             which is symmetric in a and b.  The chunk's (m, l, acc[dh]) goes to the workspace.
+ *   merge     the second launch adds the chunks 0 .. L / 256 of a (b, h) in ascending order with the same formula
+ *             (e = expf(m - M), no chunk is empty) and writes ctx[b][h dh ..] = acc / l (a correctly rounded division),
+ *             the head-concatenated layout o_proj reads.  With `advance`, lengths[b] += 1 for active rows, by the second
+ *             launch only: every wave of the first has read the lengths by then, and the second takes each row's chunk
+ *             count from the workspace.
+ * One wave per (b, h, chunk) in the first launch, four waves per workgroup, a wave whose chunk starts past L exits at
+ * once; exactly one wave per (b, h) writes the append.  K and V go straight to registers in 16-byte loads.  A row's bits
+ * are the same alone or in any batch, for any cap, any n_chunks >= L / 256 + 1, any other rows' lengths; two calls give
+ * the same bits.  No atomics.  L = 0 gives ctx = v_new exactly (up to the sign of a zero).
+ * Against fp64 on the same fp32 inputs (tests/decode_attention_rule.py derives it): with E_s the relative error of s,
+ * A_t = isq sum_i |q'_i K_ti|, Dz = max_t (E_s + (log2 GP + 7) 2^-24) A_t,
+ *     |ctx_d - ctx64_d| <= sum_t w_t |V_td| (expm1(2 Dz) + ((zmax - z_t) + Z) 2^-24 + 2 T 2^-24),
+ *     Z = sum_t w_t (zmax - z_t),   T = 256 / R + 3 * 64 / R + 4 log2 R + 4 (L / 256 + 1) + 8.
+ *
+ * workspace: aura_attn_decode_workspace_bytes(B, H, dh, n_chunks) bytes, 16-byte aligned, owned by the caller, written
+ * before it is read.  scale [B][H] or NULL receives s.
+ * AURA_E_INVAL: B < 0, H < 1, dh % 4 != 0, dh < 4 or > 128, H dh > 2048, cap < 1 or > 32768, n_chunks < 1 or
+ *   256 n_chunks > cap + 255, B H n_chunks > 2^31 - 1, a null required pointer, prosody without Wp / bp, one of wm / bm,
+ *   wm without x, a workspace too small.  AURA_E_ALIGN: q, k_new, v_new, x, wm, Kc, Vc, workspace or ctx not 16-byte
+ *   aligned, any other pointer not 4-byte aligned.  B == 0 launches nothing.  Two launches on `stream`. */
+int64_t aura_attn_decode_workspace_bytes(int64_t B, int64_t H, int64_t dh, int64_t n_chunks);
+int aura_attn_decode_step(const float* q, const float* k_new, const float* v_new, const float* x,
+                          const float* prosody_or_null, const float* Wp, const float* bp, const float* wm_or_null,
+                          const float* bm_or_null, int32_t* lengths, float* Kc, float* Vc, int64_t B, int64_t H,
+                          int64_t dh, int64_t cap, int64_t n_chunks, int advance, float* workspace,
+                          int64_t workspace_bytes, float* ctx, float* scale_or_null, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
