@@ -9,6 +9,7 @@ episodic-retrieval hot path, behind the reference's own module API.
     from aura_snn_rag_amd import ThetaGammaPositionalEncoding, embed_tokens
     from aura_snn_rag_amd import ProsodyAttentionBridge, MultiChannelSpikingAttention, prosody_channels_from_text
     from aura_snn_rag_amd import HippocampalProsodyAttention, HippocampalTransformerLayer, AttentionCache
+    from aura_snn_rag_amd import HippocampalTransformer, DecodeState      # forward, prefill / step, generate
 
 All arithmetic on the path runs in ``lib/libaura_hip.so`` (hand-written HIP, C ABI in
 ``include/aura_hip.h``); there is no CPU or eager-PyTorch fallback.
@@ -26,7 +27,9 @@ _LAZY = {"PlaceCellSemanticEncoder": "core.language_zone.place_cell_encoder",
          "prosody_channels_from_text": "core.language_zone.prosody_attention",
          "HippocampalProsodyAttention": "core.language_zone.hippocampal_attention",
          "AttentionCache": "core.language_zone.hippocampal_attention",
-         "HippocampalTransformerLayer": "core.language_zone.hippocampal_layer"}
+         "HippocampalTransformerLayer": "core.language_zone.hippocampal_layer",
+         "HippocampalTransformer": "core.language_zone.hippocampal_transformer",
+         "DecodeState": "core.language_zone.hippocampal_transformer"}
 
 
 def __getattr__(name):

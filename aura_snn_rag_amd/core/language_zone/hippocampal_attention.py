@@ -154,10 +154,11 @@ class HippocampalProsodyAttention(nn.Module):
 
     @torch.no_grad()
     def step(self, hidden_states: torch.Tensor, prosody: Optional[torch.Tensor] = None, use_memory: bool = True,
-             cache: Optional[AttentionCache] = None) -> torch.Tensor:
+             cache: Optional[AttentionCache] = None, advance: bool = True) -> torch.Tensor:
         """One new token: hidden [B, D] or [B, 1, D] (the normed row the layer feeds ``forward``), prosody [B, 4] or
         [B, 1, 4] or ``None``.  Appends the token's key and value at each row's length, attends over the cache and
-        returns the attention output [B, D]; the lengths advance on the device.  Raises when the cache may be full."""
+        returns the attention output [B, D]; the lengths advance on the device unless ``advance=False`` (caches that
+        share one lengths tensor: only the last of them advances it).  Raises when the cache may be full."""
         who = "HippocampalProsodyAttention.step"
         if hidden_states.dim() == 3 and hidden_states.shape[1] == 1:
             hidden_states = hidden_states[:, 0]
@@ -184,6 +185,6 @@ class HippocampalProsodyAttention(nn.Module):
                                    self.memory_gate.weight if memory else None,
                                    self.memory_gate.bias if memory else None,
                                    cache.lengths, cache.k, cache.v, cache.workspace, n_chunks=cache.n_chunks,
-                                   advance=True)
+                                   advance=bool(advance))
         cache.max_length += 1
         return self.o_proj(ctx)

@@ -49,10 +49,11 @@ class HippocampalTransformerLayer(nn.Module):
 
     @torch.no_grad()
     def step(self, hidden_states: torch.Tensor, prosody: Optional[torch.Tensor] = None, use_memory: bool = True,
-             cache: Optional[AttentionCache] = None) -> torch.Tensor:
-        """One new token through the layer: hidden [B, D] or [B, 1, D] -> [B, D]."""
+             cache: Optional[AttentionCache] = None, advance: bool = True) -> torch.Tensor:
+        """One new token through the layer: hidden [B, D] or [B, 1, D] -> [B, D].  ``advance=False`` leaves the
+        cache's lengths alone (a model whose layers share one lengths tensor advances it in its last layer)."""
         if hidden_states.dim() == 3 and hidden_states.shape[1] == 1:
             hidden_states = hidden_states[:, 0]
         attn_output = self.attention.step(self.attention_norm(hidden_states), prosody=prosody, use_memory=use_memory,
-                                          cache=cache)
+                                          cache=cache, advance=advance)
         return self._feed_forward(hidden_states + self.dropout(attn_output))

@@ -1,0 +1,236 @@
+"""HippocampalTransformer: the language model the package's front end, layers and decoding step add up to, with cached
+generation on a fused sampler.
+
+API-compatible with the reference's ``src/core/language_zone/hippocampal_transformer.py``: the constructor
+``(config, hippocampus)``, the attribute names (``pos_encoder``, ``semantic_encoder``, ``dropout``, ``layer_norm``,
+``layers``, ``output_head``), the ``state_dict`` keys, the weight tying (``output_head.weight is
+semantic_encoder.token_embedding.weight``), ``set_gradient_checkpointing`` and ``forward(input_ids, prosody=None,
+use_memory=True, store_memory=False, memory_ids=None) -> (logits, place_cell_activity)``.  ``forward`` is
+``embed_tokens`` (the place code and the theta-gamma add-and-norm kernels), dropout, the layers and the tied head;
+gradients flow as they do through the parts.  ``store_memory`` stores the pooled batch through
+``create_episodic_memories`` in one call instead of one write per row.
+
+New on this module: ``new_state`` / ``prefill`` / ``step`` / ``generate``.  ``generate`` has the signature users know
+from the reference's ``SNNRAGTransformer.generate``; it prefills the layers' K/V caches once, then takes one ``step`` per
+token and turns each step's logit row into a token with ``ops.sample_next`` (``csrc/aura_sample.hip``; the rule:
+``include/aura_hip.h``, "Next token"), written straight into its column of the preallocated result.  Where it differs
+from the reference's loop on purpose:
+  * it never truncates the context to ``max_seq_len`` and re-bases the positions: positions simply continue, which the
+    theta-gamma table supports (the phase is normalised by ``max_seq_len``, not bounded by it);
+  * it stops when every row has finished (each row at its own EOS; a finished row is padded), where the reference stops
+    only when every row emits EOS in the same step;
+  * top-k keeps exactly ``k`` candidates (equal logits: the lower id), and the random numbers are a function of
+    ``(seed, step, stream, token id)``, so a row draws the same tokens alone or in any batch.
+Decoding is fp32, runs under ``no_grad`` and has no CPU fallback: CPU tensors raise ``AuraDeviceError``.
+"""
+from __future__ import annotations
+
+import time
+from typing import List, Optional, Tuple
+
+import torch
+import torch.nn as nn
+from torch.utils.checkpoint import checkpoint
+
+from ... import ops
+from .hippocampal_attention import AttentionCache
+from .hippocampal_layer import HippocampalTransformerLayer
+from .place_cell_encoder import PlaceCellSemanticEncoder
+from .theta_gamma_encoding import ThetaGammaPositionalEncoding, embed_tokens
+
+_UNSET = object()
+
+
+class DecodeState:
+    """What a generation carries between steps: one ``AttentionCache`` per layer, all sharing one int32 ``lengths``
+    tensor (only the last layer's step advances it; -1 retires a row), the host-side ``position`` (prompt length plus
+    steps taken), the ``seen`` mask [B, V] uint8 of the tokens a row holds (the repetition penalty's set),
+    ``finished`` uint8 [B], and the sampler's ``seed`` and ``step`` counter."""
+    __slots__ = ("caches", "lengths", "position", "seen", "finished", "seed", "step", "capacity")
+
+    def __init__(self, caches: List[AttentionCache], seen: torch.Tensor, finished: torch.Tensor, seed: int):
+        self.caches = caches
+        self.lengths = caches[0].lengths
+        for c in caches[1:]:
+            c.lengths = self.lengths
+        self.capacity = caches[0].capacity
+        self.position = 0
+        self.seen = seen
+        self.finished = finished
+        self.seed = int(seed)
+        self.step = 0
+
+    @property
+    def batch(self) -> int:
+        return self.seen.shape[0]
+
+
+class HippocampalTransformer(nn.Module):
+    def __init__(self, config, hippocampus):
+        super().__init__()
+        self.config = config
+        self.hippocampus = hippocampus
+        self.use_gradient_checkpointing = getattr(config, 'use_gradient_checkpointing', False)
+        self.pos_encoder = ThetaGammaPositionalEncoding(config)
+        self.semantic_encoder = PlaceCellSemanticEncoder(config, hippocampus)
+        self.dropout = nn.Dropout(config.dropout)
+        self.layer_norm = nn.LayerNorm(config.embedding_dim)
+        self.layers = nn.ModuleList([HippocampalTransformerLayer(config, hippocampus)
+                                     for _ in range(config.num_layers)])
+        self.output_head = nn.Linear(config.embedding_dim, config.vocab_size, bias=False)
+        self.output_head.weight = self.semantic_encoder.token_embedding.weight      # tied, as upstream
+
+    def set_gradient_checkpointing(self, enable: bool = True):
+        self.use_gradient_checkpointing = enable
+
+    def _layer_forward(self, layer, hidden_states, prosody, use_memory):
+        return layer(hidden_states, prosody=prosody, use_memory=use_memory)
+
+    # ------------------------------------------------------------------------------------------------ full sequences
+    def forward(self, input_ids: torch.Tensor, prosody: Optional[torch.Tensor] = None, use_memory: bool = True,
+                store_memory: bool = False, memory_ids: Optional[List[str]] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        batch_size = input_ids.shape[0]
+        hidden_states, place_cell_activity = embed_tokens(input_ids, self.semantic_encoder, self.pos_encoder,
+                                                          self.layer_norm)
+        hidden_states = self.dropout(hidden_states)
+        for layer in self.layers:
+            if self.training and self.use_gradient_checkpointing:
+                hidden_states = checkpoint(self._layer_forward, layer, hidden_states, prosody, use_memory,
+                                           use_reentrant=False)
+            else:
+                hidden_states = layer(hidden_states, prosody=prosody, use_memory=use_memory)
+        logits = self.output_head(hidden_states)
+        if store_memory and self.hippocampus is not None:
+            summary = hidden_states.mean(dim=1).detach()
+            now = time.time()
+            ids = [memory_ids[b] if memory_ids and b < len(memory_ids) else f"step-{int(now)}-b{b}"
+                   for b in range(batch_size)]
+            self.hippocampus.create_episodic_memories(ids, summary)
+        return logits, place_cell_activity
+
+    # ------------------------------------------------------------------------------------------------ cached decoding
+    def new_state(self, batch: int, capacity: int, seed: int = 0) -> DecodeState:
+        """An empty decoding state for ``batch`` sequences of at most ``capacity`` positions, on the model's device."""
+        if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < (1 << 64):
+            raise ValueError(f"HippocampalTransformer.new_state: seed must be an int in [0, 2^64), got {seed!r}")
+        if len(self.layers) < 1:
+            raise ValueError("HippocampalTransformer.new_state: a model without layers has nothing to cache")
+        caches = [layer.new_cache(batch, capacity) for layer in self.layers]
+        dev = self.output_head.weight.device
+        seen = torch.zeros(batch, self.config.vocab_size, dtype=torch.uint8, device=dev)
+        finished = torch.zeros(batch, dtype=torch.uint8, device=dev)
+        return DecodeState(caches, seen, finished, seed)
+
+    def _check_state(self, who: str, state, B: int) -> None:
+        if not isinstance(state, DecodeState):
+            raise TypeError(f"{who}: state must be a DecodeState (new_state), got {type(state)}")
+        if state.batch != B or len(state.caches) != len(self.layers):
+            raise ValueError(f"{who}: the state holds {state.batch} rows and {len(state.caches)} caches, this call "
+                             f"needs {B} rows and {len(self.layers)} caches")
+
+    def prefill(self, input_ids: torch.Tensor, prosody: Optional[torch.Tensor] = None,
+                state: Optional[DecodeState] = None, use_memory: bool = True) -> torch.Tensor:
+        """``forward`` over a prompt [B, S] that also fills every layer's cache and marks the prompt's tokens in
+        ``state.seen``.  Returns the logits [B, S, V]."""
+        who = "HippocampalTransformer.prefill"
+        if input_ids.dim() != 2:
+            raise ValueError(f"{who}: input_ids is [B, S], got {tuple(input_ids.shape)}")
+        B, S = input_ids.shape
+        self._check_state(who, state, B)
+        hidden_states, _ = embed_tokens(input_ids, self.semantic_encoder, self.pos_encoder, self.layer_norm)
+        hidden_states = self.dropout(hidden_states)
+        for layer, cache in zip(self.layers, state.caches):
+            hidden_states = layer.prefill(hidden_states, prosody=prosody, use_memory=use_memory, cache=cache)
+        with torch.no_grad():
+            state.seen.scatter_(1, input_ids.to(torch.int64), 1)
+        state.position = S
+        return self.output_head(hidden_states)
+
+    @torch.no_grad()
+    def step(self, tokens: torch.Tensor, prosody: Optional[torch.Tensor] = None, state: Optional[DecodeState] = None,
+             use_memory: bool = True) -> torch.Tensor:
+        """One new token per row: tokens [B] (or [B, 1]) at position ``state.position`` -> logits [B, V].  Every
+        layer's ``step`` runs on its cache; the last one advances the shared lengths.  No host sync."""
+        who = "HippocampalTransformer.step"
+        if tokens.dim() == 1:
+            tokens = tokens[:, None]
+        if tokens.dim() != 2 or tokens.shape[1] != 1:
+            raise ValueError(f"{who}: tokens is [B] or [B, 1], got {tuple(tokens.shape)}")
+        self._check_state(who, state, tokens.shape[0])
+        hidden_states, _ = embed_tokens(tokens, self.semantic_encoder, self.pos_encoder, self.layer_norm,
+                                        start=state.position, dense=False)
+        hidden_states = self.dropout(hidden_states)[:, 0]
+        last = len(self.layers) - 1
+        for i, (layer, cache) in enumerate(zip(self.layers, state.caches)):
+            hidden_states = layer.step(hidden_states, prosody=prosody, use_memory=use_memory, cache=cache,
+                                       advance=i == last)
+        state.position += 1
+        return self.output_head(hidden_states)
+
+    def generate(self, input_ids: torch.Tensor, max_new_tokens: int = 50, temperature: float = 0.8, top_k: int = 50,
+                 top_p: float = 0.9, use_memory: bool = True, repetition_penalty: float = 1.2, *,
+                 repetition_rule: str = "divide", seed: Optional[int] = None, eos_token_id=_UNSET,
+                 pad_token_id: Optional[int] = None, sync_every: int = 8, stream_ids=None) -> torch.Tensor:
+        """Generates up to ``max_new_tokens`` tokens after the prompts ``input_ids`` [B, S] (equal lengths, as in the
+        reference) -> [B, S + n].  Runs under ``eval()`` and ``no_grad``: one ``prefill``, then per token one ``step``
+        and one ``ops.sample_next`` that writes the token into its column of the preallocated result.
+
+        ``temperature=0`` is greedy; ``repetition_penalty`` acts on the tokens a row holds (prompt and generated),
+        ``repetition_rule`` ``'divide'`` as the reference's loop or ``'signed'`` as its ``apply_repetition_penalty``.
+        ``seed=None`` takes one number from torch's default generator (``torch.manual_seed`` governs it);
+        ``stream_ids`` [B] number the rows' random streams (default: the row numbers).  ``eos_token_id`` defaults to the
+        config's; with one, a row that draws it is finished: its later tokens are ``pad_token_id`` (default: the EOS
+        id) and its cache rows are retired (length -1).  The host looks at the finished flags only every ``sync_every``
+        steps, and once at the end to trim the result to the step at which the last row finished.
+
+        Differences from the reference's loop, on purpose: the context is never truncated to ``max_seq_len`` and
+        re-based, positions simply continue (``S + max_new_tokens`` must fit ``ops.DECODE_MAX_CAP``); generation
+        stops when every row has finished, not only when every row emits EOS in the same step; top-k keeps exactly
+        ``k`` candidates and the random stream is fixed by ``(seed, step, stream, token id)`` (the rule:
+        ``include/aura_hip.h``, "Next token")."""
+        who = "HippocampalTransformer.generate"
+        if input_ids.dim() != 2 or input_ids.shape[1] < 1:
+            raise ValueError(f"{who}: input_ids is [B, S] with S >= 1, got {tuple(input_ids.shape)}")
+        for n, v in (("max_new_tokens", max_new_tokens), ("sync_every", sync_every)):
+            if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+                raise ValueError(f"{who}: {n} must be an int >= 1, got {v!r}")
+        B, S = input_ids.shape
+        capacity = S + max_new_tokens
+        if capacity > ops.DECODE_MAX_CAP:
+            raise ValueError(f"{who}: S + max_new_tokens = {capacity} exceeds the cache limit {ops.DECODE_MAX_CAP} (a "
+                             f"sliding cache is not part of this module)")
+        eos = getattr(self.config, "eos_token_id", None) if eos_token_id is _UNSET else eos_token_id
+        pad = pad_token_id if pad_token_id is not None else (eos if eos is not None else 0)
+        if seed is None:
+            seed = int(torch.randint(0, 1 << 62, (1,)).item())
+        dev = input_ids.device
+        if stream_ids is not None and not isinstance(stream_ids, torch.Tensor):
+            stream_ids = torch.as_tensor(list(stream_ids), dtype=torch.int64).to(dev)
+        self.eval()
+        with torch.no_grad():
+            state = self.new_state(B, capacity, seed=seed)
+            generated = torch.empty(B, capacity, dtype=torch.int64, device=dev)
+            generated[:, :S] = input_ids
+            logits = self.prefill(input_ids, state=state, use_memory=use_memory)[:, -1]
+            n = 0
+            while True:
+                column = generated[:, S + n]
+                ops.sample_next(logits, seen=state.seen, finished=state.finished, stream_ids=stream_ids,
+                                penalty=repetition_penalty, penalty_rule=repetition_rule, temperature=temperature,
+                                top_k=top_k, top_p=top_p, seed=state.seed, step=state.step, eos_id=eos, pad_id=pad,
+                                out=column)
+                state.step += 1
+                n += 1
+                if n == max_new_tokens:
+                    break
+                if eos is not None:
+                    state.lengths.masked_fill_(state.finished.bool(), -1)
+                    if n % sync_every == 0 and bool(state.finished.all()):
+                        break
+                logits = self.step(column, state=state, use_memory=use_memory)
+            if eos is not None:
+                # the step at which the last row finished: a column is padding when every row had finished before it
+                new = generated[:, S:S + n]
+                done_before = ((new == eos).cumsum(1) - (new == eos).to(torch.int64)) > 0
+                n = int((~done_before.all(0)).sum().item())
+        return generated[:, :S + n]

@@ -850,6 +850,152 @@ def attn_decode_step(q, k_new, v_new, x, prosody, Wp, bp, wm, bm, lengths, k_cac
 
 
 # ---------------------------------------------------------------------------------------
+# next token (the rule: include/aura_hip.h, "Next token")
+# ---------------------------------------------------------------------------------------
+
+SAMPLE_MAX_K, SAMPLE_MAX_V = 1024, 131072
+PENALTY_RULES = {"divide": 0, "signed": 1}
+
+
+def _sample_int(who: str, name: str, v, lo: int, hi: int) -> int:
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+        raise TypeError(f"{who}: {name} must be an int, got {type(v)}")
+    if not lo <= int(v) < hi:
+        raise ValueError(f"{who}: {name}={v} must be in [{lo}, {hi})")
+    return int(v)
+
+
+def _sample_args(logits, seen, finished, stream_ids, penalty, penalty_rule, temperature, top_k, top_p, seed, step,
+                 eos_id, pad_id, out):
+    """Type, shape and limit checks of ``sample_next``: ``(B, V, row_stride, scalars)`` with ``scalars`` the library's
+    arguments from ``penalty`` to ``pad_id``.  Touches no device and loads nothing."""
+    who = "sample_next"
+    if not isinstance(logits, torch.Tensor):
+        raise TypeError(f"{who}: logits must be a torch.Tensor, got {type(logits)}")
+    if logits.dtype != torch.float32:
+        raise TypeError(f"{who}: logits is {logits.dtype}; the sampler reads fp32 logits only (bf16 and fp16 are not "
+                        f"supported)")
+    if logits.dim() != 2:
+        raise ValueError(f"{who}: logits is [B, V], got {tuple(logits.shape)}")
+    B, V = logits.shape
+    if B < 1 or not 1 <= V <= SAMPLE_MAX_V:
+        raise ValueError(f"{who}: logits is [B, V] with B >= 1 and 1 <= V <= {SAMPLE_MAX_V}, got {tuple(logits.shape)}")
+    if V > 1 and logits.stride(1) != 1:
+        raise ValueError(f"{who}: the vocabulary axis of logits must be dense (stride 1), got {logits.stride(1)}")
+    row_stride = logits.stride(0) if B > 1 else V
+    if row_stride < V:
+        raise ValueError(f"{who}: the rows of logits overlap (row stride {row_stride} < V = {V})")
+    for n, t, shape in (("seen", seen, (B, V)), ("finished", finished, (B,))):
+        if t is None:
+            continue
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{who}: {n} must be a torch.Tensor, got {type(t)}")
+        if t.dtype != torch.uint8:
+            raise TypeError(f"{who}: {n} is {t.dtype}; the row state is uint8")
+        if tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f"{who}: {n} is a contiguous {list(shape)}, got {tuple(t.shape)}")
+    if stream_ids is not None:
+        if not isinstance(stream_ids, torch.Tensor):
+            ids = np.asarray(stream_ids)
+            if ids.dtype.kind not in "iu" or ids.shape != (B,) or (ids.astype(np.int64) < 0).any() \
+                    or (ids.astype(np.int64) >= (1 << 32)).any():
+                raise ValueError(f"{who}: stream_ids is [B] = ({B},) integers in [0, 2^32), got {stream_ids!r}")
+        elif stream_ids.dtype != torch.int64 or tuple(stream_ids.shape) != (B,) or not stream_ids.is_contiguous():
+            raise ValueError(f"{who}: stream_ids is a contiguous int64 [B] = ({B},), got {stream_ids.dtype} "
+                             f"{tuple(stream_ids.shape)}")
+    if out is not None:
+        if not isinstance(out, torch.Tensor):
+            raise TypeError(f"{who}: out must be a torch.Tensor, got {type(out)}")
+        if out.dtype != torch.int64:
+            raise TypeError(f"{who}: out is {out.dtype}; tokens are int64")
+        if tuple(out.shape) != (B,) or (B > 1 and out.stride(0) < 1):
+            raise ValueError(f"{who}: out is [B] = ({B},) with a positive stride (a column of the generated buffer), got "
+                             f"{tuple(out.shape)} stride {out.stride()}")
+    if penalty_rule not in PENALTY_RULES:
+        raise ValueError(f"{who}: penalty_rule must be 'divide' or 'signed', got {penalty_rule!r}")
+    top_k = _sample_int(who, "top_k", top_k, 0, SAMPLE_MAX_K + 1)
+    vals = {}
+    for n, v in (("penalty", penalty), ("temperature", temperature), ("top_p", top_p)):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise TypeError(f"{who}: {n} must be a number, got {type(v)}")
+        with np.errstate(over="ignore"):
+            vals[n] = float(np.float32(v))
+    if not (np.isfinite(vals["temperature"]) and vals["temperature"] >= 0.0):
+        raise ValueError(f"{who}: temperature={temperature} must be finite and not negative (0 is greedy)")
+    if not (np.isfinite(vals["penalty"]) and vals["penalty"] > 0.0):
+        raise ValueError(f"{who}: penalty={penalty} must be finite and positive")
+    if not vals["top_p"] >= 0.0:
+        raise ValueError(f"{who}: top_p={top_p} must be a number >= 0")
+    if top_k == 0 and vals["top_p"] < 1.0:
+        raise ValueError(f"{who}: top_p={top_p} < 1 needs 1 <= top_k <= {SAMPLE_MAX_K}: a nucleus over the whole "
+                         f"vocabulary (top_k=0) is not built, the candidate set is capped at {SAMPLE_MAX_K}")
+    seed = _sample_int(who, "seed", seed, 0, 1 << 64)
+    step = _sample_int(who, "step", step, 0, 1 << 64)
+    eos = -1 if eos_id is None else _sample_int(who, "eos_id", eos_id, 0, 1 << 62)
+    pad = _sample_int(who, "pad_id", pad_id, -(1 << 62), 1 << 62)
+    return B, V, row_stride, (vals["penalty"], PENALTY_RULES[penalty_rule], vals["temperature"], top_k, vals["top_p"],
+                              seed, step, eos, pad)
+
+
+def sample_next(logits, *, seen=None, finished=None, stream_ids=None, penalty: float = 1.0,
+                penalty_rule: str = "divide", temperature: float = 1.0, top_k: int = 50, top_p: float = 0.9,
+                seed: int = 0, step: int = 0, eos_id: Optional[int] = None, pad_id: int = 0, out=None,
+                return_candidates: bool = False):
+    """The next token of every row of fp32 ``logits`` [B, V] (rows may be a strided view: the output head's result is
+    read as it is) in one launch -- the rule: ``include/aura_hip.h``, "Next token".  Repetition penalty over the tokens
+    marked in ``seen`` (uint8 [B, V]; ``penalty_rule`` ``'divide'``: the reference ``generate``'s line, ``'signed'``: its
+    ``apply_repetition_penalty``), ``temperature`` (0: greedy argmax, nothing drawn), exactly ``min(top_k, V)``
+    candidates by (logit descending, id ascending), the nucleus ``top_p`` over them, and a Gumbel-max draw whose random
+    numbers are a function of ``(seed, step, stream, token id)`` alone; ``stream_ids`` (int64 [B] or ints) default to the
+    row numbers, so a row alone with its stream draws what it draws in the batch.  ``top_k=0`` samples the whole
+    vocabulary and needs ``top_p >= 1``.  Row state on the device: a row with ``finished`` (uint8 [B]) set writes
+    ``pad_id`` and nothing else; otherwise the token's byte of ``seen`` is set and, with ``eos_id``, ``finished`` where
+    the token is ``eos_id``.  A row without a finite logit returns -1.
+
+    Returns int64 [B], or writes into ``out`` (int64 [B], any positive stride: a column of a [B, T] buffer) and returns
+    it.  ``return_candidates``: also a dict of the kernel's own decisions -- ``ids`` int32, ``z``, ``cum``, ``d`` fp32
+    [B, k'] and ``n_kept`` int32 [B] (``top_k >= 1``), ``d`` [B, V] (``top_k=0``), empty for greedy; rows that entered
+    finished keep the fill (-1 / -inf / 0).  No host sync."""
+    B, V, row_stride, scalars = _sample_args(logits, seen, finished, stream_ids, penalty, penalty_rule, temperature,
+                                             top_k, top_p, seed, step, eos_id, pad_id, out)
+    who = "sample_next"
+    for n, t in (("logits", logits), ("seen", seen), ("finished", finished), ("out", out),
+                 ("stream_ids", stream_ids if isinstance(stream_ids, torch.Tensor) else None)):
+        if t is not None and not t.is_cuda:
+            raise AuraDeviceError(f"{who}: {n} is on {t.device}: the sampler runs only as a HIP kernel on an AMD GPU (no "
+                                  f"CPU/PyTorch fallback).")
+        if t is not None and t.device != logits.device:
+            raise ValueError(f"{who}: tensors are on different devices")
+    dev = logits.device
+    if stream_ids is not None and not isinstance(stream_ids, torch.Tensor):
+        stream_ids = torch.as_tensor(np.asarray(stream_ids, dtype=np.int64), device=dev)
+    tokens = torch.empty(B, dtype=torch.int64, device=dev) if out is None else out
+    temperature32, k_top = scalars[2], scalars[3]
+    cand = {}
+    if return_candidates and temperature32 != 0.0:
+        ninf = float("-inf")
+        if k_top == 0:
+            cand = dict(d=torch.full((B, V), ninf, dtype=torch.float32, device=dev))
+        else:
+            k = min(k_top, V)
+            cand = dict(ids=torch.full((B, k), -1, dtype=torch.int32, device=dev),
+                        z=torch.full((B, k), ninf, dtype=torch.float32, device=dev),
+                        cum=torch.full((B, k), ninf, dtype=torch.float32, device=dev),
+                        d=torch.full((B, k), ninf, dtype=torch.float32, device=dev),
+                        n_kept=torch.zeros(B, dtype=torch.int32, device=dev))
+    L = lib()
+    nbytes = L.aura_sample_workspace_bytes(B, V, k_top, temperature32)
+    if nbytes < 0:
+        raise ValueError(f"{who}: unsupported size")
+    base = _workspace(dev, nbytes) if nbytes else None
+    check(L.aura_sample_next(_p(logits), row_stride, B, V, _p(seen), _p(finished), _p(stream_ids), *scalars,
+                             _p(tokens), tokens.stride(0) if B > 1 else 1, _p(cand.get("ids")), _p(cand.get("z")),
+                             _p(cand.get("cum")), _p(cand.get("d")), _p(cand.get("n_kept")), base, nbytes, _stream()),
+          "aura_sample_next")
+    return (tokens, cand) if return_candidates else tokens
+
+
+# ---------------------------------------------------------------------------------------
 # surrogate-gradient training path + prosody-modulated GIF (fp32 and bf16)
 # ---------------------------------------------------------------------------------------
 

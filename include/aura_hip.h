@@ -1115,6 +1115,74 @@ int aura_attn_decode_step(const float* q, const float* k_new, const float* v_new
                           int64_t dh, int64_t cap, int64_t n_chunks, int advance, float* workspace,
                           int64_t workspace_bytes, float* ctx, float* scale_or_null, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Next token
+ * ------------------------------------------------------------------------------------- */
+
+/* The next token of every row of a batch from its logit row: repetition penalty, temperature, top-k, nucleus (top-p)
+ * and a seeded draw, with the row's generation state kept on the device, csrc/aura_sample.hip.  What users know as the
+ * tail of the reference's generate (src/core/language_zone/snn_rag_transformer.py:207-242), restated so that every
+ * decision can be checked exactly.  All fp32, every operation rounded on its own, `/` a correctly rounded division,
+ * expf / logf the accurate device functions.
+ *
+ * Per row b: logits z[0 .. V) (fp32, row b at logits + b * row_stride), seen[b][0 .. V) bytes or NULL, the row's stream
+ * number (stream_ids[b], or b with stream_ids NULL).
+ *   1. clean        NaN -> -inf, +inf -> FLT_MAX.  (-0 counts as +0 wherever values are ranked or returned.)
+ *   2. penalty      for tokens with seen != 0, when penalty != 1:
+ *                     AURA_PENALTY_DIVIDE  z / penalty for either sign (the reference generate's own line)
+ *                     AURA_PENALTY_SIGNED  z < 0 ? z * penalty : z / penalty (its sampling_utils.apply_repetition_penalty)
+ *                   A result of +inf is FLT_MAX again (here and in step 4); -inf stays.
+ *   3. greedy       temperature == 0: the token is the argmax of the penalised z, equal z -> the lower id; no random
+ *                   number is drawn, top_k and top_p are ignored, no inspection output is written.  Stop.
+ *   4. temperature  z / temperature.
+ *   5. top-k        1 <= top_k <= AURA_SAMPLE_MAX_K, k' = min(top_k, V): the candidates are exactly the first k' tokens
+ *                   by (z descending, id ascending), in that order; rank 0 is the largest.  The reference keeps every
+ *                   value that is not below the k-th (so all of its ties, in an order it leaves open); this rule keeps
+ *                   exactly k', which differs from the reference only among exact ties at the threshold and keeps the
+ *                   candidate set bounded.
+ *   6. nucleus      e_j = expf(z_j - z_0); c_j the inclusive prefix sum of e in rank order, S = c_{k'-1}; rank j is kept
+ *                   iff j == 0 or c_{j-1} <= fl(top_p * S); top_p >= 1 keeps every rank.  The sum: the ranks are cut
+ *                   into blocks of 16; within a block c' runs from 0 in rank order, c' = fl(c' + e_j); the block bases
+ *                   run from 0 in block order, base = fl(base + c' of the block's last rank); c_j = fl(base + c'_j).
+ *                   A function of the ranks alone (not of B, the other rows or the launch), and never decreasing.
+ *   7. draw         for a kept candidate with token id i: x = word 0 of Philox4x32-10, counter (i, stream,
+ *                   step & 0xffffffff, step >> 32), key (seed & 0xffffffff, seed >> 32), the constants of "Replay";
+ *                   u = ((x >> 9) + 0.5) * 2^-23;  d = fl(z + (-logf(-logf(u)))).  The token is the argmax of d over the
+ *                   kept candidates whose z > -inf, equal d -> the lower id.  (Gumbel-max: token i with probability
+ *                   softmax(z over the kept set)_i, what softmax followed by multinomial draws, with no sum and no sort
+ *                   in the draw itself.)
+ *   8. full vocab   top_k == 0 is allowed only with top_p >= 1: step 7 over all V tokens whose z > -inf.  top_k == 0 with
+ *                   top_p < 1 is refused: a nucleus over an unbounded set needs a sorted sum over the whole vocabulary.
+ *   9. empty rows   a row with no token whose z > -inf returns token -1 (n_kept = 0).
+ * Row state: a row with finished[b] != 0 on entry writes pad_id, marks nothing, draws nothing and leaves its inspection
+ * outputs alone.  Otherwise tokens[b * token_stride] = the token; with seen and a token >= 0, seen[b][token] = 1; with
+ * finished, eos_id >= 0 and token == eos_id, finished[b] = 1.  One workgroup owns a row; its first lane writes the state
+ * with plain stores after every lane has read the mask.  No global atomics.
+ * Consequences: a row's token depends only on its own logits, mask, stream, seed and step; it is the same alone or in
+ * any batch, with any row stride, and over repeated calls.
+ *
+ * Inspection outputs, each may be NULL.  With top_k >= 1: cand_ids int32 [B][k'], cand_z (the z of step 4), cand_cum
+ * (c), cand_d (d; -inf for a rank that is not kept) fp32 [B][k'], n_kept int32 [B].  With top_k == 0: cand_d [B][V]
+ * (-inf where z is -inf), the others are not written.
+ * workspace: aura_sample_workspace_bytes(B, V, top_k, temperature) bytes (0 for greedy and for top_k == 0), 256-byte
+ * aligned, owned by the caller, written before it is read.
+ * AURA_E_INVAL: B < 1 or > 2^31 - 1, V < 1 or > AURA_SAMPLE_MAX_V, top_k outside [0, AURA_SAMPLE_MAX_K], top_k == 0
+ *   with top_p < 1, temperature < 0 or not finite, penalty <= 0 or not finite, top_p < 0 or NaN, an unknown rule, null
+ *   logits or tokens, row_stride < V, token_stride < 1, a workspace missing or too small.  AURA_E_ALIGN: tokens or
+ *   stream_ids not 8-byte aligned, logits or an fp32 / int32 output not 4-byte aligned, the workspace not 256-byte
+ *   aligned.  One launch on `stream`, one workgroup of 1024 lanes per row. */
+#define AURA_PENALTY_DIVIDE 0
+#define AURA_PENALTY_SIGNED 1
+#define AURA_SAMPLE_MAX_K 1024
+#define AURA_SAMPLE_MAX_V 131072
+int64_t aura_sample_workspace_bytes(int64_t B, int64_t V, int64_t top_k, float temperature);
+int aura_sample_next(const float* logits, int64_t row_stride, int64_t B, int64_t V, uint8_t* seen_or_null,
+                     uint8_t* finished_or_null, const int64_t* stream_ids_or_null, float penalty, int penalty_rule,
+                     float temperature, int64_t top_k, float top_p, uint64_t seed, uint64_t step, int64_t eos_id,
+                     int64_t pad_id, int64_t* tokens, int64_t token_stride, int32_t* cand_ids, float* cand_z,
+                     float* cand_cum, float* cand_d, int32_t* n_kept, void* workspace, int64_t workspace_bytes,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif
