@@ -131,6 +131,7 @@ SIGNATURES = {
     "aura_sample_workspace_bytes": (I64, [I64, I64, I64, F]),
     "aura_sample_next": (I, [P, I64, I64, I64, P, P, P, F, I, F, I64, F, U64, U64, I64, I64, P, I64, P, P, P, P, P, P, I64,
                              P]),
+    "aura_row_linear": (I, [P, I64, I64, P, P, P, I64, P, P, P, I64, P, P, P, I64, P, P, F, P, I, P, I, P]),
     "aura_profile_begin": (I, [I]),
     "aura_debug_cs_flags": (I, [I]),
     "aura_debug_clock_mhz": (I, [P, I, P]),

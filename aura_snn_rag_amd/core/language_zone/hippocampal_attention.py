@@ -12,6 +12,8 @@ New on this module: ``new_cache`` / ``prefill`` / ``step``.  The causal forward 
 whole sequence computes, without recomputing the context: a step is the three projections of the new row (library
 calls), ``ops.attn_decode_step`` (``csrc/aura_decode.hip``, the rule: ``include/aura_hip.h``, "Decode attention") and
 ``o_proj``.  The step is fp32, runs under ``no_grad`` and has no CPU fallback: CPU tensors raise ``AuraDeviceError``.
+``step(fused=True)`` replaces the library calls by ``ops.row_linear`` (``csrc/aura_rowlin.hip``, "Row linear"): the three
+projections in one launch, with the layer's LayerNorm in front, and ``o_proj`` with the residual behind.
 """
 from __future__ import annotations
 
@@ -154,11 +156,17 @@ class HippocampalProsodyAttention(nn.Module):
 
     @torch.no_grad()
     def step(self, hidden_states: torch.Tensor, prosody: Optional[torch.Tensor] = None, use_memory: bool = True,
-             cache: Optional[AttentionCache] = None, advance: bool = True) -> torch.Tensor:
+             cache: Optional[AttentionCache] = None, advance: bool = True, *, fused: bool = False,
+             residual: Optional[torch.Tensor] = None, norm: Optional[nn.LayerNorm] = None) -> torch.Tensor:
         """One new token: hidden [B, D] or [B, 1, D] (the normed row the layer feeds ``forward``), prosody [B, 4] or
         [B, 1, 4] or ``None``.  Appends the token's key and value at each row's length, attends over the cache and
         returns the attention output [B, D]; the lengths advance on the device unless ``advance=False`` (caches that
-        share one lengths tensor: only the last of them advances it).  Raises when the cache may be full."""
+        share one lengths tensor: only the last of them advances it).  Raises when the cache may be full.
+
+        ``fused=True`` (B <= 32) makes the step four launches: one ``ops.row_linear`` for the three projections, the
+        two of ``ops.attn_decode_step`` and one ``ops.row_linear`` for ``o_proj``.  With ``norm`` (the layer's
+        ``attention_norm``) hidden is the un-normalised row and the LayerNorm runs inside the first launch; with
+        ``residual`` [B, D] the last launch adds it to the output.  Both need ``fused=True``."""
         who = "HippocampalProsodyAttention.step"
         if hidden_states.dim() == 3 and hidden_states.shape[1] == 1:
             hidden_states = hidden_states[:, 0]
@@ -180,6 +188,32 @@ class HippocampalProsodyAttention(nn.Module):
                                f"cache is not part of this module")
         x = hidden_states.contiguous()
         memory = self._memory_on(use_memory)
+        if not fused and (residual is not None or norm is not None):
+            raise ValueError(f"{who}: residual and norm are the fused step's arguments (fused=True)")
+        if fused:
+            if B > ops.ROW_LINEAR_MAX_ROWS:
+                raise ValueError(f"{who}: the fused step takes at most {ops.ROW_LINEAR_MAX_ROWS} rows, got B={B}; "
+                                 f"use fused=False")
+            if norm is not None and not isinstance(norm, nn.LayerNorm):
+                raise TypeError(f"{who}: norm must be the nn.LayerNorm in front of the attention, got {type(norm)}")
+            if norm is not None and (norm.weight is None or norm.bias is None):
+                raise ValueError(f"{who}: the fused prologue needs a LayerNorm with weight and bias")
+            weights = (self.q_proj.weight, self.k_proj.weight, self.v_proj.weight)
+            biases = (self.q_proj.bias, self.k_proj.bias, self.v_proj.bias)
+            if norm is not None:
+                (q, k, v), x = ops.row_linear(x, weights, biases, norm=(norm.weight, norm.bias), eps=norm.eps,
+                                              return_normed=True)
+            else:
+                q, k, v = ops.row_linear(x, weights, biases)
+            ctx = ops.attn_decode_step(q, k, v, x if memory else None, prosody,
+                                       self.prosody_gate.weight, self.prosody_gate.bias,
+                                       self.memory_gate.weight if memory else None,
+                                       self.memory_gate.bias if memory else None,
+                                       cache.lengths, cache.k, cache.v, cache.workspace, n_chunks=cache.n_chunks,
+                                       advance=bool(advance))
+            cache.max_length += 1
+            return ops.row_linear(ctx, self.o_proj.weight, self.o_proj.bias,
+                                  residual=None if residual is None else residual.contiguous())
         ctx = ops.attn_decode_step(self.q_proj(x), self.k_proj(x), self.v_proj(x), x if memory else None, prosody,
                                    self.prosody_gate.weight, self.prosody_gate.bias,
                                    self.memory_gate.weight if memory else None,

@@ -148,29 +148,35 @@ class HippocampalTransformer(nn.Module):
 
     @torch.no_grad()
     def step(self, tokens: torch.Tensor, prosody: Optional[torch.Tensor] = None, state: Optional[DecodeState] = None,
-             use_memory: bool = True) -> torch.Tensor:
+             use_memory: bool = True, *, fused: bool = False) -> torch.Tensor:
         """One new token per row: tokens [B] (or [B, 1]) at position ``state.position`` -> logits [B, V].  Every
-        layer's ``step`` runs on its cache; the last one advances the shared lengths.  No host sync."""
+        layer's ``step`` runs on its cache; the last one advances the shared lengths.  ``fused=True`` (B <= 32) takes
+        every layer's fused step: six launches a layer instead of fourteen; the front end and the head stay as they
+        are.  No host sync."""
         who = "HippocampalTransformer.step"
         if tokens.dim() == 1:
             tokens = tokens[:, None]
         if tokens.dim() != 2 or tokens.shape[1] != 1:
             raise ValueError(f"{who}: tokens is [B] or [B, 1], got {tuple(tokens.shape)}")
         self._check_state(who, state, tokens.shape[0])
+        if fused and tokens.shape[0] > ops.ROW_LINEAR_MAX_ROWS:
+            raise ValueError(f"{who}: the fused step takes at most {ops.ROW_LINEAR_MAX_ROWS} rows, got "
+                             f"B={tokens.shape[0]}; use fused=False")
         hidden_states, _ = embed_tokens(tokens, self.semantic_encoder, self.pos_encoder, self.layer_norm,
                                         start=state.position, dense=False)
         hidden_states = self.dropout(hidden_states)[:, 0]
         last = len(self.layers) - 1
         for i, (layer, cache) in enumerate(zip(self.layers, state.caches)):
-            hidden_states = layer.step(hidden_states, prosody=prosody, use_memory=use_memory, cache=cache,
-                                       advance=i == last)
+            hidden_states = layer.step(hidden_states.contiguous() if fused else hidden_states, prosody=prosody,
+                                       use_memory=use_memory, cache=cache, advance=i == last, fused=fused)
         state.position += 1
         return self.output_head(hidden_states)
 
     def generate(self, input_ids: torch.Tensor, max_new_tokens: int = 50, temperature: float = 0.8, top_k: int = 50,
                  top_p: float = 0.9, use_memory: bool = True, repetition_penalty: float = 1.2, *,
                  repetition_rule: str = "divide", seed: Optional[int] = None, eos_token_id=_UNSET,
-                 pad_token_id: Optional[int] = None, sync_every: int = 8, stream_ids=None) -> torch.Tensor:
+                 pad_token_id: Optional[int] = None, sync_every: int = 8, stream_ids=None,
+                 fused_step: bool = False) -> torch.Tensor:
         """Generates up to ``max_new_tokens`` tokens after the prompts ``input_ids`` [B, S] (equal lengths, as in the
         reference) -> [B, S + n].  Runs under ``eval()`` and ``no_grad``: one ``prefill``, then per token one ``step``
         and one ``ops.sample_next`` that writes the token into its column of the preallocated result.
@@ -182,6 +188,7 @@ class HippocampalTransformer(nn.Module):
         config's; with one, a row that draws it is finished: its later tokens are ``pad_token_id`` (default: the EOS
         id) and its cache rows are retired (length -1).  The host looks at the finished flags only every ``sync_every``
         steps, and once at the end to trim the result to the step at which the last row finished.
+        ``fused_step=True`` (B <= 32) decodes with the layers' fused step (``step(fused=True)``).
 
         Differences from the reference's loop, on purpose: the context is never truncated to ``max_seq_len`` and
         re-based, positions simply continue (``S + max_new_tokens`` must fit ``ops.DECODE_MAX_CAP``); generation
@@ -203,6 +210,8 @@ class HippocampalTransformer(nn.Module):
         pad = pad_token_id if pad_token_id is not None else (eos if eos is not None else 0)
         if seed is None:
             seed = int(torch.randint(0, 1 << 62, (1,)).item())
+        if fused_step and B > ops.ROW_LINEAR_MAX_ROWS:
+            raise ValueError(f"{who}: fused_step takes at most {ops.ROW_LINEAR_MAX_ROWS} rows, got B={B}")
         dev = input_ids.device
         if stream_ids is not None and not isinstance(stream_ids, torch.Tensor):
             stream_ids = torch.as_tensor(list(stream_ids), dtype=torch.int64).to(dev)
@@ -227,7 +236,7 @@ class HippocampalTransformer(nn.Module):
                     state.lengths.masked_fill_(state.finished.bool(), -1)
                     if n % sync_every == 0 and bool(state.finished.all()):
                         break
-                logits = self.step(column, state=state, use_memory=use_memory)
+                logits = self.step(column, state=state, use_memory=use_memory, fused=bool(fused_step))
             if eos is not None:
                 # the step at which the last row finished: a column is padding when every row had finished before it
                 new = generated[:, S:S + n]

@@ -850,6 +850,163 @@ def attn_decode_step(q, k_new, v_new, x, prosody, Wp, bp, wm, bm, lengths, k_cac
 
 
 # ---------------------------------------------------------------------------------------
+# row linear (the rule: include/aura_hip.h, "Row linear")
+# ---------------------------------------------------------------------------------------
+
+ROW_LINEAR_MAX_ROWS = 32
+ROW_LINEAR_MAX_K = 8192
+ROW_LINEAR_ACTIVATIONS = (None, "gelu")
+# the weight loads' cache policy: same bits either way; tools/fused_step_bench.py measures both
+ROW_LINEAR_NONTEMPORAL = False
+
+
+_RL_W, _RL_B, _RL_O = (tuple(f"{n}[{j}]" for j in range(3)) for n in ("weights", "biases", "out"))
+_RL_PAD = ((), (None,), (None, None))
+
+
+def _rl_f32(name: str, t) -> None:
+    """One tensor of ``row_linear``: fp32 and contiguous.  (A decoding step makes four of these calls per layer and
+    token on the host's clock, so the checks walk every tensor once and form no strings unless they raise.)"""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"row_linear: {name} must be a torch.Tensor, got {type(t)}")
+    if t.dtype != torch.float32:
+        raise TypeError(f"row_linear: {name} is {t.dtype}; the row linear kernel runs in fp32 only (fp32 is the limit: "
+                        f"bf16 and fp16 are not supported)")
+    if not t.is_contiguous():
+        raise ValueError(f"row_linear: {name} must be contiguous")
+
+
+def _row_linear_args(x, weights, biases, norm, eps, activation, residual, return_normed, out):
+    """Type, shape and limit checks of ``row_linear``: ``(R, K, weights, biases, outs, gamma, beta, single)`` with
+    the three tuples padded to three entries by ``None``.  Touches no device."""
+    who = "row_linear"
+    single = isinstance(weights, torch.Tensor)
+    if single:
+        weights = (weights,)
+        biases = (biases,)
+        out = None if out is None else (out,)
+    if not isinstance(weights, (tuple, list)) or not 1 <= len(weights) <= 3:
+        raise ValueError(f"{who}: weights is one tensor or a tuple of one to three, got "
+                         f"{len(weights) if isinstance(weights, (tuple, list)) else type(weights)}")
+    n = len(weights)
+    if biases is None:
+        biases = (None,) * n
+    if isinstance(biases, torch.Tensor) or not isinstance(biases, (tuple, list)) or len(biases) != n:
+        raise ValueError(f"{who}: biases come as the weights do: one entry (a tensor or None) per weight")
+    if out is not None and (isinstance(out, torch.Tensor) or not isinstance(out, (tuple, list)) or len(out) != n):
+        raise ValueError(f"{who}: out comes as the weights do: one tensor per weight")
+    outs = (None,) * n if out is None else tuple(out)
+    if x is None:
+        raise ValueError(f"{who}: x is required")
+    _rl_f32("x", x)
+    if x.dim() != 2:
+        raise ValueError(f"{who}: x is [R, K], got {tuple(x.shape)}")
+    R, K = x.shape
+    if not 1 <= R <= ROW_LINEAR_MAX_ROWS:
+        raise ValueError(f"{who}: R={R} rows must be in [1, {ROW_LINEAR_MAX_ROWS}] (more rows are a library GEMM's work)")
+    if K % 4 != 0 or not 4 <= K <= ROW_LINEAR_MAX_K:
+        raise ValueError(f"{who}: K={K} must be a multiple of 4 in [4, {ROW_LINEAR_MAX_K}]")
+    if activation is not None and activation != "gelu":
+        raise ValueError(f"{who}: activation={activation!r}: None or 'gelu' (the exact, erf GELU)")
+    total = 0
+    for j in range(n):
+        w, b, o = weights[j], biases[j], outs[j]
+        if w is None:
+            raise ValueError(f"{who}: {_RL_W[j]} is required")
+        _rl_f32(_RL_W[j], w)
+        if w.dim() != 2 or w.shape[1] != K or w.shape[0] < 1:
+            raise ValueError(f"{who}: {_RL_W[j]} is [N, K] with K={K} and N >= 1 (nn.Linear's layout), got "
+                             f"{tuple(w.shape)}")
+        N = w.shape[0]
+        total += N
+        if b is not None:
+            _rl_f32(_RL_B[j], b)
+            if b.dim() != 1 or b.shape[0] != N:
+                raise ValueError(f"{who}: {_RL_B[j]} is [N] = ({N},), got {tuple(b.shape)}")
+        if o is not None:
+            _rl_f32(_RL_O[j], o)
+            if o.dim() != 2 or o.shape[0] != R or o.shape[1] != N:
+                raise ValueError(f"{who}: {_RL_O[j]} is [R, N] = ({R}, {N}), got {tuple(o.shape)}")
+    if total > 0x7fffffff:
+        raise ValueError(f"{who}: the weights hold more than 2^31 - 1 output columns")
+    gamma = beta = None
+    if norm is not None:
+        if not isinstance(norm, (tuple, list)) or len(norm) != 2 or norm[0] is None or norm[1] is None:
+            raise ValueError(f"{who}: norm is (gamma, beta), the LayerNorm's weight and bias")
+        gamma, beta = norm
+        _rl_f32("gamma", gamma)
+        _rl_f32("beta", beta)
+        if K > DECODE_MAX_D:
+            raise ValueError(f"{who}: the LayerNorm prologue holds a row in registers: K={K} exceeds {DECODE_MAX_D}")
+        if gamma.dim() != 1 or beta.dim() != 1 or gamma.shape[0] != K or beta.shape[0] != K:
+            raise ValueError(f"{who}: gamma and beta are [K] = ({K},); got {tuple(gamma.shape)}, {tuple(beta.shape)}")
+        if isinstance(eps, bool) or not isinstance(eps, (int, float)) or not eps >= 0.0:
+            raise ValueError(f"{who}: eps={eps!r} must be a number that is not negative")
+    elif return_normed:
+        raise ValueError(f"{who}: return_normed needs norm=(gamma, beta)")
+    if residual is not None:
+        if n != 1:
+            raise ValueError(f"{who}: a residual goes with a single weight matrix, not with {n}")
+        _rl_f32("residual", residual)
+        if residual.dim() != 2 or residual.shape[0] != R or residual.shape[1] != total:
+            raise ValueError(f"{who}: residual is [R, N] = ({R}, {total}), got {tuple(residual.shape)}")
+    pad = _RL_PAD[3 - n]
+    return R, K, tuple(weights) + pad, tuple(biases) + pad, outs + pad, gamma, beta, single
+
+
+def _rl_device(name: str, t, dev, wide: bool):
+    """One tensor of ``row_linear`` on the one HIP device; the ``wide`` ones move as float4."""
+    if not t.is_cuda:
+        raise AuraDeviceError(f"row_linear: {name} is on {t.device}: aura_snn_rag_amd runs the hot path only as HIP "
+                              f"kernels on an AMD GPU (no CPU/PyTorch fallback).")
+    if dev is not None and t.device != dev:
+        raise ValueError("row_linear: tensors are on different devices")
+    if wide and t.data_ptr() % 16:
+        raise ValueError(f"row_linear: {name} is not 16-byte aligned (a view into the middle of a buffer?)")
+    return t.device
+
+
+def row_linear(x, weights, biases=None, *, norm=None, eps: float = 1e-5, activation: Optional[str] = None,
+               residual=None, return_normed: bool = False, out=None):
+    """A linear layer for a handful of rows in one launch (the rule: ``include/aura_hip.h``, "Row linear"): ``x``
+    [R, K] with R <= 32, ``weights`` one [N, K] tensor (``nn.Linear``'s layout) or a tuple of up to three that share
+    ``x``, ``biases`` alike (entries may be ``None``).  ``norm=(gamma, beta)`` applies LayerNorm with ``eps`` to the rows
+    first (K <= 2048); ``activation='gelu'`` is the exact GELU; ``residual`` [R, N] is added last (single weight only).
+    Returns ``y`` [R, N], or a tuple of them for a tuple of weights; with ``return_normed`` ``(y, xh)``, ``xh`` [R, K] the
+    normalised rows.  ``out`` (a tensor, or a tuple as the weights) receives the result.  fp32 only.  A row's bits are
+    the same alone or in any batch, and the tuple form gives the bits of single calls.  No host sync."""
+    R, K, W, b, outs, gamma, beta, single = _row_linear_args(x, weights, biases, norm, eps, activation, residual,
+                                                              return_normed, out)
+    dev = _rl_device("x", x, None, True)
+    if gamma is not None:
+        _rl_device("gamma", gamma, dev, True)
+        _rl_device("beta", beta, dev, True)
+    if residual is not None:
+        _rl_device("residual", residual, dev, False)
+    ys, N = [None, None, None], [0, 0, 0]
+    for j in range(3):
+        w = W[j]
+        if w is None:
+            break
+        _rl_device(_RL_W[j], w, dev, True)
+        if b[j] is not None:
+            _rl_device(_RL_B[j], b[j], dev, False)
+        N[j] = w.shape[0]
+        if outs[j] is not None:
+            _rl_device(_RL_O[j], outs[j], dev, False)
+            ys[j] = outs[j]
+        else:
+            ys[j] = torch.empty((R, N[j]), dtype=torch.float32, device=dev)
+    xh = torch.empty((R, K), dtype=torch.float32, device=dev) if return_normed else None
+    check(lib().aura_row_linear(x.data_ptr(), R, K, _p(W[0]), _p(b[0]), _p(ys[0]), N[0], _p(W[1]), _p(b[1]), _p(ys[1]),
+                                N[1], _p(W[2]), _p(b[2]), _p(ys[2]), N[2], _p(gamma), _p(beta), float(eps), _p(xh),
+                                int(activation == "gelu"), _p(residual), int(ROW_LINEAR_NONTEMPORAL), _stream()),
+          "aura_row_linear")
+    y = ys[0] if single else tuple(t for t in ys if t is not None)
+    return (y, xh) if return_normed else y
+
+
+# ---------------------------------------------------------------------------------------
 # next token (the rule: include/aura_hip.h, "Next token")
 # ---------------------------------------------------------------------------------------
 

@@ -1183,6 +1183,55 @@ int aura_sample_next(const float* logits, int64_t row_stride, int64_t B, int64_t
                      float* cand_cum, float* cand_d, int32_t* n_kept, void* workspace, int64_t workspace_bytes,
                      void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Row linear
+ * ------------------------------------------------------------------------------------- */
+
+/* A linear layer for a handful of rows, with LayerNorm in front and bias, exact GELU and a residual behind, in one
+ * launch, csrc/aura_rowlin.hip: what a decoding step does between its attention launches (nn.LayerNorm, nn.Linear,
+ * nn.GELU and an add, each of which is a launch of its own in torch).  All fp32, fl() = round to nearest even; products
+ * that feed a sum are fused (fmaf) where the rule says so and rounded on their own elsewhere; `/` and sqrtf are correctly
+ * rounded, erff is the accurate device function.
+ *
+ * x [R][K], 1 <= R <= 32, K % 4 == 0, 4 <= K <= 8192.  One to three matrices W_j [N_j][K] (nn.Linear's layout), N_j >= 1,
+ * each with a bias b_j [N_j] or NULL and an output y_j [R][N_j].  The matrices share x and the prologue; nothing
+ * concatenated exists in memory.
+ *   prologue  with gamma, beta [K] (K <= 2048), per row r:
+ *                 sum_K(v): lane l of a wave owns the k with (k / 4) mod 64 == l and adds v_k in ascending k from 0,
+ *                           s = fl(s + v_k); the 64 lane sums are added by the xor butterfly 32, 16, 8, 4, 2, 1.
+ *                 mu   = fl(sum_K(x[r]) / float(K))
+ *                 var  = fl(sum_K(fl(d d)) / float(K)),  d = fl(x[r][k] - mu)                     (two passes)
+ *                 rstd = fl(1 / sqrtf(fl(var + eps)))          (a zero-variance row: rstd = fl(1 / sqrtf(eps)), xh = beta)
+ *                 xh[r][k] = fl(fl(fl(d rstd) gamma[k]) + beta[k])
+ *             Without gamma and beta, xh = x.  With xh_or_null the normalised rows are also written there, [R][K].
+ *   dot       lane l of one wave chains t = fmaf(xh[r][k], W_j[n][k], t) over the k with (k / 4) mod 64 == l in
+ *             ascending k, from t = 0; the 64 lane values are added by the xor butterfly 32, 16, 8, 4, 2, 1.
+ *   epilogue  t = fl(dot + b_j[n]) (with a bias);  with gelu: t = fl(fl(0.5 t) fl(1 + erff(fl(t c)))), c = fl(1 / sqrt 2);
+ *             with res [R][N_0] (single-matrix form only): t = fl(t + res[r][n]).  y_j[r][n] = t.
+ * The order in which an element is summed is a function of K alone: not of R, N_j, the other rows, the other matrices
+ * or the launch geometry.  So a row's bits are the same alone or in any batch (a NaN or inf row leaves the others
+ * alone), the three-matrix form gives the bits of three single calls, and two calls give the same bits.
+ * Every weight element is read from memory once per launch and serves all R rows; the x tile lives in LDS.  Workgroups
+ * are independent: no atomics, no grid-wide barrier, no flag, no persistent loop; one launch is one pass.
+ * `nontemporal` != 0 streams the weights with non-temporal loads (same bits; a cache policy only).
+ * Against fp64 on the same fp32 inputs (tests/row_linear_rule.py derives it): with dxh the prologue's bound of
+ * "Theta-gamma" (n, y) for a row sum of K,
+ *     |dot - dot64| <= (K + 8) 2^-24 (sum_k |xh_k W_k| + |b|) + sum_k |W_k| dxh_k,
+ * and the GELU adds 1.13 times that, 0.5 |t| (2^-19 + 5 2^-24 (1 + |t|)) and one rounding; the residual one rounding.
+ *
+ * AURA_E_INVAL: R < 1 or > AURA_ROW_LINEAR_MAX_ROWS, K < 4 or > AURA_ROW_LINEAR_MAX_K or K % 4 != 0, a null x, W0 or
+ *   y0, N_0 < 1, a later matrix without its output or with N_j < 1 (or W2 without W1), anything of a matrix that is
+ *   not given, sum N_j > 2^31 - 1, one of gamma / beta, a prologue with K > 2048 or eps < 0 or NaN, xh without a
+ *   prologue, res with more than one matrix.  AURA_E_ALIGN: x, W_j, gamma, beta or xh not 16-byte aligned, any other
+ *   pointer not 4-byte aligned.  One launch on `stream`. */
+#define AURA_ROW_LINEAR_MAX_ROWS 32
+#define AURA_ROW_LINEAR_MAX_K 8192
+int aura_row_linear(const float* x, int64_t R, int64_t K, const float* W0, const float* b0_or_null, float* y0,
+                    int64_t N0, const float* W1_or_null, const float* b1_or_null, float* y1_or_null, int64_t N1,
+                    const float* W2_or_null, const float* b2_or_null, float* y2_or_null, int64_t N2,
+                    const float* gamma_or_null, const float* beta_or_null, float eps, float* xh_or_null, int gelu,
+                    const float* res_or_null, int nontemporal, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
