@@ -10,6 +10,7 @@ episodic-retrieval hot path, behind the reference's own module API.
     from aura_snn_rag_amd import ProsodyAttentionBridge, MultiChannelSpikingAttention, prosody_channels_from_text
     from aura_snn_rag_amd import HippocampalProsodyAttention, HippocampalTransformerLayer, AttentionCache
     from aura_snn_rag_amd import HippocampalTransformer, DecodeState      # forward, prefill / step, generate
+    from aura_snn_rag_amd import SNNRAGTransformer, MemoryAugmentedLayer, MemoryContext     # generation with memory
 
 All arithmetic on the path runs in ``lib/libaura_hip.so`` (hand-written HIP, C ABI in
 ``include/aura_hip.h``); there is no CPU or eager-PyTorch fallback.
@@ -29,7 +30,12 @@ _LAZY = {"PlaceCellSemanticEncoder": "core.language_zone.place_cell_encoder",
          "AttentionCache": "core.language_zone.hippocampal_attention",
          "HippocampalTransformerLayer": "core.language_zone.hippocampal_layer",
          "HippocampalTransformer": "core.language_zone.hippocampal_transformer",
-         "DecodeState": "core.language_zone.hippocampal_transformer"}
+         "DecodeState": "core.language_zone.hippocampal_transformer",
+         "CachedDecodingMixin": "core.language_zone.hippocampal_transformer",
+         "MemoryAugmentedLayer": "core.language_zone.memory_augmented_layer",
+         "MemoryContext": "core.language_zone.memory_augmented_layer",
+         "MemoryLayerCache": "core.language_zone.memory_augmented_layer",
+         "SNNRAGTransformer": "core.language_zone.snn_rag_transformer"}
 
 
 def __getattr__(name):

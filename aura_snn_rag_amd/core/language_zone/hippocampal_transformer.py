@@ -65,56 +65,18 @@ class DecodeState:
         return self.seen.shape[0]
 
 
-class HippocampalTransformer(nn.Module):
-    def __init__(self, config, hippocampus):
-        super().__init__()
-        self.config = config
-        self.hippocampus = hippocampus
-        self.use_gradient_checkpointing = getattr(config, 'use_gradient_checkpointing', False)
-        self.pos_encoder = ThetaGammaPositionalEncoding(config)
-        self.semantic_encoder = PlaceCellSemanticEncoder(config, hippocampus)
-        self.dropout = nn.Dropout(config.dropout)
-        self.layer_norm = nn.LayerNorm(config.embedding_dim)
-        self.layers = nn.ModuleList([HippocampalTransformerLayer(config, hippocampus)
-                                     for _ in range(config.num_layers)])
-        self.output_head = nn.Linear(config.embedding_dim, config.vocab_size, bias=False)
-        self.output_head.weight = self.semantic_encoder.token_embedding.weight      # tied, as upstream
+class CachedDecodingMixin:
+    """``new_state`` / ``step`` / ``generate`` of a model that has ``config``, ``layers`` (each with ``new_cache`` and
+    ``step``), ``semantic_encoder``, ``pos_encoder``, ``layer_norm``, ``dropout``, ``output_head`` and its own
+    ``prefill(input_ids, prosody=None, state=None, use_memory=True)``: the decode loop ``HippocampalTransformer`` and
+    ``SNNRAGTransformer`` share.  Messages name the class that raises."""
 
-    def set_gradient_checkpointing(self, enable: bool = True):
-        self.use_gradient_checkpointing = enable
-
-    def _layer_forward(self, layer, hidden_states, prosody, use_memory):
-        return layer(hidden_states, prosody=prosody, use_memory=use_memory)
-
-    # ------------------------------------------------------------------------------------------------ full sequences
-    def forward(self, input_ids: torch.Tensor, prosody: Optional[torch.Tensor] = None, use_memory: bool = True,
-                store_memory: bool = False, memory_ids: Optional[List[str]] = None) -> Tuple[torch.Tensor, torch.Tensor]:
-        batch_size = input_ids.shape[0]
-        hidden_states, place_cell_activity = embed_tokens(input_ids, self.semantic_encoder, self.pos_encoder,
-                                                          self.layer_norm)
-        hidden_states = self.dropout(hidden_states)
-        for layer in self.layers:
-            if self.training and self.use_gradient_checkpointing:
-                hidden_states = checkpoint(self._layer_forward, layer, hidden_states, prosody, use_memory,
-                                           use_reentrant=False)
-            else:
-                hidden_states = layer(hidden_states, prosody=prosody, use_memory=use_memory)
-        logits = self.output_head(hidden_states)
-        if store_memory and self.hippocampus is not None:
-            summary = hidden_states.mean(dim=1).detach()
-            now = time.time()
-            ids = [memory_ids[b] if memory_ids and b < len(memory_ids) else f"step-{int(now)}-b{b}"
-                   for b in range(batch_size)]
-            self.hippocampus.create_episodic_memories(ids, summary)
-        return logits, place_cell_activity
-
-    # ------------------------------------------------------------------------------------------------ cached decoding
     def new_state(self, batch: int, capacity: int, seed: int = 0) -> DecodeState:
         """An empty decoding state for ``batch`` sequences of at most ``capacity`` positions, on the model's device."""
         if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < (1 << 64):
-            raise ValueError(f"HippocampalTransformer.new_state: seed must be an int in [0, 2^64), got {seed!r}")
+            raise ValueError(f"{type(self).__name__}.new_state: seed must be an int in [0, 2^64), got {seed!r}")
         if len(self.layers) < 1:
-            raise ValueError("HippocampalTransformer.new_state: a model without layers has nothing to cache")
+            raise ValueError(f"{type(self).__name__}.new_state: a model without layers has nothing to cache")
         caches = [layer.new_cache(batch, capacity) for layer in self.layers]
         dev = self.output_head.weight.device
         seen = torch.zeros(batch, self.config.vocab_size, dtype=torch.uint8, device=dev)
@@ -128,24 +90,6 @@ class HippocampalTransformer(nn.Module):
             raise ValueError(f"{who}: the state holds {state.batch} rows and {len(state.caches)} caches, this call "
                              f"needs {B} rows and {len(self.layers)} caches")
 
-    def prefill(self, input_ids: torch.Tensor, prosody: Optional[torch.Tensor] = None,
-                state: Optional[DecodeState] = None, use_memory: bool = True) -> torch.Tensor:
-        """``forward`` over a prompt [B, S] that also fills every layer's cache and marks the prompt's tokens in
-        ``state.seen``.  Returns the logits [B, S, V]."""
-        who = "HippocampalTransformer.prefill"
-        if input_ids.dim() != 2:
-            raise ValueError(f"{who}: input_ids is [B, S], got {tuple(input_ids.shape)}")
-        B, S = input_ids.shape
-        self._check_state(who, state, B)
-        hidden_states, _ = embed_tokens(input_ids, self.semantic_encoder, self.pos_encoder, self.layer_norm)
-        hidden_states = self.dropout(hidden_states)
-        for layer, cache in zip(self.layers, state.caches):
-            hidden_states = layer.prefill(hidden_states, prosody=prosody, use_memory=use_memory, cache=cache)
-        with torch.no_grad():
-            state.seen.scatter_(1, input_ids.to(torch.int64), 1)
-        state.position = S
-        return self.output_head(hidden_states)
-
     @torch.no_grad()
     def step(self, tokens: torch.Tensor, prosody: Optional[torch.Tensor] = None, state: Optional[DecodeState] = None,
              use_memory: bool = True, *, fused: bool = False) -> torch.Tensor:
@@ -153,7 +97,7 @@ class HippocampalTransformer(nn.Module):
         layer's ``step`` runs on its cache; the last one advances the shared lengths.  ``fused=True`` (B <= 32) takes
         every layer's fused step: six launches a layer instead of fourteen; the front end and the head stay as they
         are.  No host sync."""
-        who = "HippocampalTransformer.step"
+        who = f"{type(self).__name__}.step"
         if tokens.dim() == 1:
             tokens = tokens[:, None]
         if tokens.dim() != 2 or tokens.shape[1] != 1:
@@ -195,7 +139,7 @@ class HippocampalTransformer(nn.Module):
         stops when every row has finished, not only when every row emits EOS in the same step; top-k keeps exactly
         ``k`` candidates and the random stream is fixed by ``(seed, step, stream, token id)`` (the rule:
         ``include/aura_hip.h``, "Next token")."""
-        who = "HippocampalTransformer.generate"
+        who = f"{type(self).__name__}.generate"
         if input_ids.dim() != 2 or input_ids.shape[1] < 1:
             raise ValueError(f"{who}: input_ids is [B, S] with S >= 1, got {tuple(input_ids.shape)}")
         for n, v in (("max_new_tokens", max_new_tokens), ("sync_every", sync_every)):
@@ -243,3 +187,66 @@ class HippocampalTransformer(nn.Module):
                 done_before = ((new == eos).cumsum(1) - (new == eos).to(torch.int64)) > 0
                 n = int((~done_before.all(0)).sum().item())
         return generated[:, :S + n]
+
+
+class HippocampalTransformer(CachedDecodingMixin, nn.Module):
+    def __init__(self, config, hippocampus):
+        super().__init__()
+        self.config = config
+        self.hippocampus = hippocampus
+        self.use_gradient_checkpointing = getattr(config, 'use_gradient_checkpointing', False)
+        self.pos_encoder = ThetaGammaPositionalEncoding(config)
+        self.semantic_encoder = PlaceCellSemanticEncoder(config, hippocampus)
+        self.dropout = nn.Dropout(config.dropout)
+        self.layer_norm = nn.LayerNorm(config.embedding_dim)
+        self.layers = nn.ModuleList([HippocampalTransformerLayer(config, hippocampus)
+                                     for _ in range(config.num_layers)])
+        self.output_head = nn.Linear(config.embedding_dim, config.vocab_size, bias=False)
+        self.output_head.weight = self.semantic_encoder.token_embedding.weight      # tied, as upstream
+
+    def set_gradient_checkpointing(self, enable: bool = True):
+        self.use_gradient_checkpointing = enable
+
+    def _layer_forward(self, layer, hidden_states, prosody, use_memory):
+        return layer(hidden_states, prosody=prosody, use_memory=use_memory)
+
+    # ------------------------------------------------------------------------------------------------ full sequences
+    def forward(self, input_ids: torch.Tensor, prosody: Optional[torch.Tensor] = None, use_memory: bool = True,
+                store_memory: bool = False, memory_ids: Optional[List[str]] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        batch_size = input_ids.shape[0]
+        hidden_states, place_cell_activity = embed_tokens(input_ids, self.semantic_encoder, self.pos_encoder,
+                                                          self.layer_norm)
+        hidden_states = self.dropout(hidden_states)
+        for layer in self.layers:
+            if self.training and self.use_gradient_checkpointing:
+                hidden_states = checkpoint(self._layer_forward, layer, hidden_states, prosody, use_memory,
+                                           use_reentrant=False)
+            else:
+                hidden_states = layer(hidden_states, prosody=prosody, use_memory=use_memory)
+        logits = self.output_head(hidden_states)
+        if store_memory and self.hippocampus is not None:
+            summary = hidden_states.mean(dim=1).detach()
+            now = time.time()
+            ids = [memory_ids[b] if memory_ids and b < len(memory_ids) else f"step-{int(now)}-b{b}"
+                   for b in range(batch_size)]
+            self.hippocampus.create_episodic_memories(ids, summary)
+        return logits, place_cell_activity
+
+    # ------------------------------------------------------------------------------------------------ cached decoding
+    def prefill(self, input_ids: torch.Tensor, prosody: Optional[torch.Tensor] = None,
+                state: Optional[DecodeState] = None, use_memory: bool = True) -> torch.Tensor:
+        """``forward`` over a prompt [B, S] that also fills every layer's cache and marks the prompt's tokens in
+        ``state.seen``.  Returns the logits [B, S, V]."""
+        who = "HippocampalTransformer.prefill"
+        if input_ids.dim() != 2:
+            raise ValueError(f"{who}: input_ids is [B, S], got {tuple(input_ids.shape)}")
+        B, S = input_ids.shape
+        self._check_state(who, state, B)
+        hidden_states, _ = embed_tokens(input_ids, self.semantic_encoder, self.pos_encoder, self.layer_norm)
+        hidden_states = self.dropout(hidden_states)
+        for layer, cache in zip(self.layers, state.caches):
+            hidden_states = layer.prefill(hidden_states, prosody=prosody, use_memory=use_memory, cache=cache)
+        with torch.no_grad():
+            state.seen.scatter_(1, input_ids.to(torch.int64), 1)
+        state.position = S
+        return self.output_head(hidden_states)

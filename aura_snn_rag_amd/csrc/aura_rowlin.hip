@@ -13,6 +13,21 @@
 //   holds row r and applies bias, GELU and residual.
 // Workgroups are independent: no atomics, no flags, one pass.  RT (the power of two >= R), CT and the waves per
 // workgroup are launch geometry only: an element's summation order depends on K alone.
+//
+// Gate epilogue (aura_row_linear_gate; the rule: "Row linear: gate epilogue").  The same kernel, instantiated a second
+// time with EPI = RL_EPI_GATE: a compile-time switch, so the instantiations behind aura_row_linear are the code they
+// were.  Two things differ.  The weight rows are ldw floats apart instead of K, so that the left half of a [N][2K]
+// parameter is streamed in place (a row's 16-byte units stay aligned: ldw % 4 == 0).  And lane r, which holds row r's
+// sum after the butterfly, loads its u, c and res element and finishes y = res + sigmoid(t + u) c: three more loads
+// and one expf per output element, behind the same dot product, in the same launch.
+//
+// GIF epilogue (aura_row_linear_gif; the rule: "Row linear: GIF epilogue").  EPI = RL_EPI_GIF_TI / RL_EPI_GIF_TM: the
+// current t = dot + b feeds the GIF step of aura_neuron.hip (the one GifModel of aura_gif_model.inl, so the bits are
+// aura_gif_run's) without a round trip through memory.  Time-invariant: lane r, which holds row r's current, runs its T
+// steps from fresh state and writes T spikes.  Time-major: the rows tok T .. tok T + T - 1 are a token's T steps; every
+// lane of the token reads them in order with __shfl (all 64 lanes take part: the branch around the loop is
+// wave-uniform) and runs the same T steps, the token's first lane divides the spike sum by T and, with the mix,
+// finishes res + ((1 - g) m + g mean), g = sigmoid(*gate) read from device memory.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -21,6 +36,8 @@
 #include "aura_common.inl"
 
 namespace {
+
+#include "aura_gif_model.inl"
 
 // Waves per workgroup.  Every workgroup stages all R rows, so its cost in L2 reads is R K per workgroup: at 16 and 32
 // rows sixteen waves share a tile where there are columns enough for it (a quarter of the L2 reads per output column
@@ -48,7 +65,21 @@ struct RowLinArgs {
     int R, K;
     int gelu, nontemporal;
     float eps;
+    // the gate epilogue's (EPI == RL_EPI_GATE; unused otherwise)
+    const float* gate_u;                // [R][N_0]
+    const float* gate_c;                // [R][N_0]
+    int64_t ldw;                        // floats between the rows of W_0, >= K
+    // the GIF epilogues' (EPI == RL_EPI_GIF_TI / RL_EPI_GIF_TM; unused otherwise)
+    float gif_decay, gif_L, gif_alpha, gif_thr;
+    int gif_T;
+    const float* mix_m;                 // [R / T][N_0] or NULL (no mix: the mean is written); with it res is [R / T][N_0]
+    const float* mix_gate;              // one float
 };
+
+constexpr int RL_EPI_PLAIN = 0;         // bias, GELU, residual
+constexpr int RL_EPI_GATE = 1;          // bias, then res + sigmoid(t + u) c
+constexpr int RL_EPI_GIF_TI = 2;        // bias, then T GIF steps on the row's own current: spikes [R][T][N]
+constexpr int RL_EPI_GIF_TM = 3;        // bias, then a token's T rows through the GIF: the T-mean [R / T][N], or the mix
 
 __device__ __forceinline__ float rl_wave_sum(float s) {
     s = s + __shfl_xor(s, 32);
@@ -179,7 +210,7 @@ struct RowLinRegs {
     }
 };
 
-template <int RT, int CT, int WAVES>
+template <int RT, int CT, int WAVES, int EPI = RL_EPI_PLAIN>
 __global__ __launch_bounds__(64 * WAVES) void row_linear_kernel(const RowLinArgs a) {
     typedef RowLinTile<RT, WAVES> T;
     constexpr int STEPS = T::STEPS, KC4 = T::KC4, WV = T::WV;
@@ -198,7 +229,7 @@ __global__ __launch_bounds__(64 * WAVES) void row_linear_kernel(const RowLinArgs
         int j = 0;
         if (g >= a.N[0]) { g -= a.N[0]; j = 1; }
         if (j == 1 && g >= a.N[1]) { g -= a.N[1]; j = 2; }
-        wrow[c] = reinterpret_cast<const rl_v4*>(a.W[j] + g * a.K);
+        wrow[c] = reinterpret_cast<const rl_v4*>(a.W[j] + g * (EPI == RL_EPI_GATE ? a.ldw : (int64_t)a.K));
     }
 
     RowLinRegs<RT, CT, WAVES> cur, nxt;
@@ -275,47 +306,105 @@ __global__ __launch_bounds__(64 * WAVES) void row_linear_kernel(const RowLinArgs
             if (lane == r) mine = v;
         }
         int64_t g = g0 + c;
+        if constexpr (EPI == RL_EPI_GIF_TI || EPI == RL_EPI_GIF_TM) {
+            if (g < a.Nt) {                                             // wave-uniform: every lane reaches the shuffles
+                float t = mine;
+                if (a.b[0]) t = t + a.b[0][g];
+                const GifModel<false> gif{a.gif_decay, a.gif_L, a.gif_alpha, a.gif_thr};
+                GifModel<false>::Lane st;
+                st.s0 = 0.0f;
+                st.s1 = a.gif_thr;
+                const int nt = a.gif_T;                                 // the neuron loop's steps
+                if constexpr (EPI == RL_EPI_GIF_TI) {
+                    if (lane < a.R) {
+                        float* const o = a.y[0] + (int64_t)lane * nt * a.N[0] + g;
+                        for (int tt = 0; tt < nt; ++tt) o[(int64_t)tt * a.N[0]] = gif.step(st, t);
+                    }
+                } else {
+                    const int first = lane - lane % nt;                 // the token's first row
+                    float acc = 0.0f;
+                    for (int tt = 0; tt < nt; ++tt) {
+                        const int src = first + tt;
+                        acc += gif.step(st, __shfl(t, src < 64 ? src : 63));
+                    }
+                    if (lane < a.R && lane == first) {
+                        float y = acc / (float)nt;
+                        const int64_t o = (int64_t)(lane / nt) * a.N[0] + g;
+                        if (a.mix_m) {
+                            const float gt = 1.0f / (1.0f + expf(-a.mix_gate[0]));
+                            const float left = (1.0f - gt) * a.mix_m[o];
+                            const float right = gt * y;
+                            y = a.res[o] + (left + right);
+                        }
+                        a.y[0][o] = y;
+                    }
+                }
+            }
+            continue;
+        }
         if (g < a.Nt && lane < a.R) {
             int j = 0;
             if (g >= a.N[0]) { g -= a.N[0]; j = 1; }
             if (j == 1 && g >= a.N[1]) { g -= a.N[1]; j = 2; }
             float t = mine;
             if (a.b[j]) t = t + a.b[j][g];
-            if (a.gelu) t = rl_gelu(t);
             const int64_t o = (int64_t)lane * a.N[j] + g;
-            if (a.res) t = t + a.res[o];
+            if constexpr (EPI == RL_EPI_GATE) {
+                const float act = t + a.gate_u[o];
+                const float s = 1.0f / (1.0f + expf(-act));
+                t = a.res[o] + s * a.gate_c[o];
+            } else {
+                if (a.gelu) t = rl_gelu(t);
+                if (a.res) t = t + a.res[o];
+            }
             a.y[j][o] = t;
         }
     }
 }
 
+inline void rl_no_gif(RowLinArgs& a) {
+    a.gif_decay = a.gif_L = a.gif_alpha = a.gif_thr = 0.0f;
+    a.gif_T = 0;
+    a.mix_m = a.mix_gate = nullptr;
+}
+
 inline bool misaligned(const void* p, uintptr_t n) { return (reinterpret_cast<uintptr_t>(p) & (n - 1)) != 0; }
 
-template <int RT, int CT, int WV>
+template <int RT, int CT, int WV, int EPI>
 int rl_launch_geometry(const RowLinArgs& a, hipStream_t s) {
     constexpr int lds = RowLinTile<RT, WV>::LDS_BYTES;
     if (lds > 48 * 1024) {                                              // above the default dynamic limit
-        const int rc = aura_ensure_lds_attr(reinterpret_cast<const void*>(&row_linear_kernel<RT, CT, WV>), lds);
+        const int rc = aura_ensure_lds_attr(reinterpret_cast<const void*>(&row_linear_kernel<RT, CT, WV, EPI>), lds);
         if (rc != AURA_OK) return rc;
     }
     const int64_t waves = ((int64_t)a.Nt + CT - 1) / CT;
     const dim3 grid((unsigned)((waves + WV - 1) / WV)), block(64 * WV);
-    hipLaunchKernelGGL((row_linear_kernel<RT, CT, WV>), grid, block, lds, s, a);
+    hipLaunchKernelGGL((row_linear_kernel<RT, CT, WV, EPI>), grid, block, lds, s, a);
     return AURA_OK;
 }
 
 // The launch geometry: a choice of speed only, an element's summation order does not depend on it.
-template <int RT>
+template <int RT, int EPI = RL_EPI_PLAIN>
 int rl_launch(const RowLinArgs& a, hipStream_t s) {
     if (RT >= 16) {
-        if (a.Nt >= 2048) return rl_launch_geometry<RT, 1, RT >= 16 ? RL_WAVES_WIDE : RL_WAVES>(a, s);
-        return rl_launch_geometry<RT, 1, RL_WAVES>(a, s);
+        if (a.Nt >= 2048) return rl_launch_geometry<RT, 1, RT >= 16 ? RL_WAVES_WIDE : RL_WAVES, EPI>(a, s);
+        return rl_launch_geometry<RT, 1, RL_WAVES, EPI>(a, s);
     }
     // more columns per wave only where enough waves remain to fill the device, and only while the RT x CT sums and
     // the two tiles of loads in flight leave registers for two workgroups a CU
-    if (a.Nt >= 8192 && RT <= 4) return rl_launch_geometry<RT, RT <= 4 ? 4 : 1, RL_WAVES>(a, s);
-    if (a.Nt >= 2048 && RT <= 8) return rl_launch_geometry<RT, RT <= 8 ? 2 : 1, RL_WAVES>(a, s);
-    return rl_launch_geometry<RT, 1, RL_WAVES>(a, s);
+    if (a.Nt >= 8192 && RT <= 4) return rl_launch_geometry<RT, RT <= 4 ? 4 : 1, RL_WAVES, EPI>(a, s);
+    if (a.Nt >= 2048 && RT <= 8) return rl_launch_geometry<RT, RT <= 8 ? 2 : 1, RL_WAVES, EPI>(a, s);
+    return rl_launch_geometry<RT, 1, RL_WAVES, EPI>(a, s);
+}
+
+template <int EPI>
+int rl_launch_rows(const RowLinArgs& a, hipStream_t s) {
+    if (a.R <= 1) return rl_launch<1, EPI>(a, s);
+    if (a.R <= 2) return rl_launch<2, EPI>(a, s);
+    if (a.R <= 4) return rl_launch<4, EPI>(a, s);
+    if (a.R <= 8) return rl_launch<8, EPI>(a, s);
+    if (a.R <= 16) return rl_launch<16, EPI>(a, s);
+    return rl_launch<32, EPI>(a, s);
 }
 
 }  // namespace
@@ -354,14 +443,73 @@ int aura_row_linear(const float* x, int64_t R, int64_t K, const float* W0, const
     a.R = (int)R; a.K = (int)K;
     a.gelu = gelu != 0; a.nontemporal = nontemporal != 0;
     a.eps = eps;
+    a.gate_u = a.gate_c = nullptr;
+    a.ldw = K;
+    rl_no_gif(a);
+    const int rc = rl_launch_rows<RL_EPI_PLAIN>(a, static_cast<hipStream_t>(stream));
+    if (rc != AURA_OK) return rc;
+    return aura_check_launch();
+}
+
+int aura_row_linear_gate(const float* x, int64_t R, int64_t K, const float* W, int64_t ldw, const float* b_or_null,
+                         const float* u, const float* c, const float* res, float* y, int64_t N, int nontemporal,
+                         void* stream) {
+    if (R < 1 || R > RL_MAX_ROWS || K < 4 || K > RL_MAX_K || K % 4 != 0) return AURA_E_INVAL;
+    if (!x || !W || !u || !c || !res || !y || N < 1 || N > 0x7fffffff) return AURA_E_INVAL;
+    if (ldw < K || ldw % 4 != 0) return AURA_E_INVAL;
+    if (misaligned(x, 16) || misaligned(W, 16) || misaligned(b_or_null, 4) || misaligned(u, 4) || misaligned(c, 4) ||
+        misaligned(res, 4) || misaligned(y, 4))
+        return AURA_E_ALIGN;
+    RowLinArgs a;
+    a.x = x;
+    a.W[0] = W; a.W[1] = nullptr; a.W[2] = nullptr;
+    a.b[0] = b_or_null; a.b[1] = nullptr; a.b[2] = nullptr;
+    a.y[0] = y; a.y[1] = nullptr; a.y[2] = nullptr;
+    a.N[0] = (int)N; a.N[1] = 0; a.N[2] = 0;
+    a.Nt = (int)N;
+    a.gamma = nullptr; a.beta = nullptr; a.res = res; a.xh = nullptr;
+    a.R = (int)R; a.K = (int)K;
+    a.gelu = 0; a.nontemporal = nontemporal != 0;
+    a.eps = 0.0f;
+    a.gate_u = u; a.gate_c = c;
+    a.ldw = ldw;
+    rl_no_gif(a);
+    const int rc = rl_launch_rows<RL_EPI_GATE>(a, static_cast<hipStream_t>(stream));
+    if (rc != AURA_OK) return rc;
+    return aura_check_launch();
+}
+
+int aura_row_linear_gif(const float* x, int64_t R, int64_t K, const float* W, const float* b_or_null, float* out,
+                        int64_t N, int64_t T, float decay, int L, float alpha, float threshold, int time_major,
+                        const float* res_or_null, const float* m_or_null, const float* gate_or_null, int nontemporal,
+                        void* stream) {
+    if (R < 1 || R > RL_MAX_ROWS || K < 4 || K > RL_MAX_K || K % 4 != 0) return AURA_E_INVAL;
+    if (!x || !W || !out || N < 1 || N > 0x7fffffff) return AURA_E_INVAL;
+    if (T < 1 || T > RL_MAX_ROWS || L < 1) return AURA_E_INVAL;
+    if (time_major && R % T != 0) return AURA_E_INVAL;
+    const int mixed = (res_or_null != nullptr) + (m_or_null != nullptr) + (gate_or_null != nullptr);
+    if (mixed != 0 && (mixed != 3 || !time_major)) return AURA_E_INVAL;
+    if (misaligned(x, 16) || misaligned(W, 16) || misaligned(b_or_null, 4) || misaligned(out, 4) ||
+        misaligned(res_or_null, 4) || misaligned(m_or_null, 4) || misaligned(gate_or_null, 4))
+        return AURA_E_ALIGN;
+    RowLinArgs a;
+    a.x = x;
+    a.W[0] = W; a.W[1] = nullptr; a.W[2] = nullptr;
+    a.b[0] = b_or_null; a.b[1] = nullptr; a.b[2] = nullptr;
+    a.y[0] = out; a.y[1] = nullptr; a.y[2] = nullptr;
+    a.N[0] = (int)N; a.N[1] = 0; a.N[2] = 0;
+    a.Nt = (int)N;
+    a.gamma = nullptr; a.beta = nullptr; a.res = res_or_null; a.xh = nullptr;
+    a.R = (int)R; a.K = (int)K;
+    a.gelu = 0; a.nontemporal = nontemporal != 0;
+    a.eps = 0.0f;
+    a.gate_u = a.gate_c = nullptr;
+    a.ldw = K;
+    a.gif_decay = decay; a.gif_L = (float)L; a.gif_alpha = alpha; a.gif_thr = threshold;
+    a.gif_T = (int)T;
+    a.mix_m = m_or_null; a.mix_gate = gate_or_null;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    int rc;
-    if (R <= 1) rc = rl_launch<1>(a, s);
-    else if (R <= 2) rc = rl_launch<2>(a, s);
-    else if (R <= 4) rc = rl_launch<4>(a, s);
-    else if (R <= 8) rc = rl_launch<8>(a, s);
-    else if (R <= 16) rc = rl_launch<16>(a, s);
-    else rc = rl_launch<32>(a, s);
+    const int rc = time_major ? rl_launch_rows<RL_EPI_GIF_TM>(a, s) : rl_launch_rows<RL_EPI_GIF_TI>(a, s);
     if (rc != AURA_OK) return rc;
     return aura_check_launch();
 }

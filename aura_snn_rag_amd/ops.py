@@ -1006,6 +1006,148 @@ def row_linear(x, weights, biases=None, *, norm=None, eps: float = 1e-5, activat
     return (y, xh) if return_normed else y
 
 
+def _row_linear_gate_args(x, weight, bias, u, c, residual, out):
+    """Type, shape and limit checks of ``row_linear_gate``: ``(R, K, N, ldw)``.  Touches no device."""
+    who = "row_linear_gate"
+    for name, t in (("x", x), ("weight", weight), ("u", u), ("c", c), ("residual", residual)):
+        if t is None:
+            raise ValueError(f"{who}: {name} is required")
+    _rl_f32("x", x)
+    if x.dim() != 2:
+        raise ValueError(f"{who}: x is [R, K], got {tuple(x.shape)}")
+    R, K = x.shape
+    if not 1 <= R <= ROW_LINEAR_MAX_ROWS:
+        raise ValueError(f"{who}: R={R} rows must be in [1, {ROW_LINEAR_MAX_ROWS}] (more rows are a library GEMM's work)")
+    if K % 4 != 0 or not 4 <= K <= ROW_LINEAR_MAX_K:
+        raise ValueError(f"{who}: K={K} must be a multiple of 4 in [4, {ROW_LINEAR_MAX_K}]")
+    if not isinstance(weight, torch.Tensor):
+        raise TypeError(f"{who}: weight must be a torch.Tensor, got {type(weight)}")
+    if weight.dtype != torch.float32:
+        raise TypeError(f"{who}: weight is {weight.dtype}; the row linear kernel runs in fp32 only")
+    if weight.dim() != 2 or weight.shape[1] != K or weight.shape[0] < 1:
+        raise ValueError(f"{who}: weight is [N, K] with K={K} and N >= 1 (nn.Linear's layout, or the left columns of a "
+                         f"wider one), got {tuple(weight.shape)}")
+    N = weight.shape[0]
+    if N > 0x7fffffff:
+        raise ValueError(f"{who}: the weight holds more than 2^31 - 1 output columns")
+    if weight.stride(1) != 1:
+        raise ValueError(f"{who}: a row of weight must be dense (stride 1), got {weight.stride(1)}")
+    ldw = weight.stride(0) if N > 1 else max(K, weight.stride(0))
+    if ldw < K or ldw % 4 != 0:
+        raise ValueError(f"{who}: the rows of weight are {ldw} floats apart: the stride must be a multiple of 4 that is "
+                         f"at least K={K}")
+    if bias is not None:
+        _rl_f32("bias", bias)
+        if bias.dim() != 1 or bias.shape[0] != N:
+            raise ValueError(f"{who}: bias is [N] = ({N},), got {tuple(bias.shape)}")
+    for name, t in (("u", u), ("c", c), ("residual", residual), ("out", out)):
+        if t is None:
+            continue
+        _rl_f32(name, t)
+        if t.dim() != 2 or t.shape[0] != R or t.shape[1] != N:
+            raise ValueError(f"{who}: {name} is [R, N] = ({R}, {N}), got {tuple(t.shape)}")
+    return R, K, N, ldw
+
+
+def row_linear_gate(x, weight, bias, u, c, residual, *, out=None):
+    """The gated injection of a decoding step in one launch (the rule: ``include/aura_hip.h``, "Row linear: gate
+    epilogue"): ``y = residual + sigmoid(x W^T + bias + u) * c`` with ``x`` [R, K], R <= 32, ``weight`` [N, K] whose rows
+    may be further apart than K (``memory_gate[0].weight[:, :D]``: the view is read in place, nothing is copied), ``bias``
+    [N] or ``None`` and the per-row ``u``, ``c``, ``residual`` [R, N].  Returns ``y`` [R, N] (``out`` receives it).  fp32
+    only.  The dot product and a row's independence of its batch are ``row_linear``'s.  No host sync."""
+    R, K, N, ldw = _row_linear_gate_args(x, weight, bias, u, c, residual, out)
+    dev = _rl_device("x", x, None, True)
+    _rl_device("weight", weight, dev, True)
+    for name, t in (("bias", bias), ("u", u), ("c", c), ("residual", residual), ("out", out)):
+        if t is not None:
+            _rl_device(name, t, dev, False)
+    y = out if out is not None else torch.empty((R, N), dtype=torch.float32, device=dev)
+    check(lib().aura_row_linear_gate(x.data_ptr(), R, K, weight.data_ptr(), ldw, _p(bias), _p(u), _p(c), _p(residual),
+                                     _p(y), N, int(ROW_LINEAR_NONTEMPORAL), _stream()),
+          "aura_row_linear_gate")
+    return y
+
+
+def _row_linear_gif_args(x, weight, bias, T, decay, L, alpha, threshold, time_major, mix, out):
+    """Type, shape and limit checks of ``row_linear_gif``: ``(R, K, N, out_shape, (res, m, gate))``.  Touches no
+    device."""
+    who = "row_linear_gif"
+    if x is None or weight is None:
+        raise ValueError(f"{who}: x and weight are required")
+    _rl_f32("x", x)
+    _rl_f32("weight", weight)
+    if x.dim() != 2:
+        raise ValueError(f"{who}: x is [R, K], got {tuple(x.shape)}")
+    R, K = x.shape
+    if not 1 <= R <= ROW_LINEAR_MAX_ROWS:
+        raise ValueError(f"{who}: R={R} rows must be in [1, {ROW_LINEAR_MAX_ROWS}]")
+    if K % 4 != 0 or not 4 <= K <= ROW_LINEAR_MAX_K:
+        raise ValueError(f"{who}: K={K} must be a multiple of 4 in [4, {ROW_LINEAR_MAX_K}]")
+    if weight.dim() != 2 or weight.shape[1] != K or weight.shape[0] < 1:
+        raise ValueError(f"{who}: weight is [N, K] with K={K} and N >= 1, got {tuple(weight.shape)}")
+    N = weight.shape[0]
+    if bias is not None:
+        _rl_f32("bias", bias)
+        if bias.dim() != 1 or bias.shape[0] != N:
+            raise ValueError(f"{who}: bias is [N] = ({N},), got {tuple(bias.shape)}")
+    for name, v in (("T", T), ("L", L)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise TypeError(f"{who}: {name} must be an int, got {type(v)}")
+    if not 1 <= T <= ROW_LINEAR_MAX_ROWS:
+        raise ValueError(f"{who}: T={T} must be in [1, {ROW_LINEAR_MAX_ROWS}]")
+    if L < 1:
+        raise ValueError(f"{who}: L={L} must be at least 1")
+    for name, v in (("decay", decay), ("alpha", alpha), ("threshold", threshold)):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise TypeError(f"{who}: {name} must be a number, got {type(v)}")
+    if time_major and R % T != 0:
+        raise ValueError(f"{who}: the time-major form takes whole tokens: R={R} is no multiple of T={T}")
+    out_shape = (R // T, N) if time_major else (R, T, N)
+    res = m = gate = None
+    if mix is not None:
+        if not time_major:
+            raise ValueError(f"{who}: the mix goes with the time-major form (time_major=True)")
+        if not isinstance(mix, (tuple, list)) or len(mix) != 3 or any(t is None for t in mix):
+            raise ValueError(f"{who}: mix is (residual, m, gate): [tokens, N], [tokens, N] and one float")
+        res, m, gate = mix
+        for name, t in (("mix residual", res), ("mix m", m)):
+            _rl_f32(name, t)
+            if tuple(t.shape) != out_shape:
+                raise ValueError(f"{who}: {name} is [tokens, N] = {out_shape}, got {tuple(t.shape)}")
+        _rl_f32("mix gate", gate)
+        if gate.numel() != 1:
+            raise ValueError(f"{who}: mix gate is one float (the HybridFFN's gate parameter), got {tuple(gate.shape)}")
+    if out is not None:
+        _rl_f32("out", out)
+        if tuple(out.shape) != out_shape:
+            raise ValueError(f"{who}: out is {out_shape}, got {tuple(out.shape)}")
+    return R, K, N, out_shape, (res, m, gate)
+
+
+def row_linear_gif(x, weight, bias=None, *, T: int, decay: float, L: int, alpha: float, threshold: float,
+                   time_major: bool = False, mix=None, out=None):
+    """A skinny linear layer whose output feeds the GIF neuron loop in the same launch (the rule: ``include/aura_hip.h``,
+    "Row linear: GIF epilogue"): ``x`` [R, K], R <= 32, ``weight`` [N, K], ``bias`` [N] or ``None``; every row or token
+    starts from fresh neuron state.  ``time_major=False``: each row runs ``T`` steps on its own current -> spikes
+    [R, T, N], the bits of ``gif_run(time_invariant=True)`` on ``row_linear``'s output.  ``time_major=True``: the rows are
+    ``R / T`` tokens of ``T`` steps each -> the mean over T [R / T, N], the bits of ``gif_run(mean_out=True)``; with
+    ``mix=(residual, m, gate)`` -> ``residual + ((1 - g) * m + g * mean)``, ``g = sigmoid(gate)`` read on the device.
+    fp32 only, 1 <= T <= 32.  No host sync."""
+    R, K, N, out_shape, (res, m, gate) = _row_linear_gif_args(x, weight, bias, T, decay, L, alpha, threshold,
+                                                                time_major, mix, out)
+    dev = _rl_device("x", x, None, True)
+    _rl_device("weight", weight, dev, True)
+    for name, t in (("bias", bias), ("mix residual", res), ("mix m", m), ("mix gate", gate), ("out", out)):
+        if t is not None:
+            _rl_device(name, t, dev, False)
+    y = out if out is not None else torch.empty(out_shape, dtype=torch.float32, device=dev)
+    check(lib().aura_row_linear_gif(x.data_ptr(), R, K, weight.data_ptr(), _p(bias), _p(y), N, int(T), float(decay),
+                                    int(L), float(alpha), float(threshold), int(bool(time_major)), _p(res), _p(m),
+                                    _p(gate), int(ROW_LINEAR_NONTEMPORAL), _stream()),
+          "aura_row_linear_gif")
+    return y
+
+
 # ---------------------------------------------------------------------------------------
 # next token (the rule: include/aura_hip.h, "Next token")
 # ---------------------------------------------------------------------------------------

@@ -1232,6 +1232,50 @@ int aura_row_linear(const float* x, int64_t R, int64_t K, const float* W0, const
                     const float* gamma_or_null, const float* beta_or_null, float eps, float* xh_or_null, int gelu,
                     const float* res_or_null, int nontemporal, void* stream);
 
+/* Row linear: gate epilogue.  The gated memory injection of a decoding step, h + sigmoid(W_g [h; ctx] + b_g) ctx, in
+ * one launch: the half of W_g that meets the memory context is folded into a per-row vector u once per generation
+ * (the retrieved memories are pinned), so a step is one skinny linear layer over h with the epilogue below.
+ *
+ * x [R][K], one matrix W [N][.] whose rows are ldw floats apart, ldw >= K, ldw % 4 == 0 (the left [N][K] block of a
+ * [N][2K] parameter is read in place: nothing is copied or concatenated), b [N] or NULL, and the per-row vectors
+ * u, c, res [R][N].  No prologue, one matrix.  dot, its summation order, the limits on R and K and the
+ * batch-independence property are those of "Row linear"; then
+ *     t = fl(dot + b[n])                      (with a bias)
+ *     a = fl(t + u[r][n])
+ *     s = fl(1 / fl(1 + expf(-a)))            (expf: the device function, 1 ulp; a = -inf..: s = 0, a = +inf: s = 1)
+ *     y[r][n] = fl(res[r][n] + fl(s c[r][n])) (the product is rounded on its own)
+ * Against fp64 on the same fp32 inputs (tests/row_linear_epilogue_rule.py derives it), with d the dot's bound above,
+ * e = 2^-24, s64 the fp64 sigmoid of the fp64 a, and every rounding of the epilogue entered at a whole ulp (2e):
+ *     da = |a - a64| <= d + 2e |a|,      g = s64 (1 - s64) da exp(da),      ds = |s - s64| <= g + 6.5 e (s64 + g),
+ *     |y - y64| <= |c| ds + 2e (|s64 c| + |y64|).
+ *
+ * AURA_E_INVAL: R, K as "Row linear"; a null x, W, u, c, res or y; N < 1 or > 2^31 - 1; ldw < K or ldw % 4 != 0.
+ * AURA_E_ALIGN: x or W not 16-byte aligned, any other pointer not 4-byte aligned.  One launch on `stream`. */
+int aura_row_linear_gate(const float* x, int64_t R, int64_t K, const float* W, int64_t ldw, const float* b_or_null,
+                         const float* u, const float* c, const float* res, float* y, int64_t N, int nontemporal,
+                         void* stream);
+
+/* Row linear: GIF epilogue.  The current t = fl(dot + b) of a skinny linear layer (one matrix, no prologue; dot, its
+ * summation order, the limits on R and K and the batch-independence property are those of "Row linear") feeds the
+ * fp32 GIF step of aura_gif_run (AURA_F32; csrc/aura_gif_model.inl holds the one definition both use) bit for bit,
+ * without the currents ever being written.  Every row, or token, starts from fresh state: v = 0, theta = threshold.
+ *   time-invariant (time_major == 0): each of the R rows runs T steps on its own current; out is the spikes [R][T][N]:
+ *       what aura_gif_run with AURA_GIF_TIME_INVARIANT makes of aura_row_linear's output.
+ *   time-major (time_major != 0): R = tokens x T, R % T == 0; the rows tok T .. tok T + T - 1 are a token's T steps in
+ *       order.  out [tokens][N] is the mean over T, fl(sum / float(T)) (AURA_GIF_MEAN_OUT): what aura_gif_run with
+ *       AURA_GIF_MEAN_OUT makes of aura_row_linear's output viewed as [tokens][T][N].
+ *       With res, m [tokens][N] and gate (one float in device memory, read by the kernel: no host read), all three
+ *       or none, out is instead the hybrid mix with the residual:
+ *           g = fl(1 / fl(1 + expf(-gate[0]))),   y = fl(res + fl(fl(fl(1 - g) m) + fl(g mean))).
+ * 1 <= T <= 32, L >= 1.
+ * AURA_E_INVAL: R, K as "Row linear"; a null x, W or out; N < 1 or > 2^31 - 1; T < 1 or > 32; L < 1; time-major with
+ *   R % T != 0; one or two of res / m / gate; the mix without time_major.  AURA_E_ALIGN: x or W not 16-byte aligned,
+ *   any other pointer not 4-byte aligned.  One launch on `stream`. */
+int aura_row_linear_gif(const float* x, int64_t R, int64_t K, const float* W, const float* b_or_null, float* out,
+                        int64_t N, int64_t T, float decay, int L, float alpha, float threshold, int time_major,
+                        const float* res_or_null, const float* m_or_null, const float* gate_or_null, int nontemporal,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif
