@@ -117,6 +117,21 @@ SIGNATURES = {
     "aura_signal_flag": (I, [P, P, U32, P]),
     "aura_knn_search_ivf2_signal": (I, [P, P, P, P, P, P, P, P, P, P, I64, I64, P, F, I64, I64, I, P, I, P, I32, P, P, P,
                                         I64, P, P, U32, P]),
+    # the list-sorted image in IEEE half: rho16 beside (writers) or instead of (readers) rho
+    "aura_bank_shadow_sorted_f16": (I, [P, P, P, P, P, P, P, I64, I64, P]),
+    "aura_ivf2_append_f16": (I, [P, P, P, P, I64, I64, P, P, P, P, P, P, P, P, P, F, P]),
+    "aura_ivf2_row_constants_f16": (I, [P, P, P, I64, I64, F, P, P]),
+    "aura_knn_search_ivf2_f16": (I, [P, P, P, P, P, P, P, P, P, P, I64, I64, P, F, I64, I64, I, P, I, I32, P, P, P, I64,
+                                     P, P]),
+    "aura_knn_search_ivf2_probed_f16": (I, [P, P, P, P, P, P, P, P, P, P, I64, I64, P, F, I64, I64, I, P, I, P, I32, P, P,
+                                            P, I64, P, P]),
+    "aura_knn_search_ivf2_staged_f16": (I, [P, P, P, P, P, P, P, P, P, P, I64, I64, P, F, I64, I64, I, P, I, P, I32, P, P,
+                                            P, I64, P, I, I, P, P]),
+    "aura_knn_search_ivf2_signal_f16": (I, [P, P, P, P, P, P, P, P, P, P, I64, I64, P, F, I64, I64, I, P, I, P, I32, P, P,
+                                            P, I64, P, P, U32, P]),
+    "aura_bank_find_repeats_f16": (I, [P, P, I64, I64, P, P, I64, P, P, I64, F, P, P, P, P, P, I64, P]),
+    "aura_bank_find_repeats_scoped_f16": (I, [P, P, I64, I64, P, P, I64, P, P, I64, F, P, P, P, P, P, I64, P, P, P]),
+    "aura_bank_blend_f16": (I, [P, P, I64, I64, I64, P, I64, I64, P, P, F, P, P, P, I64, P, P, P, P, I64, P]),
     "aura_stdp_workspace_bytes": (I64, [I64, I64, I64, I64]),
     "aura_stdp_update": (I, [P, P, P, P, P, P, P, P, F, F, F, F, F, F, F, I64, I64, I64, I64, I, I, P, I64, P]),
     "aura_place_code": (I, [P, P, P, P, I64, I64, I64, I64, P, P, P, P, P]),

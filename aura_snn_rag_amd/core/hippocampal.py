@@ -87,14 +87,16 @@ class _EpisodicView(Mapping):
 
 class _IvfState:
     """Inverted lists of the centroid index in the layout ``aura_knn_search_ivf2`` streams: a
-    list-sorted bf16 shadow with ``slack`` free entries behind every list, so that writes are
+    list-sorted 16-bit image with ``slack`` free entries behind every list, so that writes are
     appended in place (``aura_ivf2_append``) and the lists are re-packed only when the centroids
-    are rebuilt or the slack is used up."""
+    are rebuilt or the slack is used up.  The image is IEEE half (``sorted_bf16`` keeps its name): normalised rows
+    lie in [-1, 1], so half's 11 significand bits narrow the prefilter's band 5-6 times against bf16's 8 at the same
+    size; its residual norms are the bank's ``_rho16``.  The row-ordered shadow stays bf16."""
 
     def __init__(self, max_rows: int, D: int, slack: int, device):
         self.slack = slack
         self.n_alloc = ops.ivf2_alloc_rows(max_rows, slack)
-        self.sorted_bf16 = torch.empty(self.n_alloc, D, dtype=torch.bfloat16, device=device)
+        self.sorted_bf16 = torch.empty(self.n_alloc, D, dtype=torch.float16, device=device)
         self.sorted_rows = torch.empty(self.n_alloc, dtype=torch.int32, device=device)
         self.pad_off = torch.zeros(257, dtype=torch.int32, device=device)
         self.list_len = torch.zeros(256, dtype=torch.int32, device=device)
@@ -236,6 +238,7 @@ class HippocampalFormation(nn.Module):
         self._use_shadow = bool(bf16_shadow) and feature_dim % 8 == 0 and feature_dim <= 768
         self._shadow = None
         self._rho = None
+        self._rho16 = None            # residual norms of the list-sorted half image (one per bank row, beside _rho)
         self._shadow_valid_upto = 0
 
         self.id_to_idx: Dict[str, int] = {}
@@ -304,6 +307,7 @@ class HippocampalFormation(nn.Module):
         dev = self.memory_features.device
         if self._rho is None or self._rho.device != dev:
             self._rho = torch.zeros(self.max_memories, dtype=torch.float32, device=dev)
+            self._rho16 = torch.zeros(self.max_memories, dtype=torch.float32, device=dev)
             self._shadow_valid_upto = 0
             if self._ivf is not None:
                 self._ivf.valid = False
@@ -360,7 +364,7 @@ class HippocampalFormation(nn.Module):
         return self._lists[:4]
 
     def _ensure_ivf(self) -> Optional[_IvfState]:
-        """The list-sorted bf16 shadow for the two-stage inverted-list recall (re-packed only after a
+        """The list-sorted half image (and ``_rho16``) for the two-stage inverted-list recall (re-packed only after a
         centroid rebuild or when the slack behind the lists is used up); None when it does not apply."""
         if not self._shadow_applies():
             return None
@@ -384,7 +388,7 @@ class HippocampalFormation(nn.Module):
             st.flag.zero_()
             st.rowc_live = False
             ops.bank_shadow_sorted(self.memory_features, self._inv_norm, st.sorted_rows, st.sorted_bf16, rho,
-                                   st.pos_of_row, st.n_sorted)
+                                   st.pos_of_row, st.n_sorted, rho16=self._rho16)
             st.appended = 0
             st.valid = True
         return st
@@ -398,8 +402,8 @@ class HippocampalFormation(nn.Module):
             st.rowc_live = False
         ver = self.memory_metadata._version
         if not (st.rowc_live and st.rowc_now == nowf and st.rowc_version == ver):
-            ops.ivf2_row_constants(self.memory_metadata, self._rho, st.sorted_rows, st.n_sorted,
-                                   self.memory_features.shape[1], nowf, st.rowc)
+            ops.ivf2_row_constants(self.memory_metadata, self._rho16, st.sorted_rows, st.n_sorted,
+                                   self.memory_features.shape[1], nowf, st.rowc, half=True)
             st.rowc_live, st.rowc_now, st.rowc_version = True, nowf, ver
         return st.rowc
 
@@ -420,7 +424,7 @@ class HippocampalFormation(nn.Module):
         live = st.rowc is not None and st.rowc_live and meta_v0 is not None and st.rowc_version == meta_v0
         ops.ivf2_append(self.memory_features, self._inv_norm, self.memory_metadata, uniq_slots, st.sorted_bf16,
                         st.sorted_rows, st.pad_off, st.list_len, st.pos_of_row, self._rho, st.flag,
-                        row_constants=st.rowc if live else None, row_constants_now=st.rowc_now)
+                        row_constants=st.rowc if live else None, row_constants_now=st.rowc_now, rho16=self._rho16)
         st.appended += n_rows
         st.rowc_live = live
         st.rowc_version = self.memory_metadata._version
@@ -1117,7 +1121,7 @@ class HippocampalFormation(nn.Module):
                     mode = 'shadow'
                 else:
                     kw = dict(image=ivf.sorted_bf16, image_rows=ivf.sorted_rows, n_image=ivf.n_sorted, rho=self._rho,
-                              lists_flag=ivf.flag)
+                              rho16=self._rho16, lists_flag=ivf.flag)
             if mode == 'shadow':
                 shadow = self._ensure_shadow()
                 if shadow is None:
@@ -1168,7 +1172,7 @@ class HippocampalFormation(nn.Module):
         if row0 < 0 and st is not None and st.valid and self._rho is not None and \
                 st.sorted_bf16.device == self.memory_features.device:
             kw.update(sorted_bf16=st.sorted_bf16, sorted_rows=st.sorted_rows, pos_of_row=st.pos_of_row,
-                      n_sorted=st.n_sorted)
+                      n_sorted=st.n_sorted, rho16=self._rho16)
         if kw:
             kw["rho"] = self._rho
         ops.bank_blend(self.memory_features, self._inv_norm, self.memory_count, packed_dev[:n], packed_dev[n:2 * n],
@@ -1785,7 +1789,7 @@ class HippocampalFormation(nn.Module):
         """The validated handle of the current lists (rebuilt only when one of its tensors was replaced)."""
         args = (self.memory_features, self._inv_norm, self.memory_metadata, self.centroids, nprobe, ivf.sorted_bf16,
                 self._rho, ivf.sorted_rows, ivf.pad_off, ivf.list_len, ivf.n_sorted, ivf.flag,
-                self._ivf_row_constants(ivf, now))
+                self._ivf_row_constants(ivf, now), self._rho16)
         if ivf.lists is None or not ivf.lists.holds(*args):
             ivf.lists = ops.Ivf2Lists(*args)
         return ivf.lists

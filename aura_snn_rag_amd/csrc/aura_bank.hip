@@ -45,12 +45,16 @@ __global__ __launch_bounds__(256) void bank_shadow_kernel(const float* __restric
 }
 
 // list-sorted shadow: sorted row i holds the shadow row of bank row sorted_rows[i] (zeros for -1);
-// also refreshes rho[row] and, when given, the reverse map pos_of_row[row] = i
+// also refreshes rho[row] and, when given, the reverse map pos_of_row[row] = i.  F16: the image is IEEE half
+// (aura_row.inl's rule); rho[row] still receives the bf16 residual, bit for bit what bank_shadow_kernel writes (the
+// row-ordered shadow shares that array), and rho16[row], when given, the half image's own
+template <bool F16>
 __global__ __launch_bounds__(256) void bank_shadow_sorted_kernel(const float* __restrict__ bank,
                                                                  const float* __restrict__ inv_norm,
                                                                  const int32_t* __restrict__ sorted_rows,
                                                                  uint16_t* __restrict__ out,
                                                                  float* __restrict__ rho,
+                                                                 float* __restrict__ rho16,
                                                                  int32_t* __restrict__ pos_of_row,
                                                                  int64_t n_sorted, int64_t D) {
     const int lane = threadIdx.x & 63;
@@ -60,9 +64,12 @@ __global__ __launch_bounds__(256) void bank_shadow_sorted_kernel(const float* __
             shadow_zero_row(out + i * D, D, lane);
             continue;
         }
-        const float r = shadow_convert_row(bank + (int64_t)row * D, inv_norm[row], out + i * D, D, lane);
+        float r, r16 = 0.0f;
+        if constexpr (F16) r16 = shadow_convert_row_f16(bank + (int64_t)row * D, inv_norm[row], out + i * D, D, lane, r);
+        else r = shadow_convert_row(bank + (int64_t)row * D, inv_norm[row], out + i * D, D, lane);
         if (lane == 0) {
             rho[row] = r;
+            if (F16 && rho16) rho16[row] = r16;
             if (pos_of_row) pos_of_row[row] = (int32_t)i;
         }
     }
@@ -72,7 +79,9 @@ __global__ __launch_bounds__(256) void bank_shadow_sorted_kernel(const float* __
 // entry (if any) becomes a hole (sorted_rows = -1: scanned as padding), and the row is appended to the
 // list of its centroid id meta[slot][2] (none if < 0) inside the list's slack.  One wave per row.
 // The host guarantees the slack suffices (it counts appended rows and re-packs in time); a list that is
-// full nevertheless sets *flag and drops the row from the lists.
+// full nevertheless sets *flag and drops the row from the lists.  F16: a half image; rho as ever, rho16 (when given)
+// the half residual; the cached constants are those of the half image and need rho16.
+template <bool F16>
 __global__ __launch_bounds__(256) void ivf2_append_kernel(const float* __restrict__ bank,
                                                           const float* __restrict__ inv_norm,
                                                           const float* __restrict__ meta,
@@ -82,7 +91,8 @@ __global__ __launch_bounds__(256) void ivf2_append_kernel(const float* __restric
                                                           const int32_t* __restrict__ pad_off,
                                                           int32_t* __restrict__ list_len,
                                                           int32_t* __restrict__ pos_of_row,
-                                                          float* __restrict__ rho, int32_t* __restrict__ flag,
+                                                          float* __restrict__ rho, float* __restrict__ rho16,
+                                                          int32_t* __restrict__ flag,
                                                           float4* __restrict__ rowc, float rowc_now) {
     const int lane = threadIdx.x & 63;
     const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -93,7 +103,7 @@ __global__ __launch_bounds__(256) void ivf2_append_kernel(const float* __restric
         const int old = pos_of_row[slot];
         if (old >= 0) {
             sorted_rows[old] = -1;
-            if (rowc) rowc[old] = ivf2_row_constants(-1, meta, rho, rowc_now, (float)D);
+            if (rowc) rowc[old] = ivf2_row_constants(-1, meta, rho, rowc_now, (float)D, F16);
         }
         const int c = (int)meta[slot * 4 + 2];
         if (c >= 0 && c < 256) {
@@ -110,13 +120,18 @@ __global__ __launch_bounds__(256) void ivf2_append_kernel(const float* __restric
     }
     pos = __shfl(pos, 0);
     if (pos < 0) return;
-    const float r = shadow_convert_row(bank + slot * D, inv_norm[slot], sorted_bf16 + (int64_t)pos * D, D, lane);
+    float r, r16 = 0.0f;
+    if constexpr (F16) r16 = shadow_convert_row_f16(bank + slot * D, inv_norm[slot], sorted_bf16 + (int64_t)pos * D, D, lane, r);
+    else r = shadow_convert_row(bank + slot * D, inv_norm[slot], sorted_bf16 + (int64_t)pos * D, D, lane);
     if (lane == 0) {
         rho[slot] = r;
+        if (F16 && rho16) rho16[slot] = r16;
         // the caller's cached score constants (aura_ivf2_row_constants) follow the new entry
         if (rowc) {
             const float4 m = *reinterpret_cast<const float4*>(meta + slot * 4);
-            rowc[pos] = coarse_row_constants(m, 0.0f, &r, rowc_now, aura_e_fix((float)D), 0.0f, coarse_eq_worst((float)D),
+            const float r_img = F16 ? r16 : r;
+            rowc[pos] = coarse_row_constants(m, 0.0f, &r_img, rowc_now, aura_e_fix((float)D), 0.0f,
+                                             F16 ? coarse_eq_worst_f16((float)D) : coarse_eq_worst((float)D),
                                              __int_as_float((int32_t)slot));
         }
     }
@@ -378,18 +393,62 @@ int aura_bank_shadow_update(const float* bank, const float* inv_norm, uint16_t* 
     return aura_check_launch();
 }
 
+static int bank_shadow_sorted_impl(bool f16, const float* bank, const float* inv_norm, const int32_t* sorted_rows,
+                                   uint16_t* image, float* rho, float* rho16, int32_t* pos_of_row, int64_t n_sorted,
+                                   int64_t D, void* stream) {
+    if (n_sorted < 0 || D <= 0 || (D & 7)) return AURA_E_INVAL;
+    if (n_sorted == 0) return AURA_OK;
+    if (!bank || !inv_norm || !sorted_rows || !image || !rho) return AURA_E_INVAL;
+    if ((reinterpret_cast<uintptr_t>(bank) & 15) || (reinterpret_cast<uintptr_t>(image) & 15)) return AURA_E_ALIGN;
+    int64_t blocks = (n_sorted + 3) / 4;
+    if (blocks > 16384) blocks = 16384;
+    if (f16)
+        hipLaunchKernelGGL(bank_shadow_sorted_kernel<true>, dim3((unsigned)blocks), dim3(256), 0,
+                           static_cast<hipStream_t>(stream), bank, inv_norm, sorted_rows, image, rho, rho16, pos_of_row,
+                           n_sorted, D);
+    else
+        hipLaunchKernelGGL(bank_shadow_sorted_kernel<false>, dim3((unsigned)blocks), dim3(256), 0,
+                           static_cast<hipStream_t>(stream), bank, inv_norm, sorted_rows, image, rho, rho16, pos_of_row,
+                           n_sorted, D);
+    return aura_check_launch();
+}
+
 int aura_bank_shadow_sorted(const float* bank, const float* inv_norm, const int32_t* sorted_rows,
                             uint16_t* sorted_bf16, float* rho, int32_t* pos_of_row, int64_t n_sorted, int64_t D,
                             void* stream) {
-    if (n_sorted < 0 || D <= 0 || (D & 7)) return AURA_E_INVAL;
-    if (n_sorted == 0) return AURA_OK;
-    if (!bank || !inv_norm || !sorted_rows || !sorted_bf16 || !rho) return AURA_E_INVAL;
-    if ((reinterpret_cast<uintptr_t>(bank) & 15) || (reinterpret_cast<uintptr_t>(sorted_bf16) & 15)) return AURA_E_ALIGN;
-    int64_t blocks = (n_sorted + 3) / 4;
-    if (blocks > 16384) blocks = 16384;
-    hipLaunchKernelGGL(bank_shadow_sorted_kernel, dim3((unsigned)blocks), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), bank, inv_norm, sorted_rows, sorted_bf16, rho, pos_of_row,
-                       n_sorted, D);
+    return bank_shadow_sorted_impl(false, bank, inv_norm, sorted_rows, sorted_bf16, rho, nullptr, pos_of_row, n_sorted, D,
+                                   stream);
+}
+
+int aura_bank_shadow_sorted_f16(const float* bank, const float* inv_norm, const int32_t* sorted_rows,
+                                uint16_t* sorted_f16, float* rho, float* rho16, int32_t* pos_of_row, int64_t n_sorted,
+                                int64_t D, void* stream) {
+    return bank_shadow_sorted_impl(true, bank, inv_norm, sorted_rows, sorted_f16, rho, rho16, pos_of_row, n_sorted, D,
+                                   stream);
+}
+
+static int ivf2_append_impl(bool f16, const float* bank, const float* inv_norm, const float* meta, const int64_t* slots,
+                            int64_t n, int64_t D, uint16_t* image, int32_t* sorted_rows, const int32_t* pad_off,
+                            int32_t* list_len, int32_t* pos_of_row, float* rho, float* rho16, int32_t* flag,
+                            float* row_constants, float row_constants_now, void* stream) {
+    if (n < 0 || D <= 0 || (D & 7)) return AURA_E_INVAL;
+    if (reinterpret_cast<uintptr_t>(row_constants) & 15) return AURA_E_ALIGN;
+    if (n == 0) return AURA_OK;
+    if (!bank || !inv_norm || !meta || !slots || !image || !sorted_rows || !pad_off || !list_len ||
+        !pos_of_row || !rho || !flag)
+        return AURA_E_INVAL;
+    if (f16 && row_constants && !rho16) return AURA_E_INVAL;   // the half image's constants come from rho16
+    if ((reinterpret_cast<uintptr_t>(bank) & 15) || (reinterpret_cast<uintptr_t>(image) & 15)) return AURA_E_ALIGN;
+    if (f16)
+        hipLaunchKernelGGL(ivf2_append_kernel<true>, dim3((unsigned)((n + 3) / 4)), dim3(256), 0,
+                           static_cast<hipStream_t>(stream), bank, inv_norm, meta, slots, n, D, image, sorted_rows,
+                           pad_off, list_len, pos_of_row, rho, rho16, flag, reinterpret_cast<float4*>(row_constants),
+                           row_constants_now);
+    else
+        hipLaunchKernelGGL(ivf2_append_kernel<false>, dim3((unsigned)((n + 3) / 4)), dim3(256), 0,
+                           static_cast<hipStream_t>(stream), bank, inv_norm, meta, slots, n, D, image, sorted_rows,
+                           pad_off, list_len, pos_of_row, rho, rho16, flag, reinterpret_cast<float4*>(row_constants),
+                           row_constants_now);
     return aura_check_launch();
 }
 
@@ -397,18 +456,16 @@ int aura_ivf2_append(const float* bank, const float* inv_norm, const float* meta
                      int64_t n, int64_t D, uint16_t* sorted_bf16, int32_t* sorted_rows, const int32_t* pad_off,
                      int32_t* list_len, int32_t* pos_of_row, float* rho, int32_t* flag, float* row_constants,
                      float row_constants_now, void* stream) {
-    if (n < 0 || D <= 0 || (D & 7)) return AURA_E_INVAL;
-    if (reinterpret_cast<uintptr_t>(row_constants) & 15) return AURA_E_ALIGN;
-    if (n == 0) return AURA_OK;
-    if (!bank || !inv_norm || !meta || !slots || !sorted_bf16 || !sorted_rows || !pad_off || !list_len ||
-        !pos_of_row || !rho || !flag)
-        return AURA_E_INVAL;
-    if ((reinterpret_cast<uintptr_t>(bank) & 15) || (reinterpret_cast<uintptr_t>(sorted_bf16) & 15)) return AURA_E_ALIGN;
-    hipLaunchKernelGGL(ivf2_append_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), bank, inv_norm, meta, slots, n, D, sorted_bf16, sorted_rows,
-                       pad_off, list_len, pos_of_row, rho, flag, reinterpret_cast<float4*>(row_constants),
-                       row_constants_now);
-    return aura_check_launch();
+    return ivf2_append_impl(false, bank, inv_norm, meta, slots, n, D, sorted_bf16, sorted_rows, pad_off, list_len,
+                            pos_of_row, rho, nullptr, flag, row_constants, row_constants_now, stream);
+}
+
+int aura_ivf2_append_f16(const float* bank, const float* inv_norm, const float* meta, const int64_t* slots,
+                         int64_t n, int64_t D, uint16_t* sorted_f16, int32_t* sorted_rows, const int32_t* pad_off,
+                         int32_t* list_len, int32_t* pos_of_row, float* rho, float* rho16, int32_t* flag,
+                         float* row_constants, float row_constants_now, void* stream) {
+    return ivf2_append_impl(true, bank, inv_norm, meta, slots, n, D, sorted_f16, sorted_rows, pad_off, list_len,
+                            pos_of_row, rho, rho16, flag, row_constants, row_constants_now, stream);
 }
 
 int64_t aura_kmeans_means_workspace_bytes(int64_t N, int64_t D, int k) {

@@ -45,6 +45,8 @@ struct BlendArgs {
     const int32_t* sorted_rows;
     const int32_t* pos_of_row;
     int64_t n_sorted;
+    bool image_f16;                     // the list-sorted image is IEEE half (aura_bank_blend_f16)
+    float* rho16;                       // ... and this, when given, receives its residual norm; rho the bf16 one as ever
 };
 
 // Group key of batch row i as one int: held row r -> r; batch row j -> -2 - j; BLEND_NONE otherwise.  Every id is
@@ -136,8 +138,13 @@ __global__ __launch_bounds__(256) void bank_blend_kernel(const BlendArgs a) {
     if (a.sorted_bf16) {
         const int p = a.pos_of_row[kr];
         if (p >= 0 && p < a.n_sorted && a.sorted_rows[p] == (int32_t)kr) {
-            const float r = shadow_convert_row(g, inv, a.sorted_bf16 + (int64_t)p * D, D, lane);
-            if (lane == 0) a.rho[kr] = r;
+            float r, r16 = 0.0f;
+            if (a.image_f16) r16 = shadow_convert_row_f16(g, inv, a.sorted_bf16 + (int64_t)p * D, D, lane, r);
+            else r = shadow_convert_row(g, inv, a.sorted_bf16 + (int64_t)p * D, D, lane);
+            if (lane == 0) {
+                a.rho[kr] = r;
+                if (a.image_f16 && a.rho16) a.rho16[kr] = r16;
+            }
         }
     }
 }
@@ -148,11 +155,11 @@ inline bool misaligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p)
 
 extern "C" {
 
-int aura_bank_blend(float* bank, float* inv_norm, int64_t N, int64_t rows, int64_t D, const float* feats,
-                    int64_t feats_row0, int64_t n, const int32_t* stored_target, const int32_t* batch_leader,
-                    float beta, float* out_feats, uint16_t* shadow_bf16, float* rho, int64_t shadow_upto,
-                    uint16_t* sorted_bf16, const int32_t* sorted_rows, const int32_t* pos_of_row, int64_t n_sorted,
-                    void* stream) {
+static int bank_blend_impl(float* bank, float* inv_norm, int64_t N, int64_t rows, int64_t D, const float* feats,
+                           int64_t feats_row0, int64_t n, const int32_t* stored_target, const int32_t* batch_leader,
+                           float beta, float* out_feats, uint16_t* shadow_bf16, float* rho, int64_t shadow_upto,
+                           uint16_t* sorted_bf16, const int32_t* sorted_rows, const int32_t* pos_of_row, int64_t n_sorted,
+                           void* stream, bool image_f16, float* rho16) {
     if (n < 0 || n > 1024 || D < 1 || D > 4096 || N < 0 || rows < N || rows > 0x7fffffff) return AURA_E_INVAL;
     if (!(beta > 0.0f && beta <= 1.0f)) return AURA_E_INVAL;
     if (feats_row0 < -1) return AURA_E_INVAL;
@@ -175,6 +182,7 @@ int aura_bank_blend(float* bank, float* inv_norm, int64_t N, int64_t rows, int64
     a.n = n; a.stored = stored_target; a.leader = batch_leader; a.beta = beta;
     a.shadow = shadow_bf16; a.rho = rho; a.shadow_upto = shadow_bf16 ? shadow_upto : 0;
     a.sorted_bf16 = sorted_bf16; a.sorted_rows = sorted_rows; a.pos_of_row = pos_of_row; a.n_sorted = n_sorted;
+    a.image_f16 = image_f16 && has_image; a.rho16 = a.image_f16 ? rho16 : nullptr;
     // 16-byte accesses exactly where aura_bank_row_norms takes them (D % 4 == 0, an aligned bank): the sum of squares
     // must associate alike.  Batch rows that such a bank cannot be read with are refused, not read narrower.
     const bool vec4 = (D % 4 == 0) && !misaligned16(bank);
@@ -186,6 +194,27 @@ int aura_bank_blend(float* bank, float* inv_norm, int64_t N, int64_t rows, int64
     if (vec4) hipLaunchKernelGGL(bank_blend_kernel<true>, grid, block, lds, s, a);
     else hipLaunchKernelGGL(bank_blend_kernel<false>, grid, block, lds, s, a);
     return aura_check_launch();
+}
+
+int aura_bank_blend(float* bank, float* inv_norm, int64_t N, int64_t rows, int64_t D, const float* feats,
+                    int64_t feats_row0, int64_t n, const int32_t* stored_target, const int32_t* batch_leader,
+                    float beta, float* out_feats, uint16_t* shadow_bf16, float* rho, int64_t shadow_upto,
+                    uint16_t* sorted_bf16, const int32_t* sorted_rows, const int32_t* pos_of_row, int64_t n_sorted,
+                    void* stream) {
+    return bank_blend_impl(bank, inv_norm, N, rows, D, feats, feats_row0, n, stored_target, batch_leader, beta, out_feats,
+                           shadow_bf16, rho, shadow_upto, sorted_bf16, sorted_rows, pos_of_row, n_sorted, stream, false,
+                           nullptr);
+}
+
+// aura_bank_blend with an IEEE half list-sorted image; rho16 (optional) follows the image, rho the bf16 residual
+int aura_bank_blend_f16(float* bank, float* inv_norm, int64_t N, int64_t rows, int64_t D, const float* feats,
+                        int64_t feats_row0, int64_t n, const int32_t* stored_target, const int32_t* batch_leader,
+                        float beta, float* out_feats, uint16_t* shadow_bf16, float* rho, int64_t shadow_upto,
+                        uint16_t* sorted_f16, float* rho16, const int32_t* sorted_rows, const int32_t* pos_of_row,
+                        int64_t n_sorted, void* stream) {
+    return bank_blend_impl(bank, inv_norm, N, rows, D, feats, feats_row0, n, stored_target, batch_leader, beta, out_feats,
+                           shadow_bf16, rho, shadow_upto, sorted_f16, sorted_rows, pos_of_row, n_sorted, stream, true,
+                           rho16);
 }
 
 }  // extern "C"

@@ -42,6 +42,7 @@ namespace {
 
 typedef float f32x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned long long u64;
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));     // (HIP's uint4 is a struct: arrays of it stay in scratch)
 
@@ -131,9 +132,19 @@ __global__ __launch_bounds__(256) void cs_prep_kernel(const float* __restrict__ 
                 const int64_t k = 8 * (int64_t)c + e;
                 v[e] = (ok && k < D) ? x[(int64_t)q * D + k] * iq : 0.0f;
             }
-            const bf16x8 bv = __builtin_convertvector(v, bf16x8);
-            *reinterpret_cast<bf16x8*>(dst + 8 * c) = bv;
-            const f32x8 back = __builtin_convertvector(bv, f32x8);
+            f32x8 back;
+            if (with_image == 2) {            // IEEE half under the image's rule: nearest-even, |x| < 2^-14 stored as 0
+                f32x8 vf = v;
+#pragma unroll
+                for (int e = 0; e < 8; ++e) vf[e] = fabsf(v[e]) < 6.103515625e-05f ? 0.0f : v[e];
+                const f16x8 hv = __builtin_convertvector(vf, f16x8);
+                *reinterpret_cast<f16x8*>(dst + 8 * c) = hv;
+                back = __builtin_convertvector(hv, f32x8);
+            } else {
+                const bf16x8 bv = __builtin_convertvector(v, bf16x8);
+                *reinterpret_cast<bf16x8*>(dst + 8 * c) = bv;
+                back = __builtin_convertvector(bv, f32x8);
+            }
 #pragma unroll
             for (int e = 0; e < 8; ++e) { const float d = back[e] - v[e]; e2 = fmaf(d, d, e2); }
         }
@@ -156,7 +167,9 @@ __global__ __launch_bounds__(256) void cs_prep_kernel(const float* __restrict__ 
 }
 
 // ---- image scan.  KS = 16-column steps held per image row (a multiple of 8: the swizzle works on 16 chunks).
-template <int KS, bool SCOPED>
+// F16: image and batch rows are IEEE half (the list-sorted image of the inverted lists), rho is that image's rho16 and
+// the MFMA the f16 one of the same shape.
+template <int KS, bool SCOPED, bool F16>
 __global__ __launch_bounds__(256, 1) void cs_scan_kernel(const uint16_t* __restrict__ image,
                                                          const int32_t* __restrict__ image_rows, int64_t n_image,
                                                          int64_t N, int D, const float* __restrict__ rho,
@@ -243,8 +256,12 @@ __global__ __launch_bounds__(256, 1) void cs_scan_kernel(const uint16_t* __restr
             __builtin_amdgcn_sched_barrier(0);          // (the scheduler sinks the reads to their MFMAs otherwise)
 #pragma unroll
             for (int j = 0; j < 4; ++j)
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[4 * g + j], __builtin_bit_cast(bf16x8, bq[g & 1][j]), acc,
-                                                              0, 0, 0);
+                if constexpr (F16)
+                    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a[4 * g + j]),
+                                                                 __builtin_bit_cast(f16x8, bq[g & 1][j]), acc, 0, 0, 0);
+                else
+                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[4 * g + j], __builtin_bit_cast(bf16x8, bq[g & 1][j]), acc,
+                                                                  0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
         }
         // survive: cos_bf16 + rho_r + eq + rho_r eq + fix >= tau
@@ -500,16 +517,16 @@ __global__ __launch_bounds__(256) void cs_touch_kernel(float* __restrict__ meta,
     if (r >= 0 && (int64_t)r < count) meta[(int64_t)r * 4 + 1] = now;      // duplicates store the same value
 }
 
-template <int KS, bool SCOPED>
+template <int KS, bool SCOPED, bool F16>
 int launch_scan(const uint16_t* image, const int32_t* image_rows, int64_t n_image, int64_t N, int D, const float* rho,
                 const Workspace& w, int n_tiles, float tau, float fix, const float* meta, hipStream_t s) {
     constexpr int lds = 2 * 32 * 2 * KS * 16;
     if (lds > 64 * 1024) {
-        const int rc = aura_ensure_lds_attr(reinterpret_cast<const void*>(&cs_scan_kernel<KS, SCOPED>), lds);
+        const int rc = aura_ensure_lds_attr(reinterpret_cast<const void*>(&cs_scan_kernel<KS, SCOPED, F16>), lds);
         if (rc != AURA_OK) return rc;
     }
     const unsigned blocks = (unsigned)((n_image + 127) / 128);
-    hipLaunchKernelGGL((cs_scan_kernel<KS, SCOPED>), dim3(blocks), dim3(256), lds, s, image, image_rows, n_image, N, D,
+    hipLaunchKernelGGL((cs_scan_kernel<KS, SCOPED, F16>), dim3(blocks), dim3(256), lds, s, image, image_rows, n_image, N, D,
                        rho, w.qhat, w.eq, n_tiles, tau, fix, w.cnt, w.list, meta, w.tag);
     return aura_check_launch();
 }
@@ -529,7 +546,7 @@ int launch_dense(bool vec, const float* A, const float* ainv, int64_t NA, const 
 }
 
 
-template <bool SCOPED>
+template <bool SCOPED, bool F16 = false>      // F16: the image is IEEE half and `rho` its rho16
 int find_repeats_impl(const float* bank, const float* inv_norm, int64_t N, int64_t D, const uint16_t* image_bf16,
                       const int32_t* image_rows, int64_t n_image, const float* rho, const float* feats, int64_t n,
                       float tau, int32_t* stored_target, int32_t* batch_leader, float* cos_out, int32_t* overflow_out,
@@ -556,7 +573,7 @@ int find_repeats_impl(const float* bank, const float* inv_norm, int64_t N, int64
     const Workspace w = carve(workspace, n_pad);
     const int ks = with_image ? (int)((D + 127) / 128) * 8 : 0;          // 16-column steps, a multiple of 8
     hipLaunchKernelGGL(cs_prep_kernel, dim3((unsigned)(n_pad / 4)), dim3(256), 0, s, feats, nn, n_pad, D, ks * 16, w,
-                       with_image ? 1 : 0, overflow_out, SCOPED ? batch_tags : nullptr);
+                       with_image ? (F16 ? 2 : 1) : 0, overflow_out, SCOPED ? batch_tags : nullptr);
     int rc = aura_check_launch();
     if (rc != AURA_OK) return rc;
     if (with_image && n_image > 0) {
@@ -564,12 +581,12 @@ int find_repeats_impl(const float* bank, const float* inv_norm, int64_t N, int64
         const float fix = 2.0f * (float)D * 5.9604645e-8f + 1e-5f;
         const int n_tiles = (nn + 31) / 32;
         switch (ks) {
-        case 8: rc = launch_scan<8, SCOPED>(image_bf16, image_rows, n_image, N, (int)D, rho, w, n_tiles, tau, fix, meta, s); break;
-        case 16: rc = launch_scan<16, SCOPED>(image_bf16, image_rows, n_image, N, (int)D, rho, w, n_tiles, tau, fix, meta, s); break;
-        case 24: rc = launch_scan<24, SCOPED>(image_bf16, image_rows, n_image, N, (int)D, rho, w, n_tiles, tau, fix, meta, s); break;
-        case 32: rc = launch_scan<32, SCOPED>(image_bf16, image_rows, n_image, N, (int)D, rho, w, n_tiles, tau, fix, meta, s); break;
-        case 40: rc = launch_scan<40, SCOPED>(image_bf16, image_rows, n_image, N, (int)D, rho, w, n_tiles, tau, fix, meta, s); break;
-        default: rc = launch_scan<48, SCOPED>(image_bf16, image_rows, n_image, N, (int)D, rho, w, n_tiles, tau, fix, meta, s); break;
+        case 8: rc = launch_scan<8, SCOPED, F16>(image_bf16, image_rows, n_image, N, (int)D, rho, w, n_tiles, tau, fix, meta, s); break;
+        case 16: rc = launch_scan<16, SCOPED, F16>(image_bf16, image_rows, n_image, N, (int)D, rho, w, n_tiles, tau, fix, meta, s); break;
+        case 24: rc = launch_scan<24, SCOPED, F16>(image_bf16, image_rows, n_image, N, (int)D, rho, w, n_tiles, tau, fix, meta, s); break;
+        case 32: rc = launch_scan<32, SCOPED, F16>(image_bf16, image_rows, n_image, N, (int)D, rho, w, n_tiles, tau, fix, meta, s); break;
+        case 40: rc = launch_scan<40, SCOPED, F16>(image_bf16, image_rows, n_image, N, (int)D, rho, w, n_tiles, tau, fix, meta, s); break;
+        default: rc = launch_scan<48, SCOPED, F16>(image_bf16, image_rows, n_image, N, (int)D, rho, w, n_tiles, tau, fix, meta, s); break;
         }
         if (rc != AURA_OK) return rc;
     }
@@ -619,6 +636,27 @@ int aura_bank_find_repeats_scoped(const float* bank, const float* inv_norm, int6
     return find_repeats_impl<true>(bank, inv_norm, N, D, image_bf16, image_rows, n_image, rho, feats, n, tau,
                                    stored_target, batch_leader, cos_out, overflow_out, workspace, workspace_bytes, stream,
                                    meta, batch_tags);
+}
+
+// ---- the same over an IEEE half image (aura_bank_shadow_sorted_f16) with its rho16 ----
+int aura_bank_find_repeats_f16(const float* bank, const float* inv_norm, int64_t N, int64_t D, const uint16_t* image_f16,
+                               const int32_t* image_rows, int64_t n_image, const float* rho16, const float* feats,
+                               int64_t n, float tau, int32_t* stored_target, int32_t* batch_leader, float* cos_out,
+                               int32_t* overflow_out, void* workspace, int64_t workspace_bytes, void* stream) {
+    return find_repeats_impl<false, true>(bank, inv_norm, N, D, image_f16, image_rows, n_image, rho16, feats, n, tau,
+                                          stored_target, batch_leader, cos_out, overflow_out, workspace, workspace_bytes,
+                                          stream, nullptr, nullptr);
+}
+
+int aura_bank_find_repeats_scoped_f16(const float* bank, const float* inv_norm, int64_t N, int64_t D,
+                                      const uint16_t* image_f16, const int32_t* image_rows, int64_t n_image,
+                                      const float* rho16, const float* feats, int64_t n, float tau,
+                                      int32_t* stored_target, int32_t* batch_leader, float* cos_out,
+                                      int32_t* overflow_out, void* workspace, int64_t workspace_bytes, void* stream,
+                                      const float* meta, const int32_t* batch_tags) {
+    return find_repeats_impl<true, true>(bank, inv_norm, N, D, image_f16, image_rows, n_image, rho16, feats, n, tau,
+                                         stored_target, batch_leader, cos_out, overflow_out, workspace, workspace_bytes,
+                                         stream, meta, batch_tags);
 }
 
 int aura_bank_touch(float* meta, int64_t count, const int32_t* rows, int64_t n, float now, void* stream) {

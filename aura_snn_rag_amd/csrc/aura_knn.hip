@@ -3013,7 +3013,8 @@ int aura_centroid_probe(const float* centroids, const float* queries, int64_t D,
     return launch_probe(centroids, queries, D, (int)nq, nprobe, dist, mask, ids_out, static_cast<hipStream_t>(stream));
 }
 
-static int knn_search_ivf2_impl(const float* bank, const float* inv_norm, const float* meta,
+// f16: the sorted image is IEEE half (aura_bank_shadow_sorted_f16) and `rho` is its rho16
+static int knn_search_ivf2_impl(bool f16, const float* bank, const float* inv_norm, const float* meta,
                          const uint16_t* sorted_bf16, const float* rho, const int32_t* sorted_rows, const int32_t* pad_off,
                          const int32_t* list_len, const int32_t* lists_flag, int64_t n_sorted, int64_t N,
                          const float* queries, float now,
@@ -3082,7 +3083,7 @@ static int knn_search_ivf2_impl(const float* bank, const float* inv_norm, const 
     if (!rowc) {
         if (stage_a) {
             hipLaunchKernelGGL(ivf2_rowc_kernel, dim3((unsigned)((n_sorted + 255) / 256)), dim3(256), 0, s,
-                               meta, rho, sorted_rows, n_sorted, now, (float)D, w.rowc);
+                               meta, rho, sorted_rows, n_sorted, now, (float)D, w.rowc, f16);
             if ((rc = aura_check_launch())) return rc;
         }
         rowc = w.rowc;
@@ -3092,9 +3093,14 @@ static int knn_search_ivf2_impl(const float* bank, const float* inv_norm, const 
         const float* qptr = queries + qb0 * D;
         if (stage_a) {
         // per query: 1/||q||, bf16 fragments, eq; resets of the pass (per-list counters, qslot, the call's flag)
-        hipLaunchKernelGGL(ivf2_qprep_kernel, dim3((unsigned)((nqb + 1 + 3) / 4)), dim3(256), 0, s,
-                           qptr, (int64_t)nqb, D, KS, w.qhat, w.inv_q, w.eq_q, w.qslot, w.lq_cnt,
-                           qb0 == 0 ? overflow_out : nullptr, lists_flag);
+        if (f16)
+            hipLaunchKernelGGL(ivf2_qprep_kernel<true>, dim3((unsigned)((nqb + 1 + 3) / 4)), dim3(256), 0, s,
+                               qptr, (int64_t)nqb, D, KS, w.qhat, w.inv_q, w.eq_q, w.qslot, w.lq_cnt,
+                               qb0 == 0 ? overflow_out : nullptr, lists_flag);
+        else
+            hipLaunchKernelGGL(ivf2_qprep_kernel<false>, dim3((unsigned)((nqb + 1 + 3) / 4)), dim3(256), 0, s,
+                               qptr, (int64_t)nqb, D, KS, w.qhat, w.inv_q, w.eq_q, w.qslot, w.lq_cnt,
+                               qb0 == 0 ? overflow_out : nullptr, lists_flag);
         if ((rc = aura_check_launch())) return rc;
         stage("query prep");
         // the probe launch also fills the per-list query lists (lq_cnt / lq_list); probes that the caller
@@ -3129,20 +3135,24 @@ static int knn_search_ivf2_impl(const float* bank, const float* inv_norm, const 
         c.gmax = w.gmax; c.gmax_ld = 2 * stiles; c.item_off = w.sitem_off;
         const int cs_dbg = cs_dbg_flags();
         c.dbg = cs_dbg;
-        auto launch = [&](int mode) -> int {
+        auto launch_fmt = [&](int mode, auto F) -> int {
+            constexpr bool F16 = decltype(F)::value;
             if (wg4) {
-                if (KS == 8) return launch_coarse_ivf<8, 4, 2>(c, mode, 2 * cus, s);
-                if (KS == 16) return launch_coarse_ivf<16, 4, 2>(c, mode, 2 * cus, s);
-                return launch_coarse_ivf<24, 4, 2>(c, mode, 2 * cus, s);
+                if (KS == 8) return launch_coarse_ivf<8, 4, 2, F16>(c, mode, 2 * cus, s);
+                if (KS == 16) return launch_coarse_ivf<16, 4, 2, F16>(c, mode, 2 * cus, s);
+                return launch_coarse_ivf<24, 4, 2, F16>(c, mode, 2 * cus, s);
             }
             if (w4) {
-                if (KS == 8) return launch_coarse_ivf<8, 4>(c, mode, cus, s);
-                if (KS == 16) return launch_coarse_ivf<16, 4>(c, mode, cus, s);
-                return launch_coarse_ivf<24, 4>(c, mode, cus, s);
+                if (KS == 8) return launch_coarse_ivf<8, 4, 4, F16>(c, mode, cus, s);
+                if (KS == 16) return launch_coarse_ivf<16, 4, 4, F16>(c, mode, cus, s);
+                return launch_coarse_ivf<24, 4, 4, F16>(c, mode, cus, s);
             }
-            if (KS == 8) return launch_coarse_ivf<8, 8>(c, mode, cus, s);
-            if (KS == 16) return launch_coarse_ivf<16, 8>(c, mode, cus, s);
-            return launch_coarse_ivf<24, 8>(c, mode, cus, s);
+            if (KS == 8) return launch_coarse_ivf<8, 8, 2, F16>(c, mode, cus, s);
+            if (KS == 16) return launch_coarse_ivf<16, 8, 2, F16>(c, mode, cus, s);
+            return launch_coarse_ivf<24, 8, 2, F16>(c, mode, cus, s);
+        };
+        auto launch = [&](int mode) -> int {
+            return f16 ? launch_fmt(mode, std::true_type{}) : launch_fmt(mode, std::false_type{});
         };
         if (stage_a) {
         if ((rc = launch(CS_MODE_SAMPLE))) return rc;
@@ -3208,7 +3218,8 @@ static int knn_search_ivf2_impl(const float* bank, const float* inv_norm, const 
         RefineArgs r{};
         r.bank = bank; r.inv_norm = inv_norm; r.meta = meta; r.queries = qptr; r.inv_q = w.inv_q;
         r.now = now; r.e_cos = 0.0f; r.N = N; r.D = D; r.k = k; r.cnt = w.cnt;
-        r.rho = rho; r.eq = w.eq_q; r.e_fix = e_fix; r.eq_worst = coarse_eq_worst((float)D);
+        r.rho = rho; r.eq = w.eq_q; r.e_fix = e_fix;
+        r.eq_worst = f16 ? coarse_eq_worst_f16((float)D) : coarse_eq_worst((float)D);
         r.cand_scores = w.cand_scores; r.cand_idx = w.cand_idx; r.cap = w.cap; r.idx_base = idx_base;
         r.out_scores = out_scores + qb0 * k; r.out_idx = out_idx + qb0 * k; r.overflow = overflow_out;
         if (stg == 4) {
@@ -3266,7 +3277,7 @@ int aura_ivf2_row_constants(const float* meta, const float* rho, const int32_t* 
     if ((reinterpret_cast<uintptr_t>(meta) & 15) || (reinterpret_cast<uintptr_t>(row_constants) & 15)) return AURA_E_ALIGN;
     hipLaunchKernelGGL(ivf2_rowc_kernel, dim3((unsigned)((n_sorted + 255) / 256)), dim3(256), 0,
                        static_cast<hipStream_t>(stream), meta, rho, sorted_rows, n_sorted, now, (float)D,
-                       reinterpret_cast<float4*>(row_constants));
+                       reinterpret_cast<float4*>(row_constants), false);
     return aura_check_launch();
 }
 
@@ -3279,7 +3290,7 @@ int aura_knn_search_ivf2(const float* bank, const float* inv_norm, const float* 
                          int32_t* out_idx, void* workspace, int64_t workspace_bytes,
                          int32_t* overflow_out, void* stream) {
     if (reinterpret_cast<uintptr_t>(row_constants) & 15) return AURA_E_ALIGN;
-    return knn_search_ivf2_impl(bank, inv_norm, meta, sorted_bf16, rho, sorted_rows, pad_off, list_len, lists_flag,
+    return knn_search_ivf2_impl(false, bank, inv_norm, meta, sorted_bf16, rho, sorted_rows, pad_off, list_len, lists_flag,
                                 n_sorted, N, queries, now, D, nq, k, centroids, nprobe, idx_base, out_scores, out_idx,
                                 workspace, workspace_bytes, overflow_out, nullptr,
                                 reinterpret_cast<const float4*>(row_constants), stream);
@@ -3295,7 +3306,51 @@ int aura_knn_search_ivf2_probed(const float* bank, const float* inv_norm, const 
                                 int32_t* overflow_out, void* stream) {
     if (!probe_ids) return AURA_E_INVAL;
     if (reinterpret_cast<uintptr_t>(row_constants) & 15) return AURA_E_ALIGN;
-    return knn_search_ivf2_impl(bank, inv_norm, meta, sorted_bf16, rho, sorted_rows, pad_off, list_len, lists_flag,
+    return knn_search_ivf2_impl(false, bank, inv_norm, meta, sorted_bf16, rho, sorted_rows, pad_off, list_len, lists_flag,
+                                n_sorted, N, queries, now, D, nq, k, centroids, nprobe, idx_base, out_scores, out_idx,
+                                workspace, workspace_bytes, overflow_out, probe_ids,
+                                reinterpret_cast<const float4*>(row_constants), stream);
+}
+
+// ---- the same entry points over an IEEE half image (aura_bank_shadow_sorted_f16): `rho16` in rho's place ----
+int aura_ivf2_row_constants_f16(const float* meta, const float* rho16, const int32_t* sorted_rows, int64_t n_sorted,
+                            int64_t D, float now, float* row_constants, void* stream) {
+    if (n_sorted < 0 || n_sorted > 0x7ffffff0LL || D <= 0) return AURA_E_INVAL;
+    if (n_sorted == 0) return AURA_OK;
+    if (!meta || !rho16 || !sorted_rows || !row_constants) return AURA_E_INVAL;
+    if ((reinterpret_cast<uintptr_t>(meta) & 15) || (reinterpret_cast<uintptr_t>(row_constants) & 15)) return AURA_E_ALIGN;
+    hipLaunchKernelGGL(ivf2_rowc_kernel, dim3((unsigned)((n_sorted + 255) / 256)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), meta, rho16, sorted_rows, n_sorted, now, (float)D,
+                       reinterpret_cast<float4*>(row_constants), true);
+    return aura_check_launch();
+}
+
+int aura_knn_search_ivf2_f16(const float* bank, const float* inv_norm, const float* meta,
+                         const uint16_t* sorted_f16, const float* rho16, const int32_t* sorted_rows, const int32_t* pad_off,
+                         const int32_t* list_len, const int32_t* lists_flag, const float* row_constants,
+                         int64_t n_sorted, int64_t N,
+                         const float* queries, float now, int64_t D, int64_t nq, int k,
+                         const float* centroids, int nprobe, int32_t idx_base, float* out_scores,
+                         int32_t* out_idx, void* workspace, int64_t workspace_bytes,
+                         int32_t* overflow_out, void* stream) {
+    if (reinterpret_cast<uintptr_t>(row_constants) & 15) return AURA_E_ALIGN;
+    return knn_search_ivf2_impl(true, bank, inv_norm, meta, sorted_f16, rho16, sorted_rows, pad_off, list_len, lists_flag,
+                                n_sorted, N, queries, now, D, nq, k, centroids, nprobe, idx_base, out_scores, out_idx,
+                                workspace, workspace_bytes, overflow_out, nullptr,
+                                reinterpret_cast<const float4*>(row_constants), stream);
+}
+
+int aura_knn_search_ivf2_probed_f16(const float* bank, const float* inv_norm, const float* meta,
+                                const uint16_t* sorted_f16, const float* rho16, const int32_t* sorted_rows,
+                                const int32_t* pad_off, const int32_t* list_len, const int32_t* lists_flag,
+                                const float* row_constants,
+                                int64_t n_sorted, int64_t N, const float* queries, float now, int64_t D, int64_t nq,
+                                int k, const float* centroids, int nprobe, const int32_t* probe_ids, int32_t idx_base,
+                                float* out_scores, int32_t* out_idx, void* workspace, int64_t workspace_bytes,
+                                int32_t* overflow_out, void* stream) {
+    if (!probe_ids) return AURA_E_INVAL;
+    if (reinterpret_cast<uintptr_t>(row_constants) & 15) return AURA_E_ALIGN;
+    return knn_search_ivf2_impl(true, bank, inv_norm, meta, sorted_f16, rho16, sorted_rows, pad_off, list_len, lists_flag,
                                 n_sorted, N, queries, now, D, nq, k, centroids, nprobe, idx_base, out_scores, out_idx,
                                 workspace, workspace_bytes, overflow_out, probe_ids,
                                 reinterpret_cast<const float4*>(row_constants), stream);
@@ -3335,7 +3390,7 @@ int aura_knn_search_ivf2_signal(const float* bank, const float* inv_norm, const 
                                 int32_t* overflow_out, uint32_t* host_word, uint32_t host_seq, void* stream) {
     if (!host_word || !overflow_out) return AURA_E_INVAL;
     if (reinterpret_cast<uintptr_t>(row_constants) & 15) return AURA_E_ALIGN;
-    return knn_search_ivf2_impl(bank, inv_norm, meta, sorted_bf16, rho, sorted_rows, pad_off, list_len, lists_flag,
+    return knn_search_ivf2_impl(false, bank, inv_norm, meta, sorted_bf16, rho, sorted_rows, pad_off, list_len, lists_flag,
                                 n_sorted, N, queries, now, D, nq, k, centroids, nprobe, idx_base, out_scores, out_idx,
                                 workspace, workspace_bytes, overflow_out, probe_ids,
                                 reinterpret_cast<const float4*>(row_constants), stream, 0, 0, nullptr, host_word, host_seq);
@@ -3351,7 +3406,40 @@ int aura_knn_search_ivf2_staged(const float* bank, const float* inv_norm, const 
                                 int32_t* overflow_out, int stage, int k2, float* bounds, void* stream) {
     if (stage < 1 || stage > 4) return AURA_E_INVAL;        // 1, 2, 4 + 3 (see the header)
     if (reinterpret_cast<uintptr_t>(row_constants) & 15) return AURA_E_ALIGN;
-    return knn_search_ivf2_impl(bank, inv_norm, meta, sorted_bf16, rho, sorted_rows, pad_off, list_len, lists_flag,
+    return knn_search_ivf2_impl(false, bank, inv_norm, meta, sorted_bf16, rho, sorted_rows, pad_off, list_len, lists_flag,
+                                n_sorted, N, queries, now, D, nq, k, centroids, nprobe, idx_base, out_scores, out_idx,
+                                workspace, workspace_bytes, overflow_out, probe_ids,
+                                reinterpret_cast<const float4*>(row_constants), stream, stage, k2, bounds);
+}
+
+// ---- the same entry points over an IEEE half image: `rho16` in rho's place ----
+int aura_knn_search_ivf2_signal_f16(const float* bank, const float* inv_norm, const float* meta,
+                                const uint16_t* sorted_f16, const float* rho16, const int32_t* sorted_rows,
+                                const int32_t* pad_off, const int32_t* list_len, const int32_t* lists_flag,
+                                const float* row_constants,
+                                int64_t n_sorted, int64_t N, const float* queries, float now, int64_t D, int64_t nq,
+                                int k, const float* centroids, int nprobe, const int32_t* probe_ids, int32_t idx_base,
+                                float* out_scores, int32_t* out_idx, void* workspace, int64_t workspace_bytes,
+                                int32_t* overflow_out, uint32_t* host_word, uint32_t host_seq, void* stream) {
+    if (!host_word || !overflow_out) return AURA_E_INVAL;
+    if (reinterpret_cast<uintptr_t>(row_constants) & 15) return AURA_E_ALIGN;
+    return knn_search_ivf2_impl(true, bank, inv_norm, meta, sorted_f16, rho16, sorted_rows, pad_off, list_len, lists_flag,
+                                n_sorted, N, queries, now, D, nq, k, centroids, nprobe, idx_base, out_scores, out_idx,
+                                workspace, workspace_bytes, overflow_out, probe_ids,
+                                reinterpret_cast<const float4*>(row_constants), stream, 0, 0, nullptr, host_word, host_seq);
+}
+
+int aura_knn_search_ivf2_staged_f16(const float* bank, const float* inv_norm, const float* meta,
+                                const uint16_t* sorted_f16, const float* rho16, const int32_t* sorted_rows,
+                                const int32_t* pad_off, const int32_t* list_len, const int32_t* lists_flag,
+                                const float* row_constants,
+                                int64_t n_sorted, int64_t N, const float* queries, float now, int64_t D, int64_t nq,
+                                int k, const float* centroids, int nprobe, const int32_t* probe_ids, int32_t idx_base,
+                                float* out_scores, int32_t* out_idx, void* workspace, int64_t workspace_bytes,
+                                int32_t* overflow_out, int stage, int k2, float* bounds, void* stream) {
+    if (stage < 1 || stage > 4) return AURA_E_INVAL;        // 1, 2, 4 + 3 (see the header)
+    if (reinterpret_cast<uintptr_t>(row_constants) & 15) return AURA_E_ALIGN;
+    return knn_search_ivf2_impl(true, bank, inv_norm, meta, sorted_f16, rho16, sorted_rows, pad_off, list_len, lists_flag,
                                 n_sorted, N, queries, now, D, nq, k, centroids, nprobe, idx_base, out_scores, out_idx,
                                 workspace, workspace_bytes, overflow_out, probe_ids,
                                 reinterpret_cast<const float4*>(row_constants), stream, stage, k2, bounds);

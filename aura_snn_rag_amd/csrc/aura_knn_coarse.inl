@@ -241,75 +241,18 @@ __device__ __forceinline__ uint32_t cs_swz32(uint32_t row) {
 #endif
 }
 
-template <bool QA, bool LAST, bool PAD, bool COND = false>
-__device__ __forceinline__ void mfma_bf16_q(f32x4v& acc, const bf16x8v& af, const bf16x8v& q, int on = 1) {
-    // COND: the MFMA runs only when `on` (wave-uniform, in an SGPR) is non-zero -- a scalar compare and
-    // branch inside the statement, so the compiler sees one definition of the accumulator either way.
-    if constexpr (COND) {
-#define AURA_SKIP_IN "s_cmp_eq_u32 %3, 0\n\ts_cbranch_scc1 .Laura_skip%=\n\t"
-#define AURA_SKIP_OUT "\n.Laura_skip%=:"
-#define AURA_NOP1C "s_nop 1\n\t"
-#define AURA_MFMAC "v_mfma_f32_16x16x32_bf16 "
-        if constexpr (PAD) {
-            if constexpr (QA && LAST)
-                asm volatile(AURA_SKIP_IN AURA_NOP1C AURA_MFMAC "%0, %1, %2, %0\n\ts_nop 7\n\ts_nop 4" AURA_SKIP_OUT : "+a"(acc) : "v"(af), "a"(q), "s"(on) : "scc");
-            else if constexpr (QA)
-                asm volatile(AURA_SKIP_IN AURA_NOP1C AURA_MFMAC "%0, %1, %2, %0" AURA_SKIP_OUT : "+a"(acc) : "v"(af), "a"(q), "s"(on) : "scc");
-            else if constexpr (LAST)
-                asm volatile(AURA_SKIP_IN AURA_NOP1C AURA_MFMAC "%0, %1, %2, %0\n\ts_nop 7\n\ts_nop 4" AURA_SKIP_OUT : "+a"(acc) : "v"(af), "v"(q), "s"(on) : "scc");
-            else
-                asm volatile(AURA_SKIP_IN AURA_NOP1C AURA_MFMAC "%0, %1, %2, %0" AURA_SKIP_OUT : "+a"(acc) : "v"(af), "v"(q), "s"(on) : "scc");
-        } else {
-            if constexpr (QA && LAST)
-                asm volatile(AURA_SKIP_IN AURA_MFMAC "%0, %1, %2, %0\n\ts_nop 7\n\ts_nop 4" AURA_SKIP_OUT : "+a"(acc) : "v"(af), "a"(q), "s"(on) : "scc");
-            else if constexpr (QA)
-                asm volatile(AURA_SKIP_IN AURA_MFMAC "%0, %1, %2, %0" AURA_SKIP_OUT : "+a"(acc) : "v"(af), "a"(q), "s"(on) : "scc");
-            else if constexpr (LAST)
-                asm volatile(AURA_SKIP_IN AURA_MFMAC "%0, %1, %2, %0\n\ts_nop 7\n\ts_nop 4" AURA_SKIP_OUT : "+a"(acc) : "v"(af), "v"(q), "s"(on) : "scc");
-            else
-                asm volatile(AURA_SKIP_IN AURA_MFMAC "%0, %1, %2, %0" AURA_SKIP_OUT : "+a"(acc) : "v"(af), "v"(q), "s"(on) : "scc");
-        }
-        return;
-    }
-    // PAD: s_nop 1 in front = the two wait states between a VALU write of an operand register and the
-    // MFMA reading it (hipcc pads nothing inside inline asm).  The fp32-row kernels need it: their A
-    // fragment comes out of v_cvt_pk_bf16_f32 right before.  The bf16-row kernels run without: the A
-    // fragment comes from ds_read_b128 behind an s_waitcnt, the query fragments are never rewritten and
-    // the accumulator set-up is several instructions away -- tools/check_mfma_hazards.py (a CPU test)
-    // verifies exactly that on the generated code of every build (0.6 ns of the 8.2 ns per MFMA).
-    // LAST (the tile's final k-step): 12 wait states behind the MFMA, INSIDE the statement, because
-    // the compiler may read or move the accumulator right after it (it has no idea this is an MFMA).
-    // AURA_CS_EXP_*: timing experiments only (tools/build_variant.sh; results are wrong with them)
-#if defined(AURA_CS_EXP_NONOP)
-#define AURA_NOP1 ""
-#else
-#define AURA_NOP1 "s_nop 1\n\t"
-#endif
-#ifdef AURA_CS_EXP_NOMFMA
-#define AURA_MFMA "; "
-#else
-#define AURA_MFMA "v_mfma_f32_16x16x32_bf16 "
-#endif
-    if constexpr (PAD) {
-        if constexpr (QA && LAST)
-            asm volatile(AURA_NOP1 AURA_MFMA "%0, %1, %2, %0\n\ts_nop 7\n\ts_nop 4" : "+a"(acc) : "v"(af), "a"(q));
-        else if constexpr (QA)
-            asm volatile(AURA_NOP1 AURA_MFMA "%0, %1, %2, %0" : "+a"(acc) : "v"(af), "a"(q));
-        else if constexpr (LAST)
-            asm volatile(AURA_NOP1 AURA_MFMA "%0, %1, %2, %0\n\ts_nop 7\n\ts_nop 4" : "+a"(acc) : "v"(af), "v"(q));
-        else
-            asm volatile(AURA_NOP1 AURA_MFMA "%0, %1, %2, %0" : "+a"(acc) : "v"(af), "v"(q));
-    } else {
-        if constexpr (QA && LAST)
-            asm volatile(AURA_MFMA "%0, %1, %2, %0\n\ts_nop 7\n\ts_nop 4" : "+a"(acc) : "v"(af), "a"(q));
-        else if constexpr (QA)
-            asm volatile(AURA_MFMA "%0, %1, %2, %0" : "+a"(acc) : "v"(af), "a"(q));
-        else if constexpr (LAST)
-            asm volatile(AURA_MFMA "%0, %1, %2, %0\n\ts_nop 7\n\ts_nop 4" : "+a"(acc) : "v"(af), "v"(q));
-        else
-            asm volatile(AURA_MFMA "%0, %1, %2, %0" : "+a"(acc) : "v"(af), "v"(q));
-    }
-}
+// mfma_bf16_q / mfma_f16_q: one body, two mnemonics (aura_mfma_q.inl).  The fragments are passed as 128-bit register
+// contents typed bf16x8v either way; the half kernels only ever move those bits.
+#define AURA_MFMA_FN mfma_bf16_q
+#define AURA_MFMA_OP "v_mfma_f32_16x16x32_bf16 "
+#include "aura_mfma_q.inl"
+#undef AURA_MFMA_FN
+#undef AURA_MFMA_OP
+#define AURA_MFMA_FN mfma_f16_q
+#define AURA_MFMA_OP "v_mfma_f32_16x16x32_f16 "
+#include "aura_mfma_q.inl"
+#undef AURA_MFMA_FN
+#undef AURA_MFMA_OP
 
 // (query part of the error bound: aura_eq_from_e2, aura_common.inl; coarse_eq_worst, coarse_row_constants:
 // aura_rowc.inl)
@@ -437,8 +380,11 @@ constexpr bool CS_TIMERS = AURA_CS_TIMERS != 0;
 
 template <int NW, int QBT> constexpr int cs_min_waves() { return (NW == 4 && QBT == 2) ? 2 : 1; }
 template <int NW, int QBT> constexpr int cs_cand_buf() { return (NW == 4 && QBT == 2) ? 512 : CS_BUF; }
-template <int KS, int MODE, bool SRC16, bool MASKED, bool IVF = false, int NW = 4, int QBT = 16 / NW>
+// F16 (inverted lists only): the sorted image and the query fragments are IEEE half, the MFMA is the f16 one -- same
+// bytes, same LDS image, same tile loop; only the mnemonic changes (mfma_f16_q).
+template <int KS, int MODE, bool SRC16, bool MASKED, bool IVF = false, int NW = 4, int QBT = 16 / NW, bool F16 = false>
 __global__ __launch_bounds__(64 * NW, (cs_min_waves<NW, QBT>())) void coarse_scan_kernel(const CoarseArgs a) {
+    static_assert(!F16 || IVF, "only the list-sorted image of the inverted lists is kept in half");
     static_assert(!MASKED || SRC16, "the probe masks need the LDS the bf16 rows leave free");
     static_assert(!IVF || (SRC16 && !MASKED), "inverted lists run over the sorted bf16 shadow");
     static_assert(NW == 4 || (NW == 8 && SRC16), "8 waves: bf16 rows only");
@@ -883,7 +829,8 @@ __global__ __launch_bounds__(64 * NW, (cs_min_waves<NW, QBT>())) void coarse_sca
                     // scalar branch inside the statement, so the accumulators keep one definition)
                     constexpr bool CND = NBc == 2 && b == 1;
                     constexpr bool INA = b * KS + s < QA;
-                    mfma_bf16_q<INA, s == KS - 1, !SRC16, CND>(acc[b], af, qf[b][s], nb - 1);
+                    if constexpr (F16) mfma_f16_q<INA, s == KS - 1, !SRC16, CND>(acc[b], af, qf[b][s], nb - 1);
+                    else mfma_bf16_q<INA, s == KS - 1, !SRC16, CND>(acc[b], af, qf[b][s], nb - 1);
                 });
                 // the epilogue's row constants are fetched behind the last two k-steps
                 if constexpr (s == S_RC)

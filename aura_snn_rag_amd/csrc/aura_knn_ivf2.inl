@@ -5,7 +5,8 @@
 // (src/core/hippocampal.py:259-270).  aura_knn_search_ivf streams every probed list once per batch
 // on the fp32 matrix pipe and writes ALL candidate scores; here the same restriction runs on the
 // bf16 prefilter + fp32 re-scoring machinery of aura_knn_coarse.inl:
-//   * the caller keeps a LIST-SORTED bf16 shadow of the bank (rows grouped by centroid, every list
+//   * the caller keeps a LIST-SORTED 16-bit shadow of the bank -- bf16, or IEEE half through the *_f16 entry points
+//     (what HippocampalFormation keeps: a five times narrower band, see aura_hip.h) -- (rows grouped by centroid, every list
 //     padded to a multiple of 16 rows; `sorted_rows[i]` = bank row of sorted row i, -1 for pads),
 //     rebuilt whenever its inverted lists are (aura_bank_shadow_sorted);
 //   * a batch is regrouped BY LIST (ivf_prepare_kernel): block B = (list, up to 256 of the queries
@@ -172,6 +173,9 @@ __global__ __launch_bounds__(256) void ivf2_lists_from_ids_kernel(const int32_t*
 //      scan's lanes find their slot's query through slotq (rounds 1-2 wrote one set per (query, probe) slot:
 //      25 MB per 2048 queries, 31 us) -- its part eq of the error bound, and the pass's resets: qslot = -1,
 //      the per-list counters, the call's flag, the all-zero entry nq that unused slots read ----
+//      F16: the fragments are IEEE half under the image's rule (aura_row.inl: nearest-even, |x| < 2^-14 stored as 0),
+//      eq from that residual ----
+template <bool F16>
 __global__ __launch_bounds__(256) void ivf2_qprep_kernel(const float* __restrict__ x, int64_t nq, int64_t D, int KS,
                                                          uint16_t* __restrict__ qfrag, float* __restrict__ inv,
                                                          float* __restrict__ eq_q, int32_t* __restrict__ qslot,
@@ -212,9 +216,16 @@ __global__ __launch_bounds__(256) void ivf2_qprep_kernel(const float* __restrict
                 v[4] = w.x * iqv; v[5] = w.y * iqv; v[6] = w.z * iqv; v[7] = w.w * iqv;
             }
         }
-        const bf16x8v bv = __builtin_convertvector(v, bf16x8v);
-        *reinterpret_cast<bf16x8v*>(base + c * 8) = bv;
-        const f32x8v back = __builtin_convertvector(bv, f32x8v);
+        f32x8v back;
+        if constexpr (F16) {
+            const f16x8b hv = __builtin_convertvector(aura_half_flush(v), f16x8b);
+            *reinterpret_cast<f16x8b*>(base + c * 8) = hv;
+            back = __builtin_convertvector(hv, f32x8v);
+        } else {
+            const bf16x8v bv = __builtin_convertvector(v, bf16x8v);
+            *reinterpret_cast<bf16x8v*>(base + c * 8) = bv;
+            back = __builtin_convertvector(bv, f32x8v);
+        }
 #pragma unroll
         for (int e = 0; e < 8; ++e) { const float d = back[e] - v[e]; e2 = fmaf(d, d, e2); }
     }
@@ -261,10 +272,10 @@ __global__ __launch_bounds__(256) void ivf2_slots_kernel(const int32_t* __restri
 //      entries it touches), otherwise they are recomputed per call into the workspace ----
 __global__ __launch_bounds__(256) void ivf2_rowc_kernel(const float* __restrict__ meta, const float* __restrict__ rho,
                                                         const int32_t* __restrict__ sorted_rows, int64_t Npad,
-                                                        float now, float D, float4* __restrict__ rowc) {
+                                                        float now, float D, float4* __restrict__ rowc, bool f16) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= Npad) return;
-    rowc[i] = ivf2_row_constants(sorted_rows[i], meta, rho, now, D);
+    rowc[i] = ivf2_row_constants(sorted_rows[i], meta, rho, now, D, f16);   // f16: rho is the half image's rho16
 }
 
 // ---- thresholds: one wave per query over the group maxima of its nprobe lists' sample tiles ----
@@ -420,17 +431,17 @@ static Ivf2Workspace carve_ivf2(void* base, int64_t Npad, int64_t nq, int k) {
     return w;
 }
 
-template <int KS, int NW, int QBT = 16 / NW>
+template <int KS, int NW, int QBT = 16 / NW, bool F16 = false>
 inline int launch_coarse_ivf(const CoarseArgs& a, int mode, int grid, hipStream_t s) {
     constexpr int BLKQ = NW * 16 * QBT;
     const size_t lds = (size_t)cs_lds_slots<true, false, NW>() * (KS * 1024 + CS_AUX_BYTES) + (size_t)cs_cand_buf<NW, QBT>() * 12 +
                        BLKQ * 4 + BLKQ * 4;
-    if (aura_ensure_lds_attr(reinterpret_cast<const void*>(coarse_scan_kernel<KS, CS_MODE_SAMPLE, true, false, true, NW, QBT>), (int)lds) ||
-        aura_ensure_lds_attr(reinterpret_cast<const void*>(coarse_scan_kernel<KS, CS_MODE_FILTER, true, false, true, NW, QBT>), (int)lds))
+    if (aura_ensure_lds_attr(reinterpret_cast<const void*>(coarse_scan_kernel<KS, CS_MODE_SAMPLE, true, false, true, NW, QBT, F16>), (int)lds) ||
+        aura_ensure_lds_attr(reinterpret_cast<const void*>(coarse_scan_kernel<KS, CS_MODE_FILTER, true, false, true, NW, QBT, F16>), (int)lds))
         return AURA_E_LAUNCH;
     if (mode == CS_MODE_SAMPLE)
-        hipLaunchKernelGGL((coarse_scan_kernel<KS, CS_MODE_SAMPLE, true, false, true, NW, QBT>), dim3(grid), dim3(64 * NW), lds, s, a);
+        hipLaunchKernelGGL((coarse_scan_kernel<KS, CS_MODE_SAMPLE, true, false, true, NW, QBT, F16>), dim3(grid), dim3(64 * NW), lds, s, a);
     else
-        hipLaunchKernelGGL((coarse_scan_kernel<KS, CS_MODE_FILTER, true, false, true, NW, QBT>), dim3(grid), dim3(64 * NW), lds, s, a);
+        hipLaunchKernelGGL((coarse_scan_kernel<KS, CS_MODE_FILTER, true, false, true, NW, QBT, F16>), dim3(grid), dim3(64 * NW), lds, s, a);
     return aura_check_launch();
 }

@@ -40,6 +40,23 @@ def _need(t: torch.Tensor, name: str, dtype=None) -> torch.Tensor:
     return t
 
 
+def _need_image(t: torch.Tensor, name: str) -> bool:
+    """A 16-bit image of normalised rows: bf16, or IEEE half (the list-sorted image of the inverted lists).  Returns
+    whether it is half -- the dtype selects the ``*_f16`` entry points."""
+    _need(t, name)
+    if t.dtype not in (torch.bfloat16, torch.float16):
+        raise TypeError(f"{name}: expected dtype torch.bfloat16 or torch.float16, got {t.dtype}")
+    return t.dtype == torch.float16
+
+
+def half_image_rho_bound(rho: torch.Tensor, D: int) -> torch.Tensor:
+    """A rigorous (loose) residual bound of the HALF image from the bf16 residual norms ``rho``, for one-shot callers that
+    hold a half image without its ``rho16``: every element that stays normal is rounded to a grid that contains the
+    bf16 grid (error <= the bf16 error), every element stored as 0 errs by less than 2^-14, so
+    ``rho16 <= rho + sqrt(D) 2^-14``.  Owners of an image keep the measured ``rho16`` instead."""
+    return rho + float(D) ** 0.5 * 2.0 ** -14 * 1.001
+
+
 def _p(t: Optional[torch.Tensor]) -> Optional[int]:
     return None if t is None else t.data_ptr()
 
@@ -1834,7 +1851,7 @@ CONSOLIDATE_MAX_IMAGE_DIM = 768
 
 
 def find_repeats(bank, inv_norm, count: int, feats, tau: float, image=None, image_rows=None,
-                 n_image: Optional[int] = None, rho=None, lists_flag=None):
+                 n_image: Optional[int] = None, rho=None, lists_flag=None, rho16=None):
     """Which rows of the batch ``feats`` (fp32 [n, D], n <= 1024) repeat a row of ``bank[:count]`` or an earlier row of
     the batch, at cosine >= ``tau`` (the rule in full: ``include/aura_hip.h``) ->
     ``(stored_target int32 [n], batch_leader int32 [n], cos fp32 [n], packed int32 [3 n + 2])``.  The three results are
@@ -1843,12 +1860,15 @@ def find_repeats(bank, inv_norm, count: int, feats, tau: float, image=None, imag
     ``lists_flag`` (int32 [1], device; 0 without one), so that ONE device-to-host read of ``packed`` brings the
     results and both flags.  ``image``: a current bf16 image of the normalised rows -- the row-ordered shadow
     (``image_rows`` None) or the list-sorted shadow with ``image_rows = sorted_rows`` and ``n_image = n_sorted`` --
-    with ``rho`` as ``bank_shadow_update`` leaves it; None: the dense fp32 scan.  No host sync."""
-    return _find_repeats(bank, inv_norm, count, feats, tau, image, image_rows, n_image, rho, lists_flag, None, None)
+    with ``rho`` as ``bank_shadow_update`` leaves it; None: the dense fp32 scan.  A float16 image (the list-sorted image
+    as ``HippocampalFormation`` keeps it) goes with its ``rho16``; without one the bound is derived from ``rho``
+    (``half_image_rho_bound``).  No host sync."""
+    return _find_repeats(bank, inv_norm, count, feats, tau, image, image_rows, n_image, rho, lists_flag, None, None,
+                         rho16)
 
 
 def find_repeats_scoped(bank, inv_norm, meta, count: int, feats, tags, tau: float, image=None, image_rows=None,
-                        n_image: Optional[int] = None, rho=None, lists_flag=None):
+                        n_image: Optional[int] = None, rho=None, lists_flag=None, rho16=None):
     """``find_repeats`` within tags (``aura_bank_find_repeats_scoped``; the rule: ``include/aura_hip.h``): a held row is
     eligible for batch row i only when ``int(meta[r, 3]) == tags[i]``, an in-batch pair only when both rows carry the
     same tag; tag 0 is a scope like any other, a tag outside ``[0, 2^24)`` matches nothing (that row is kept).  ``meta``:
@@ -1857,10 +1877,12 @@ def find_repeats_scoped(bank, inv_norm, meta, count: int, feats, tags, tau: floa
     load per surviving pair.  No host sync."""
     if meta is None or tags is None:
         raise ValueError("find_repeats_scoped: meta and tags are required")
-    return _find_repeats(bank, inv_norm, count, feats, tau, image, image_rows, n_image, rho, lists_flag, meta, tags)
+    return _find_repeats(bank, inv_norm, count, feats, tau, image, image_rows, n_image, rho, lists_flag, meta, tags,
+                         rho16)
 
 
-def _find_repeats(bank, inv_norm, count, feats, tau, image, image_rows, n_image, rho, lists_flag, meta, tags):
+def _find_repeats(bank, inv_norm, count, feats, tau, image, image_rows, n_image, rho, lists_flag, meta, tags,
+                  rho16=None):
     _need(bank, "bank", torch.float32); _need(inv_norm, "inv_norm", torch.float32); _need(feats, "feats", torch.float32)
     if bank.dim() != 2 or not (0 <= count <= bank.shape[0]) or inv_norm.numel() != bank.shape[0]:
         raise ValueError("find_repeats: bank must be [rows, D] with count <= rows and one inv_norm per row")
@@ -1878,8 +1900,13 @@ def _find_repeats(bank, inv_norm, count, feats, tau, image, image_rows, n_image,
     if feats.device != bank.device or inv_norm.device != bank.device:
         raise ValueError("find_repeats: tensors are on different devices")
     ni = 0
+    half = False
     if image is not None:
-        _need(image, "image", torch.bfloat16); _need(rho, "rho", torch.float32)
+        half = _need_image(image, "image")
+        if half:                                # the half image's own residuals, or a bound derived from the bf16 ones
+            rho = _need(rho16, "rho16", torch.float32) if rho16 is not None else \
+                half_image_rho_bound(_need(rho, "rho", torch.float32), D)
+        _need(rho, "rho", torch.float32)
         if D % 8 or D > CONSOLIDATE_MAX_IMAGE_DIM or image.dim() != 2 or image.shape[1] != D or rho.numel() != M:
             raise ValueError("find_repeats: an image needs D % 8 == 0, D <= 768, [rows, D] bf16 and one rho per bank row")
         if image_rows is None:
@@ -1918,15 +1945,17 @@ def _find_repeats(bank, inv_norm, count, feats, tau, image, image_rows, n_image,
     args = (_p(bank), _p(inv_norm), count, D, _p(image), _p(image_rows), ni, _p(rho), _p(feats), n, tau, _p(stored),
             _p(leader), _p(cos), _p(packed[3 * n:]), base, nbytes, _stream())
     if meta is None:
-        check(L.aura_bank_find_repeats(*args), "aura_bank_find_repeats")
+        fn = L.aura_bank_find_repeats_f16 if half else L.aura_bank_find_repeats
+        check(fn(*args), "aura_bank_find_repeats")
     else:
-        check(L.aura_bank_find_repeats_scoped(*args, _p(meta), _p(tags)), "aura_bank_find_repeats_scoped")
+        fn = L.aura_bank_find_repeats_scoped_f16 if half else L.aura_bank_find_repeats_scoped
+        check(fn(*args, _p(meta), _p(tags)), "aura_bank_find_repeats_scoped")
     return stored, leader, cos, packed
 
 
 def bank_blend(bank, inv_norm, count: int, stored_target, batch_leader, beta: float, feats=None, out=None,
                feats_row0: int = -1, shadow=None, rho=None, shadow_upto: int = 0, sorted_bf16=None, sorted_rows=None,
-               pos_of_row=None, n_sorted: Optional[int] = None) -> None:
+               pos_of_row=None, n_sorted: Optional[int] = None, rho16=None) -> None:
     """Blending merges (the rule: ``include/aura_hip.h``, "Blending merges"): every memory that rows of the batch
     repeat moves toward them, ``g = g + beta * (f_i - g)`` over its members in ascending batch order, in one launch.
     ``stored_target`` / ``batch_leader``: int32 [n] on the bank's device, as ONE ``find_repeats`` call against
@@ -1937,7 +1966,9 @@ def bank_blend(bank, inv_norm, count: int, stored_target, batch_leader, beta: fl
     also refreshes ``inv_norm`` (``bank_row_norms``' bits), with ``shadow`` + ``rho`` the row's bf16 shadow and residual
     if it lies below ``shadow_upto`` (``bank_shadow_update``'s bits), and with ``sorted_bf16`` + ``sorted_rows`` +
     ``pos_of_row`` (+ ``rho``) its entry of the list-sorted image, in place.  ``rho`` goes with a shadow or an image,
-    and only with one; the image's three tensors go together.  Entries out of range are ignored.  No host sync."""
+    and only with one; the image's three tensors go together.  The image may be float16 (the dtype selects the entry
+    point); ``rho16``, which goes only with such an image, then receives the half residual while ``rho`` receives the
+    bf16 one as ever.  Entries out of range are ignored.  No host sync."""
     _need(bank, "bank", torch.float32); _need(inv_norm, "inv_norm", torch.float32)
     _need(stored_target, "stored_target", torch.int32); _need(batch_leader, "batch_leader", torch.int32)
     beta = float(beta)
@@ -1982,18 +2013,31 @@ def bank_blend(bank, inv_norm, count: int, stored_target, batch_leader, beta: fl
     else:
         shadow_upto = 0
     ns = 0
+    half = False
     if has_image:
-        _need(sorted_bf16, "sorted_bf16", torch.bfloat16); _need(sorted_rows, "sorted_rows", torch.int32)
+        half = _need_image(sorted_bf16, "sorted_bf16"); _need(sorted_rows, "sorted_rows", torch.int32)
         _need(pos_of_row, "pos_of_row", torch.int32)
         ns = sorted_rows.numel() if n_sorted is None else int(n_sorted)
         if sorted_bf16.dim() != 2 or sorted_bf16.shape[1] != D or pos_of_row.numel() != M or \
                 not (0 <= ns <= min(sorted_rows.numel(), sorted_bf16.shape[0])):
             raise ValueError("bank_blend: the image is [>= n_sorted, D] bf16 with sorted_rows [>= n_sorted] and "
                              "pos_of_row [rows]")
-    for t in (inv_norm, stored_target, batch_leader, feats, out, shadow, rho, sorted_bf16, sorted_rows, pos_of_row):
+    if rho16 is not None:
+        if not half:
+            raise ValueError("bank_blend: rho16 goes with a float16 list-sorted image")
+        _need(rho16, "rho16", torch.float32)
+        if rho16.numel() != M:
+            raise ValueError("bank_blend: one rho16 per bank row")
+    for t in (inv_norm, stored_target, batch_leader, feats, out, shadow, rho, sorted_bf16, sorted_rows, pos_of_row, rho16):
         if t is not None and t.device != bank.device:
             raise ValueError("bank_blend: tensors are on different devices")
     if n == 0:
+        return
+    if half:
+        check(lib().aura_bank_blend_f16(_p(bank), _p(inv_norm), count, M, D, _p(feats), feats_row0, n, _p(stored_target),
+                                        _p(batch_leader), beta, _p(out), _p(shadow), _p(rho), shadow_upto,
+                                        _p(sorted_bf16), _p(rho16), _p(sorted_rows), _p(pos_of_row), ns, _stream()),
+              "aura_bank_blend_f16")
         return
     check(lib().aura_bank_blend(_p(bank), _p(inv_norm), count, M, D, _p(feats), feats_row0, n, _p(stored_target),
                                 _p(batch_leader), beta, _p(out), _p(shadow), _p(rho), shadow_upto, _p(sorted_bf16),
@@ -2417,12 +2461,19 @@ def ivf2_layout(order, seg_off, slack: int, sorted_rows, pad_off, list_len) -> N
         sorted_rows[dst[listed]] = order[listed]
 
 
-def bank_shadow_sorted(bank, inv_norm, sorted_rows, out, rho, pos_of_row=None, n_sorted: Optional[int] = None) -> None:
-    """out[i] = bf16 shadow row of bank row sorted_rows[i] (zeros where it is -1) for i < n_sorted;
-    refreshes rho[row] and the reverse map pos_of_row[row] = i."""
+def bank_shadow_sorted(bank, inv_norm, sorted_rows, out, rho, pos_of_row=None, n_sorted: Optional[int] = None,
+                       rho16=None) -> None:
+    """out[i] = 16-bit shadow row of bank row sorted_rows[i] (zeros where it is -1) for i < n_sorted;
+    refreshes rho[row] and the reverse map pos_of_row[row] = i.  ``out`` bf16: the row-ordered shadow's format.
+    ``out`` float16: IEEE half, nearest-even, |x| < 2^-14 stored as 0 (no subnormals); ``rho`` still receives the bf16
+    residual, bit for bit ``bank_shadow_update``'s, and ``rho16`` (optional) the half image's own."""
     _need(bank, "bank", torch.float32); _need(sorted_rows, "sorted_rows", torch.int32)
     _need(inv_norm, "inv_norm", torch.float32); _need(rho, "rho", torch.float32)
-    _need(out, "out", torch.bfloat16)
+    half = _need_image(out, "out")
+    if rho16 is not None:
+        _need(rho16, "rho16", torch.float32)
+        if not half or rho16.numel() != bank.shape[0]:
+            raise ValueError("bank_shadow_sorted: rho16 (one per bank row) goes with a float16 image")
     M, D = bank.shape
     n = sorted_rows.numel() if n_sorted is None else int(n_sorted)
     if D % 8 or out.shape[1] != D or not (0 <= n <= min(sorted_rows.numel(), out.shape[0])) or \
@@ -2432,20 +2483,29 @@ def bank_shadow_sorted(bank, inv_norm, sorted_rows, out, rho, pos_of_row=None, n
         _need(pos_of_row, "pos_of_row", torch.int32)
         if pos_of_row.numel() != M:
             raise ValueError("bank_shadow_sorted: pos_of_row must have one entry per bank row")
+    if half:
+        check(lib().aura_bank_shadow_sorted_f16(_p(bank), _p(inv_norm), _p(sorted_rows), _p(out), _p(rho), _p(rho16),
+                                                _p(pos_of_row), n, D, _stream()), "aura_bank_shadow_sorted_f16")
+        return
     check(lib().aura_bank_shadow_sorted(_p(bank), _p(inv_norm), _p(sorted_rows), _p(out), _p(rho), _p(pos_of_row),
                                         n, D, _stream()), "aura_bank_shadow_sorted")
 
 
-def build_ivf2(bank, inv_norm, cids, slack: int = 0, max_rows: Optional[int] = None, rho=None):
+def build_ivf2(bank, inv_norm, cids, slack: int = 0, max_rows: Optional[int] = None, rho=None,
+               dtype=torch.float16):
     """Inverted lists in the layout of ``knn_search_ivf2`` for rows [0, n) with centroid ids ``cids``
-    (any numeric dtype, < 0: no list): returns a dict with sorted_bf16, rho, sorted_rows, pad_off,
-    list_len, pos_of_row, flag, n_sorted (sorted rows in use)."""
+    (any numeric dtype, < 0: no list): returns a dict with sorted_bf16 (the image; IEEE half unless ``dtype`` is
+    torch.bfloat16 -- the key keeps its name), rho, rho16 (the half image's residuals; None for bf16), sorted_rows,
+    pad_off, list_len, pos_of_row, flag, n_sorted (sorted rows in use)."""
+    if dtype not in (torch.float16, torch.bfloat16):
+        raise TypeError("build_ivf2: the image is torch.float16 or torch.bfloat16")
     dev = bank.device
     M, D = bank.shape
     n = cids.numel()
     order, seg_off = group_by_cluster(cids, 256)
     n_alloc = ivf2_alloc_rows(M if max_rows is None else max_rows, slack)
-    st = dict(sorted_bf16=torch.empty(n_alloc, D, dtype=torch.bfloat16, device=dev),
+    st = dict(sorted_bf16=torch.empty(n_alloc, D, dtype=dtype, device=dev),
+              rho16=torch.zeros(M, dtype=torch.float32, device=dev) if dtype == torch.float16 else None,
               sorted_rows=torch.empty(n_alloc, dtype=torch.int32, device=dev),
               pad_off=torch.zeros(257, dtype=torch.int32, device=dev),
               list_len=torch.zeros(256, dtype=torch.int32, device=dev),
@@ -2455,18 +2515,25 @@ def build_ivf2(bank, inv_norm, cids, slack: int = 0, max_rows: Optional[int] = N
               n_sorted=min(n_alloc, ivf2_alloc_rows(n, slack)), slack=slack)
     ivf2_layout(order, seg_off, slack, st["sorted_rows"], st["pad_off"], st["list_len"])
     bank_shadow_sorted(bank, inv_norm, st["sorted_rows"], st["sorted_bf16"], st["rho"], st["pos_of_row"],
-                       st["n_sorted"])
+                       st["n_sorted"], rho16=st["rho16"])
     return st
 
 
 def ivf2_append(bank, inv_norm, meta, slots, sorted_shadow, sorted_rows, pad_off, list_len, pos_of_row, rho,
-                flag, row_constants=None, row_constants_now: float = 0.0) -> None:
+                flag, row_constants=None, row_constants_now: float = 0.0, rho16=None) -> None:
     """Keep the inverted lists current after a write of the DISTINCT rows ``slots`` (int64 [n]): the
     row's old entry becomes a hole, the row is appended to the list of meta[slot][2].  ``row_constants``
-    (``ivf2_row_constants`` for ``row_constants_now``): the cached table follows the touched entries."""
+    (``ivf2_row_constants`` for ``row_constants_now``): the cached table follows the touched entries.  A float16
+    image takes ``rho16`` beside ``rho`` (required with ``row_constants``: the table is the half image's)."""
     _need(bank, "bank", torch.float32); _need(inv_norm, "inv_norm", torch.float32)
     _need(meta, "meta", torch.float32); _need(slots, "slots", torch.int64)
-    _need(sorted_shadow, "sorted_shadow", torch.bfloat16); _need(rho, "rho", torch.float32)
+    half = _need_image(sorted_shadow, "sorted_shadow"); _need(rho, "rho", torch.float32)
+    if rho16 is not None:
+        _need(rho16, "rho16", torch.float32)
+        if not half or rho16.numel() != bank.shape[0]:
+            raise ValueError("ivf2_append: rho16 (one per bank row) goes with a float16 image")
+    elif half and row_constants is not None:
+        raise ValueError("ivf2_append: a float16 image's row constants need rho16")
     for t, n_ in ((sorted_rows, "sorted_rows"), (pad_off, "pad_off"), (list_len, "list_len"),
                   (pos_of_row, "pos_of_row"), (flag, "flag")):
         _need(t, n_, torch.int32)
@@ -2478,23 +2545,30 @@ def ivf2_append(bank, inv_norm, meta, slots, sorted_shadow, sorted_rows, pad_off
         _need(row_constants, "row_constants", torch.float32)
         if row_constants.dim() != 2 or row_constants.shape[1] != 4 or row_constants.shape[0] < sorted_rows.numel():
             raise ValueError("ivf2_append: row_constants must be [>= sorted rows, 4]")
+    if half:
+        check(lib().aura_ivf2_append_f16(_p(bank), _p(inv_norm), _p(meta), _p(slots), slots.numel(), D, _p(sorted_shadow),
+                                         _p(sorted_rows), _p(pad_off), _p(list_len), _p(pos_of_row), _p(rho), _p(rho16),
+                                         _p(flag), _p(row_constants), float(row_constants_now), _stream()),
+              "aura_ivf2_append_f16")
+        return
     check(lib().aura_ivf2_append(_p(bank), _p(inv_norm), _p(meta), _p(slots), slots.numel(), D, _p(sorted_shadow),
                                  _p(sorted_rows), _p(pad_off), _p(list_len), _p(pos_of_row), _p(rho), _p(flag),
                                  _p(row_constants), float(row_constants_now), _stream()), "aura_ivf2_append")
 
 
-def ivf2_row_constants(meta, rho, sorted_rows, n_sorted: int, D: int, now: float, out) -> None:
+def ivf2_row_constants(meta, rho, sorted_rows, n_sorted: int, D: int, now: float, out, half: bool = False) -> None:
     """out[i] (fp32 [>= n_sorted, 4]) = the score constants of sorted row i at time ``now`` (see
     ``aura_ivf2_row_constants``): pass ``out`` to ``knn_search_ivf2(row_constants=...)`` for calls with the
-    same ``now`` while metadata, rho and the list layout are unchanged."""
+    same ``now`` while metadata, rho and the list layout are unchanged.  ``half``: the table of a float16 image --
+    ``rho`` is then that image's ``rho16``."""
     _need(meta, "meta", torch.float32); _need(rho, "rho", torch.float32)
     _need(sorted_rows, "sorted_rows", torch.int32); _need(out, "out", torch.float32)
     n = int(n_sorted)
     if out.dim() != 2 or out.shape[1] != 4 or not (0 <= n <= min(out.shape[0], sorted_rows.numel())) or \
             meta.dim() != 2 or meta.shape[1] != 4 or rho.numel() != meta.shape[0]:
         raise ValueError("ivf2_row_constants: shape mismatch")
-    check(lib().aura_ivf2_row_constants(_p(meta), _p(rho), _p(sorted_rows), n, int(D), float(now), _p(out), _stream()),
-          "aura_ivf2_row_constants")
+    fn = lib().aura_ivf2_row_constants_f16 if half else lib().aura_ivf2_row_constants
+    check(fn(_p(meta), _p(rho), _p(sorted_rows), n, int(D), float(now), _p(out), _stream()), "aura_ivf2_row_constants")
 
 
 def centroid_probe(queries, centroids, nprobe: int = 8) -> torch.Tensor:
@@ -2521,12 +2595,17 @@ STAGED_MAX_QUERIES = 8192            # queries per staged pass (aura_knn_search_
 
 def knn_search_ivf2(bank, inv_norm, meta, queries, k: int, now: float, centroids, nprobe: int,
                     sorted_shadow, rho, sorted_rows, pad_off, list_len, idx_base: int = 0,
-                    n_sorted: Optional[int] = None, lists_flag=None, probe_ids=None, row_constants=None
+                    n_sorted: Optional[int] = None, lists_flag=None, probe_ids=None, row_constants=None, rho16=None
                     ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """Inverted-list recall through the two-stage scan: (scores [nq, k], idx [nq, k], overflow flag [1]).
-    Same results as ``knn_search_ivf``; the arguments are those of ``Ivf2Lists`` and ``Ivf2Lists.search``."""
+    Same results as ``knn_search_ivf``; the arguments are those of ``Ivf2Lists`` and ``Ivf2Lists.search``.  A float16
+    image without ``rho16`` is searched with the bound ``half_image_rho_bound(rho)`` -- rigorous, looser than the
+    measured one, and good for this one call only."""
+    if rho16 is None and isinstance(sorted_shadow, torch.Tensor) and sorted_shadow.dtype == torch.float16 \
+            and row_constants is None:
+        rho16 = half_image_rho_bound(_need(rho, "rho", torch.float32), bank.shape[1])
     lists = Ivf2Lists(bank, inv_norm, meta, centroids, nprobe, sorted_shadow, rho, sorted_rows, pad_off, list_len,
-                      n_sorted, lists_flag, row_constants)
+                      n_sorted, lists_flag, row_constants, rho16)
     return lists.search(queries, k, now, probe_ids=probe_ids, idx_base=idx_base)
 
 
@@ -2540,16 +2619,27 @@ class Ivf2Lists:
     sorted rows in use (a multiple of 16 that covers pad_off[256]; default: all of ``sorted_rows``).
     ``lists_flag``: ``ivf2_append``'s flag; if it is set the returned overflow flag carries ``KNN_FLAG_LISTS_STALE``.
     ``row_constants``: ``ivf2_row_constants`` of the current lists for exactly the ``now`` of every call (fp32).
-    The handle keeps its tensors alive and caches their pointers: an owner rebuilds it when ``holds`` fails."""
+    The handle keeps its tensors alive and caches their pointers: an owner rebuilds it when ``holds`` fails.
+    A float16 ``sorted_shadow`` (IEEE half, ``bank_shadow_sorted``) selects the ``*_f16`` entry points and requires
+    ``rho16``, that image's residual norms, which the kernels then read in ``rho``'s place (``row_constants`` must be
+    the half table, ``ivf2_row_constants(..., half=True)``)."""
 
     def __init__(self, bank, inv_norm, meta, centroids, nprobe: int, sorted_shadow, rho, sorted_rows, pad_off, list_len,
-                 n_sorted: Optional[int] = None, lists_flag=None, row_constants=None):
+                 n_sorted: Optional[int] = None, lists_flag=None, row_constants=None, rho16=None):
         _need(bank, "bank", torch.float32); _need(inv_norm, "inv_norm", torch.float32)
         _need(meta, "meta", torch.float32); _need(centroids, "centroids", torch.float32)
-        _need(sorted_shadow, "sorted_shadow", torch.bfloat16); _need(rho, "rho", torch.float32)
+        half = _need_image(sorted_shadow, "sorted_shadow"); _need(rho, "rho", torch.float32)
         for t, n in ((sorted_rows, "sorted_rows"), (pad_off, "pad_off"), (list_len, "list_len")):
             _need(t, n, torch.int32)
         M, D = bank.shape
+        if half:
+            if rho16 is None:
+                raise ValueError("Ivf2Lists: a float16 image needs rho16 (bank_shadow_sorted fills it)")
+            _need(rho16, "rho16", torch.float32)
+            if rho16.numel() != M:
+                raise ValueError("Ivf2Lists: one rho16 per bank row")
+        elif rho16 is not None:
+            raise ValueError("Ivf2Lists: rho16 goes with a float16 image")
         ns = sorted_rows.numel() if n_sorted is None else int(n_sorted)
         if meta.shape != (M, 4) or rho.numel() != M:
             raise ValueError("Ivf2Lists: shape mismatch")
@@ -2568,21 +2658,29 @@ class Ivf2Lists:
                 raise ValueError("Ivf2Lists: row_constants must be [>= n_sorted, 4]")
         # (the first ten in the order of the C entry points' leading arguments)
         self._keep = (bank, inv_norm, meta, sorted_shadow, rho, sorted_rows, pad_off, list_len, lists_flag, row_constants,
-                      centroids)
+                      centroids, rho16)
         self._ptrs = tuple(_p(t) for t in self._keep[:10])
+        if half:                                                       # the readers take rho16 in rho's place
+            self._ptrs = self._ptrs[:4] + (_p(rho16),) + self._ptrs[5:]
         self._cent = centroids.data_ptr()
         self.M, self.D, self.ns, self.nprobe, self.device = M, D, ns, int(nprobe), bank.device
         self._bytes = {}
-        self._lib = lib()
+        self._lib = L = lib()
+        self.half = half
+        self._fn = (L.aura_knn_search_ivf2_f16, L.aura_knn_search_ivf2_probed_f16, L.aura_knn_search_ivf2_signal_f16,
+                    L.aura_knn_search_ivf2_staged_f16) if half else \
+                   (L.aura_knn_search_ivf2, L.aura_knn_search_ivf2_probed, L.aura_knn_search_ivf2_signal,
+                    L.aura_knn_search_ivf2_staged)
 
     def holds(self, bank, inv_norm, meta, centroids, nprobe: int, sorted_shadow, rho, sorted_rows, pad_off, list_len,
-              n_sorted: Optional[int] = None, lists_flag=None, row_constants=None) -> bool:
+              n_sorted: Optional[int] = None, lists_flag=None, row_constants=None, rho16=None) -> bool:
         """Whether this handle was built from exactly these tensors (the constructor's arguments)."""
         k = self._keep
         ns = sorted_rows.numel() if n_sorted is None else int(n_sorted)
         return (k[0] is bank and k[1] is inv_norm and k[2] is meta and k[3] is sorted_shadow and k[4] is rho
                 and k[5] is sorted_rows and k[6] is pad_off and k[7] is list_len and k[8] is lists_flag
-                and k[9] is row_constants and k[10] is centroids and self.ns == ns and self.nprobe == int(nprobe))
+                and k[9] is row_constants and k[10] is centroids and k[11] is rho16 and self.ns == ns
+                and self.nprobe == int(nprobe))
 
     def _call_args(self, queries, k: int, probe_ids):
         """Checks of one call's queries, ``k`` and probes: (nq, probe pointer or None)."""
@@ -2628,18 +2726,19 @@ class Ivf2Lists:
                 word.arm(None)
             return out_s, out_i, torch.zeros(1, dtype=torch.int32, device=dev)
         nbytes, base, ovf, stream = self._scratch(nq, k)
-        h, L = self._ptrs, self._lib
+        h = self._ptrs
+        f_plain, f_probed, f_signal, _ = self._fn
         if word is not None:
-            check(L.aura_knn_search_ivf2_signal(*h, self.ns, self.M, queries.data_ptr(), now, self.D, nq, k, self._cent,
+            check(f_signal(*h, self.ns, self.M, queries.data_ptr(), now, self.D, nq, k, self._cent,
                                                 self.nprobe, pid, idx_base, out_s.data_ptr(), out_i.data_ptr(), base,
                                                 nbytes, ovf.data_ptr(), word.ptr, word.arm(ovf), stream),
                   "aura_knn_search_ivf2_signal")
         elif pid is not None:
-            check(L.aura_knn_search_ivf2_probed(*h, self.ns, self.M, queries.data_ptr(), now, self.D, nq, k, self._cent,
+            check(f_probed(*h, self.ns, self.M, queries.data_ptr(), now, self.D, nq, k, self._cent,
                                                 self.nprobe, pid, idx_base, out_s.data_ptr(), out_i.data_ptr(), base,
                                                 nbytes, ovf.data_ptr(), stream), "aura_knn_search_ivf2_probed")
         else:
-            check(L.aura_knn_search_ivf2(*h, self.ns, self.M, queries.data_ptr(), now, self.D, nq, k, self._cent,
+            check(f_plain(*h, self.ns, self.M, queries.data_ptr(), now, self.D, nq, k, self._cent,
                                          self.nprobe, idx_base, out_s.data_ptr(), out_i.data_ptr(), base, nbytes,
                                          ovf.data_ptr(), stream), "aura_knn_search_ivf2")
         return out_s, out_i, ovf
@@ -2681,8 +2780,7 @@ class Ivf2Pass:
         self._args = args
 
     def _call(self, stage: int, k2: int, bounds) -> None:
-        check(lib().aura_knn_search_ivf2_staged(*self._args, stage, k2, _p(bounds), _stream()),
-              "aura_knn_search_ivf2_staged")
+        check(self._keep[0]._fn[3](*self._args, stage, k2, _p(bounds), _stream()), "aura_knn_search_ivf2_staged")
 
     def _bound(self, bound: torch.Tensor) -> torch.Tensor:
         _need(bound, "bound", torch.float32)

@@ -621,7 +621,7 @@ int aura_knn_search_shadow(const float* bank, const uint16_t* bank_bf16, const f
                            const float* centroids, int nprobe, void* stream);
 
 /* Centroid-index recall (hippocampal.py:259-270) as inverted lists on the two-stage machinery: the
- * caller keeps a LIST-SORTED bf16 shadow -- sorted row i holds the shadow row of bank row
+ * caller keeps a LIST-SORTED bf16 shadow (IEEE half: the *_f16 forms below) -- sorted row i holds the shadow row of bank row
  * sorted_rows[i] (-1: no row, scanned as padding), the rows of one centroid contiguous.
  * pad_off [257]: first sorted row of each list, multiples of 16 (pad_off[256] <= n_sorted);
  * list_len [256]: entries in use, list_len[c] <= pad_off[c+1] - pad_off[c] -- the difference is
@@ -730,6 +730,77 @@ int aura_knn_search_ivf2_staged(const float* bank, const float* inv_norm, const 
                                 int k, const float* centroids, int nprobe, const int32_t* probe_ids, int32_t idx_base,
                                 float* out_scores, int32_t* out_idx, void* workspace, int64_t workspace_bytes,
                                 int32_t* overflow_out, int stage, int k2, float* bounds, void* stream);
+
+/* The list-sorted image in IEEE half.  Normalised rows and queries lie in [-1, 1], so half (11 significand bits)
+ * covers them at the size of bf16 (8 bits) and the prefilter's band U - L = 2 (rho_row + E_fix + eq) becomes 5-6
+ * times narrower at D = 768: fewer candidates leave the filter scan and fewer survivors are gathered in fp32 by the
+ * refine.  Results are unchanged (the rows and score bits of the fp32 scan).
+ *   Conversion: fl(bank[r] * inv_norm[r]) rounded to nearest, ties to even; an element with |x| < 2^-14 is stored as
+ *     +0, so the image holds no subnormal and the bound does not depend on how the matrix pipe treats them; the
+ *     residual is taken against what is stored.  Queries are converted alike.
+ *   rho16 [rows of the bank]: the residual norm of the half image, aura_bank_shadow_update's formula on that residual.
+ *     The writers below keep writing the bf16 residual into `rho` bit for bit as their bf16 forms do (the row-ordered
+ *     shadow shares that array) and write rho16 when it is not NULL.  The readers (row constants, the four searches,
+ *     the consolidate scan) take rho16 in rho's place.  aura_ivf2_append_f16 with a table of row constants needs rho16.
+ *   Negative strengths use their own worst-case query bound, (1.001 (2^-11 1.00001 + sqrt(D) 2^-14) + (D/2 + 3) 2^-24)
+ *     (1 + 2^-7): 2^-11 relative on the elements that stay normal, at most 2^-14 each on those stored as 0.
+ * Every other argument, limit and return code is that of the entry point without the suffix. */
+int aura_bank_shadow_sorted_f16(const float* bank, const float* inv_norm, const int32_t* sorted_rows,
+                                uint16_t* sorted_f16, float* rho, float* rho16, int32_t* pos_of_row, int64_t n_sorted,
+                                int64_t D, void* stream);
+int aura_ivf2_append_f16(const float* bank, const float* inv_norm, const float* meta, const int64_t* slots,
+                         int64_t n, int64_t D, uint16_t* sorted_f16, int32_t* sorted_rows, const int32_t* pad_off,
+                         int32_t* list_len, int32_t* pos_of_row, float* rho, float* rho16, int32_t* flag,
+                         float* row_constants, float row_constants_now, void* stream);
+int aura_ivf2_row_constants_f16(const float* meta, const float* rho16, const int32_t* sorted_rows, int64_t n_sorted,
+                                int64_t D, float now, float* row_constants, void* stream);
+int aura_knn_search_ivf2_f16(const float* bank, const float* inv_norm, const float* meta,
+                             const uint16_t* sorted_f16, const float* rho16, const int32_t* sorted_rows,
+                             const int32_t* pad_off, const int32_t* list_len, const int32_t* lists_flag,
+                             const float* row_constants,
+                             int64_t n_sorted, int64_t N, const float* queries, float now, int64_t D, int64_t nq, int k,
+                             const float* centroids, int nprobe, int32_t idx_base, float* out_scores,
+                             int32_t* out_idx, void* workspace, int64_t workspace_bytes, int32_t* overflow_out,
+                             void* stream);
+int aura_knn_search_ivf2_probed_f16(const float* bank, const float* inv_norm, const float* meta,
+                                    const uint16_t* sorted_f16, const float* rho16, const int32_t* sorted_rows,
+                                    const int32_t* pad_off, const int32_t* list_len, const int32_t* lists_flag,
+                                    const float* row_constants,
+                                    int64_t n_sorted, int64_t N, const float* queries, float now, int64_t D, int64_t nq,
+                                    int k, const float* centroids, int nprobe, const int32_t* probe_ids, int32_t idx_base,
+                                    float* out_scores, int32_t* out_idx, void* workspace, int64_t workspace_bytes,
+                                    int32_t* overflow_out, void* stream);
+int aura_knn_search_ivf2_signal_f16(const float* bank, const float* inv_norm, const float* meta,
+                                    const uint16_t* sorted_f16, const float* rho16, const int32_t* sorted_rows,
+                                    const int32_t* pad_off, const int32_t* list_len, const int32_t* lists_flag,
+                                    const float* row_constants,
+                                    int64_t n_sorted, int64_t N, const float* queries, float now, int64_t D, int64_t nq,
+                                    int k, const float* centroids, int nprobe, const int32_t* probe_ids, int32_t idx_base,
+                                    float* out_scores, int32_t* out_idx, void* workspace, int64_t workspace_bytes,
+                                    int32_t* overflow_out, uint32_t* host_word, uint32_t host_seq, void* stream);
+int aura_knn_search_ivf2_staged_f16(const float* bank, const float* inv_norm, const float* meta,
+                                    const uint16_t* sorted_f16, const float* rho16, const int32_t* sorted_rows,
+                                    const int32_t* pad_off, const int32_t* list_len, const int32_t* lists_flag,
+                                    const float* row_constants,
+                                    int64_t n_sorted, int64_t N, const float* queries, float now, int64_t D, int64_t nq,
+                                    int k, const float* centroids, int nprobe, const int32_t* probe_ids, int32_t idx_base,
+                                    float* out_scores, int32_t* out_idx, void* workspace, int64_t workspace_bytes,
+                                    int32_t* overflow_out, int stage, int k2, float* bounds, void* stream);
+int aura_bank_find_repeats_f16(const float* bank, const float* inv_norm, int64_t N, int64_t D, const uint16_t* image_f16,
+                               const int32_t* image_rows, int64_t n_image, const float* rho16, const float* feats,
+                               int64_t n, float tau, int32_t* stored_target, int32_t* batch_leader, float* cos_out,
+                               int32_t* overflow_out, void* workspace, int64_t workspace_bytes, void* stream);
+int aura_bank_find_repeats_scoped_f16(const float* bank, const float* inv_norm, int64_t N, int64_t D,
+                                      const uint16_t* image_f16, const int32_t* image_rows, int64_t n_image,
+                                      const float* rho16, const float* feats, int64_t n, float tau,
+                                      int32_t* stored_target, int32_t* batch_leader, float* cos_out,
+                                      int32_t* overflow_out, void* workspace, int64_t workspace_bytes, void* stream,
+                                      const float* meta, const int32_t* batch_tags);
+int aura_bank_blend_f16(float* bank, float* inv_norm, int64_t N, int64_t rows, int64_t D, const float* feats,
+                        int64_t feats_row0, int64_t n, const int32_t* stored_target, const int32_t* batch_leader,
+                        float beta, float* out_feats, uint16_t* shadow_bf16, float* rho, int64_t shadow_upto,
+                        uint16_t* sorted_f16, float* rho16, const int32_t* sorted_rows, const int32_t* pos_of_row,
+                        int64_t n_sorted, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * Surrogate-gradient training path and the prosody-modulated GIF (fp32, [rows][T][H] layout)

@@ -253,7 +253,8 @@ def main():
 
         def kernels():
             return ops.find_repeats(hf.memory_features, hf._inv_norm, hf.memory_count, f, TAU, image=ivf.sorted_bf16,
-                                    image_rows=ivf.sorted_rows, n_image=ivf.n_sorted, rho=hf._rho, lists_flag=ivf.flag)
+                                    image_rows=ivf.sorted_rows, n_image=ivf.n_sorted, rho=hf._rho, rho16=hf._rho16,
+                                    lists_flag=ivf.flag)
         ev, ev_iters = alternated({
             "find_repeats_kernels": kernels,
             "recall_k1_kernels": lambda: hf.recall_batch(f, k=1, now=now, use_candidates=False, check_overflow=False)},
@@ -283,7 +284,7 @@ def main():
         def kernels_scoped():
             return ops.find_repeats_scoped(hf.memory_features, hf._inv_norm, hf.memory_metadata, hf.memory_count, f, bt,
                                            TAU, image=ivf.sorted_bf16, image_rows=ivf.sorted_rows, n_image=ivf.n_sorted,
-                                           rho=hf._rho, lists_flag=ivf.flag)
+                                           rho=hf._rho, rho16=hf._rho16, lists_flag=ivf.flag)
         ev, ev_iters = alternated({"unscoped_a": kernels, "scoped": kernels_scoped, "unscoped_b": kernels}, events_window)
         wl, wl_iters = alternated({"call_unscoped_a": lambda: hf.find_repeats(f, TAU),
                                    "call_scoped": lambda: hf.find_repeats(f, TAU, tags=bt),
