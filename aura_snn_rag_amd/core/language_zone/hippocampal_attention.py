@@ -7,13 +7,15 @@ bias each) and ``forward(hidden, prosody=None, use_memory=True) -> (output, None
 arithmetic from torch ops with the library's causal attention (the projections and the S x S attention
 are library GEMMs), gradients included.
 
-New on this module: ``new_cache`` / ``prefill`` / ``step``.  The causal forward at position t is a function of the rows
+New on this module: ``new_cache`` / ``prefill`` / ``step`` / ``extend``.  The causal forward at position t is a function of the rows
 0 .. t alone, so ``prefill`` over a prompt followed by one ``step`` per new token computes what ``forward`` over the
 whole sequence computes, without recomputing the context: a step is the three projections of the new row (library
 calls), ``ops.attn_decode_step`` (``csrc/aura_decode.hip``, the rule: ``include/aura_hip.h``, "Decode attention") and
 ``o_proj``.  The step is fp32, runs under ``no_grad`` and has no CPU fallback: CPU tensors raise ``AuraDeviceError``.
 ``step(fused=True)`` replaces the library calls by ``ops.row_linear`` (``csrc/aura_rowlin.hip``, "Row linear"): the three
 projections in one launch, with the layer's LayerNorm in front, and ``o_proj`` with the residual behind.
+``extend`` appends ``m`` tokens to a cache that already holds a context: the three projections of the ``B m`` rows,
+``ops.attn_decode_extend`` (one pass over K and V for all ``m`` queries; "Decode attention: extend") and ``o_proj``.
 """
 from __future__ import annotations
 
@@ -30,8 +32,10 @@ class AttentionCache:
     """The K/V cache of one attention module: ``k`` and ``v`` [B, H, capacity, dh] fp32, ``lengths`` int32 [B] on the
     device (the next position of each row; -1 retires a row: its steps return zeros and leave its cache alone), the
     partials ``workspace`` of the step, allocated once, and ``max_length``: a host-side upper bound of the lengths
-    (prompt length plus steps taken), so that a step past ``capacity`` raises without reading the device."""
-    __slots__ = ("k", "v", "lengths", "workspace", "n_chunks", "capacity", "max_length")
+    (prompt length plus steps taken), so that a step past ``capacity`` raises without reading the device.
+    ``extend_workspace`` is the partials workspace of ``extend``, allocated at first use and grown when a later call
+    feeds more tokens at once."""
+    __slots__ = ("k", "v", "lengths", "workspace", "n_chunks", "capacity", "max_length", "extend_workspace")
 
     def __init__(self, batch: int, heads: int, capacity: int, head_dim: int, device=None):
         for n, v in (("batch", batch), ("capacity", capacity)):
@@ -49,10 +53,19 @@ class AttentionCache:
         self.workspace = torch.empty(ops.attn_decode_workspace_floats(batch, heads, head_dim, self.n_chunks),
                                      dtype=torch.float32, device=device)
         self.max_length = 0
+        self.extend_workspace = None
 
     @property
     def batch(self) -> int:
         return self.k.shape[0]
+
+    def extend_workspace_for(self, m: int) -> torch.Tensor:
+        """The workspace of an extend of ``m`` tokens: kept between calls, re-allocated only to grow."""
+        B, H, _, dh = self.k.shape
+        need = ops.attn_decode_extend_workspace_floats(B, m, H, dh, self.n_chunks)
+        if self.extend_workspace is None or self.extend_workspace.numel() < need:
+            self.extend_workspace = torch.empty(need, dtype=torch.float32, device=self.k.device)
+        return self.extend_workspace
 
     def retire(self, rows) -> None:
         """Marks rows as finished (``lengths = -1``): their steps return zeros and write nothing."""
@@ -221,4 +234,39 @@ class HippocampalProsodyAttention(nn.Module):
                                    cache.lengths, cache.k, cache.v, cache.workspace, n_chunks=cache.n_chunks,
                                    advance=bool(advance))
         cache.max_length += 1
+        return self.o_proj(ctx)
+
+    @torch.no_grad()
+    def extend(self, hidden_states: torch.Tensor, prosody: Optional[torch.Tensor] = None, use_memory: bool = True,
+               cache: Optional[AttentionCache] = None, advance: bool = True) -> torch.Tensor:
+        """``m`` new tokens per row: hidden [B, m, D] (the normed rows), prosody [B, m, 4] or ``None``, ``1 <= m <=
+        ops.DECODE_EXTEND_MAX``.  Appends their keys and values at each row's length, attends (token ``j`` over the
+        cache and the new tokens up to itself) and returns the attention output [B, m, D]: what ``m`` calls of ``step``
+        return, from one pass over the cache.  The lengths advance by ``m`` on the device unless ``advance=False``.
+        Raises when the cache may not hold ``m`` more positions."""
+        who = "HippocampalProsodyAttention.extend"
+        if hidden_states.dim() != 3 or hidden_states.shape[-1] != self.hidden_size:
+            raise ValueError(f"{who}: hidden is [B, m, {self.hidden_size}], got {tuple(hidden_states.shape)}")
+        B, m, _ = hidden_states.shape
+        if not 1 <= m <= ops.DECODE_EXTEND_MAX:
+            raise ValueError(f"{who}: m={m} new tokens must be in [1, {ops.DECODE_EXTEND_MAX}]")
+        self._check_cache(who, cache, B)
+        if hidden_states.dtype != torch.float32:
+            raise TypeError(f"{who}: hidden is {hidden_states.dtype}; the decode extend runs in fp32 only")
+        if prosody is not None:
+            if tuple(prosody.shape) != (B, m, 4):
+                raise ValueError(f"{who}: prosody is [B, m, 4] = ({B}, {m}, 4), got {tuple(prosody.shape)}")
+            prosody = prosody.contiguous()
+        if cache.max_length + m > cache.capacity:
+            raise RuntimeError(f"{who}: {m} more positions do not fit the cache ({cache.max_length} of "
+                               f"{cache.capacity} may be held); a sliding cache is not part of this module")
+        x = hidden_states.contiguous()
+        memory = self._memory_on(use_memory)
+        ctx = ops.attn_decode_extend(self.q_proj(x), self.k_proj(x), self.v_proj(x), x if memory else None, prosody,
+                                     self.prosody_gate.weight, self.prosody_gate.bias,
+                                     self.memory_gate.weight if memory else None,
+                                     self.memory_gate.bias if memory else None,
+                                     cache.lengths, cache.k, cache.v, cache.extend_workspace_for(m),
+                                     n_chunks=cache.n_chunks, advance=bool(advance))
+        cache.max_length += m
         return self.o_proj(ctx)

@@ -2,7 +2,7 @@
 
 API-compatible with the reference's ``src/core/language_zone/hippocampal_layer.py`` (constructor, ``state_dict`` keys
 ``attention_norm`` / ``attention.*`` / ``ffn_norm`` / ``ffn.0`` / ``ffn.2``, ``forward``).  New on this module:
-``new_cache`` / ``prefill`` / ``step`` wrap the norms, the residuals and the feed-forward around the attention's, so
+``new_cache`` / ``prefill`` / ``step`` / ``extend`` wrap the norms, the residuals and the feed-forward around the attention's, so
 that a stack of layers decodes one token at a time, layer by layer, each with its own cache.  ``step(fused=True)`` is
 the same step in six launches (``ops.row_linear``, ``csrc/aura_rowlin.hip``)."""
 from __future__ import annotations
@@ -64,6 +64,15 @@ class HippocampalTransformerLayer(nn.Module):
             return self._fused_step(hidden_states, prosody, use_memory, cache, advance)
         attn_output = self.attention.step(self.attention_norm(hidden_states), prosody=prosody, use_memory=use_memory,
                                           cache=cache, advance=advance)
+        return self._feed_forward(hidden_states + self.dropout(attn_output))
+
+    @torch.no_grad()
+    def extend(self, hidden_states: torch.Tensor, prosody: Optional[torch.Tensor] = None, use_memory: bool = True,
+               cache: Optional[AttentionCache] = None, advance: bool = True) -> torch.Tensor:
+        """``m`` new tokens through the layer: hidden [B, m, D] -> [B, m, D], the layer's formula around the
+        attention's ``extend``."""
+        attn_output = self.attention.extend(self.attention_norm(hidden_states), prosody=prosody,
+                                            use_memory=use_memory, cache=cache, advance=advance)
         return self._feed_forward(hidden_states + self.dropout(attn_output))
 
     def _fused_step(self, hidden_states, prosody, use_memory, cache, advance) -> torch.Tensor:

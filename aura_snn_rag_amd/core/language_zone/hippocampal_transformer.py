@@ -45,8 +45,15 @@ class DecodeState:
     """What a generation carries between steps: one ``AttentionCache`` per layer, all sharing one int32 ``lengths``
     tensor (only the last layer's step advances it; -1 retires a row), the host-side ``position`` (prompt length plus
     steps taken), the ``seen`` mask [B, V] uint8 of the tokens a row holds (the repetition penalty's set),
-    ``finished`` uint8 [B], and the sampler's ``seed`` and ``step`` counter."""
-    __slots__ = ("caches", "lengths", "position", "seen", "finished", "seed", "step", "capacity")
+    ``finished`` uint8 [B], and the sampler's ``seed`` and ``step`` counter.
+
+    ``ragged`` (default False): the rows no longer share one position.  ``step`` and ``extend`` then take the new
+    tokens' positions from the device lengths, ``lengths[:, None] + arange(m)``, and ``position`` is only an upper
+    bound.  ``pending`` int64 [B] or ``None``: the last token of every row's history, which has not been through the
+    model yet (what ``generate(.., return_state=True)`` leaves; the next ``generate(.., state=)`` feeds it first).
+    ``stream_ids``: the rows' random streams of the generation that returned the state."""
+    __slots__ = ("caches", "lengths", "position", "seen", "finished", "seed", "step", "capacity", "ragged", "pending",
+                 "stream_ids")
 
     def __init__(self, caches: List[AttentionCache], seen: torch.Tensor, finished: torch.Tensor, seed: int):
         self.caches = caches
@@ -59,6 +66,9 @@ class DecodeState:
         self.finished = finished
         self.seed = int(seed)
         self.step = 0
+        self.ragged = False
+        self.pending = None
+        self.stream_ids = None
 
     @property
     def batch(self) -> int:
@@ -66,8 +76,8 @@ class DecodeState:
 
 
 class CachedDecodingMixin:
-    """``new_state`` / ``step`` / ``generate`` of a model that has ``config``, ``layers`` (each with ``new_cache`` and
-    ``step``), ``semantic_encoder``, ``pos_encoder``, ``layer_norm``, ``dropout``, ``output_head`` and its own
+    """``new_state`` / ``step`` / ``extend`` / ``generate`` of a model that has ``config``, ``layers`` (each with ``new_cache`` and
+    ``step`` and ``extend``), ``semantic_encoder``, ``pos_encoder``, ``layer_norm``, ``dropout``, ``output_head`` and its own
     ``prefill(input_ids, prosody=None, state=None, use_memory=True)``: the decode loop ``HippocampalTransformer`` and
     ``SNNRAGTransformer`` share.  Messages name the class that raises."""
 
@@ -96,7 +106,8 @@ class CachedDecodingMixin:
         """One new token per row: tokens [B] (or [B, 1]) at position ``state.position`` -> logits [B, V].  Every
         layer's ``step`` runs on its cache; the last one advances the shared lengths.  ``fused=True`` (B <= 32) takes
         every layer's fused step: six launches a layer instead of fourteen; the front end and the head stay as they
-        are.  No host sync."""
+        are.  With ``state.ragged`` every row's position is its device length instead of ``state.position``.  No host
+        sync."""
         who = f"{type(self).__name__}.step"
         if tokens.dim() == 1:
             tokens = tokens[:, None]
@@ -106,8 +117,12 @@ class CachedDecodingMixin:
         if fused and tokens.shape[0] > ops.ROW_LINEAR_MAX_ROWS:
             raise ValueError(f"{who}: the fused step takes at most {ops.ROW_LINEAR_MAX_ROWS} rows, got "
                              f"B={tokens.shape[0]}; use fused=False")
-        hidden_states, _ = embed_tokens(tokens, self.semantic_encoder, self.pos_encoder, self.layer_norm,
-                                        start=state.position, dense=False)
+        if state.ragged:
+            hidden_states, _ = embed_tokens(tokens, self.semantic_encoder, self.pos_encoder, self.layer_norm,
+                                            dense=False, positions=state.lengths[:, None])
+        else:
+            hidden_states, _ = embed_tokens(tokens, self.semantic_encoder, self.pos_encoder, self.layer_norm,
+                                            start=state.position, dense=False)
         hidden_states = self.dropout(hidden_states)[:, 0]
         last = len(self.layers) - 1
         for i, (layer, cache) in enumerate(zip(self.layers, state.caches)):
@@ -116,11 +131,52 @@ class CachedDecodingMixin:
         state.position += 1
         return self.output_head(hidden_states)
 
+    @torch.no_grad()
+    def extend(self, tokens: torch.Tensor, prosody: Optional[torch.Tensor] = None, state: Optional[DecodeState] = None,
+               use_memory: bool = True) -> torch.Tensor:
+        """``m >= 1`` new tokens per row appended to a state that holds a context: tokens [B, m] (prosody [B, m, 4] or
+        ``None``) at the positions after each row's context -> logits [B, m, V], what ``m`` calls of ``step`` return.
+        The tokens go through the layers' ``extend`` in pieces of at most ``ops.DECODE_EXTEND_MAX``; in each piece the
+        last layer advances the shared lengths.  Marks the tokens in ``state.seen``.  No host sync."""
+        who = f"{type(self).__name__}.extend"
+        if tokens.dim() != 2 or tokens.shape[1] < 1:
+            raise ValueError(f"{who}: tokens is [B, m] with m >= 1, got {tuple(tokens.shape)}")
+        B, m = tokens.shape
+        self._check_state(who, state, B)
+        if prosody is not None and tuple(prosody.shape) != (B, m, 4):
+            raise ValueError(f"{who}: prosody is [B, m, 4] = ({B}, {m}, 4), got {tuple(prosody.shape)}")
+        held = max(cache.max_length for cache in state.caches)
+        if held + m > state.capacity:
+            raise RuntimeError(f"{who}: {m} more positions do not fit the caches ({held} of {state.capacity} may be "
+                               f"held); a sliding cache is not part of this module")
+        last = len(self.layers) - 1
+        logits = []
+        for t0 in range(0, m, ops.DECODE_EXTEND_MAX):
+            piece = tokens[:, t0:t0 + ops.DECODE_EXTEND_MAX]
+            n = piece.shape[1]
+            if state.ragged:
+                positions = state.lengths[:, None] + torch.arange(n, dtype=torch.int32, device=state.lengths.device)
+                hidden_states, _ = embed_tokens(piece, self.semantic_encoder, self.pos_encoder, self.layer_norm,
+                                                dense=False, positions=positions)
+            else:
+                hidden_states, _ = embed_tokens(piece, self.semantic_encoder, self.pos_encoder, self.layer_norm,
+                                                start=state.position, dense=False)
+            hidden_states = self.dropout(hidden_states)
+            part = None if prosody is None else prosody[:, t0:t0 + n]
+            for i, (layer, cache) in enumerate(zip(self.layers, state.caches)):
+                hidden_states = layer.extend(hidden_states, prosody=part, use_memory=use_memory, cache=cache,
+                                             advance=i == last)
+            state.position += n
+            logits.append(self.output_head(hidden_states))
+        state.seen.scatter_(1, tokens.to(torch.int64), 1)
+        return logits[0] if len(logits) == 1 else torch.cat(logits, dim=1)
+
     def generate(self, input_ids: torch.Tensor, max_new_tokens: int = 50, temperature: float = 0.8, top_k: int = 50,
                  top_p: float = 0.9, use_memory: bool = True, repetition_penalty: float = 1.2, *,
                  repetition_rule: str = "divide", seed: Optional[int] = None, eos_token_id=_UNSET,
                  pad_token_id: Optional[int] = None, sync_every: int = 8, stream_ids=None,
-                 fused_step: bool = False) -> torch.Tensor:
+                 fused_step: bool = False, state: Optional[DecodeState] = None, return_state: bool = False,
+                 capacity: Optional[int] = None):
         """Generates up to ``max_new_tokens`` tokens after the prompts ``input_ids`` [B, S] (equal lengths, as in the
         reference) -> [B, S + n].  Runs under ``eval()`` and ``no_grad``: one ``prefill``, then per token one ``step``
         and one ``ops.sample_next`` that writes the token into its column of the preallocated result.
@@ -138,7 +194,16 @@ class CachedDecodingMixin:
         re-based, positions simply continue (``S + max_new_tokens`` must fit ``ops.DECODE_MAX_CAP``); generation
         stops when every row has finished, not only when every row emits EOS in the same step; top-k keeps exactly
         ``k`` candidates and the random stream is fixed by ``(seed, step, stream, token id)`` (the rule:
-        ``include/aura_hip.h``, "Next token")."""
+        ``include/aura_hip.h``, "Next token").
+
+        Continuing.  ``return_state=True`` returns ``(tokens, state)``; ``capacity`` (default ``S + max_new_tokens``)
+        reserves cache room for later turns.  In the returned state every row stands at the end of its own history
+        (the prompt and what it generated up to and including its EOS, or all ``n`` tokens without one): the last
+        history token has not been through the model, so ``lengths[b] = len(history_b) - 1`` and ``pending[b]`` is
+        that token; ``finished`` is clear and ``ragged`` set.  ``generate(new_ids [B, S2], state=state, ..)`` feeds
+        ``[pending, new_ids]`` through ``extend``, samples from the last position and decodes as above -> [B, S2 + n];
+        ``state.step`` and ``state.seen`` carry on, the seed and the streams are the state's unless given.  It raises
+        on the host, without reading the device, when the turn may not fit the state's capacity."""
         who = f"{type(self).__name__}.generate"
         if input_ids.dim() != 2 or input_ids.shape[1] < 1:
             raise ValueError(f"{who}: input_ids is [B, S] with S >= 1, got {tuple(input_ids.shape)}")
@@ -146,13 +211,28 @@ class CachedDecodingMixin:
             if isinstance(v, bool) or not isinstance(v, int) or v < 1:
                 raise ValueError(f"{who}: {n} must be an int >= 1, got {v!r}")
         B, S = input_ids.shape
-        capacity = S + max_new_tokens
-        if capacity > ops.DECODE_MAX_CAP:
+        width = S + max_new_tokens
+        if state is not None:
+            self._check_state(who, state, B)
+            if state.pending is None or not state.ragged:
+                raise ValueError(f"{who}: state must be one that generate(.., return_state=True) returned")
+            if capacity is not None:
+                raise ValueError(f"{who}: capacity is set where the state is made; this one holds {state.capacity}")
+            held = max(cache.max_length for cache in state.caches)
+            if held + width > state.capacity:
+                raise RuntimeError(f"{who}: this turn needs S + max_new_tokens = {width} more positions, the state "
+                                   f"may hold {held} of {state.capacity} (reserve room with capacity= in the first "
+                                   f"call; a sliding cache is not part of this module)")
+        elif capacity is None:
+            capacity = width
+        elif isinstance(capacity, bool) or not isinstance(capacity, int) or capacity < width:
+            raise ValueError(f"{who}: capacity must be an int >= S + max_new_tokens = {width}, got {capacity!r}")
+        if state is None and capacity > ops.DECODE_MAX_CAP:
             raise ValueError(f"{who}: S + max_new_tokens = {capacity} exceeds the cache limit {ops.DECODE_MAX_CAP} (a "
                              f"sliding cache is not part of this module)")
         eos = getattr(self.config, "eos_token_id", None) if eos_token_id is _UNSET else eos_token_id
         pad = pad_token_id if pad_token_id is not None else (eos if eos is not None else 0)
-        if seed is None:
+        if seed is None and state is None:
             seed = int(torch.randint(0, 1 << 62, (1,)).item())
         if fused_step and B > ops.ROW_LINEAR_MAX_ROWS:
             raise ValueError(f"{who}: fused_step takes at most {ops.ROW_LINEAR_MAX_ROWS} rows, got B={B}")
@@ -161,10 +241,26 @@ class CachedDecodingMixin:
             stream_ids = torch.as_tensor(list(stream_ids), dtype=torch.int64).to(dev)
         self.eval()
         with torch.no_grad():
-            state = self.new_state(B, capacity, seed=seed)
-            generated = torch.empty(B, capacity, dtype=torch.int64, device=dev)
+            generated = torch.empty(B, width, dtype=torch.int64, device=dev)
             generated[:, :S] = input_ids
-            logits = self.prefill(input_ids, state=state, use_memory=use_memory)[:, -1]
+            if state is None:
+                state = self.new_state(B, capacity, seed=seed)
+                state.stream_ids = stream_ids
+                logits = self.prefill(input_ids, state=state, use_memory=use_memory)[:, -1]
+            else:
+                if seed is not None:
+                    if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < (1 << 64):
+                        raise ValueError(f"{who}: seed must be an int in [0, 2^64), got {seed!r}")
+                    state.seed = seed
+                if stream_ids is None:
+                    stream_ids = state.stream_ids
+                else:
+                    state.stream_ids = stream_ids
+                turn = torch.cat([state.pending.to(dev)[:, None], input_ids.to(torch.int64)], dim=1)
+                state.pending = None
+                logits = self.extend(turn, state=state, use_memory=use_memory)[:, -1]
+            # every row's length with the prompt consumed, before the first retirement: what the returned state counts from
+            base = state.lengths.clone() if return_state else None
             n = 0
             while True:
                 column = generated[:, S + n]
@@ -186,7 +282,24 @@ class CachedDecodingMixin:
                 new = generated[:, S:S + n]
                 done_before = ((new == eos).cumsum(1) - (new == eos).to(torch.int64)) > 0
                 n = int((~done_before.all(0)).sum().item())
-        return generated[:, :S + n]
+            if return_state:
+                self._stand_at_history_end(state, base, generated[:, S:S + n], eos)
+        return (generated[:, :S + n], state) if return_state else generated[:, :S + n]
+
+    @staticmethod
+    def _stand_at_history_end(state: DecodeState, base: torch.Tensor, new: torch.Tensor, eos) -> None:
+        """Leaves ``state`` where a next turn starts (see ``generate``): ``new`` [B, n] are the generated columns,
+        ``base`` the lengths before the first of them was fed.  A row's history holds ``count`` of them, up to and
+        including its first EOS; ``count - 1`` went through the model.  Device ops only."""
+        n = new.shape[1]
+        count = torch.full((new.shape[0],), n, dtype=torch.int64, device=new.device)
+        if eos is not None:
+            before = ((new == eos).cumsum(dim=1) == 0).sum(dim=1)         # columns before the row's first EOS; n: none
+            count = torch.clamp(before + 1, max=n)
+        state.lengths.copy_(base.to(torch.int64) + count - 1)
+        state.pending = new.gather(1, (count - 1)[:, None])[:, 0].clone()
+        state.finished.zero_()
+        state.ragged = True
 
 
 class HippocampalTransformer(CachedDecodingMixin, nn.Module):

@@ -15,11 +15,11 @@ the memories fixed the layer is causal, and ``prefill`` plus ``step`` computes w
 the whole sequence computes.  Re-retrieval during a generation is not part of this module.
   * ``retrieve_context(hidden_states)`` -> ``MemoryContext`` or ``None`` (no bank, or an empty one);
   * ``forward(.., memory=context)`` injects the given context as it is and retrieves nothing;
-  * ``new_cache`` / ``prefill`` / ``step``: ``prefill`` pins the context (retrieved from the prompt, or given) in the
-    cache together with the constants of the generation, ``step`` is one token through the layer.  ``step(fused=True)``
-    replaces the strings of small torch launches by ``ops.row_linear``, for the ``gate`` injection
-    ``ops.row_linear_gate`` and for the spiking FFN ``ops.row_linear_gif`` (``csrc/aura_rowlin.hip``); it raises where
-    it does not apply and never falls back.
+  * ``new_cache`` / ``prefill`` / ``step`` / ``extend``: ``prefill`` pins the context (retrieved from the prompt, or
+    given) in the cache together with the constants of the generation, ``step`` is one token through the layer,
+    ``extend`` several at once (``ops.attn_decode_extend``).  ``step(fused=True)`` replaces the strings of small torch
+    launches by ``ops.row_linear``, for the ``gate`` injection ``ops.row_linear_gate`` and for the spiking FFN
+    ``ops.row_linear_gif`` (``csrc/aura_rowlin.hip``); it raises where it does not apply and never falls back.
 """
 from __future__ import annotations
 
@@ -235,6 +235,18 @@ class MemoryAugmentedLayer(BatchedMemoryMixin, nn.Module):
                                           cache=cache.attention, advance=advance)
         hidden_states = (hidden_states + self.dropout(attn_output))[:, None]
         return self._after_attention(hidden_states, memory is not None, memory)[:, 0]
+
+    @torch.no_grad()
+    def extend(self, hidden_states: torch.Tensor, prosody: Optional[torch.Tensor] = None, use_memory: bool = True,
+               cache: Optional[MemoryLayerCache] = None, advance: bool = True) -> torch.Tensor:
+        """``m`` new tokens through the layer: hidden [B, m, D] -> [B, m, D], the layer's formula around the
+        attention's ``extend``, with the memories ``prefill`` pinned injected at every new position
+        (``use_memory=False`` injects nothing)."""
+        self._check_cache("MemoryAugmentedLayer.extend", cache)
+        memory = cache.memory if use_memory else None
+        attn_output = self.attention.extend(self.attention_norm(hidden_states), prosody=prosody,
+                                            use_memory=use_memory, cache=cache.attention, advance=advance)
+        return self._after_attention(hidden_states + self.dropout(attn_output), memory is not None, memory)
 
     def _mlp(self):
         return self.ffn.mlp if self.use_snn_ffn else self.ffn

@@ -125,9 +125,12 @@ class ThetaGammaPositionalEncoding(nn.Module):
 
 
 def embed_tokens(input_ids: torch.Tensor, semantic_encoder, pos_encoder: ThetaGammaPositionalEncoding,
-                 norm: nn.LayerNorm, start: int = 0, dense: bool = True):
+                 norm: nn.LayerNorm, start: int = 0, dense: bool = True, positions: Optional[torch.Tensor] = None):
     """The front end of both reference models, tokens to first hidden state (up to, not including, dropout):
     ``semantic, code = semantic_encoder(input_ids)``, ``hidden = norm(semantic + pos_encoder(arange(S)))``.  Returns
-    ``(hidden [B, S, D], place_cell_activity [B, S, P])``, or with ``dense=False`` the code as a ``PlaceCode``."""
+    ``(hidden [B, S, D], place_cell_activity [B, S, P])``, or with ``dense=False`` the code as a ``PlaceCode``.
+    ``positions`` [B, S] (instead of ``start``) gives every row its own positions, as ``encode_add_norm`` takes them."""
     semantic, code = semantic_encoder(input_ids) if dense else semantic_encoder.forward_sparse(input_ids)
+    if positions is not None:
+        return pos_encoder.encode_add_norm(semantic, norm, positions=positions), code
     return pos_encoder.encode_add_norm(semantic, norm, start=start), code

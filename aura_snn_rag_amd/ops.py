@@ -866,6 +866,108 @@ def attn_decode_step(q, k_new, v_new, x, prosody, Wp, bp, wm, bm, lengths, k_cac
     return (ctx, scale) if return_scale else ctx
 
 
+DECODE_EXTEND_MAX = 32
+
+
+def attn_decode_extend_workspace_floats(B: int, m: int, H: int, dh: int, n_chunks: int) -> int:
+    """Floats of partials workspace of an extend of ``m`` tokens: the step's for ``B m`` rows."""
+    return attn_decode_workspace_floats(B * m, H, dh, n_chunks)
+
+
+def _attn_decode_extend_shapes(q, k_new, v_new, x, prosody, Wp, bp, wm, bm, lengths, k_cache, v_cache, workspace,
+                               n_chunks) -> Tuple[int, int, int, int, int, int]:
+    """Type, shape and limit checks of ``attn_decode_extend``: ``(B, m, H, dh, cap, n_chunks)``.  Touches no device."""
+    who = "attn_decode_extend"
+    _theta_required(who, (("q", q), ("k_new", k_new), ("v_new", v_new), ("lengths", lengths), ("k_cache", k_cache),
+                          ("v_cache", v_cache), ("workspace", workspace)))
+    _place_fp32(who, (("q", q), ("k_new", k_new), ("v_new", v_new), ("x", x), ("prosody", prosody), ("Wp", Wp),
+                      ("bp", bp), ("wm", wm), ("bm", bm), ("k_cache", k_cache), ("v_cache", v_cache),
+                      ("workspace", workspace)), "the decode extend runs")
+    if not isinstance(lengths, torch.Tensor):
+        raise TypeError(f"{who}: lengths must be a torch.Tensor, got {type(lengths)}")
+    if lengths.dtype != torch.int32:
+        raise TypeError(f"{who}: lengths is {lengths.dtype}; the kernel reads and advances int32 lengths")
+    if not lengths.is_contiguous():
+        raise ValueError(f"{who}: lengths must be contiguous")
+    if k_cache.dim() != 4 or v_cache.shape != k_cache.shape:
+        raise ValueError(f"{who}: k_cache and v_cache are [B, H, cap, dh]; got {tuple(k_cache.shape)}, "
+                         f"{tuple(v_cache.shape)}")
+    B, H, cap, dh = k_cache.shape
+    D = H * dh
+    if H < 1 or dh % 4 != 0 or not 4 <= dh <= DECODE_MAX_HEAD:
+        raise ValueError(f"{who}: dh={dh} must be a multiple of 4 in [4, {DECODE_MAX_HEAD}] (H={H})")
+    if D > DECODE_MAX_D:
+        raise ValueError(f"{who}: D = H dh = {D} exceeds {DECODE_MAX_D}")
+    if not 1 <= cap <= DECODE_MAX_CAP:
+        raise ValueError(f"{who}: cap={cap} must be in [1, {DECODE_MAX_CAP}]")
+    if q.dim() != 3 or q.shape[0] != B or q.shape[2] != D:
+        raise ValueError(f"{who}: q is [B, m, D] = ({B}, m, {D}), got {tuple(q.shape)}")
+    m = q.shape[1]
+    if not 1 <= m <= DECODE_EXTEND_MAX:
+        raise ValueError(f"{who}: m={m} new tokens must be in [1, {DECODE_EXTEND_MAX}]")
+    for n, t in (("k_new", k_new), ("v_new", v_new)):
+        if tuple(t.shape) != (B, m, D):
+            raise ValueError(f"{who}: {n} is [B, m, D] = ({B}, {m}, {D}), got {tuple(t.shape)}")
+    if tuple(lengths.shape) != (B,):
+        raise ValueError(f"{who}: lengths is [B] = ({B},), got {tuple(lengths.shape)}")
+    if prosody is not None:
+        if tuple(prosody.shape) != (B, m, 4):
+            raise ValueError(f"{who}: prosody is [B, m, 4] = ({B}, {m}, 4), got {tuple(prosody.shape)}")
+        _theta_required(who, (("Wp (with prosody)", Wp), ("bp (with prosody)", bp)))
+        if tuple(Wp.shape) != (H, 4) or tuple(bp.shape) != (H,):
+            raise ValueError(f"{who}: Wp is [H, 4] and bp [H] with H={H}; got {tuple(Wp.shape)}, {tuple(bp.shape)}")
+    if (wm is None) != (bm is None):
+        raise ValueError(f"{who}: wm and bm are the memory gate's weight and bias: give both or neither")
+    if wm is not None:
+        _theta_required(who, (("x (with wm)", x),))
+        if wm.numel() != D or bm.numel() != 1:
+            raise ValueError(f"{who}: wm holds D={D} weights and bm one bias; got {tuple(wm.shape)}, {tuple(bm.shape)}")
+        if tuple(x.shape) != (B, m, D):
+            raise ValueError(f"{who}: x is [B, m, D] = ({B}, {m}, {D}), got {tuple(x.shape)}")
+    if n_chunks is None:
+        n_chunks = attn_decode_chunks(cap)
+    if isinstance(n_chunks, bool) or not isinstance(n_chunks, int):
+        raise TypeError(f"{who}: n_chunks must be an int, got {type(n_chunks)}")
+    if n_chunks < 1 or n_chunks * DECODE_CHUNK > cap + DECODE_CHUNK - 1:
+        raise ValueError(f"{who}: n_chunks={n_chunks} must be in [1, ceil(cap / {DECODE_CHUNK})] with cap={cap}")
+    if B * m * H * n_chunks > 0x7fffffff:
+        raise ValueError(f"{who}: B m H n_chunks = {B * m * H * n_chunks} partials exceed 2^31 - 1")
+    need = attn_decode_extend_workspace_floats(B, m, H, dh, n_chunks)
+    if workspace.numel() < need:
+        raise ValueError(f"{who}: workspace holds {workspace.numel()} floats, an extend of {m} needs {need}")
+    return B, m, H, dh, cap, n_chunks
+
+
+def attn_decode_extend(q, k_new, v_new, x, prosody, Wp, bp, wm, bm, lengths, k_cache, v_cache, workspace,
+                       n_chunks: Optional[int] = None, advance: bool = True, return_scale: bool = False):
+    """``m`` new tokens per row appended to a cache that holds a context, in two launches and one pass over K and V (the
+    rule: ``include/aura_hip.h``, "Decode attention: extend"): ``q``, ``k_new``, ``v_new``, ``x`` [B, m, D] and
+    ``prosody`` [B, m, 4] are ``attn_decode_step``'s arguments for ``m`` successive steps, ``1 <= m <=
+    DECODE_EXTEND_MAX``.  Query ``j`` attends positions ``0 .. lengths[b] + j``; the ``m`` keys and values go to
+    positions ``lengths[b] ..``.  Returns ``ctx`` [B, m, D].  A row with a negative length, or that does not fit whole
+    (``lengths[b] + m > cap``), is inactive: zeros, nothing written.  ``advance`` adds ``m`` to the active rows'
+    lengths.  ``workspace``: ``attn_decode_extend_workspace_floats`` fp32.  ``return_scale`` also returns ``s``
+    [B, m, H].  Every bit of the results, the caches and the lengths is what the ``m`` steps leave.  No host sync."""
+    B, m, H, dh, cap, n_chunks = _attn_decode_extend_shapes(q, k_new, v_new, x, prosody, Wp, bp, wm, bm, lengths,
+                                                            k_cache, v_cache, workspace, n_chunks)
+    if prosody is None:
+        Wp = bp = None
+    if wm is None:
+        x = None
+    dev = _theta_device("attn_decode_extend", (("q", q), ("k_new", k_new), ("v_new", v_new), ("x", x),
+                                               ("prosody", prosody), ("Wp", Wp), ("bp", bp), ("wm", wm), ("bm", bm),
+                                               ("lengths", lengths), ("k_cache", k_cache), ("v_cache", v_cache),
+                                               ("workspace", workspace)),
+                        wide=("q", "k_new", "v_new", "x", "wm", "k_cache", "v_cache", "workspace"))
+    ctx = torch.empty(B, m, H * dh, dtype=torch.float32, device=dev)
+    scale = torch.empty(B, m, H, dtype=torch.float32, device=dev) if return_scale else None
+    check(lib().aura_attn_decode_extend(_p(q), _p(k_new), _p(v_new), _p(x), _p(prosody), _p(Wp), _p(bp), _p(wm), _p(bm),
+                                        _p(lengths), _p(k_cache), _p(v_cache), B, m, H, dh, cap, n_chunks,
+                                        int(bool(advance)), _p(workspace), workspace.numel() * 4, _p(ctx), _p(scale),
+                                        _stream()), "aura_attn_decode_extend")
+    return (ctx, scale) if return_scale else ctx
+
+
 # ---------------------------------------------------------------------------------------
 # row linear (the rule: include/aura_hip.h, "Row linear")
 # ---------------------------------------------------------------------------------------

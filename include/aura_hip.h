@@ -1186,6 +1186,40 @@ int aura_attn_decode_step(const float* q, const float* k_new, const float* v_new
                           int64_t dh, int64_t cap, int64_t n_chunks, int advance, float* workspace,
                           int64_t workspace_bytes, float* ctx, float* scale_or_null, void* stream);
 
+/* Decode attention: extend.  m new tokens per row appended to a cache that already holds a context, in one pass over K
+ * and V, csrc/aura_decode.hip.  Not a new formula: the rule above, once per query.
+ *
+ * q, k_new, v_new, x, ctx [B][m][D]; prosody [B][m][4] or NULL; scale [B][m][H] or NULL; 1 <= m <= 32; everything else as
+ * in the step.  Per row b, L = lengths[b]:
+ *   inactive  L < 0 or L + m > min(cap, 256 n_chunks): the row fits whole or is inactive whole.  Nothing is written to
+ *             either cache, lengths[b] stays, ctx[b][j] = 0 and scale[b][j][h] = 0 for every j.
+ *   active    for j = 0 .. m - 1: scale, q', scores, chunks and merge are the step's rule with L replaced by
+ *             L_j = L + j and row j of q, x and prosody; query j attends the positions 0 .. L + j, whose keys and values
+ *             are the cache's below L and k_new[b][t - L], v_new[b][t - L] from L on.
+ *   append    Kc[b][h][L + j] = k_new[b][j][h dh ..], Vc alike, bit copies.  Positions >= L are taken from k_new /
+ *             v_new by whoever needs them and never read from the cache in the launch that appends them; each is
+ *             written by exactly one wave, that of the chunk (L + j) / 256.
+ *   lengths   with `advance`, lengths[b] += m for active rows, by the second launch only.
+ * Hence, on the same inputs, ctx[b][j], the scales, both caches and the lengths after one extend of m are bit for bit
+ * what m successive calls of aura_attn_decode_step leave (step j given row j); m = 1 is the step.  The reason it holds
+ * without effort: a query's operation sequence, its cut into chunks, slots and blocks by position alone and the
+ * symmetric merges do not depend on what else a wave computes, and a block in which a query has no position leaves its
+ * (m, l, acc) alone.
+ * One wave per (b, h, chunk, group of 8 queries) in the first launch: it loads a block once and updates the running
+ * states of its queries from it; a wave whose queries do not reach its chunk exits at once.  One wave per (b, j, h) in
+ * the second, the chunks 0 .. (L + j) / 256 in ascending order.  No atomics; nothing depends on the batch, cap, n_chunks or the grid.
+ *
+ * workspace: aura_attn_decode_extend_workspace_bytes(B, m, H, dh, n_chunks) bytes (the step's for B m rows; -1 for
+ * arguments the call refuses), 16-byte aligned, owned by the caller, written before it is read.
+ * AURA_E_INVAL / AURA_E_ALIGN: the step's conditions, and m < 1, m > 32, B m H n_chunks > 2^31 - 1.  B == 0 launches
+ * nothing.  Two launches on `stream`. */
+int64_t aura_attn_decode_extend_workspace_bytes(int64_t B, int64_t m, int64_t H, int64_t dh, int64_t n_chunks);
+int aura_attn_decode_extend(const float* q, const float* k_new, const float* v_new, const float* x,
+                            const float* prosody_or_null, const float* Wp, const float* bp, const float* wm_or_null,
+                            const float* bm_or_null, int32_t* lengths, float* Kc, float* Vc, int64_t B, int64_t m,
+                            int64_t H, int64_t dh, int64_t cap, int64_t n_chunks, int advance, float* workspace,
+                            int64_t workspace_bytes, float* ctx, float* scale_or_null, void* stream);
+
 /* ---------------------------------------------------------------------------------------
  * Next token
  * ------------------------------------------------------------------------------------- */
