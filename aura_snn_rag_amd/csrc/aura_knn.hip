@@ -2465,29 +2465,31 @@ inline int launch_refine_for(const RefineArgs& r_in, int nqb, int64_t D, int cus
         }
     }
     const int grid_q = r.heavy ? (nqb < 2 * cus ? nqb : 2 * cus) : nqb;   // heavy list: a small grid walks it
-    auto launch_refine = [&](auto rows_tag, auto kc_tag) -> int {
+    auto launch_refine = [&](auto rows_tag, auto kc_tag, auto whole_tag) -> int {
         constexpr int ROWS = decltype(rows_tag)::value, KC = decltype(kc_tag)::value;
+        constexpr bool WHOLE = decltype(whole_tag)::value;
         size_t lds = (size_t)8 * ROWS * (KC + 4) * 4 + (size_t)Dpad * 4;
         if (lds < (size_t)RF_CAP * 12) lds = (size_t)RF_CAP * 12;
         if (r.heavy) {
-            if (aura_ensure_lds_attr(reinterpret_cast<const void*>(coarse_refine_list_kernel<ROWS, KC>),
+            if (aura_ensure_lds_attr(reinterpret_cast<const void*>(coarse_refine_list_kernel<ROWS, KC, WHOLE>),
                                 8 * ROWS * (KC + 4) * 4 + 768 * 4))
                 return AURA_E_LAUNCH;
-            hipLaunchKernelGGL((coarse_refine_list_kernel<ROWS, KC>), dim3((unsigned)grid_q), dim3(RF_THREADS), lds, s, r);
+            hipLaunchKernelGGL((coarse_refine_list_kernel<ROWS, KC, WHOLE>), dim3((unsigned)grid_q), dim3(RF_THREADS), lds, s, r);
             return aura_check_launch();
         }
-        if (aura_ensure_lds_attr(reinterpret_cast<const void*>(coarse_refine_kernel<ROWS, KC>),
+        if (aura_ensure_lds_attr(reinterpret_cast<const void*>(coarse_refine_kernel<ROWS, KC, WHOLE>),
                             8 * ROWS * (KC + 4) * 4 + 768 * 4))
             return AURA_E_LAUNCH;
-        hipLaunchKernelGGL((coarse_refine_kernel<ROWS, KC>), dim3((unsigned)grid_q), dim3(RF_THREADS), lds, s, r);
+        hipLaunchKernelGGL((coarse_refine_kernel<ROWS, KC, WHOLE>), dim3((unsigned)grid_q), dim3(RF_THREADS), lds, s, r);
         return aura_check_launch();
     };
     static const int geom = getenv("AURA_RF_GEOM") ? atoi(getenv("AURA_RF_GEOM")) : 0;   // A/B runs
-    if (geom == 1) return launch_refine(std::integral_constant<int, 8>{}, std::integral_constant<int, 128>{});
-    if (geom == 2) return launch_refine(std::integral_constant<int, 6>{}, std::integral_constant<int, 128>{});
-    if (geom == 3) return launch_refine(std::integral_constant<int, 16>{}, std::integral_constant<int, 256>{});
-    if (nqb > cus) return launch_refine(std::integral_constant<int, 10>{}, std::integral_constant<int, 192>{});
-    return launch_refine(std::integral_constant<int, 16>{}, std::integral_constant<int, 256>{});
+    if (geom == 1) return launch_refine(std::integral_constant<int, 8>{}, std::integral_constant<int, 128>{}, std::false_type{});
+    if (geom == 2) return launch_refine(std::integral_constant<int, 6>{}, std::integral_constant<int, 128>{}, std::false_type{});
+    if (geom == 3) return launch_refine(std::integral_constant<int, 16>{}, std::integral_constant<int, 256>{}, std::false_type{});
+    // more queries than CUs: whole rows in flight, 6 survivors per wave and round (48 per round), 53 KB of LDS
+    if (nqb > cus) return launch_refine(std::integral_constant<int, 6>{}, std::integral_constant<int, 256>{}, std::true_type{});
+    return launch_refine(std::integral_constant<int, 16>{}, std::integral_constant<int, 256>{}, std::false_type{});
 }
 
 // AURA_CS_DBG bit 64 (builds with -DAURA_CS_TIMERS=1 only): per-wave phase times of a filter launch (written by

@@ -71,9 +71,10 @@ constexpr int RF_CAP = 4096;             // candidates per query the refine kern
 constexpr int RF_SURV = 1024;            // survivors re-scored per query at most
 // re-scoring geometry (template parameters of coarse_refine_kernel): survivors per wave and round x
 // k-chunk.  <16, 256>: 133 KB of LDS, one workgroup per CU, 3 chunks -- passes with at most one query
-// per CU.  <10, 192>: 66 KB, two workgroups per CU, 4 chunks -- larger passes (e.g. the row-sharded
-// multi-GPU layout, where a rank refines every rank's queries).  Survivors are dealt round-robin so
-// the usual ~70 keep all 8 waves busy in either geometry.
+// per CU.  <6, 256, whole rows>: 53 KB, two workgroups per CU, 3 chunks, every chunk of a round's rows
+// requested before the first chain -- larger passes (the 2048-query headline; the row-sharded multi-GPU
+// layout, where a rank refines every rank's queries).  Survivors are dealt round-robin so the usual
+// 36-70 keep all 8 waves loading in either geometry.
 
 struct CoarseArgs {
     const float* bank;
@@ -1315,7 +1316,9 @@ __global__ __launch_bounds__(RF_THREADS) void coarse_refine_bounds_kernel(const 
     if (lane == 0) { out[(int64_t)q * 2] = tk; out[(int64_t)q * 2 + 1] = tk2; }
 }
 
-template <int RF_ROWS, int RF_KC>
+// RF_WHOLE: the re-scoring requests a survivor's whole row before its first chain starts (RF_KC = 256: a lane's
+// j-th 16 bytes of a row are the row's chunk j); otherwise one chunk is in flight ahead of the chain.
+template <int RF_ROWS, int RF_KC, bool RF_WHOLE = false>
 __device__ __forceinline__ void refine_one_query(const RefineArgs& a, const int q) {
     extern __shared__ __attribute__((aligned(16))) char rsmem[];
     // phase A: candidate arrays; phase B (aliases A): per-wave row chunks + the query
@@ -1336,6 +1339,15 @@ __device__ __forceinline__ void refine_one_query(const RefineArgs& a, const int 
     uint32_t tst[7] = {0u, 0u, 0u, 0u, 0u, 0u, 0u};
     auto stamp = [&](int i) { if (tm) tst[i] = (uint32_t)__builtin_amdgcn_s_memrealtime(); };
     stamp(0);
+    // the query, requested first: its address is known here, its place in the LDS (s_q) is free only once the
+    // candidate arrays are dead.  D <= 768 (coarse_eligible): at most two floats per thread.  The address is clamped
+    // and the padding zeroed at the store, so the loads are unconditional (see centroid_probe_kernel).
+    float qpre[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int64_t i = tid + j * RF_THREADS;
+        qpre[j] = a.queries[(int64_t)q * D + (i < D ? i : D - 1)];
+    }
     int n = a.cnt[(int64_t)q * CNT_STRIDE];
     bool ovf = false;
     const int capn = a.cap < RF_CAP ? a.cap : RF_CAP;
@@ -1425,67 +1437,131 @@ __device__ __forceinline__ void refine_one_query(const RefineArgs& a, const int 
     float* const s_q = reinterpret_cast<float*>(rsmem) + 8 * (RF_ROWS * RSTRIDE);   // [Dpad]
     const int64_t Dpad = (D + 31) / 32 * 32;
     stamp(3);
-    for (int64_t i = tid; i < Dpad; i += RF_THREADS) s_q[i] = i < D ? a.queries[(int64_t)q * D + i] : 0.0f;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {                            // (requested at the top)
+        const int64_t i = tid + j * RF_THREADS;
+        if (i < Dpad) s_q[i] = i < D ? qpre[j] : 0.0f;
+    }
     __syncthreads();
     stamp(4);
     const float iq = a.inv_q[q];
-    const bool ld_lane = lane * 4 < RF_KC;                   // lanes that move a row chunk
-    for (int base = 0; base < S; base += 8 * RF_ROWS) {
-        int cntw = (S - base - wave + 7) / 8;                // survivors of this wave in this round
-        cntw = cntw < 0 ? 0 : (cntw > RF_ROWS ? RF_ROWS : cntw);
-        if (cntw <= 0) continue;                             // wave-uniform
-        const float* rowp[RF_ROWS];
-#pragma unroll
-        for (int r = 0; r < RF_ROWS; ++r)
-            rowp[r] = (r < cntw && ld_lane) ? a.bank + (int64_t)s_surv[base + 8 * r + wave] * D + lane * 4 : nullptr;
-        float4 pre[RF_ROWS];
-        auto fetch = [&](int64_t k0) {                       // chunk [k0, k0 + RF_KC): lane -> 16 bytes
+    // one chunk of the fp32 chain: lane r runs survivor slot r's over kc floats of the stage
+    auto chain = [&](float acc, const float* rp, const float* qp, const int kc) -> float {
+        // (hipcc issues the 16 LDS reads of an unrolled body together and the 32 fmaf behind them.  A query with ONE
+        // survivor still spends 7 us re-scoring: a gather and 768 dependent fmaf with their reads in front.  Reading
+        // the next body ahead takes 64 more registers and is not built; on <10, 192> four groups ahead changed
+        // nothing.  AURA_CS_DBG=128 prints the phase times.)
+#pragma unroll 4
+        for (int kk = 0; kk < kc; kk += 8) {
+            const float4 b0 = *reinterpret_cast<const float4*>(rp + kk);
+            const float4 b1 = *reinterpret_cast<const float4*>(rp + kk + 4);
+            const float4 q0 = *reinterpret_cast<const float4*>(qp + kk);
+            const float4 q1 = *reinterpret_cast<const float4*>(qp + kk + 4);
+            acc = fmaf(q0.x, b0.x, acc); acc = fmaf(q1.x, b1.x, acc);
+            acc = fmaf(q0.y, b0.y, acc); acc = fmaf(q1.y, b1.y, acc);
+            acc = fmaf(q0.z, b0.z, acc); acc = fmaf(q1.z, b1.z, acc);
+            acc = fmaf(q0.w, b0.w, acc); acc = fmaf(q1.w, b1.w, acc);
+        }
+        return acc;
+    };
+    auto finish = [&](const int si, const float acc) {       // the survivor's exact key
+        const int32_t row = s_surv[si];
+        const float inv_m = a.inv_norm[row];
+        const float4 m = *reinterpret_cast<const float4*>(a.meta + (int64_t)row * 4);
+        const float comb = aura_score(acc, iq, inv_m, aura_time_weight(a.now, m.y), m.x);
+        s_key[si] = ((unsigned long long)ord_key(comb) << 32) | (uint32_t)(~(uint32_t)row);
+    };
+    if constexpr (RF_WHOLE) {
+        // Whole rows in flight, the chains of a round side by side in ONE wave.
+        //  * A wave requests every 16-byte piece of its rows of the round -- RF_NCH per lane and row -- before the
+        //    first chain starts, so a round waits for ONE gather from HBM, not for one per chunk.  Lane l's piece j
+        //    of a row is floats [256 j + 4 l, + 4): piece j of all lanes is the row's chunk j, which goes to the
+        //    stage once chain j - 1 is done.  The loads are unconditional and back to back: a slot beyond the wave's
+        //    share repeats a valid survivor (its result is discarded), a column beyond D is clamped into the row and
+        //    zeroed at the store to the stage (with a branch around each load hipcc waits for every load in turn,
+        //    see centroid_probe_kernel).
+        //  * The stage is one array of 8 x RF_ROWS rows and wave 0 runs all their chains, one lane per row: an LDS
+        //    read serves 48 lanes instead of 6, and the other waves issue none.  Measured per query at the headline
+        //    (36 survivors): 13.4 us with one chunk in flight, 11.0 with whole rows and the chains dealt to the
+        //    waves that staged them, 10.0 in this form.
+        static_assert(RF_KC == 256, "a lane's pieces of a row are the row's chunks");
+        static_assert(8 * RF_ROWS <= 64, "one lane of wave 0 per row of the round");
+        constexpr int RF_NCH = 3;                            // D <= 768 (coarse_eligible)
+        float* const s_stage = reinterpret_cast<float*>(rsmem);   // [8 RF_ROWS][RSTRIDE]: row wave * RF_ROWS + r
+        for (int base = 0; base < S; base += 8 * RF_ROWS) {  // (uniform over the workgroup: barriers inside)
+            const float* rowp[RF_ROWS];
 #pragma unroll
             for (int r = 0; r < RF_ROWS; ++r) {
-                pre[r] = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (rowp[r] && k0 + lane * 4 < D) pre[r] = *reinterpret_cast<const float4*>(rowp[r] + k0);
+                const int si = base + 8 * r + wave;
+                rowp[r] = a.bank + (int64_t)s_surv[si < S ? si : S - 1] * D;
             }
-        };
-        float acc = 0.0f;
-        fetch(0);
-        for (int64_t k0 = 0; k0 < Dpad; k0 += RF_KC) {
-            const int kc = (int)((Dpad - k0) < RF_KC ? (Dpad - k0) : RF_KC);
-            if (ld_lane) {
+            float4 pre[RF_NCH][RF_ROWS];
 #pragma unroll
-                for (int r = 0; r < RF_ROWS; ++r)
-                    *reinterpret_cast<float4*>(s_rows + r * RSTRIDE + lane * 4) = pre[r];
+            for (int c = 0; c < RF_NCH; ++c) {
+                const int64_t col = c * RF_KC + lane * 4;
+                const int64_t colc = col < D ? col : D - 4;  // (D is a multiple of 4)
+#pragma unroll
+                for (int r = 0; r < RF_ROWS; ++r) pre[c][r] = *reinterpret_cast<const float4*>(rowp[r] + colc);
             }
-            if (k0 + RF_KC < Dpad) fetch(k0 + RF_KC);        // next chunk flies during the chain
-            __builtin_amdgcn_wave_barrier();
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            if (lane < RF_ROWS) {
-                const float* rp = s_rows + lane * RSTRIDE;
-                const float* qp = s_q + k0;
-                // (measured: running the LDS reads four groups ahead of the chain changes nothing -- the
-                // phase is bound by the gather of the survivors' fp32 rows, 256 x 71 x 3 KB = 56 MB of
-                // random 1-KB pieces per launch at ~4 TB/s; AURA_CS_DBG=128 prints the phase times)
-#pragma unroll 4
-                for (int kk = 0; kk < kc; kk += 8) {
-                    const float4 b0 = *reinterpret_cast<const float4*>(rp + kk);
-                    const float4 b1 = *reinterpret_cast<const float4*>(rp + kk + 4);
-                    const float4 q0 = *reinterpret_cast<const float4*>(qp + kk);
-                    const float4 q1 = *reinterpret_cast<const float4*>(qp + kk + 4);
-                    acc = fmaf(q0.x, b0.x, acc); acc = fmaf(q1.x, b1.x, acc);
-                    acc = fmaf(q0.y, b0.y, acc); acc = fmaf(q1.y, b1.y, acc);
-                    acc = fmaf(q0.z, b0.z, acc); acc = fmaf(q1.z, b1.z, acc);
-                    acc = fmaf(q0.w, b0.w, acc); acc = fmaf(q1.w, b1.w, acc);
+            float acc = 0.0f;
+#pragma unroll
+            for (int c = 0; c < RF_NCH; ++c) {
+                const int64_t k0 = c * RF_KC;
+                if (c == 0 || k0 < Dpad) {                   // uniform (chunk 0 unconditional: hipcc sinks a chunk's
+                                                             // loads into its branch, behind the others')
+                    const int kc = (int)((Dpad - k0) < RF_KC ? (Dpad - k0) : RF_KC);
+                    const bool live = k0 + lane * 4 < D;
+#pragma unroll
+                    for (int r = 0; r < RF_ROWS; ++r) {
+                        float4 v = pre[c][r];
+                        v.x = live ? v.x : 0.0f; v.y = live ? v.y : 0.0f; v.z = live ? v.z : 0.0f; v.w = live ? v.w : 0.0f;
+                        *reinterpret_cast<float4*>(s_rows + r * RSTRIDE + lane * 4) = v;
+                    }
+                    __syncthreads();
+                    if (wave == 0 && lane < 8 * RF_ROWS) acc = chain(acc, s_stage + lane * RSTRIDE, s_q + k0, kc);
+                    __syncthreads();
                 }
             }
-            __builtin_amdgcn_wave_barrier();
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            if (wave == 0 && lane < 8 * RF_ROWS) {           // stage row `lane` is wave lane / RF_ROWS's slot lane % RF_ROWS
+                const int si = base + 8 * (lane % RF_ROWS) + lane / RF_ROWS;
+                if (si < S) finish(si, acc);
+            }
         }
-        if (lane < cntw) {
-            const int si = base + 8 * lane + wave;
-            const int32_t row = s_surv[si];
-            const float inv_m = a.inv_norm[row];
-            const float4 m = *reinterpret_cast<const float4*>(a.meta + (int64_t)row * 4);
-            const float comb = aura_score(acc, iq, inv_m, aura_time_weight(a.now, m.y), m.x);
-            s_key[si] = ((unsigned long long)ord_key(comb) << 32) | (uint32_t)(~(uint32_t)row);
+    } else {
+        const bool ld_lane = lane * 4 < RF_KC;                   // lanes that move a row chunk
+        for (int base = 0; base < S; base += 8 * RF_ROWS) {
+            int cntw = (S - base - wave + 7) / 8;                // survivors of this wave in this round
+            cntw = cntw < 0 ? 0 : (cntw > RF_ROWS ? RF_ROWS : cntw);
+            if (cntw <= 0) continue;                             // wave-uniform
+            const float* rowp[RF_ROWS];
+#pragma unroll
+            for (int r = 0; r < RF_ROWS; ++r)
+                rowp[r] = (r < cntw && ld_lane) ? a.bank + (int64_t)s_surv[base + 8 * r + wave] * D + lane * 4 : nullptr;
+            float4 pre[RF_ROWS];
+            auto fetch = [&](int64_t k0) {                       // chunk [k0, k0 + RF_KC): lane -> 16 bytes
+#pragma unroll
+                for (int r = 0; r < RF_ROWS; ++r) {
+                    pre[r] = make_float4(0.f, 0.f, 0.f, 0.f);
+                    if (rowp[r] && k0 + lane * 4 < D) pre[r] = *reinterpret_cast<const float4*>(rowp[r] + k0);
+                }
+            };
+            float acc = 0.0f;
+            fetch(0);
+            for (int64_t k0 = 0; k0 < Dpad; k0 += RF_KC) {
+                const int kc = (int)((Dpad - k0) < RF_KC ? (Dpad - k0) : RF_KC);
+                if (ld_lane) {
+#pragma unroll
+                    for (int r = 0; r < RF_ROWS; ++r)
+                        *reinterpret_cast<float4*>(s_rows + r * RSTRIDE + lane * 4) = pre[r];
+                }
+                if (k0 + RF_KC < Dpad) fetch(k0 + RF_KC);        // next chunk flies during the chain
+                __builtin_amdgcn_wave_barrier();
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                if (lane < RF_ROWS) acc = chain(acc, s_rows + lane * RSTRIDE, s_q + k0, kc);
+                __builtin_amdgcn_wave_barrier();
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            }
+            if (lane < cntw) finish(base + 8 * lane + wave, acc);
         }
     }
     __syncthreads();
@@ -1516,17 +1592,17 @@ __device__ __forceinline__ void refine_one_query(const RefineArgs& a, const int 
 }
 
 // one workgroup per query
-template <int RF_ROWS, int RF_KC>
+template <int RF_ROWS, int RF_KC, bool RF_WHOLE = false>
 __global__ __launch_bounds__(RF_THREADS) void coarse_refine_kernel(const RefineArgs a) {
-    refine_one_query<RF_ROWS, RF_KC>(a, (int)blockIdx.x);
+    refine_one_query<RF_ROWS, RF_KC, RF_WHOLE>(a, (int)blockIdx.x);
 }
 
 // a small grid walks the list of queries coarse_refine_wave_kernel left over (a.heavy; usually empty)
-template <int RF_ROWS, int RF_KC>
+template <int RF_ROWS, int RF_KC, bool RF_WHOLE = false>
 __global__ __launch_bounds__(RF_THREADS) void coarse_refine_list_kernel(const RefineArgs a) {
     const int n_items = a.heavy[0];
     for (int item = blockIdx.x; item < n_items; item += gridDim.x) {
-        refine_one_query<RF_ROWS, RF_KC>(a, a.heavy[1 + item]);
+        refine_one_query<RF_ROWS, RF_KC, RF_WHOLE>(a, a.heavy[1 + item]);
         __syncthreads();                                     // the shared arrays are reused
     }
 }
