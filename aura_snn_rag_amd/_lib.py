@@ -21,6 +21,7 @@ ERRORS = {-1: "AURA_E_INVAL (bad argument)", -2: "AURA_E_LAUNCH (HIP launch erro
           -3: "AURA_E_ALIGN (pointer alignment)"}
 
 DTYPE_F32, DTYPE_BF16 = 0, 1
+IMAGE_BF16, IMAGE_F16 = 0, 1   # AURA_IMAGE_*: the 16-bit format of a list-sorted image
 GIF_TIME_INVARIANT, GIF_MEAN_OUT = 1, 2
 STDP_PRE_TIME_INVARIANT, STDP_NO_APPLY = 1, 2
 KNN_FORCE_DENSE = 1
@@ -59,9 +60,8 @@ SIGNATURES = {
     "aura_diverse_select_workspace_bytes": (I64, [I64, I64, I64]),
     "aura_diverse_select": (I, [P, P, I64, I64, P, P, I64, I64, I64, F, F, P, P, P, I64, P]),
     "aura_bank_find_repeats_workspace_bytes": (I64, [I64]),
-    "aura_bank_find_repeats": (I, [P, P, I64, I64, P, P, I64, P, P, I64, F, P, P, P, P, P, I64, P]),
-    "aura_bank_find_repeats_scoped": (I, [P, P, I64, I64, P, P, I64, P, P, I64, F, P, P, P, P, P, I64, P, P, P]),
-    "aura_bank_blend": (I, [P, P, I64, I64, I64, P, I64, I64, P, P, F, P, P, P, I64, P, P, P, I64, P]),
+    "aura_bank_find_repeats": (I, [P, P, I64, I64, P, P, I64, P, P, I64, F, P, P, P, P, P, I64, P, P, I, P]),
+    "aura_bank_blend": (I, [P, P, I64, I64, I64, P, I64, I64, P, P, F, P, P, P, I64, P, P, P, P, I64, I, P]),
     "aura_bank_touch": (I, [P, I64, P, I64, F, P]),
     "aura_bank_compact_round_rows": (I64, []),
     "aura_bank_compact_workspace_bytes": (I64, [I64, I64, I]),
@@ -102,36 +102,16 @@ SIGNATURES = {
     "aura_bank_shadow_update": (I, [P, P, P, P, P, I64, I64, I64, P]),
     "aura_knn_search_shadow": (I, [P, P, P, P, P, P, F, I64, I64, I64, I, I32, P, P, P, I64, I, P, P, I, P]),
     "aura_knn_ivf2_workspace_bytes": (I64, [I64, I64, I]),
-    "aura_bank_shadow_sorted": (I, [P, P, P, P, P, P, I64, I64, P]),
-    "aura_ivf2_append": (I, [P, P, P, P, I64, I64, P, P, P, P, P, P, P, P, F, P]),
-    "aura_ivf2_row_constants": (I, [P, P, P, I64, I64, F, P, P]),
-    "aura_knn_search_ivf2": (I, [P, P, P, P, P, P, P, P, P, P, I64, I64, P, F, I64, I64, I, P, I, I32, P, P, P, I64, P, P]),
+    # the inverted lists: the image's format (IMAGE_BF16 / IMAGE_F16) is an argument, the layout an Ivf2ListsStruct
+    "aura_bank_shadow_sorted": (I, [P, P, P, P, P, P, P, I64, I64, I, P]),
+    "aura_ivf2_append": (I, [P, P, P, P, I64, I64, P, P, P, P, P, P, P, P, P, F, I, P]),
+    "aura_ivf2_row_constants": (I, [P, P, P, I64, I64, F, P, I, P]),
+    "aura_knn_search_ivf2": (I, [P, P, F, I64, I, P, I32, P, P, P, I64, P, I, I, P, P, U32, P]),
     "aura_centroid_probe_workspace_bytes": (I64, [I64]),
     "aura_centroid_probe": (I, [P, P, I64, I64, I, P, P, I64, P]),
-    "aura_knn_search_ivf2_probed": (I, [P, P, P, P, P, P, P, P, P, P, I64, I64, P, F, I64, I64, I, P, I, P, I32, P, P, P,
-                                        I64, P, P]),
-    "aura_knn_search_ivf2_staged": (I, [P, P, P, P, P, P, P, P, P, P, I64, I64, P, F, I64, I64, I, P, I, P, I32, P, P, P,
-                                        I64, P, I, I, P, P]),
     "aura_host_word_alloc": (I, [P]),
     "aura_host_word_free": (I, [P]),
     "aura_signal_flag": (I, [P, P, U32, P]),
-    "aura_knn_search_ivf2_signal": (I, [P, P, P, P, P, P, P, P, P, P, I64, I64, P, F, I64, I64, I, P, I, P, I32, P, P, P,
-                                        I64, P, P, U32, P]),
-    # the list-sorted image in IEEE half: rho16 beside (writers) or instead of (readers) rho
-    "aura_bank_shadow_sorted_f16": (I, [P, P, P, P, P, P, P, I64, I64, P]),
-    "aura_ivf2_append_f16": (I, [P, P, P, P, I64, I64, P, P, P, P, P, P, P, P, P, F, P]),
-    "aura_ivf2_row_constants_f16": (I, [P, P, P, I64, I64, F, P, P]),
-    "aura_knn_search_ivf2_f16": (I, [P, P, P, P, P, P, P, P, P, P, I64, I64, P, F, I64, I64, I, P, I, I32, P, P, P, I64,
-                                     P, P]),
-    "aura_knn_search_ivf2_probed_f16": (I, [P, P, P, P, P, P, P, P, P, P, I64, I64, P, F, I64, I64, I, P, I, P, I32, P, P,
-                                            P, I64, P, P]),
-    "aura_knn_search_ivf2_staged_f16": (I, [P, P, P, P, P, P, P, P, P, P, I64, I64, P, F, I64, I64, I, P, I, P, I32, P, P,
-                                            P, I64, P, I, I, P, P]),
-    "aura_knn_search_ivf2_signal_f16": (I, [P, P, P, P, P, P, P, P, P, P, I64, I64, P, F, I64, I64, I, P, I, P, I32, P, P,
-                                            P, I64, P, P, U32, P]),
-    "aura_bank_find_repeats_f16": (I, [P, P, I64, I64, P, P, I64, P, P, I64, F, P, P, P, P, P, I64, P]),
-    "aura_bank_find_repeats_scoped_f16": (I, [P, P, I64, I64, P, P, I64, P, P, I64, F, P, P, P, P, P, I64, P, P, P]),
-    "aura_bank_blend_f16": (I, [P, P, I64, I64, I64, P, I64, I64, P, P, F, P, P, P, I64, P, P, P, P, I64, P]),
     "aura_stdp_workspace_bytes": (I64, [I64, I64, I64, I64]),
     "aura_stdp_update": (I, [P, P, P, P, P, P, P, P, F, F, F, F, F, F, F, I64, I64, I64, I64, I, I, P, I64, P]),
     "aura_place_code": (I, [P, P, P, P, I64, I64, I64, I64, P, P, P, P, P]),
@@ -159,6 +139,13 @@ SIGNATURES = {
     "aura_profile_last_scan": (I, [P, P]),
     "aura_profile_last_scan_kind": (I, []),
 }
+
+
+class Ivf2ListsStruct(ctypes.Structure):
+    """``aura_ivf2_lists``: the same fields in the same order (pointers and 64-bit sizes first: no interior padding)."""
+    _fields_ = [(name, P) for name in ("bank", "inv_norm", "meta", "centroids", "image", "rho", "sorted_rows",
+                                       "pad_off", "list_len", "lists_flag", "row_constants")] + \
+               [("n_sorted", I64), ("N", I64), ("D", I64), ("nprobe", I32), ("image_format", I32)]
 
 
 class AuraHipUnavailable(RuntimeError):

@@ -32,7 +32,7 @@ Reference defects on this path (SURVEY.md 8a "hazards") and what this class does
     ``recall_batch(tags=..., newer_than=..., older_than=..., min_strength=...)`` recalls exactly within a scope
     (``aura_knn_search_scoped``); a bank that never uses tags is bit for bit what it was.  Consolidation can stay
     within tags (``merge_within_tags``, ``find_repeats(tags=...)``, ``consolidate(within_tags=...)``:
-    ``aura_bank_find_repeats_scoped``); off by default, and then scope-blind as before.
+    ``aura_bank_find_repeats`` by tag); off by default, and then scope-blind as before.
 """
 from __future__ import annotations
 
@@ -981,7 +981,7 @@ class HippocampalFormation(nn.Module):
         tags.  Off, ``tags`` together with a consolidating write raises ``ValueError``: the plain ``find_repeats`` is
         scope-blind, and a near-copy from one scope must not vanish into a memory of another.  On, the two go together:
         a row repeats only a held memory, or a stored earlier row of the batch, that carries ITS tag
-        (``find_repeats(tags=...)``, ``aura_bank_find_repeats_scoped``); rows without a tag are tag 0 and merge only
+        (``find_repeats(tags=...)``, ``aura_bank_find_repeats`` by tag); rows without a tag are tag 0 and merge only
         into untagged memories.  Per chunk the order stays reinforce, touch, write, and the kept rows are written WITH
         their tags before the next chunk searches."""
         tau = self.merge_similarity if merge_similarity is _INSTANCE_DEFAULT else merge_similarity
@@ -1796,7 +1796,7 @@ class HippocampalFormation(nn.Module):
 
     def _recall_staged(self, lists: "ops.Ivf2Lists", q, kk: int, now: float, probe_ids, bound_exchange):
         """Inverted-list recall in passes of at most 8192 queries, each in stages with the shards' bounds combined
-        in between (``aura_knn_search_ivf2_staged``): ``(scores, rows, overflow flag)``."""
+        in between (``aura_knn_search_ivf2``, staged): ``(scores, rows, overflow flag)``."""
         fn, parts = bound_exchange
         k2 = max(1, -(-kk // max(int(parts), 1)))
         step = ops.STAGED_MAX_QUERIES

@@ -393,9 +393,16 @@ int aura_bank_shadow_update(const float* bank, const float* inv_norm, uint16_t* 
     return aura_check_launch();
 }
 
-static int bank_shadow_sorted_impl(bool f16, const float* bank, const float* inv_norm, const int32_t* sorted_rows,
-                                   uint16_t* image, float* rho, float* rho16, int32_t* pos_of_row, int64_t n_sorted,
-                                   int64_t D, void* stream) {
+// image_format with rho16: AURA_IMAGE_F16, or AURA_IMAGE_BF16 without a rho16 (the half image's residuals)
+static bool bad_image_format(int image_format, const float* rho16) {
+    return image_format != AURA_IMAGE_F16 && (image_format != AURA_IMAGE_BF16 || rho16);
+}
+
+int aura_bank_shadow_sorted(const float* bank, const float* inv_norm, const int32_t* sorted_rows, uint16_t* image,
+                            float* rho, float* rho16, int32_t* pos_of_row, int64_t n_sorted, int64_t D,
+                            int image_format, void* stream) {
+    if (bad_image_format(image_format, rho16)) return AURA_E_INVAL;
+    const bool f16 = image_format == AURA_IMAGE_F16;
     if (n_sorted < 0 || D <= 0 || (D & 7)) return AURA_E_INVAL;
     if (n_sorted == 0) return AURA_OK;
     if (!bank || !inv_norm || !sorted_rows || !image || !rho) return AURA_E_INVAL;
@@ -413,24 +420,12 @@ static int bank_shadow_sorted_impl(bool f16, const float* bank, const float* inv
     return aura_check_launch();
 }
 
-int aura_bank_shadow_sorted(const float* bank, const float* inv_norm, const int32_t* sorted_rows,
-                            uint16_t* sorted_bf16, float* rho, int32_t* pos_of_row, int64_t n_sorted, int64_t D,
-                            void* stream) {
-    return bank_shadow_sorted_impl(false, bank, inv_norm, sorted_rows, sorted_bf16, rho, nullptr, pos_of_row, n_sorted, D,
-                                   stream);
-}
-
-int aura_bank_shadow_sorted_f16(const float* bank, const float* inv_norm, const int32_t* sorted_rows,
-                                uint16_t* sorted_f16, float* rho, float* rho16, int32_t* pos_of_row, int64_t n_sorted,
-                                int64_t D, void* stream) {
-    return bank_shadow_sorted_impl(true, bank, inv_norm, sorted_rows, sorted_f16, rho, rho16, pos_of_row, n_sorted, D,
-                                   stream);
-}
-
-static int ivf2_append_impl(bool f16, const float* bank, const float* inv_norm, const float* meta, const int64_t* slots,
-                            int64_t n, int64_t D, uint16_t* image, int32_t* sorted_rows, const int32_t* pad_off,
-                            int32_t* list_len, int32_t* pos_of_row, float* rho, float* rho16, int32_t* flag,
-                            float* row_constants, float row_constants_now, void* stream) {
+int aura_ivf2_append(const float* bank, const float* inv_norm, const float* meta, const int64_t* slots,
+                     int64_t n, int64_t D, uint16_t* image, int32_t* sorted_rows, const int32_t* pad_off,
+                     int32_t* list_len, int32_t* pos_of_row, float* rho, float* rho16, int32_t* flag,
+                     float* row_constants, float row_constants_now, int image_format, void* stream) {
+    if (bad_image_format(image_format, rho16)) return AURA_E_INVAL;
+    const bool f16 = image_format == AURA_IMAGE_F16;
     if (n < 0 || D <= 0 || (D & 7)) return AURA_E_INVAL;
     if (reinterpret_cast<uintptr_t>(row_constants) & 15) return AURA_E_ALIGN;
     if (n == 0) return AURA_OK;
@@ -450,22 +445,6 @@ static int ivf2_append_impl(bool f16, const float* bank, const float* inv_norm, 
                            pad_off, list_len, pos_of_row, rho, rho16, flag, reinterpret_cast<float4*>(row_constants),
                            row_constants_now);
     return aura_check_launch();
-}
-
-int aura_ivf2_append(const float* bank, const float* inv_norm, const float* meta, const int64_t* slots,
-                     int64_t n, int64_t D, uint16_t* sorted_bf16, int32_t* sorted_rows, const int32_t* pad_off,
-                     int32_t* list_len, int32_t* pos_of_row, float* rho, int32_t* flag, float* row_constants,
-                     float row_constants_now, void* stream) {
-    return ivf2_append_impl(false, bank, inv_norm, meta, slots, n, D, sorted_bf16, sorted_rows, pad_off, list_len,
-                            pos_of_row, rho, nullptr, flag, row_constants, row_constants_now, stream);
-}
-
-int aura_ivf2_append_f16(const float* bank, const float* inv_norm, const float* meta, const int64_t* slots,
-                         int64_t n, int64_t D, uint16_t* sorted_f16, int32_t* sorted_rows, const int32_t* pad_off,
-                         int32_t* list_len, int32_t* pos_of_row, float* rho, float* rho16, int32_t* flag,
-                         float* row_constants, float row_constants_now, void* stream) {
-    return ivf2_append_impl(true, bank, inv_norm, meta, slots, n, D, sorted_f16, sorted_rows, pad_off, list_len,
-                            pos_of_row, rho, rho16, flag, row_constants, row_constants_now, stream);
 }
 
 int64_t aura_kmeans_means_workspace_bytes(int64_t N, int64_t D, int k) {

@@ -45,7 +45,7 @@ struct BlendArgs {
     const int32_t* sorted_rows;
     const int32_t* pos_of_row;
     int64_t n_sorted;
-    bool image_f16;                     // the list-sorted image is IEEE half (aura_bank_blend_f16)
+    bool image_f16;                     // the list-sorted image is IEEE half (AURA_IMAGE_F16)
     float* rho16;                       // ... and this, when given, receives its residual norm; rho the bf16 one as ever
 };
 
@@ -155,11 +155,14 @@ inline bool misaligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p)
 
 extern "C" {
 
-static int bank_blend_impl(float* bank, float* inv_norm, int64_t N, int64_t rows, int64_t D, const float* feats,
-                           int64_t feats_row0, int64_t n, const int32_t* stored_target, const int32_t* batch_leader,
-                           float beta, float* out_feats, uint16_t* shadow_bf16, float* rho, int64_t shadow_upto,
-                           uint16_t* sorted_bf16, const int32_t* sorted_rows, const int32_t* pos_of_row, int64_t n_sorted,
-                           void* stream, bool image_f16, float* rho16) {
+// rho16 (optional, AURA_IMAGE_F16 only) follows the half image, rho the bf16 residual
+int aura_bank_blend(float* bank, float* inv_norm, int64_t N, int64_t rows, int64_t D, const float* feats,
+                    int64_t feats_row0, int64_t n, const int32_t* stored_target, const int32_t* batch_leader,
+                    float beta, float* out_feats, uint16_t* shadow_bf16, float* rho, int64_t shadow_upto,
+                    uint16_t* sorted_bf16, float* rho16, const int32_t* sorted_rows, const int32_t* pos_of_row,
+                    int64_t n_sorted, int image_format, void* stream) {
+    if (image_format != AURA_IMAGE_F16 && (image_format != AURA_IMAGE_BF16 || rho16)) return AURA_E_INVAL;
+    const bool image_f16 = image_format == AURA_IMAGE_F16;
     if (n < 0 || n > 1024 || D < 1 || D > 4096 || N < 0 || rows < N || rows > 0x7fffffff) return AURA_E_INVAL;
     if (!(beta > 0.0f && beta <= 1.0f)) return AURA_E_INVAL;
     if (feats_row0 < -1) return AURA_E_INVAL;
@@ -194,27 +197,6 @@ static int bank_blend_impl(float* bank, float* inv_norm, int64_t N, int64_t rows
     if (vec4) hipLaunchKernelGGL(bank_blend_kernel<true>, grid, block, lds, s, a);
     else hipLaunchKernelGGL(bank_blend_kernel<false>, grid, block, lds, s, a);
     return aura_check_launch();
-}
-
-int aura_bank_blend(float* bank, float* inv_norm, int64_t N, int64_t rows, int64_t D, const float* feats,
-                    int64_t feats_row0, int64_t n, const int32_t* stored_target, const int32_t* batch_leader,
-                    float beta, float* out_feats, uint16_t* shadow_bf16, float* rho, int64_t shadow_upto,
-                    uint16_t* sorted_bf16, const int32_t* sorted_rows, const int32_t* pos_of_row, int64_t n_sorted,
-                    void* stream) {
-    return bank_blend_impl(bank, inv_norm, N, rows, D, feats, feats_row0, n, stored_target, batch_leader, beta, out_feats,
-                           shadow_bf16, rho, shadow_upto, sorted_bf16, sorted_rows, pos_of_row, n_sorted, stream, false,
-                           nullptr);
-}
-
-// aura_bank_blend with an IEEE half list-sorted image; rho16 (optional) follows the image, rho the bf16 residual
-int aura_bank_blend_f16(float* bank, float* inv_norm, int64_t N, int64_t rows, int64_t D, const float* feats,
-                        int64_t feats_row0, int64_t n, const int32_t* stored_target, const int32_t* batch_leader,
-                        float beta, float* out_feats, uint16_t* shadow_bf16, float* rho, int64_t shadow_upto,
-                        uint16_t* sorted_f16, float* rho16, const int32_t* sorted_rows, const int32_t* pos_of_row,
-                        int64_t n_sorted, void* stream) {
-    return bank_blend_impl(bank, inv_norm, N, rows, D, feats, feats_row0, n, stored_target, batch_leader, beta, out_feats,
-                           shadow_bf16, rho, shadow_upto, sorted_f16, sorted_rows, pos_of_row, n_sorted, stream, true,
-                           rho16);
 }
 
 }  // extern "C"

@@ -6,7 +6,7 @@
 // 1 / max(||.||, 1e-12); stored_target[i] = the held row of largest cos(f_i, r) >= tau (equal cosines -> the lowest
 // r), else -1; rows without a stored target are walked in order and repeat the KEPT earlier row of largest cosine
 // >= tau (equal -> the lowest j), else they are kept; rows with a NaN / Inf component or of norm 0 are kept and are
-// nobody's target.  aura_bank_find_repeats_scoped applies the same rule within tags: a held row is eligible for a batch
+// nobody's target.  With batch_tags the call applies the same rule within tags: a held row is eligible for a batch
 // row only when its tag (metadata column 3) equals the batch row's, an in-batch pair only when both rows carry one tag.
 // The predicate is one SCOPED template parameter of the scan, dense and walk kernels: it sits where a pair is decided
 // (before a survivor is appended, before the packed atomicMax, before pend[] is set, before a kept row offers its Gram
@@ -32,6 +32,7 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
+#include <type_traits>
 
 #include "../../include/aura_hip.h"
 #include "aura_common.inl"
@@ -619,44 +620,21 @@ int64_t aura_bank_find_repeats_workspace_bytes(int64_t n) {
     return carve(nullptr, pad_batch(n > 0 ? n : 1)).bytes;
 }
 
-int aura_bank_find_repeats(const float* bank, const float* inv_norm, int64_t N, int64_t D, const uint16_t* image_bf16,
+// batch_tags selects the scoped search (meta is ignored without it), image_format the image's format and its rho
+int aura_bank_find_repeats(const float* bank, const float* inv_norm, int64_t N, int64_t D, const uint16_t* image,
                            const int32_t* image_rows, int64_t n_image, const float* rho, const float* feats, int64_t n,
                            float tau, int32_t* stored_target, int32_t* batch_leader, float* cos_out,
-                           int32_t* overflow_out, void* workspace, int64_t workspace_bytes, void* stream) {
-    return find_repeats_impl<false>(bank, inv_norm, N, D, image_bf16, image_rows, n_image, rho, feats, n, tau,
-                                    stored_target, batch_leader, cos_out, overflow_out, workspace, workspace_bytes, stream,
-                                    nullptr, nullptr);
-}
-
-int aura_bank_find_repeats_scoped(const float* bank, const float* inv_norm, int64_t N, int64_t D,
-                                  const uint16_t* image_bf16, const int32_t* image_rows, int64_t n_image,
-                                  const float* rho, const float* feats, int64_t n, float tau, int32_t* stored_target,
-                                  int32_t* batch_leader, float* cos_out, int32_t* overflow_out, void* workspace,
-                                  int64_t workspace_bytes, void* stream, const float* meta, const int32_t* batch_tags) {
-    return find_repeats_impl<true>(bank, inv_norm, N, D, image_bf16, image_rows, n_image, rho, feats, n, tau,
-                                   stored_target, batch_leader, cos_out, overflow_out, workspace, workspace_bytes, stream,
-                                   meta, batch_tags);
-}
-
-// ---- the same over an IEEE half image (aura_bank_shadow_sorted_f16) with its rho16 ----
-int aura_bank_find_repeats_f16(const float* bank, const float* inv_norm, int64_t N, int64_t D, const uint16_t* image_f16,
-                               const int32_t* image_rows, int64_t n_image, const float* rho16, const float* feats,
-                               int64_t n, float tau, int32_t* stored_target, int32_t* batch_leader, float* cos_out,
-                               int32_t* overflow_out, void* workspace, int64_t workspace_bytes, void* stream) {
-    return find_repeats_impl<false, true>(bank, inv_norm, N, D, image_f16, image_rows, n_image, rho16, feats, n, tau,
-                                          stored_target, batch_leader, cos_out, overflow_out, workspace, workspace_bytes,
-                                          stream, nullptr, nullptr);
-}
-
-int aura_bank_find_repeats_scoped_f16(const float* bank, const float* inv_norm, int64_t N, int64_t D,
-                                      const uint16_t* image_f16, const int32_t* image_rows, int64_t n_image,
-                                      const float* rho16, const float* feats, int64_t n, float tau,
-                                      int32_t* stored_target, int32_t* batch_leader, float* cos_out,
-                                      int32_t* overflow_out, void* workspace, int64_t workspace_bytes, void* stream,
-                                      const float* meta, const int32_t* batch_tags) {
-    return find_repeats_impl<true, true>(bank, inv_norm, N, D, image_f16, image_rows, n_image, rho16, feats, n, tau,
-                                         stored_target, batch_leader, cos_out, overflow_out, workspace, workspace_bytes,
-                                         stream, meta, batch_tags);
+                           int32_t* overflow_out, void* workspace, int64_t workspace_bytes, const float* meta,
+                           const int32_t* batch_tags, int image_format, void* stream) {
+    if (image_format != AURA_IMAGE_BF16 && image_format != AURA_IMAGE_F16) return AURA_E_INVAL;
+    auto call = [&](auto scoped, auto f16) {
+        return find_repeats_impl<decltype(scoped)::value, decltype(f16)::value>(
+            bank, inv_norm, N, D, image, image_rows, n_image, rho, feats, n, tau, stored_target, batch_leader, cos_out,
+            overflow_out, workspace, workspace_bytes, stream, decltype(scoped)::value ? meta : nullptr, batch_tags);
+    };
+    using T = std::true_type; using F = std::false_type;
+    if (image_format == AURA_IMAGE_BF16) return !batch_tags ? call(F{}, F{}) : call(T{}, F{});
+    return !batch_tags ? call(F{}, T{}) : call(T{}, T{});
 }
 
 int aura_bank_touch(float* meta, int64_t count, const int32_t* rows, int64_t n, float now, void* stream) {

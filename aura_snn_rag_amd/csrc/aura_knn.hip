@@ -3015,21 +3015,28 @@ int aura_centroid_probe(const float* centroids, const float* queries, int64_t D,
     return launch_probe(centroids, queries, D, (int)nq, nprobe, dist, mask, ids_out, static_cast<hipStream_t>(stream));
 }
 
-// f16: the sorted image is IEEE half (aura_bank_shadow_sorted_f16) and `rho` is its rho16
-static int knn_search_ivf2_impl(bool f16, const float* bank, const float* inv_norm, const float* meta,
-                         const uint16_t* sorted_bf16, const float* rho, const int32_t* sorted_rows, const int32_t* pad_off,
-                         const int32_t* list_len, const int32_t* lists_flag, int64_t n_sorted, int64_t N,
-                         const float* queries, float now,
-                         int64_t D, int64_t nq, int k,
-                         const float* centroids, int nprobe, int32_t idx_base, float* out_scores,
-                         int32_t* out_idx, void* workspace, int64_t workspace_bytes,
-                         int32_t* overflow_out, const int32_t* probe_ids, const float4* rowc_cached, void* stream,
-                         int stg = 0, int k2 = 0, float* bounds = nullptr, uint32_t* host_word = nullptr,
-                         uint32_t host_seq = 0) {
+int aura_knn_search_ivf2(const aura_ivf2_lists* lists, const float* queries, float now, int64_t nq, int k,
+                         const int32_t* probe_ids, int32_t idx_base, float* out_scores, int32_t* out_idx,
+                         void* workspace, int64_t workspace_bytes, int32_t* overflow_out, int stg, int k2,
+                         float* bounds, uint32_t* host_word, uint32_t host_seq, void* stream) {
     // stg: 0 = the whole recall; 1 = up to the sampled bounds, written to bounds[nq][2] = {k-th, k2-th largest
     // sampled lower bound}; 2 = from there on (same workspace, untouched in between), every query's threshold
-    // first raised to bounds[q] (one float per query: the caller's combination of all shards' stage-1 bounds).
-    // Staged calls are single passes (nq <= 8192).
+    // first raised to bounds[q] (one float per query: the caller's combination of all shards' stage-1 bounds);
+    // 4 + 3: see the header.  Staged calls are single passes (nq <= 8192).
+    if (!lists) return AURA_E_INVAL;
+    if (reinterpret_cast<uintptr_t>(lists->row_constants) & 15) return AURA_E_ALIGN;
+    if (lists->image_format != AURA_IMAGE_BF16 && lists->image_format != AURA_IMAGE_F16) return AURA_E_INVAL;
+    if (stg < 0 || stg > 4) return AURA_E_INVAL;
+    if (host_word && (!overflow_out || stg != 0)) return AURA_E_INVAL;
+    const bool f16 = lists->image_format == AURA_IMAGE_F16;    // the image is IEEE half and `rho` its rho16
+    const float* const bank = lists->bank; const float* const inv_norm = lists->inv_norm;
+    const float* const meta = lists->meta; const float* const centroids = lists->centroids;
+    const uint16_t* const sorted_bf16 = lists->image; const float* const rho = lists->rho;
+    const int32_t* const sorted_rows = lists->sorted_rows; const int32_t* const pad_off = lists->pad_off;
+    const int32_t* const list_len = lists->list_len; const int32_t* const lists_flag = lists->lists_flag;
+    const float4* const rowc_cached = reinterpret_cast<const float4*>(lists->row_constants);
+    const int64_t n_sorted = lists->n_sorted, N = lists->N, D = lists->D;
+    const int nprobe = lists->nprobe;
     if (n_sorted <= 0 || N <= 0 || N > 0x7ffffff0LL || D <= 0 || D > 768 || (D & 7) || nq < 0 || k <= 0 ||
         k > COARSE_MAX_K)
         return AURA_E_INVAL;
@@ -3272,90 +3279,16 @@ static int knn_search_ivf2_impl(bool f16, const float* bank, const float* inv_no
 }
 
 int aura_ivf2_row_constants(const float* meta, const float* rho, const int32_t* sorted_rows, int64_t n_sorted,
-                            int64_t D, float now, float* row_constants, void* stream) {
+                            int64_t D, float now, float* row_constants, int image_format, void* stream) {
+    if (image_format != AURA_IMAGE_BF16 && image_format != AURA_IMAGE_F16) return AURA_E_INVAL;
     if (n_sorted < 0 || n_sorted > 0x7ffffff0LL || D <= 0) return AURA_E_INVAL;
     if (n_sorted == 0) return AURA_OK;
     if (!meta || !rho || !sorted_rows || !row_constants) return AURA_E_INVAL;
     if ((reinterpret_cast<uintptr_t>(meta) & 15) || (reinterpret_cast<uintptr_t>(row_constants) & 15)) return AURA_E_ALIGN;
     hipLaunchKernelGGL(ivf2_rowc_kernel, dim3((unsigned)((n_sorted + 255) / 256)), dim3(256), 0,
                        static_cast<hipStream_t>(stream), meta, rho, sorted_rows, n_sorted, now, (float)D,
-                       reinterpret_cast<float4*>(row_constants), false);
+                       reinterpret_cast<float4*>(row_constants), image_format == AURA_IMAGE_F16);
     return aura_check_launch();
-}
-
-int aura_knn_search_ivf2(const float* bank, const float* inv_norm, const float* meta,
-                         const uint16_t* sorted_bf16, const float* rho, const int32_t* sorted_rows, const int32_t* pad_off,
-                         const int32_t* list_len, const int32_t* lists_flag, const float* row_constants,
-                         int64_t n_sorted, int64_t N,
-                         const float* queries, float now, int64_t D, int64_t nq, int k,
-                         const float* centroids, int nprobe, int32_t idx_base, float* out_scores,
-                         int32_t* out_idx, void* workspace, int64_t workspace_bytes,
-                         int32_t* overflow_out, void* stream) {
-    if (reinterpret_cast<uintptr_t>(row_constants) & 15) return AURA_E_ALIGN;
-    return knn_search_ivf2_impl(false, bank, inv_norm, meta, sorted_bf16, rho, sorted_rows, pad_off, list_len, lists_flag,
-                                n_sorted, N, queries, now, D, nq, k, centroids, nprobe, idx_base, out_scores, out_idx,
-                                workspace, workspace_bytes, overflow_out, nullptr,
-                                reinterpret_cast<const float4*>(row_constants), stream);
-}
-
-int aura_knn_search_ivf2_probed(const float* bank, const float* inv_norm, const float* meta,
-                                const uint16_t* sorted_bf16, const float* rho, const int32_t* sorted_rows,
-                                const int32_t* pad_off, const int32_t* list_len, const int32_t* lists_flag,
-                                const float* row_constants,
-                                int64_t n_sorted, int64_t N, const float* queries, float now, int64_t D, int64_t nq,
-                                int k, const float* centroids, int nprobe, const int32_t* probe_ids, int32_t idx_base,
-                                float* out_scores, int32_t* out_idx, void* workspace, int64_t workspace_bytes,
-                                int32_t* overflow_out, void* stream) {
-    if (!probe_ids) return AURA_E_INVAL;
-    if (reinterpret_cast<uintptr_t>(row_constants) & 15) return AURA_E_ALIGN;
-    return knn_search_ivf2_impl(false, bank, inv_norm, meta, sorted_bf16, rho, sorted_rows, pad_off, list_len, lists_flag,
-                                n_sorted, N, queries, now, D, nq, k, centroids, nprobe, idx_base, out_scores, out_idx,
-                                workspace, workspace_bytes, overflow_out, probe_ids,
-                                reinterpret_cast<const float4*>(row_constants), stream);
-}
-
-// ---- the same entry points over an IEEE half image (aura_bank_shadow_sorted_f16): `rho16` in rho's place ----
-int aura_ivf2_row_constants_f16(const float* meta, const float* rho16, const int32_t* sorted_rows, int64_t n_sorted,
-                            int64_t D, float now, float* row_constants, void* stream) {
-    if (n_sorted < 0 || n_sorted > 0x7ffffff0LL || D <= 0) return AURA_E_INVAL;
-    if (n_sorted == 0) return AURA_OK;
-    if (!meta || !rho16 || !sorted_rows || !row_constants) return AURA_E_INVAL;
-    if ((reinterpret_cast<uintptr_t>(meta) & 15) || (reinterpret_cast<uintptr_t>(row_constants) & 15)) return AURA_E_ALIGN;
-    hipLaunchKernelGGL(ivf2_rowc_kernel, dim3((unsigned)((n_sorted + 255) / 256)), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), meta, rho16, sorted_rows, n_sorted, now, (float)D,
-                       reinterpret_cast<float4*>(row_constants), true);
-    return aura_check_launch();
-}
-
-int aura_knn_search_ivf2_f16(const float* bank, const float* inv_norm, const float* meta,
-                         const uint16_t* sorted_f16, const float* rho16, const int32_t* sorted_rows, const int32_t* pad_off,
-                         const int32_t* list_len, const int32_t* lists_flag, const float* row_constants,
-                         int64_t n_sorted, int64_t N,
-                         const float* queries, float now, int64_t D, int64_t nq, int k,
-                         const float* centroids, int nprobe, int32_t idx_base, float* out_scores,
-                         int32_t* out_idx, void* workspace, int64_t workspace_bytes,
-                         int32_t* overflow_out, void* stream) {
-    if (reinterpret_cast<uintptr_t>(row_constants) & 15) return AURA_E_ALIGN;
-    return knn_search_ivf2_impl(true, bank, inv_norm, meta, sorted_f16, rho16, sorted_rows, pad_off, list_len, lists_flag,
-                                n_sorted, N, queries, now, D, nq, k, centroids, nprobe, idx_base, out_scores, out_idx,
-                                workspace, workspace_bytes, overflow_out, nullptr,
-                                reinterpret_cast<const float4*>(row_constants), stream);
-}
-
-int aura_knn_search_ivf2_probed_f16(const float* bank, const float* inv_norm, const float* meta,
-                                const uint16_t* sorted_f16, const float* rho16, const int32_t* sorted_rows,
-                                const int32_t* pad_off, const int32_t* list_len, const int32_t* lists_flag,
-                                const float* row_constants,
-                                int64_t n_sorted, int64_t N, const float* queries, float now, int64_t D, int64_t nq,
-                                int k, const float* centroids, int nprobe, const int32_t* probe_ids, int32_t idx_base,
-                                float* out_scores, int32_t* out_idx, void* workspace, int64_t workspace_bytes,
-                                int32_t* overflow_out, void* stream) {
-    if (!probe_ids) return AURA_E_INVAL;
-    if (reinterpret_cast<uintptr_t>(row_constants) & 15) return AURA_E_ALIGN;
-    return knn_search_ivf2_impl(true, bank, inv_norm, meta, sorted_f16, rho16, sorted_rows, pad_off, list_len, lists_flag,
-                                n_sorted, N, queries, now, D, nq, k, centroids, nprobe, idx_base, out_scores, out_idx,
-                                workspace, workspace_bytes, overflow_out, probe_ids,
-                                reinterpret_cast<const float4*>(row_constants), stream);
 }
 
 int aura_host_word_alloc(void** host_word_out) {
@@ -3380,71 +3313,6 @@ int aura_signal_flag(const int32_t* flag_dev, uint32_t* host_word, uint32_t host
 int aura_host_word_free(void* host_word) {
     if (!host_word) return AURA_OK;
     return hipHostFree(host_word) == hipSuccess ? AURA_OK : AURA_E_LAUNCH;
-}
-
-int aura_knn_search_ivf2_signal(const float* bank, const float* inv_norm, const float* meta,
-                                const uint16_t* sorted_bf16, const float* rho, const int32_t* sorted_rows,
-                                const int32_t* pad_off, const int32_t* list_len, const int32_t* lists_flag,
-                                const float* row_constants,
-                                int64_t n_sorted, int64_t N, const float* queries, float now, int64_t D, int64_t nq,
-                                int k, const float* centroids, int nprobe, const int32_t* probe_ids, int32_t idx_base,
-                                float* out_scores, int32_t* out_idx, void* workspace, int64_t workspace_bytes,
-                                int32_t* overflow_out, uint32_t* host_word, uint32_t host_seq, void* stream) {
-    if (!host_word || !overflow_out) return AURA_E_INVAL;
-    if (reinterpret_cast<uintptr_t>(row_constants) & 15) return AURA_E_ALIGN;
-    return knn_search_ivf2_impl(false, bank, inv_norm, meta, sorted_bf16, rho, sorted_rows, pad_off, list_len, lists_flag,
-                                n_sorted, N, queries, now, D, nq, k, centroids, nprobe, idx_base, out_scores, out_idx,
-                                workspace, workspace_bytes, overflow_out, probe_ids,
-                                reinterpret_cast<const float4*>(row_constants), stream, 0, 0, nullptr, host_word, host_seq);
-}
-
-int aura_knn_search_ivf2_staged(const float* bank, const float* inv_norm, const float* meta,
-                                const uint16_t* sorted_bf16, const float* rho, const int32_t* sorted_rows,
-                                const int32_t* pad_off, const int32_t* list_len, const int32_t* lists_flag,
-                                const float* row_constants,
-                                int64_t n_sorted, int64_t N, const float* queries, float now, int64_t D, int64_t nq,
-                                int k, const float* centroids, int nprobe, const int32_t* probe_ids, int32_t idx_base,
-                                float* out_scores, int32_t* out_idx, void* workspace, int64_t workspace_bytes,
-                                int32_t* overflow_out, int stage, int k2, float* bounds, void* stream) {
-    if (stage < 1 || stage > 4) return AURA_E_INVAL;        // 1, 2, 4 + 3 (see the header)
-    if (reinterpret_cast<uintptr_t>(row_constants) & 15) return AURA_E_ALIGN;
-    return knn_search_ivf2_impl(false, bank, inv_norm, meta, sorted_bf16, rho, sorted_rows, pad_off, list_len, lists_flag,
-                                n_sorted, N, queries, now, D, nq, k, centroids, nprobe, idx_base, out_scores, out_idx,
-                                workspace, workspace_bytes, overflow_out, probe_ids,
-                                reinterpret_cast<const float4*>(row_constants), stream, stage, k2, bounds);
-}
-
-// ---- the same entry points over an IEEE half image: `rho16` in rho's place ----
-int aura_knn_search_ivf2_signal_f16(const float* bank, const float* inv_norm, const float* meta,
-                                const uint16_t* sorted_f16, const float* rho16, const int32_t* sorted_rows,
-                                const int32_t* pad_off, const int32_t* list_len, const int32_t* lists_flag,
-                                const float* row_constants,
-                                int64_t n_sorted, int64_t N, const float* queries, float now, int64_t D, int64_t nq,
-                                int k, const float* centroids, int nprobe, const int32_t* probe_ids, int32_t idx_base,
-                                float* out_scores, int32_t* out_idx, void* workspace, int64_t workspace_bytes,
-                                int32_t* overflow_out, uint32_t* host_word, uint32_t host_seq, void* stream) {
-    if (!host_word || !overflow_out) return AURA_E_INVAL;
-    if (reinterpret_cast<uintptr_t>(row_constants) & 15) return AURA_E_ALIGN;
-    return knn_search_ivf2_impl(true, bank, inv_norm, meta, sorted_f16, rho16, sorted_rows, pad_off, list_len, lists_flag,
-                                n_sorted, N, queries, now, D, nq, k, centroids, nprobe, idx_base, out_scores, out_idx,
-                                workspace, workspace_bytes, overflow_out, probe_ids,
-                                reinterpret_cast<const float4*>(row_constants), stream, 0, 0, nullptr, host_word, host_seq);
-}
-
-int aura_knn_search_ivf2_staged_f16(const float* bank, const float* inv_norm, const float* meta,
-                                const uint16_t* sorted_f16, const float* rho16, const int32_t* sorted_rows,
-                                const int32_t* pad_off, const int32_t* list_len, const int32_t* lists_flag,
-                                const float* row_constants,
-                                int64_t n_sorted, int64_t N, const float* queries, float now, int64_t D, int64_t nq,
-                                int k, const float* centroids, int nprobe, const int32_t* probe_ids, int32_t idx_base,
-                                float* out_scores, int32_t* out_idx, void* workspace, int64_t workspace_bytes,
-                                int32_t* overflow_out, int stage, int k2, float* bounds, void* stream) {
-    if (stage < 1 || stage > 4) return AURA_E_INVAL;        // 1, 2, 4 + 3 (see the header)
-    if (reinterpret_cast<uintptr_t>(row_constants) & 15) return AURA_E_ALIGN;
-    return knn_search_ivf2_impl(true, bank, inv_norm, meta, sorted_f16, rho16, sorted_rows, pad_off, list_len, lists_flag,
-                                n_sorted, N, queries, now, D, nq, k, centroids, nprobe, idx_base, out_scores, out_idx,
-                                workspace, workspace_bytes, overflow_out, probe_ids,
-                                reinterpret_cast<const float4*>(row_constants), stream, stage, k2, bounds);
 }
 
 int aura_knn_search(const float* bank, const float* inv_norm, const float* meta, const float* loc,

@@ -5,7 +5,7 @@
 // (src/core/hippocampal.py:259-270).  aura_knn_search_ivf streams every probed list once per batch
 // on the fp32 matrix pipe and writes ALL candidate scores; here the same restriction runs on the
 // bf16 prefilter + fp32 re-scoring machinery of aura_knn_coarse.inl:
-//   * the caller keeps a LIST-SORTED 16-bit shadow of the bank -- bf16, or IEEE half through the *_f16 entry points
+//   * the caller keeps a LIST-SORTED 16-bit shadow of the bank -- bf16, or IEEE half with image_format AURA_IMAGE_F16
 //     (what HippocampalFormation keeps: a five times narrower band, see aura_hip.h) -- (rows grouped by centroid, every list
 //     padded to a multiple of 16 rows; `sorted_rows[i]` = bank row of sorted row i, -1 for pads),
 //     rebuilt whenever its inverted lists are (aura_bank_shadow_sorted);
@@ -127,7 +127,7 @@ __global__ __launch_bounds__(256) void ivf2_plan_kernel(const int32_t* __restric
     if (tid == 0) { item_off[s_nb[256]] = s_it[256]; sitem_off[s_nb[256]] = s_st[256]; }
 }
 
-// ---- per-list query lists from probe ids the caller already has (aura_knn_search_ivf2_probed) ----
+// ---- per-list query lists from probe ids the caller already has (aura_knn_search_ivf2's probe_ids) ----
 // A workgroup takes 8192 ids: ranks inside the workgroup come from an LDS histogram (returning LDS atomics), ONE
 // global atomic per list and workgroup reserves the block of list entries.  (One returning global atomic per id --
 // 65 536 of them on 256 counters for a pass of 8192 queries -- took 45 us, 8 % of a shard's share at 8 ranks.)
@@ -344,7 +344,7 @@ __global__ __launch_bounds__(256) void ivf2_threshold_kernel(const float* __rest
     }
 }
 
-// Completion word (aura_knn_search_ivf2_signal): launched behind the call's last kernel, so the flag is final.
+// Completion word (host_word, aura_signal_flag): launched behind the call's last kernel, so the flag is final.
 // (The first version counted finished workgroups inside the refine kernel: 2048 atomics on one address cost the
 // launch 80 us.)
 __global__ void ivf2_signal_kernel(const int32_t* __restrict__ flag, volatile uint32_t* host_word, uint32_t seq) {

@@ -40,13 +40,13 @@ def _need(t: torch.Tensor, name: str, dtype=None) -> torch.Tensor:
     return t
 
 
-def _need_image(t: torch.Tensor, name: str) -> bool:
+def _need_image(t: torch.Tensor, name: str) -> int:
     """A 16-bit image of normalised rows: bf16, or IEEE half (the list-sorted image of the inverted lists).  Returns
-    whether it is half -- the dtype selects the ``*_f16`` entry points."""
+    the C ABI's ``image_format`` of its dtype, ``_lib.IMAGE_BF16`` or ``_lib.IMAGE_F16``."""
     _need(t, name)
     if t.dtype not in (torch.bfloat16, torch.float16):
         raise TypeError(f"{name}: expected dtype torch.bfloat16 or torch.float16, got {t.dtype}")
-    return t.dtype == torch.float16
+    return _lib.IMAGE_F16 if t.dtype == torch.float16 else _lib.IMAGE_BF16
 
 
 def half_image_rho_bound(rho: torch.Tensor, D: int) -> torch.Tensor:
@@ -1971,7 +1971,7 @@ def find_repeats(bank, inv_norm, count: int, feats, tau: float, image=None, imag
 
 def find_repeats_scoped(bank, inv_norm, meta, count: int, feats, tags, tau: float, image=None, image_rows=None,
                         n_image: Optional[int] = None, rho=None, lists_flag=None, rho16=None):
-    """``find_repeats`` within tags (``aura_bank_find_repeats_scoped``; the rule: ``include/aura_hip.h``): a held row is
+    """``find_repeats`` within tags (``aura_bank_find_repeats`` by tag; the rule: ``include/aura_hip.h``): a held row is
     eligible for batch row i only when ``int(meta[r, 3]) == tags[i]``, an in-batch pair only when both rows carry the
     same tag; tag 0 is a scope like any other, a tag outside ``[0, 2^24)`` matches nothing (that row is kept).  ``meta``:
     the bank's metadata (fp32 [rows, 4]); ``tags``: int32 [n] on the bank's device.  Same validation, same four results
@@ -2002,10 +2002,10 @@ def _find_repeats(bank, inv_norm, count, feats, tau, image, image_rows, n_image,
     if feats.device != bank.device or inv_norm.device != bank.device:
         raise ValueError("find_repeats: tensors are on different devices")
     ni = 0
-    half = False
+    fmt = _lib.IMAGE_BF16
     if image is not None:
-        half = _need_image(image, "image")
-        if half:                                # the half image's own residuals, or a bound derived from the bf16 ones
+        fmt = _need_image(image, "image")
+        if fmt == _lib.IMAGE_F16:               # the half image's own residuals, or a bound derived from the bf16 ones
             rho = _need(rho16, "rho16", torch.float32) if rho16 is not None else \
                 half_image_rho_bound(_need(rho, "rho", torch.float32), D)
         _need(rho, "rho", torch.float32)
@@ -2044,14 +2044,9 @@ def _find_repeats(bank, inv_norm, count, feats, tau, image, image_rows, n_image,
     if nbytes < 0:
         raise ValueError("find_repeats: unsupported size")
     base = _workspace(bank.device, nbytes)
-    args = (_p(bank), _p(inv_norm), count, D, _p(image), _p(image_rows), ni, _p(rho), _p(feats), n, tau, _p(stored),
-            _p(leader), _p(cos), _p(packed[3 * n:]), base, nbytes, _stream())
-    if meta is None:
-        fn = L.aura_bank_find_repeats_f16 if half else L.aura_bank_find_repeats
-        check(fn(*args), "aura_bank_find_repeats")
-    else:
-        fn = L.aura_bank_find_repeats_scoped_f16 if half else L.aura_bank_find_repeats_scoped
-        check(fn(*args, _p(meta), _p(tags)), "aura_bank_find_repeats_scoped")
+    check(L.aura_bank_find_repeats(_p(bank), _p(inv_norm), count, D, _p(image), _p(image_rows), ni, _p(rho), _p(feats),
+                                   n, tau, _p(stored), _p(leader), _p(cos), _p(packed[3 * n:]), base, nbytes, _p(meta),
+                                   _p(tags), fmt, _stream()), "aura_bank_find_repeats")
     return stored, leader, cos, packed
 
 
@@ -2068,9 +2063,9 @@ def bank_blend(bank, inv_norm, count: int, stored_target, batch_leader, beta: fl
     also refreshes ``inv_norm`` (``bank_row_norms``' bits), with ``shadow`` + ``rho`` the row's bf16 shadow and residual
     if it lies below ``shadow_upto`` (``bank_shadow_update``'s bits), and with ``sorted_bf16`` + ``sorted_rows`` +
     ``pos_of_row`` (+ ``rho``) its entry of the list-sorted image, in place.  ``rho`` goes with a shadow or an image,
-    and only with one; the image's three tensors go together.  The image may be float16 (the dtype selects the entry
-    point); ``rho16``, which goes only with such an image, then receives the half residual while ``rho`` receives the
-    bf16 one as ever.  Entries out of range are ignored.  No host sync."""
+    and only with one; the image's three tensors go together.  The image may be float16 (the dtype is the call's
+    ``image_format``); ``rho16``, which goes only with such an image, then receives the half residual while ``rho``
+    receives the bf16 one as ever.  Entries out of range are ignored.  No host sync."""
     _need(bank, "bank", torch.float32); _need(inv_norm, "inv_norm", torch.float32)
     _need(stored_target, "stored_target", torch.int32); _need(batch_leader, "batch_leader", torch.int32)
     beta = float(beta)
@@ -2115,9 +2110,9 @@ def bank_blend(bank, inv_norm, count: int, stored_target, batch_leader, beta: fl
     else:
         shadow_upto = 0
     ns = 0
-    half = False
+    fmt = _lib.IMAGE_BF16
     if has_image:
-        half = _need_image(sorted_bf16, "sorted_bf16"); _need(sorted_rows, "sorted_rows", torch.int32)
+        fmt = _need_image(sorted_bf16, "sorted_bf16"); _need(sorted_rows, "sorted_rows", torch.int32)
         _need(pos_of_row, "pos_of_row", torch.int32)
         ns = sorted_rows.numel() if n_sorted is None else int(n_sorted)
         if sorted_bf16.dim() != 2 or sorted_bf16.shape[1] != D or pos_of_row.numel() != M or \
@@ -2125,7 +2120,7 @@ def bank_blend(bank, inv_norm, count: int, stored_target, batch_leader, beta: fl
             raise ValueError("bank_blend: the image is [>= n_sorted, D] bf16 with sorted_rows [>= n_sorted] and "
                              "pos_of_row [rows]")
     if rho16 is not None:
-        if not half:
+        if fmt != _lib.IMAGE_F16:
             raise ValueError("bank_blend: rho16 goes with a float16 list-sorted image")
         _need(rho16, "rho16", torch.float32)
         if rho16.numel() != M:
@@ -2135,15 +2130,9 @@ def bank_blend(bank, inv_norm, count: int, stored_target, batch_leader, beta: fl
             raise ValueError("bank_blend: tensors are on different devices")
     if n == 0:
         return
-    if half:
-        check(lib().aura_bank_blend_f16(_p(bank), _p(inv_norm), count, M, D, _p(feats), feats_row0, n, _p(stored_target),
-                                        _p(batch_leader), beta, _p(out), _p(shadow), _p(rho), shadow_upto,
-                                        _p(sorted_bf16), _p(rho16), _p(sorted_rows), _p(pos_of_row), ns, _stream()),
-              "aura_bank_blend_f16")
-        return
     check(lib().aura_bank_blend(_p(bank), _p(inv_norm), count, M, D, _p(feats), feats_row0, n, _p(stored_target),
                                 _p(batch_leader), beta, _p(out), _p(shadow), _p(rho), shadow_upto, _p(sorted_bf16),
-                                _p(sorted_rows), _p(pos_of_row), ns, _stream()), "aura_bank_blend")
+                                _p(rho16), _p(sorted_rows), _p(pos_of_row), ns, fmt, _stream()), "aura_bank_blend")
 
 
 def bank_touch(meta, count: int, rows, now: float) -> None:
@@ -2571,10 +2560,10 @@ def bank_shadow_sorted(bank, inv_norm, sorted_rows, out, rho, pos_of_row=None, n
     residual, bit for bit ``bank_shadow_update``'s, and ``rho16`` (optional) the half image's own."""
     _need(bank, "bank", torch.float32); _need(sorted_rows, "sorted_rows", torch.int32)
     _need(inv_norm, "inv_norm", torch.float32); _need(rho, "rho", torch.float32)
-    half = _need_image(out, "out")
+    fmt = _need_image(out, "out")
     if rho16 is not None:
         _need(rho16, "rho16", torch.float32)
-        if not half or rho16.numel() != bank.shape[0]:
+        if fmt != _lib.IMAGE_F16 or rho16.numel() != bank.shape[0]:
             raise ValueError("bank_shadow_sorted: rho16 (one per bank row) goes with a float16 image")
     M, D = bank.shape
     n = sorted_rows.numel() if n_sorted is None else int(n_sorted)
@@ -2585,12 +2574,8 @@ def bank_shadow_sorted(bank, inv_norm, sorted_rows, out, rho, pos_of_row=None, n
         _need(pos_of_row, "pos_of_row", torch.int32)
         if pos_of_row.numel() != M:
             raise ValueError("bank_shadow_sorted: pos_of_row must have one entry per bank row")
-    if half:
-        check(lib().aura_bank_shadow_sorted_f16(_p(bank), _p(inv_norm), _p(sorted_rows), _p(out), _p(rho), _p(rho16),
-                                                _p(pos_of_row), n, D, _stream()), "aura_bank_shadow_sorted_f16")
-        return
-    check(lib().aura_bank_shadow_sorted(_p(bank), _p(inv_norm), _p(sorted_rows), _p(out), _p(rho), _p(pos_of_row),
-                                        n, D, _stream()), "aura_bank_shadow_sorted")
+    check(lib().aura_bank_shadow_sorted(_p(bank), _p(inv_norm), _p(sorted_rows), _p(out), _p(rho), _p(rho16),
+                                        _p(pos_of_row), n, D, fmt, _stream()), "aura_bank_shadow_sorted")
 
 
 def build_ivf2(bank, inv_norm, cids, slack: int = 0, max_rows: Optional[int] = None, rho=None,
@@ -2629,12 +2614,12 @@ def ivf2_append(bank, inv_norm, meta, slots, sorted_shadow, sorted_rows, pad_off
     image takes ``rho16`` beside ``rho`` (required with ``row_constants``: the table is the half image's)."""
     _need(bank, "bank", torch.float32); _need(inv_norm, "inv_norm", torch.float32)
     _need(meta, "meta", torch.float32); _need(slots, "slots", torch.int64)
-    half = _need_image(sorted_shadow, "sorted_shadow"); _need(rho, "rho", torch.float32)
+    fmt = _need_image(sorted_shadow, "sorted_shadow"); _need(rho, "rho", torch.float32)
     if rho16 is not None:
         _need(rho16, "rho16", torch.float32)
-        if not half or rho16.numel() != bank.shape[0]:
+        if fmt != _lib.IMAGE_F16 or rho16.numel() != bank.shape[0]:
             raise ValueError("ivf2_append: rho16 (one per bank row) goes with a float16 image")
-    elif half and row_constants is not None:
+    elif fmt == _lib.IMAGE_F16 and row_constants is not None:
         raise ValueError("ivf2_append: a float16 image's row constants need rho16")
     for t, n_ in ((sorted_rows, "sorted_rows"), (pad_off, "pad_off"), (list_len, "list_len"),
                   (pos_of_row, "pos_of_row"), (flag, "flag")):
@@ -2647,15 +2632,9 @@ def ivf2_append(bank, inv_norm, meta, slots, sorted_shadow, sorted_rows, pad_off
         _need(row_constants, "row_constants", torch.float32)
         if row_constants.dim() != 2 or row_constants.shape[1] != 4 or row_constants.shape[0] < sorted_rows.numel():
             raise ValueError("ivf2_append: row_constants must be [>= sorted rows, 4]")
-    if half:
-        check(lib().aura_ivf2_append_f16(_p(bank), _p(inv_norm), _p(meta), _p(slots), slots.numel(), D, _p(sorted_shadow),
-                                         _p(sorted_rows), _p(pad_off), _p(list_len), _p(pos_of_row), _p(rho), _p(rho16),
-                                         _p(flag), _p(row_constants), float(row_constants_now), _stream()),
-              "aura_ivf2_append_f16")
-        return
     check(lib().aura_ivf2_append(_p(bank), _p(inv_norm), _p(meta), _p(slots), slots.numel(), D, _p(sorted_shadow),
-                                 _p(sorted_rows), _p(pad_off), _p(list_len), _p(pos_of_row), _p(rho), _p(flag),
-                                 _p(row_constants), float(row_constants_now), _stream()), "aura_ivf2_append")
+                                 _p(sorted_rows), _p(pad_off), _p(list_len), _p(pos_of_row), _p(rho), _p(rho16),
+                                 _p(flag), _p(row_constants), float(row_constants_now), fmt, _stream()), "aura_ivf2_append")
 
 
 def ivf2_row_constants(meta, rho, sorted_rows, n_sorted: int, D: int, now: float, out, half: bool = False) -> None:
@@ -2669,8 +2648,9 @@ def ivf2_row_constants(meta, rho, sorted_rows, n_sorted: int, D: int, now: float
     if out.dim() != 2 or out.shape[1] != 4 or not (0 <= n <= min(out.shape[0], sorted_rows.numel())) or \
             meta.dim() != 2 or meta.shape[1] != 4 or rho.numel() != meta.shape[0]:
         raise ValueError("ivf2_row_constants: shape mismatch")
-    fn = lib().aura_ivf2_row_constants_f16 if half else lib().aura_ivf2_row_constants
-    check(fn(_p(meta), _p(rho), _p(sorted_rows), n, int(D), float(now), _p(out), _stream()), "aura_ivf2_row_constants")
+    fmt = _lib.IMAGE_F16 if half else _lib.IMAGE_BF16
+    check(lib().aura_ivf2_row_constants(_p(meta), _p(rho), _p(sorted_rows), n, int(D), float(now), _p(out), fmt, _stream()),
+          "aura_ivf2_row_constants")
 
 
 def centroid_probe(queries, centroids, nprobe: int = 8) -> torch.Tensor:
@@ -2692,7 +2672,7 @@ def centroid_probe(queries, centroids, nprobe: int = 8) -> torch.Tensor:
     return ids
 
 
-STAGED_MAX_QUERIES = 8192            # queries per staged pass (aura_knn_search_ivf2_staged)
+STAGED_MAX_QUERIES = 8192            # queries per staged pass (aura_knn_search_ivf2 with stage != 0)
 
 
 def knn_search_ivf2(bank, inv_norm, meta, queries, k: int, now: float, centroids, nprobe: int,
@@ -2721,8 +2701,9 @@ class Ivf2Lists:
     sorted rows in use (a multiple of 16 that covers pad_off[256]; default: all of ``sorted_rows``).
     ``lists_flag``: ``ivf2_append``'s flag; if it is set the returned overflow flag carries ``KNN_FLAG_LISTS_STALE``.
     ``row_constants``: ``ivf2_row_constants`` of the current lists for exactly the ``now`` of every call (fp32).
-    The handle keeps its tensors alive and caches their pointers: an owner rebuilds it when ``holds`` fails.
-    A float16 ``sorted_shadow`` (IEEE half, ``bank_shadow_sorted``) selects the ``*_f16`` entry points and requires
+    The handle keeps its tensors alive and their pointers in ONE ``aura_ivf2_lists`` struct, filled here: a call passes
+    the struct's cached address and converts only its own scalars.  An owner rebuilds the handle when ``holds`` fails.
+    A float16 ``sorted_shadow`` (IEEE half, ``bank_shadow_sorted``) sets the struct's ``image_format`` and requires
     ``rho16``, that image's residual norms, which the kernels then read in ``rho``'s place (``row_constants`` must be
     the half table, ``ivf2_row_constants(..., half=True)``)."""
 
@@ -2730,7 +2711,8 @@ class Ivf2Lists:
                  n_sorted: Optional[int] = None, lists_flag=None, row_constants=None, rho16=None):
         _need(bank, "bank", torch.float32); _need(inv_norm, "inv_norm", torch.float32)
         _need(meta, "meta", torch.float32); _need(centroids, "centroids", torch.float32)
-        half = _need_image(sorted_shadow, "sorted_shadow"); _need(rho, "rho", torch.float32)
+        fmt = _need_image(sorted_shadow, "sorted_shadow"); _need(rho, "rho", torch.float32)
+        half = fmt == _lib.IMAGE_F16
         for t, n in ((sorted_rows, "sorted_rows"), (pad_off, "pad_off"), (list_len, "list_len")):
             _need(t, n, torch.int32)
         M, D = bank.shape
@@ -2758,21 +2740,19 @@ class Ivf2Lists:
             _need(row_constants, "row_constants", torch.float32)
             if row_constants.dim() != 2 or row_constants.shape[1] != 4 or row_constants.shape[0] < ns:
                 raise ValueError("Ivf2Lists: row_constants must be [>= n_sorted, 4]")
-        # (the first ten in the order of the C entry points' leading arguments)
         self._keep = (bank, inv_norm, meta, sorted_shadow, rho, sorted_rows, pad_off, list_len, lists_flag, row_constants,
                       centroids, rho16)
-        self._ptrs = tuple(_p(t) for t in self._keep[:10])
-        if half:                                                       # the readers take rho16 in rho's place
-            self._ptrs = self._ptrs[:4] + (_p(rho16),) + self._ptrs[5:]
-        self._cent = centroids.data_ptr()
         self.M, self.D, self.ns, self.nprobe, self.device = M, D, ns, int(nprobe), bank.device
         self._bytes = {}
-        self._lib = L = lib()
+        self._lib = lib()
         self.half = half
-        self._fn = (L.aura_knn_search_ivf2_f16, L.aura_knn_search_ivf2_probed_f16, L.aura_knn_search_ivf2_signal_f16,
-                    L.aura_knn_search_ivf2_staged_f16) if half else \
-                   (L.aura_knn_search_ivf2, L.aura_knn_search_ivf2_probed, L.aura_knn_search_ivf2_signal,
-                    L.aura_knn_search_ivf2_staged)
+        # the layout as the C call takes it, filled once: the per-call path passes its address and the call's scalars
+        self._struct = _lib.Ivf2ListsStruct(
+            bank=_p(bank), inv_norm=_p(inv_norm), meta=_p(meta), centroids=_p(centroids), image=_p(sorted_shadow),
+            rho=_p(rho16 if half else rho),                            # the readers take rho16 in rho's place
+            sorted_rows=_p(sorted_rows), pad_off=_p(pad_off), list_len=_p(list_len), lists_flag=_p(lists_flag),
+            row_constants=_p(row_constants), n_sorted=ns, N=M, D=D, nprobe=self.nprobe, image_format=fmt)
+        self._addr = ctypes.addressof(self._struct)
 
     def holds(self, bank, inv_norm, meta, centroids, nprobe: int, sorted_shadow, rho, sorted_rows, pad_off, list_len,
               n_sorted: Optional[int] = None, lists_flag=None, row_constants=None, rho16=None) -> bool:
@@ -2828,21 +2808,10 @@ class Ivf2Lists:
                 word.arm(None)
             return out_s, out_i, torch.zeros(1, dtype=torch.int32, device=dev)
         nbytes, base, ovf, stream = self._scratch(nq, k)
-        h = self._ptrs
-        f_plain, f_probed, f_signal, _ = self._fn
-        if word is not None:
-            check(f_signal(*h, self.ns, self.M, queries.data_ptr(), now, self.D, nq, k, self._cent,
-                                                self.nprobe, pid, idx_base, out_s.data_ptr(), out_i.data_ptr(), base,
-                                                nbytes, ovf.data_ptr(), word.ptr, word.arm(ovf), stream),
-                  "aura_knn_search_ivf2_signal")
-        elif pid is not None:
-            check(f_probed(*h, self.ns, self.M, queries.data_ptr(), now, self.D, nq, k, self._cent,
-                                                self.nprobe, pid, idx_base, out_s.data_ptr(), out_i.data_ptr(), base,
-                                                nbytes, ovf.data_ptr(), stream), "aura_knn_search_ivf2_probed")
-        else:
-            check(f_plain(*h, self.ns, self.M, queries.data_ptr(), now, self.D, nq, k, self._cent,
-                                         self.nprobe, idx_base, out_s.data_ptr(), out_i.data_ptr(), base, nbytes,
-                                         ovf.data_ptr(), stream), "aura_knn_search_ivf2")
+        hw, seq = (None, 0) if word is None else (word.ptr, word.arm(ovf))
+        check(self._lib.aura_knn_search_ivf2(self._addr, queries.data_ptr(), now, nq, k, pid, idx_base,
+                                             out_s.data_ptr(), out_i.data_ptr(), base, nbytes, ovf.data_ptr(), 0, 0, None,
+                                             hw, seq, stream), "aura_knn_search_ivf2")
         return out_s, out_i, ovf
 
     def staged(self, queries, k: int, now: float, probe_ids=None, out=None, idx_base: int = 0) -> "Ivf2Pass":
@@ -2860,13 +2829,13 @@ class Ivf2Lists:
                 and out_i.dtype == torch.int32 and out_s.device == dev and out_i.device == dev):
             raise ValueError("Ivf2Lists.staged: out must be contiguous (fp32 [nq, k], int32 [nq, k]) on the bank's device")
         nbytes, base, ovf, _ = self._scratch(nq, k)
-        args = self._ptrs + (self.ns, self.M, queries.data_ptr(), now, self.D, nq, k, self._cent, self.nprobe, pid,
-                             idx_base, out_s.data_ptr(), out_i.data_ptr(), base, nbytes, ovf.data_ptr())
+        args = (self._addr, queries.data_ptr(), now, nq, k, pid, idx_base, out_s.data_ptr(), out_i.data_ptr(), base,
+                nbytes, ovf.data_ptr())
         return Ivf2Pass(self, queries, probe_ids, out_s, out_i, ovf, args)
 
 
 class Ivf2Pass:
-    """One staged pass of ``Ivf2Lists.staged`` (``aura_knn_search_ivf2_staged``): ``stage1(k2)`` -> bounds [nq, 2]
+    """One staged pass of ``Ivf2Lists.staged`` (``aura_knn_search_ivf2``, staged): ``stage1(k2)`` -> bounds [nq, 2]
     (the k-th and the k2-th largest sampled lower bound of every query on this bank), ``stage2_bounds(bound [nq], k2)``
     -> the filtered candidates' own bounds [nq, 2], ``stage3(bound2 [nq])`` -> the result re-scored only where a
     candidate can still reach ``bound2``.  Between the calls the caller combines the bounds of all shards of a
@@ -2882,7 +2851,8 @@ class Ivf2Pass:
         self._args = args
 
     def _call(self, stage: int, k2: int, bounds) -> None:
-        check(self._keep[0]._fn[3](*self._args, stage, k2, _p(bounds), _stream()), "aura_knn_search_ivf2_staged")
+        check(self._keep[0]._lib.aura_knn_search_ivf2(*self._args, stage, k2, _p(bounds), None, 0, _stream()),
+              "aura_knn_search_ivf2 (staged)")
 
     def _bound(self, bound: torch.Tensor) -> torch.Tensor:
         _need(bound, "bound", torch.float32)
@@ -2916,7 +2886,7 @@ class CompletionWord:
     """A host-mapped word that receives a recall's flag and a sequence number behind the recall's last launch:
     ``wait()`` polls it -- no device-to-host copy, no stream synchronisation (a blocking wait on a ~1 ms stream costs
     the host 1-2 ms on this runtime).  ``Ivf2Lists.search(word=...)`` fills it from the call's last workgroup
-    (``aura_knn_search_ivf2_signal``); ``signal(flag)`` enqueues a one-thread launch that copies a flag tensor into
+    (``aura_knn_search_ivf2``'s ``host_word``); ``signal(flag)`` enqueues a one-thread launch that copies a flag tensor into
     it (a chain that ends in an entry point without one: the staged recall)."""
 
     def __init__(self, device):

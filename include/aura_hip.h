@@ -35,6 +35,11 @@ extern "C" {
 #define AURA_DTYPE_F32 0
 #define AURA_DTYPE_BF16 1
 
+/* image_format: the 16-bit format of a list-sorted image of the inverted lists (and of any image that
+ * aura_bank_find_repeats scans).  Any other value is AURA_E_INVAL. */
+#define AURA_IMAGE_BF16 0
+#define AURA_IMAGE_F16  1   /* IEEE half, conversion and rho16 as documented under "The list-sorted image in IEEE half" */
+
 /* gif flags */
 #define AURA_GIF_TIME_INVARIANT 1 /* h is [rows, H]: the same current at every timestep */
 #define AURA_GIF_MEAN_OUT 2       /* out is [rows, H] = mean over T of the spikes */
@@ -183,32 +188,25 @@ int aura_diverse_select(const float* bank, const float* inv_norm, int64_t count,
  *   A row with a NaN or Inf component and a row of norm 0 are kept and are nobody's target (their cosines are NaN
  *     or 0).  The norm is the fp32 one: a batch row whose SQUARED norm overflows fp32 (||f|| > 1.8e19) or underflows
  *     to 0 (||f|| < 1e-23) counts as such a row.
- * The scan.  image_bf16 != NULL: a CURRENT bf16 image of the normalised held rows ([n_image][D], D % 8 == 0,
- *   D <= 768, 16-byte aligned) -- the row-ordered shadow (image_rows == NULL, n_image = N: image row i is bank row i)
- *   or the list-sorted shadow of the inverted lists (image_rows = sorted_rows, n_image = n_sorted; -1 entries are
- *   padding or holes) -- with rho [rows of the bank] as aura_bank_shadow_update leaves it.  One pass over the image
- *   on the bf16 matrix pipe against the batch's normalised bf16 rows; a pair survives when cos_bf16 + err >= tau
- *   with the prefilter's bound err = rho_row + rho_q + rho_row rho_q + 2 D 2^-24 + 1e-5 (aura_knn_search_ex);
- *   survivors go to per-row lists of 256 entries and a second launch re-scores them in fp32 from the fp32 bank.  A
- *   list that overflows sets *overflow_out (device int32, reset by every call) to non-zero: the results are then
- *   incomplete and the caller repeats the call with image_bf16 == NULL.
- *   image_bf16 == NULL: a dense fp32 scan of the fp32 bank (any D <= 4096), the per-row maximum by a packed
- *   (ordered cosine bits, ~row) 64-bit atomicMax; it cannot overflow.
+ * The scan.  image != NULL: a CURRENT 16-bit image of the normalised held rows ([n_image][D], D % 8 == 0, D <= 768,
+ *   16-byte aligned) in `image_format` -- the row-ordered bf16 shadow (image_rows == NULL, n_image = N: image row i is
+ *   bank row i) or the list-sorted image of the inverted lists (image_rows = sorted_rows, n_image = n_sorted; -1
+ *   entries are padding or holes) -- with rho [rows of the bank], the residual norms of THIS image: rho as
+ *   aura_bank_shadow_update leaves it for AURA_IMAGE_BF16, the image's rho16 for AURA_IMAGE_F16.  One pass over the
+ *   image on the 16-bit matrix pipe against the batch's normalised rows in the same format; a pair survives when
+ *   cos_16 + err >= tau with the prefilter's bound err = rho_row + rho_q + rho_row rho_q + 2 D 2^-24 + 1e-5
+ *   (aura_knn_search_ex); survivors go to per-row lists of 256 entries and a second launch re-scores them in fp32 from
+ *   the fp32 bank.  A list that overflows sets *overflow_out (device int32, reset by every call) to non-zero: the
+ *   results are then incomplete and the caller repeats the call with image == NULL.
+ *   image == NULL: a dense fp32 scan of the fp32 bank (any D <= 4096), the per-row maximum by a packed
+ *   (ordered cosine bits, ~row) 64-bit atomicMax; it cannot overflow.  image_format must still be a valid value.
  * The n x n cosines of the batch are computed in fp32 on the matrix pipe (lower triangle); only rows that have a
  *   pair >= tau among rows without a stored target enter the ordered walk.
  * stored_target, batch_leader: int32 [n]; cos_out: fp32 [n]; workspace: *_workspace_bytes(n) bytes (negative for an
  * unsupported n), 256-byte aligned.  Nothing is written to the bank.
- * aura_bank_touch: meta[r][1] = now for every 0 <= r < count among rows[0 .. n) (int32; others are ignored;
- *   duplicates store the same value). */
-int64_t aura_bank_find_repeats_workspace_bytes(int64_t n);
-int aura_bank_find_repeats(const float* bank, const float* inv_norm, int64_t N, int64_t D, const uint16_t* image_bf16,
-                           const int32_t* image_rows, int64_t n_image, const float* rho, const float* feats, int64_t n,
-                           float tau, int32_t* stored_target, int32_t* batch_leader, float* cos_out,
-                           int32_t* overflow_out, void* workspace, int64_t workspace_bytes, void* stream);
-int aura_bank_touch(float* meta, int64_t count, const int32_t* rows, int64_t n, float now, void* stream);
-
-/* Consolidation within tags (csrc/aura_consolidate.hip): aura_bank_find_repeats with two more inputs and nothing else
- * of its rule changed.
+ *
+ * Consolidation within tags: batch_tags != NULL selects the scoped search -- two more inputs and nothing else of the
+ * rule changed.  batch_tags == NULL: the scope-blind search above; meta is then ignored.
  *   meta [rows of the bank][4]: the bank's metadata; column 3 holds the tag as a float, read as
  *     aura_knn_search_scoped reads it (a value outside (-1, 2^24) is no tag and matches nothing).
  *   batch_tags int32 [n], on the device: one tag per batch row.
@@ -224,19 +222,23 @@ int aura_bank_touch(float* meta, int64_t count, const int32_t* rows, int64_t n, 
  *   appended to a list (rows of other tags cannot fill the 256 entries; with a list-sorted image the tag is that of bank
  *   row image_rows[ir], read from meta, so the image needs no upkeep when a tag changes), the dense scan before the
  *   packed atomicMax, the Gram before a row is marked pending, the walk before a kept row offers its cosine.  The
- *   overflow flag, the workspace (the same *_workspace_bytes) and every other argument are those of
- *   aura_bank_find_repeats.  AURA_E_INVAL also for batch_tags == NULL, or meta == NULL with N > 0. */
-int aura_bank_find_repeats_scoped(const float* bank, const float* inv_norm, int64_t N, int64_t D,
-                                  const uint16_t* image_bf16, const int32_t* image_rows, int64_t n_image,
-                                  const float* rho, const float* feats, int64_t n, float tau, int32_t* stored_target,
-                                  int32_t* batch_leader, float* cos_out, int32_t* overflow_out, void* workspace,
-                                  int64_t workspace_bytes, void* stream, const float* meta, const int32_t* batch_tags);
+ *   overflow flag, the workspace and every other argument are unchanged.  AURA_E_INVAL also for batch_tags != NULL
+ *   with meta == NULL and N > 0; AURA_E_ALIGN for a meta or batch_tags that is not 4-byte aligned.
+ * aura_bank_touch: meta[r][1] = now for every 0 <= r < count among rows[0 .. n) (int32; others are ignored;
+ *   duplicates store the same value). */
+int64_t aura_bank_find_repeats_workspace_bytes(int64_t n);
+int aura_bank_find_repeats(const float* bank, const float* inv_norm, int64_t N, int64_t D, const uint16_t* image,
+                           const int32_t* image_rows, int64_t n_image, const float* rho, const float* feats, int64_t n,
+                           float tau, int32_t* stored_target, int32_t* batch_leader, float* cos_out,
+                           int32_t* overflow_out, void* workspace, int64_t workspace_bytes, const float* meta,
+                           const int32_t* batch_tags, int image_format, void* stream);
+int aura_bank_touch(float* meta, int64_t count, const int32_t* rows, int64_t n, float now, void* stream);
 
 /* Blending merges: a repeated memory moves toward the rows that repeat it (csrc/aura_blend.hip).  [build-side] the
  * reference's centroid index keeps an online running mean of what it absorbs (hippocampal.py:226-228); its bank stores
  * every row.
  *
- * THE RULE.  Inputs: the stored_target / batch_leader of ONE aura_bank_find_repeats[_scoped] call for a batch
+ * THE RULE.  Inputs: the stored_target / batch_leader of ONE aura_bank_find_repeats call (scoped or not) for a batch
  * f_0 .. f_{n-1} (n <= 1024) against the N held rows, and a rate beta in (0, 1], fp32.
  *   Group key of batch row i.  stored_target[i] = r >= 0: held row r.  Else batch_leader[i] = j >= 0: batch row j.
  *     Else row i is kept and is a member of nothing.
@@ -254,9 +256,10 @@ int aura_bank_find_repeats_scoped(const float* bank, const float* inv_norm, int6
  * aura_bank_blend applies the rule in one launch and keeps the derived state of every BANK row it moves current:
  *   bank[r]; inv_norm[r] with aura_bank_row_norms' arithmetic, bit for bit; when shadow_bf16 is given and
  *   r < shadow_upto, shadow_bf16[r] and rho[r] with aura_bank_shadow_update's arithmetic; when the list-sorted image is
- *   given and pos_of_row[r] = p with 0 <= p < n_sorted and sorted_rows[p] == r, the same bf16 bits into sorted_bf16[p]
- *   (and rho[r]), in place -- the centroid id has not changed, so the lists gain no hole and use no slack.  A cached
- *   table of aura_ivf2_row_constants is stale afterwards (rho changed).
+ *   given and pos_of_row[r] = p with 0 <= p < n_sorted and sorted_rows[p] == r, the row in `image_format` into image[p]
+ *   (for AURA_IMAGE_BF16 the same bf16 bits; rho[r] receives the bf16 residual either way, and with AURA_IMAGE_F16
+ *   rho16[r], when rho16 is not NULL, the half image's), in place -- the centroid id has not changed, so the lists
+ *   gain no hole and use no slack.  A cached table of aura_ivf2_row_constants is stale afterwards (rho changed).
  * The batch.  feats_row0 == -1: feats [n][D]; blended batch keys go to out_feats [n][D], which the caller has filled
  *   with a copy of feats (only blended rows are written; feats itself never is); the write that stores them derives
  *   their norms and shadows as for any row.  feats_row0 >= 0: the batch IS bank rows [feats_row0, feats_row0 + n)
@@ -270,13 +273,14 @@ int aura_bank_find_repeats_scoped(const float* bank, const float* inv_norm, int6
  * AURA_E_INVAL: n outside [0, 1024], D outside [1, 4096], rows < N or rows >= 2^31, beta outside (0, 1] or NaN,
  *   feats_row0 < -1 or a slab outside [N, rows], a null array that is needed, rho given without shadow_bf16 or the
  *   image (or the reverse), the image's three arrays not all given, an image or shadow with D % 8 != 0, shadow_upto
- *   outside [0, rows].  AURA_E_ALIGN: a shadow or image that is not 16-byte aligned or comes with an unaligned bank;
- *   an aligned bank with D % 4 == 0 whose feats / out_feats are not 16-byte aligned. */
+ *   outside [0, rows], an image_format that is not one, rho16 with AURA_IMAGE_BF16.  AURA_E_ALIGN: a shadow or image
+ *   that is not 16-byte aligned or comes with an unaligned bank; an aligned bank with D % 4 == 0 whose feats /
+ *   out_feats are not 16-byte aligned. */
 int aura_bank_blend(float* bank, float* inv_norm, int64_t N, int64_t rows, int64_t D, const float* feats,
                     int64_t feats_row0, int64_t n, const int32_t* stored_target, const int32_t* batch_leader,
                     float beta, float* out_feats, uint16_t* shadow_bf16, float* rho, int64_t shadow_upto,
-                    uint16_t* sorted_bf16, const int32_t* sorted_rows, const int32_t* pos_of_row, int64_t n_sorted,
-                    void* stream);
+                    uint16_t* image, float* rho16, const int32_t* sorted_rows, const int32_t* pos_of_row,
+                    int64_t n_sorted, int image_format, void* stream);
 
 /* In-place compaction of the bank (csrc/aura_compact.hip): the primitive under forgetting, pruning and the
  * consolidation of held rows.  [build-side] no upstream counterpart (the reference's pruning ends in `pass`).
@@ -621,8 +625,9 @@ int aura_knn_search_shadow(const float* bank, const uint16_t* bank_bf16, const f
                            const float* centroids, int nprobe, void* stream);
 
 /* Centroid-index recall (hippocampal.py:259-270) as inverted lists on the two-stage machinery: the
- * caller keeps a LIST-SORTED bf16 shadow (IEEE half: the *_f16 forms below) -- sorted row i holds the shadow row of bank row
- * sorted_rows[i] (-1: no row, scanned as padding), the rows of one centroid contiguous.
+ * caller keeps a LIST-SORTED 16-bit image of the bank, bf16 or IEEE half -- `image_format` says which, one
+ * argument of every function below -- sorted row i holds the shadow row of bank row sorted_rows[i] (-1: no
+ * row, scanned as padding), the rows of one centroid contiguous.
  * pad_off [257]: first sorted row of each list, multiples of 16 (pad_off[256] <= n_sorted);
  * list_len [256]: entries in use, list_len[c] <= pad_off[c+1] - pad_off[c] -- the difference is
  * slack that aura_ivf2_append fills after writes, so the lists are re-packed only when the centroids
@@ -631,19 +636,13 @@ int aura_knn_search_shadow(const float* bank, const uint16_t* bank_bf16, const f
  * receives the reverse map bank row -> sorted row for aura_ivf2_append).
  * aura_ivf2_append: after a write of n DISTINCT bank rows `slots` (device int64) whose centroid ids
  * are in meta[.][2]: the row's previous entry becomes a hole (-1), the row is appended to its list
- * (bf16 row converted, rho refreshed, pos_of_row updated).  A row whose list has no free entry left is
+ * (image row converted, rho refreshed, pos_of_row updated).  A row whose list has no free entry left is
  * dropped from the lists and *flag |= 1: pass that flag to aura_knn_search_ivf2 as lists_flag (it is
  * reported as AURA_KNN_FLAG_LISTS_STALE) or re-pack after at most `slack` appended rows.
- * aura_knn_search_ivf2: each probed list is streamed once per 256 of the queries that probe it, in
- * passes of up to 8192 queries; results (rows, score bits) equal aura_knn_search_ivf's.  N = rows of
- * the bank (every sorted_rows entry is < N).  D % 8 == 0, D <= 768, k <= 256, nprobe <= 8;
- * overflow_out as in aura_knn_search_ex (non-zero: re-run aura_knn_search_ivf or the masked scan).
  * aura_centroid_probe: ids_out[q][p] (p < nprobe, [nq][8] int32) = the p-th nearest of the 256 centroid
  * rows to query q (L2 on the unnormalised query, ties to the lower row: hippocampal.py:261-262), exactly
  * what aura_knn_search_ivf2 computes for itself; workspace: aura_centroid_probe_workspace_bytes(nq)
- * bytes, 256-byte aligned.  aura_knn_search_ivf2_probed takes such ids (of the same queries and
- * centroid table) instead of recomputing them: a bank sharded over ranks that share one centroid table
- * probes every query once, on the rank that owns it, not once per rank.
+ * bytes, 256-byte aligned.
  * row_constants (optional, [n_sorted][4] fp32, 16-byte aligned): the sorted rows' score constants
  * {0.5 strength, temporal term + error, temporal term - error, bank row id bits} -- the per-row half of
  * hippocampal.py:290-303's combined score as the prefilter bounds it.  They depend on the bank's metadata,
@@ -651,63 +650,81 @@ int aura_knn_search_shadow(const float* bank, const uint16_t* bank_bf16, const f
  * and pass them to every search that uses the SAME `now` (fp32: the reference's fp32 timestamps give it a
  * 128-second grain) until metadata or layout change; aura_ivf2_append keeps a table current for the
  * entries it touches (pass the table and its `now`; NULL: no table).  NULL in the search: computed per
- * call into the workspace. */
+ * call into the workspace.
+ *
+ * The list-sorted image in IEEE half (AURA_IMAGE_F16).  Normalised rows and queries lie in [-1, 1], so half (11
+ * significand bits) covers them at the size of bf16 (8 bits) and the prefilter's band U - L = 2 (rho_row + E_fix + eq)
+ * becomes 5-6 times narrower at D = 768: fewer candidates leave the filter scan and fewer survivors are gathered in
+ * fp32 by the refine.  Results are unchanged (the rows and score bits of the fp32 scan).
+ *   Conversion: fl(bank[r] * inv_norm[r]) rounded to nearest, ties to even; an element with |x| < 2^-14 is stored as
+ *     +0, so the image holds no subnormal and the bound does not depend on how the matrix pipe treats them; the
+ *     residual is taken against what is stored.  Queries are converted alike.
+ *   rho16 [rows of the bank]: the residual norm of the half image, aura_bank_shadow_update's formula on that residual.
+ *     The writers (aura_bank_shadow_sorted, aura_ivf2_append, aura_bank_blend) keep writing the bf16 residual into
+ *     `rho` bit for bit as they do for a bf16 image (the row-ordered shadow shares that array) and write rho16 when it
+ *     is not NULL.  The readers (aura_ivf2_row_constants, aura_knn_search_ivf2, the aura_bank_find_repeats scan) take
+ *     rho16 in rho's place.  aura_ivf2_append with a table of row constants needs rho16.  With AURA_IMAGE_BF16 rho16
+ *     must be NULL (AURA_E_INVAL otherwise).
+ *   Negative strengths use their own worst-case query bound, (1.001 (2^-11 1.00001 + sqrt(D) 2^-14) + (D/2 + 3) 2^-24)
+ *     (1 + 2^-7): 2^-11 relative on the elements that stay normal, at most 2^-14 each on those stored as 0.
+ * Every other argument, limit and return code is the same for both formats. */
+/* `rho`: the residual norms of THIS image -- rho for AURA_IMAGE_BF16, rho16 for AURA_IMAGE_F16. */
 int aura_ivf2_row_constants(const float* meta, const float* rho, const int32_t* sorted_rows, int64_t n_sorted,
-                            int64_t D, float now, float* row_constants, void* stream);
+                            int64_t D, float now, float* row_constants, int image_format, void* stream);
 int64_t aura_knn_ivf2_workspace_bytes(int64_t n_sorted, int64_t nq, int k);
 int64_t aura_centroid_probe_workspace_bytes(int64_t nq);
 int aura_centroid_probe(const float* centroids, const float* queries, int64_t D, int64_t nq, int nprobe,
                         int32_t* ids_out, void* workspace, int64_t workspace_bytes, void* stream);
-int aura_bank_shadow_sorted(const float* bank, const float* inv_norm, const int32_t* sorted_rows,
-                            uint16_t* sorted_bf16, float* rho, int32_t* pos_of_row, int64_t n_sorted, int64_t D,
-                            void* stream);
+int aura_bank_shadow_sorted(const float* bank, const float* inv_norm, const int32_t* sorted_rows, uint16_t* image,
+                            float* rho, float* rho16, int32_t* pos_of_row, int64_t n_sorted, int64_t D,
+                            int image_format, void* stream);
 int aura_ivf2_append(const float* bank, const float* inv_norm, const float* meta, const int64_t* slots,
-                     int64_t n, int64_t D, uint16_t* sorted_bf16, int32_t* sorted_rows, const int32_t* pad_off,
-                     int32_t* list_len, int32_t* pos_of_row, float* rho, int32_t* flag, float* row_constants,
-                     float row_constants_now, void* stream);
-int aura_knn_search_ivf2(const float* bank, const float* inv_norm, const float* meta,
-                         const uint16_t* sorted_bf16, const float* rho, const int32_t* sorted_rows,
-                         const int32_t* pad_off, const int32_t* list_len, const int32_t* lists_flag,
-                         const float* row_constants,
-                         int64_t n_sorted, int64_t N, const float* queries, float now, int64_t D, int64_t nq, int k,
-                         const float* centroids, int nprobe, int32_t idx_base, float* out_scores,
-                         int32_t* out_idx, void* workspace, int64_t workspace_bytes, int32_t* overflow_out,
-                         void* stream);
-int aura_knn_search_ivf2_probed(const float* bank, const float* inv_norm, const float* meta,
-                                const uint16_t* sorted_bf16, const float* rho, const int32_t* sorted_rows,
-                                const int32_t* pad_off, const int32_t* list_len, const int32_t* lists_flag,
-                                const float* row_constants,
-                                int64_t n_sorted, int64_t N, const float* queries, float now, int64_t D, int64_t nq,
-                                int k, const float* centroids, int nprobe, const int32_t* probe_ids, int32_t idx_base,
-                                float* out_scores, int32_t* out_idx, void* workspace, int64_t workspace_bytes,
-                                int32_t* overflow_out, void* stream);
+                     int64_t n, int64_t D, uint16_t* image, int32_t* sorted_rows, const int32_t* pad_off,
+                     int32_t* list_len, int32_t* pos_of_row, float* rho, float* rho16, int32_t* flag,
+                     float* row_constants, float row_constants_now, int image_format, void* stream);
 
-/* aura_knn_search_ivf2[_probed] (probe_ids may be NULL) that also tells the HOST when the call is done and what
- * its flag is, without a device-to-host copy: host_word is 64 bytes of host-mapped memory from
+/* One layout of the inverted lists, as described above; what ops.Ivf2Lists validates once.  Pointers and 64-bit
+ * fields first, the two 32-bit ints last: no interior padding. */
+typedef struct aura_ivf2_lists {
+    const float* bank;                /* [N][D] fp32, 16-byte aligned */
+    const float* inv_norm;            /* [N] */
+    const float* meta;                /* [N][4], 16-byte aligned; the centroid ids are in meta[.][2] */
+    const float* centroids;           /* [256][D] */
+    const uint16_t* image;            /* [n_sorted][D] in image_format, 16-byte aligned */
+    const float* rho;                 /* [N]: residual norms of THIS image (rho16 for AURA_IMAGE_F16) */
+    const int32_t* sorted_rows;       /* [n_sorted]: the sorted rows' bank rows, all < N; -1: padding or a hole */
+    const int32_t* pad_off;           /* [257] */
+    const int32_t* list_len;          /* [256] */
+    const int32_t* lists_flag;        /* optional: aura_ivf2_append's flag, reported as AURA_KNN_FLAG_LISTS_STALE */
+    const float* row_constants;       /* optional, 16-byte aligned, for exactly the `now` of the call */
+    int64_t n_sorted;                 /* sorted rows in use: a multiple of 16, > 0 */
+    int64_t N;                        /* rows of the bank */
+    int64_t D;                        /* D % 8 == 0, D <= 768 */
+    int32_t nprobe;                   /* 1..8 */
+    int32_t image_format;             /* AURA_IMAGE_BF16 or AURA_IMAGE_F16 */
+} aura_ivf2_lists;
+
+/* The recall: each probed list is streamed once per 256 of the queries that probe it, in passes of up to 8192
+ * queries; results (rows, score bits) equal aura_knn_search_ivf's.  k <= 256; overflow_out as in aura_knn_search_ex
+ * (non-zero: re-run aura_knn_search_ivf or the masked scan); workspace: aura_knn_ivf2_workspace_bytes(n_sorted, nq,
+ * k) bytes, 256-byte aligned; queries [nq][D] fp32, 16-byte aligned.  nq == 0 launches nothing.
+ *
+ * probe_ids (optional, [nq][8] int32): aura_centroid_probe's ids of the same queries and centroid table, taken
+ * instead of recomputing them: a bank sharded over ranks that share one centroid table probes every query once, on
+ * the rank that owns it, not once per rank.  NULL: the call computes the probes.
+ *
+ * The completion word.  host_word != NULL (stage 0 only, overflow_out required): the call also tells the HOST when
+ * it is done and what its flag is, without a device-to-host copy: host_word is 64 bytes of host-mapped memory from
  * aura_host_word_alloc; a one-thread launch behind the call's last kernel stores the flag into host_word[0] and then
  * host_seq into host_word[1].  The caller polls host_word[1] == host_seq (choose a new host_seq per call) and reads
  * the flag from host_word[0]; results are then final on the stream as after any launch.  One call in flight per
  * host_word.  (The flag read costs the reference-style caller a stream synchronisation per recall otherwise:
- * hippocampal.py's retrieval is synchronous too, every .item() in :311-317 waits for the GPU.) */
-int aura_host_word_alloc(void** host_word_out);
-int aura_host_word_free(void* host_word);
-/* The completion signal of aura_knn_search_ivf2_signal on its own: a one-thread launch on `stream` stores *flag_dev
- * (0 if NULL) into host_word[0], then host_seq into host_word[1].  For call chains that end in another entry point
- * (the staged recall): poll instead of a stream synchronisation. */
-int aura_signal_flag(const int32_t* flag_dev, uint32_t* host_word, uint32_t host_seq, void* stream);
-int aura_knn_search_ivf2_signal(const float* bank, const float* inv_norm, const float* meta,
-                                const uint16_t* sorted_bf16, const float* rho, const int32_t* sorted_rows,
-                                const int32_t* pad_off, const int32_t* list_len, const int32_t* lists_flag,
-                                const float* row_constants,
-                                int64_t n_sorted, int64_t N, const float* queries, float now, int64_t D, int64_t nq,
-                                int k, const float* centroids, int nprobe, const int32_t* probe_ids, int32_t idx_base,
-                                float* out_scores, int32_t* out_idx, void* workspace, int64_t workspace_bytes,
-                                int32_t* overflow_out, uint32_t* host_word, uint32_t host_seq, void* stream);
-
-/* aura_knn_search_ivf2[_probed] in stages, for a bank that is row-sharded over ranks: the
- * prefilter's threshold of a query is a lower bound of its k-th best score, and bounds found on different
- * shards can be combined before any shard filters -- every shard then keeps about 1/S of the candidates
- * and survivors it would keep against its own bound.
+ * hippocampal.py's retrieval is synchronous too, every .item() in :311-317 waits for the GPU.)
+ *
+ * The recall in stages (stage != 0; stage 0 is the whole recall, k2 and bounds are then unused), for a bank that is
+ * row-sharded over ranks: the prefilter's threshold of a query is a lower bound of its k-th best score,
+ * and bounds found on different shards can be combined before any shard filters -- every shard then keeps about 1/S
+ * of the candidates and survivors it would keep against its own bound.
  *   stage 1: everything up to the sampled bounds; bounds[q][0] = the k-th, bounds[q][1] = the k2-th
  *            (1 <= k2 <= k; 0: same as k) largest sampled lower bound of query q on THIS bank: at least k
  *            (k2) distinct rows of this bank score at least that.
@@ -721,86 +738,23 @@ int aura_knn_search_ivf2_signal(const float* bank, const float* inv_norm, const 
  *            they are close to the global k-th best score itself.  Stage 3: bounds[q] = that combination (one
  *            float per query); the refine re-scores only candidates whose upper bound reaches it, so a shard
  *            returns the rows of its top k that can be in the global top k and -1 for the rest.
- * probe_ids may be NULL (probes computed in stage 1).  nq <= 8192 per staged call. */
-int aura_knn_search_ivf2_staged(const float* bank, const float* inv_norm, const float* meta,
-                                const uint16_t* sorted_bf16, const float* rho, const int32_t* sorted_rows,
-                                const int32_t* pad_off, const int32_t* list_len, const int32_t* lists_flag,
-                                const float* row_constants,
-                                int64_t n_sorted, int64_t N, const float* queries, float now, int64_t D, int64_t nq,
-                                int k, const float* centroids, int nprobe, const int32_t* probe_ids, int32_t idx_base,
-                                float* out_scores, int32_t* out_idx, void* workspace, int64_t workspace_bytes,
-                                int32_t* overflow_out, int stage, int k2, float* bounds, void* stream);
-
-/* The list-sorted image in IEEE half.  Normalised rows and queries lie in [-1, 1], so half (11 significand bits)
- * covers them at the size of bf16 (8 bits) and the prefilter's band U - L = 2 (rho_row + E_fix + eq) becomes 5-6
- * times narrower at D = 768: fewer candidates leave the filter scan and fewer survivors are gathered in fp32 by the
- * refine.  Results are unchanged (the rows and score bits of the fp32 scan).
- *   Conversion: fl(bank[r] * inv_norm[r]) rounded to nearest, ties to even; an element with |x| < 2^-14 is stored as
- *     +0, so the image holds no subnormal and the bound does not depend on how the matrix pipe treats them; the
- *     residual is taken against what is stored.  Queries are converted alike.
- *   rho16 [rows of the bank]: the residual norm of the half image, aura_bank_shadow_update's formula on that residual.
- *     The writers below keep writing the bf16 residual into `rho` bit for bit as their bf16 forms do (the row-ordered
- *     shadow shares that array) and write rho16 when it is not NULL.  The readers (row constants, the four searches,
- *     the consolidate scan) take rho16 in rho's place.  aura_ivf2_append_f16 with a table of row constants needs rho16.
- *   Negative strengths use their own worst-case query bound, (1.001 (2^-11 1.00001 + sqrt(D) 2^-14) + (D/2 + 3) 2^-24)
- *     (1 + 2^-7): 2^-11 relative on the elements that stay normal, at most 2^-14 each on those stored as 0.
- * Every other argument, limit and return code is that of the entry point without the suffix. */
-int aura_bank_shadow_sorted_f16(const float* bank, const float* inv_norm, const int32_t* sorted_rows,
-                                uint16_t* sorted_f16, float* rho, float* rho16, int32_t* pos_of_row, int64_t n_sorted,
-                                int64_t D, void* stream);
-int aura_ivf2_append_f16(const float* bank, const float* inv_norm, const float* meta, const int64_t* slots,
-                         int64_t n, int64_t D, uint16_t* sorted_f16, int32_t* sorted_rows, const int32_t* pad_off,
-                         int32_t* list_len, int32_t* pos_of_row, float* rho, float* rho16, int32_t* flag,
-                         float* row_constants, float row_constants_now, void* stream);
-int aura_ivf2_row_constants_f16(const float* meta, const float* rho16, const int32_t* sorted_rows, int64_t n_sorted,
-                                int64_t D, float now, float* row_constants, void* stream);
-int aura_knn_search_ivf2_f16(const float* bank, const float* inv_norm, const float* meta,
-                             const uint16_t* sorted_f16, const float* rho16, const int32_t* sorted_rows,
-                             const int32_t* pad_off, const int32_t* list_len, const int32_t* lists_flag,
-                             const float* row_constants,
-                             int64_t n_sorted, int64_t N, const float* queries, float now, int64_t D, int64_t nq, int k,
-                             const float* centroids, int nprobe, int32_t idx_base, float* out_scores,
-                             int32_t* out_idx, void* workspace, int64_t workspace_bytes, int32_t* overflow_out,
-                             void* stream);
-int aura_knn_search_ivf2_probed_f16(const float* bank, const float* inv_norm, const float* meta,
-                                    const uint16_t* sorted_f16, const float* rho16, const int32_t* sorted_rows,
-                                    const int32_t* pad_off, const int32_t* list_len, const int32_t* lists_flag,
-                                    const float* row_constants,
-                                    int64_t n_sorted, int64_t N, const float* queries, float now, int64_t D, int64_t nq,
-                                    int k, const float* centroids, int nprobe, const int32_t* probe_ids, int32_t idx_base,
-                                    float* out_scores, int32_t* out_idx, void* workspace, int64_t workspace_bytes,
-                                    int32_t* overflow_out, void* stream);
-int aura_knn_search_ivf2_signal_f16(const float* bank, const float* inv_norm, const float* meta,
-                                    const uint16_t* sorted_f16, const float* rho16, const int32_t* sorted_rows,
-                                    const int32_t* pad_off, const int32_t* list_len, const int32_t* lists_flag,
-                                    const float* row_constants,
-                                    int64_t n_sorted, int64_t N, const float* queries, float now, int64_t D, int64_t nq,
-                                    int k, const float* centroids, int nprobe, const int32_t* probe_ids, int32_t idx_base,
-                                    float* out_scores, int32_t* out_idx, void* workspace, int64_t workspace_bytes,
-                                    int32_t* overflow_out, uint32_t* host_word, uint32_t host_seq, void* stream);
-int aura_knn_search_ivf2_staged_f16(const float* bank, const float* inv_norm, const float* meta,
-                                    const uint16_t* sorted_f16, const float* rho16, const int32_t* sorted_rows,
-                                    const int32_t* pad_off, const int32_t* list_len, const int32_t* lists_flag,
-                                    const float* row_constants,
-                                    int64_t n_sorted, int64_t N, const float* queries, float now, int64_t D, int64_t nq,
-                                    int k, const float* centroids, int nprobe, const int32_t* probe_ids, int32_t idx_base,
-                                    float* out_scores, int32_t* out_idx, void* workspace, int64_t workspace_bytes,
-                                    int32_t* overflow_out, int stage, int k2, float* bounds, void* stream);
-int aura_bank_find_repeats_f16(const float* bank, const float* inv_norm, int64_t N, int64_t D, const uint16_t* image_f16,
-                               const int32_t* image_rows, int64_t n_image, const float* rho16, const float* feats,
-                               int64_t n, float tau, int32_t* stored_target, int32_t* batch_leader, float* cos_out,
-                               int32_t* overflow_out, void* workspace, int64_t workspace_bytes, void* stream);
-int aura_bank_find_repeats_scoped_f16(const float* bank, const float* inv_norm, int64_t N, int64_t D,
-                                      const uint16_t* image_f16, const int32_t* image_rows, int64_t n_image,
-                                      const float* rho16, const float* feats, int64_t n, float tau,
-                                      int32_t* stored_target, int32_t* batch_leader, float* cos_out,
-                                      int32_t* overflow_out, void* workspace, int64_t workspace_bytes, void* stream,
-                                      const float* meta, const int32_t* batch_tags);
-int aura_bank_blend_f16(float* bank, float* inv_norm, int64_t N, int64_t rows, int64_t D, const float* feats,
-                        int64_t feats_row0, int64_t n, const int32_t* stored_target, const int32_t* batch_leader,
-                        float beta, float* out_feats, uint16_t* shadow_bf16, float* rho, int64_t shadow_upto,
-                        uint16_t* sorted_f16, float* rho16, const int32_t* sorted_rows, const int32_t* pos_of_row,
-                        int64_t n_sorted, void* stream);
+ * probe_ids may be NULL (probes computed in stage 1).  nq <= 8192 per staged call; bounds is required.
+ *
+ * Refusals, in this order: lists == NULL (AURA_E_INVAL); a row_constants that is not 16-byte aligned (AURA_E_ALIGN);
+ * an image_format that is not one, a stage outside 0..4, host_word with overflow_out == NULL or stage != 0
+ * (AURA_E_INVAL); then the sizes (AURA_E_INVAL), nq == 0 (AURA_OK), a NULL required pointer (AURA_E_INVAL), the
+ * alignments (AURA_E_ALIGN), n_sorted % 16 and the workspace size (AURA_E_INVAL), the staged conditions
+ * (AURA_E_INVAL). */
+int aura_knn_search_ivf2(const aura_ivf2_lists* lists, const float* queries, float now, int64_t nq, int k,
+                         const int32_t* probe_ids, int32_t idx_base, float* out_scores, int32_t* out_idx,
+                         void* workspace, int64_t workspace_bytes, int32_t* overflow_out, int stage, int k2,
+                         float* bounds, uint32_t* host_word, uint32_t host_seq, void* stream);
+int aura_host_word_alloc(void** host_word_out);
+int aura_host_word_free(void* host_word);
+/* The completion signal of aura_knn_search_ivf2 on its own: a one-thread launch on `stream` stores *flag_dev
+ * (0 if NULL) into host_word[0], then host_seq into host_word[1].  For call chains that end in a call without one
+ * (the staged recall): poll instead of a stream synchronisation. */
+int aura_signal_flag(const int32_t* flag_dev, uint32_t* host_word, uint32_t host_seq, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * Surrogate-gradient training path and the prosody-modulated GIF (fp32, [rows][T][H] layout)

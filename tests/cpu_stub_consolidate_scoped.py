@@ -1,7 +1,7 @@
 """Consolidation within tags in torch fp64 on the CPU: ``find_repeats_scoped`` on top of ``tests/cpu_stub_scoped.py``
 (which brings ``find_repeats``, ``bank_compact``, ``bank_set_tags`` and every other stand-in) -- TEST INFRASTRUCTURE ONLY.
 
-The rule (``include/aura_hip.h``, ``aura_bank_find_repeats_scoped``) is the rule of ``tests/cpu_stub_consolidate.py``
+The rule (``include/aura_hip.h``, ``aura_bank_find_repeats`` by tag) is the rule of ``tests/cpu_stub_consolidate.py``
 applied to masked cosines: ``cs[i, r] = -inf`` where the held row's tag differs from ``tags[i]``, ``cb[i, j] = -inf``
 where ``tags[i] != tags[j]``.  A held row's tag is ``int(meta[r, 3])`` when that lies in (-1, 2^24), else no tag at all; a
 batch tag outside [0, 2^24) matches nothing, not even the same value on another batch row.  ``rule``, ``undecided`` and

@@ -1,4 +1,4 @@
-"""GPU tests of consolidation within tags (``aura_bank_find_repeats_scoped`` and everything above it) against the rule
+"""GPU tests of consolidation within tags (``aura_bank_find_repeats`` by tag and everything above it) against the rule
 restated in torch fp64 on the CPU: the cosines of tests/cpu_stub_consolidate.py with every ineligible pair at -inf
 (tests/cpu_stub_consolidate_scoped.py), then that stub's ``rule``, ``undecided`` and ``replay_check`` unchanged.
 

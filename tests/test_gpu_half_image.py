@@ -1,4 +1,4 @@
-"""The list-sorted image of the inverted lists in IEEE half (aura_bank_shadow_sorted_f16 and the *_f16 readers):
+"""The list-sorted image of the inverted lists in IEEE half (image_format = AURA_IMAGE_F16 in the writers and readers):
 the rigorous bound on rows and queries built to round the worst way, recall through the half image against the fp32
 lists and the fp32 scan (rows and score bits), and the image's upkeep by appends and blends.
 
@@ -191,6 +191,58 @@ def test_recall_through_the_half_image(dev, N, D, ncent):
             s2, r2, o2 = ops.knn_search_ivf(bank, inv, meta, q, k, NOW, N, cent, 8, order, off, lens, cap)
             assert int(o2.item()) == 0
             assert torch.equal(r2, r1) and torch.equal(s2, s1), f"nq={nq} k={k}: differs from the fp32 lists"
+
+
+@pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16])
+def test_every_call_form_through_the_one_entry_point(dev, dtype):
+    """aura_knn_search_ivf2 is one function: plain, with the caller's probes, with a completion word and in stages it
+    gives the same rows and score bits on a half and on a bf16 image -- and probes that the caller FORCES to lists 0..3
+    are obeyed, which no other case notices if the function drops ``probe_ids``.  N = 4096, D = 64, 256 centroids drawn
+    from the bank, strengths of both signs, nq = 33 (not a multiple of 4 or 32), k = 8, nprobe = 4."""
+    from aura_snn_rag_amd import ops
+    N, D, nq, k, nprobe = 4096, 64, 33, 8, 4
+    g = torch.Generator().manual_seed(5)
+    bank = torch.randn(N, D, generator=g).to(dev).contiguous()
+    inv = _norms(ops, bank)
+    meta = torch.zeros(N, 4)
+    meta[:, 0] = 0.3 + 0.7 * torch.rand(N, generator=g)
+    meta[::5, 0] *= -1.0
+    meta[:, 1] = NOW - 7200 * torch.rand(N, generator=g)
+    meta = meta.to(dev).contiguous()
+    cent = bank[torch.randperm(N, generator=g)[:256].to(dev)].contiguous()
+    meta[:, 2] = ops.kmeans_assign(bank, cent, N, 256).float()
+    assert int((meta[:, 2] < 4).sum()) >= k, "lists 0..3 must hold at least k rows"
+    st = ops.build_ivf2(bank, inv, meta[:, 2], dtype=dtype)
+    assert st["sorted_bf16"].dtype == dtype and (st["rho16"] is None) == (dtype == torch.bfloat16)
+    lists = ops.Ivf2Lists(bank, inv, meta, cent, nprobe, st["sorted_bf16"], st["rho"], st["sorted_rows"], st["pad_off"],
+                          st["list_len"], st["n_sorted"], None, None, st["rho16"])
+    q = bank[torch.randint(0, N, (nq,), generator=g).to(dev)] + 0.3 * torch.randn(nq, D, generator=g).to(dev)
+    q = q.contiguous()
+
+    def same(res, what):
+        assert torch.equal(res[1], ref[1]) and torch.equal(res[0], ref[0]), what
+        assert int(res[2].item()) == 0, what
+
+    s0, r0 = ops.knn_search(bank, inv, meta, q, k, NOW, centroids=cent, nprobe=nprobe, fp32_scan=True)
+    ref = lists.search(q, k, NOW)
+    ref = (ref[0].clone(), ref[1].clone(), ref[2].clone())
+    assert torch.equal(ref[1], r0) and torch.equal(ref[0], s0), "the plain call differs from the fp32 scan"
+    assert int(ref[2].item()) == 0
+    same(lists.search(q, k, NOW, probe_ids=ops.centroid_probe(q, cent, nprobe)), "the caller's own probes")
+    word = ops.CompletionWord(dev)
+    res = lists.search(q, k, NOW, word=word)
+    assert word.wait() == int(res[2].item())
+    same(res, "with a completion word")
+    p = lists.staged(q, k, NOW)
+    b = p.stage1(k2=k)
+    b2 = p.stage2_bounds(b[:, 0].contiguous(), k)
+    same(p.stage3(b2[:, 0].contiguous()), "staged on its own bounds")
+    forced = torch.full((nq, 8), -1, dtype=torch.int32, device=dev)
+    forced[:, :4] = torch.arange(4, dtype=torch.int32, device=dev)
+    sf, rf, of = lists.search(q, k, NOW, probe_ids=forced)
+    assert int(of.item()) == 0 and bool((rf >= 0).all())
+    assert bool((meta[rf.long().flatten(), 2] < 4).all()), "a row from a list that was not probed"
+    assert bool((rf != ref[1]).any(dim=1).any()), "forced probes changed nothing"
 
 
 def test_fuzz_sweep_once(dev):

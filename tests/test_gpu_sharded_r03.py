@@ -87,7 +87,7 @@ def test_collectives_over_rccl_world_of_one(tmp_path):
 
 
 def test_staged_inverted_list_recall_equals_unstaged(dev):
-    """aura_knn_search_ivf2_staged: stage 1 -> bounds, stage 2 with (a) the bank's own bound, (b) a TIGHTER valid
+    """aura_knn_search_ivf2 in stages: stage 1 -> bounds, stage 2 with (a) the bank's own bound, (b) a TIGHTER valid
     bound (the true k-th best score minus a hair: what other shards may contribute), (c) a useless bound: rows and
     score bits always equal the unstaged recall; the tighter bound shrinks the candidate lists."""
     from aura_snn_rag_amd import ops
