@@ -126,6 +126,8 @@ SIGNATURES = {
     "aura_attn_decode_extend_workspace_bytes": (I64, [I64, I64, I64, I64, I64]),
     "aura_attn_decode_extend": (I, [P, P, P, P, P, P, P, P, P, P, P, P, I64, I64, I64, I64, I64, I64, I, P, I64, P, P,
                                     P]),
+    "aura_attn_decode_extend_counts": (I, [P, P, P, P, P, P, P, P, P, P, P, P, P, I64, I64, I64, I64, I64, I64, I, P,
+                                           I64, P, P, P]),
     "aura_sample_workspace_bytes": (I64, [I64, I64, I64, F]),
     "aura_sample_next": (I, [P, I64, I64, I64, P, P, P, F, I, F, I64, F, U64, U64, I64, I64, P, I64, P, P, P, P, P, P, I64,
                              P]),

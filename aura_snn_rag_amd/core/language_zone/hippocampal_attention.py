@@ -28,6 +28,24 @@ import torch.nn.functional as F
 from ... import ops
 
 
+def row_counts(who: str, name: str, counts, B: int, lo: int, hi: int, device, dtype=torch.int32):
+    """Per-row counts [B] for a ragged call -> ``(tensor of dtype on device, host values or None)``.  A host sequence
+    (list, tuple, CPU tensor) is checked against ``lo <= c <= hi`` here and its values are returned; a tensor that is
+    already on another device is only shaped and typed: its values are never read on the host."""
+    if isinstance(counts, torch.Tensor):
+        if counts.dtype not in (torch.int32, torch.int64) or tuple(counts.shape) != (B,):
+            raise ValueError(f"{who}: {name} is [B] = ({B},) integers, got {counts.dtype} {tuple(counts.shape)}")
+        known = counts.tolist() if counts.device.type == "cpu" else None
+    else:
+        known = list(counts)
+        if len(known) != B or any(isinstance(c, bool) or not isinstance(c, int) for c in known):
+            raise ValueError(f"{who}: {name} is [B] = ({B},) integers, got {counts!r}")
+        counts = torch.tensor(known, dtype=dtype)
+    if known is not None and any(not lo <= c <= hi for c in known):
+        raise ValueError(f"{who}: {name} {known} must lie in [{lo}, {hi}]")
+    return counts.to(device=device, dtype=dtype).contiguous(), known
+
+
 class AttentionCache:
     """The K/V cache of one attention module: ``k`` and ``v`` [B, H, capacity, dh] fp32, ``lengths`` int32 [B] on the
     device (the next position of each row; -1 retires a row: its steps return zeros and leave its cache alone), the
@@ -238,12 +256,19 @@ class HippocampalProsodyAttention(nn.Module):
 
     @torch.no_grad()
     def extend(self, hidden_states: torch.Tensor, prosody: Optional[torch.Tensor] = None, use_memory: bool = True,
-               cache: Optional[AttentionCache] = None, advance: bool = True) -> torch.Tensor:
+               cache: Optional[AttentionCache] = None, advance: bool = True, counts=None,
+               count_bound: Optional[int] = None) -> torch.Tensor:
         """``m`` new tokens per row: hidden [B, m, D] (the normed rows), prosody [B, m, 4] or ``None``, ``1 <= m <=
         ops.DECODE_EXTEND_MAX``.  Appends their keys and values at each row's length, attends (token ``j`` over the
         cache and the new tokens up to itself) and returns the attention output [B, m, D]: what ``m`` calls of ``step``
         return, from one pass over the cache.  The lengths advance by ``m`` on the device unless ``advance=False``.
-        Raises when the cache may not hold ``m`` more positions."""
+        Raises when the cache may not hold ``m`` more positions.
+
+        ``counts`` [B] (ints in ``[0, m]``; a host sequence or a tensor): row ``b`` is right-padded and only its first
+        ``counts[b]`` tokens are new; the padded places are read by nobody, append nothing and return ``o_proj``'s
+        bias.  The lengths advance by ``counts[b]``.  The host-side bound ``max_length`` advances by the largest count
+        where the host knows it (a host sequence, or ``count_bound``), by ``m`` otherwise; the same number is what the
+        capacity check asks room for."""
         who = "HippocampalProsodyAttention.extend"
         if hidden_states.dim() != 3 or hidden_states.shape[-1] != self.hidden_size:
             raise ValueError(f"{who}: hidden is [B, m, {self.hidden_size}], got {tuple(hidden_states.shape)}")
@@ -257,16 +282,26 @@ class HippocampalProsodyAttention(nn.Module):
             if tuple(prosody.shape) != (B, m, 4):
                 raise ValueError(f"{who}: prosody is [B, m, 4] = ({B}, {m}, 4), got {tuple(prosody.shape)}")
             prosody = prosody.contiguous()
-        if cache.max_length + m > cache.capacity:
-            raise RuntimeError(f"{who}: {m} more positions do not fit the cache ({cache.max_length} of "
+        need = m
+        if counts is not None:
+            counts, known = row_counts(who, "counts", counts, B, 0, m, cache.lengths.device)
+            if known is not None:
+                need = max(known, default=0)
+            if count_bound is not None:
+                need = min(need, int(count_bound))
+        elif count_bound is not None:
+            raise ValueError(f"{who}: count_bound bounds counts; there are none")
+        if cache.max_length + need > cache.capacity:
+            raise RuntimeError(f"{who}: {need} more positions do not fit the cache ({cache.max_length} of "
                                f"{cache.capacity} may be held); a sliding cache is not part of this module")
         x = hidden_states.contiguous()
         memory = self._memory_on(use_memory)
+        ragged = {} if counts is None else dict(counts=counts)          # without counts: the call as it was
         ctx = ops.attn_decode_extend(self.q_proj(x), self.k_proj(x), self.v_proj(x), x if memory else None, prosody,
                                      self.prosody_gate.weight, self.prosody_gate.bias,
                                      self.memory_gate.weight if memory else None,
                                      self.memory_gate.bias if memory else None,
                                      cache.lengths, cache.k, cache.v, cache.extend_workspace_for(m),
-                                     n_chunks=cache.n_chunks, advance=bool(advance))
-        cache.max_length += m
+                                     n_chunks=cache.n_chunks, advance=bool(advance), **ragged)
+        cache.max_length += need
         return self.o_proj(ctx)

@@ -68,11 +68,14 @@ class HippocampalTransformerLayer(nn.Module):
 
     @torch.no_grad()
     def extend(self, hidden_states: torch.Tensor, prosody: Optional[torch.Tensor] = None, use_memory: bool = True,
-               cache: Optional[AttentionCache] = None, advance: bool = True) -> torch.Tensor:
+               cache: Optional[AttentionCache] = None, advance: bool = True, counts=None,
+               count_bound: Optional[int] = None) -> torch.Tensor:
         """``m`` new tokens through the layer: hidden [B, m, D] -> [B, m, D], the layer's formula around the
-        attention's ``extend``."""
+        attention's ``extend``.  ``counts`` [B]: right-padded rows (see the attention's ``extend``); what the padded
+        places return is unspecified."""
+        ragged = {} if counts is None and count_bound is None else dict(counts=counts, count_bound=count_bound)
         attn_output = self.attention.extend(self.attention_norm(hidden_states), prosody=prosody,
-                                            use_memory=use_memory, cache=cache, advance=advance)
+                                            use_memory=use_memory, cache=cache, advance=advance, **ragged)
         return self._feed_forward(hidden_states + self.dropout(attn_output))
 
     def _fused_step(self, hidden_states, prosody, use_memory, cache, advance) -> torch.Tensor:

@@ -33,7 +33,7 @@ import torch.nn as nn
 from torch.utils.checkpoint import checkpoint
 
 from ... import ops
-from .hippocampal_attention import AttentionCache
+from .hippocampal_attention import AttentionCache, row_counts
 from .hippocampal_layer import HippocampalTransformerLayer
 from .place_cell_encoder import PlaceCellSemanticEncoder
 from .theta_gamma_encoding import ThetaGammaPositionalEncoding, embed_tokens
@@ -133,12 +133,21 @@ class CachedDecodingMixin:
 
     @torch.no_grad()
     def extend(self, tokens: torch.Tensor, prosody: Optional[torch.Tensor] = None, state: Optional[DecodeState] = None,
-               use_memory: bool = True) -> torch.Tensor:
+               use_memory: bool = True, counts=None) -> torch.Tensor:
         """``m >= 1`` new tokens per row appended to a state that holds a context: tokens [B, m] (prosody [B, m, 4] or
         ``None``) at the positions after each row's context -> logits [B, m, V], what ``m`` calls of ``step`` return.
         The tokens go through the layers' ``extend`` in pieces of at most ``ops.DECODE_EXTEND_MAX``; in each piece the
-        last layer advances the shared lengths.  Marks the tokens in ``state.seen``.  No host sync."""
+        last layer advances the shared lengths.  Marks the tokens in ``state.seen``.  No host sync.
+
+        ``counts`` [B] (ints, ``0 <= counts[b] <= m``, on the host or the device): the rows are right-padded and row
+        ``b`` appends only its first ``counts[b]`` tokens, at its own positions (the state becomes ``ragged``).  What
+        the padding holds is ignored and the logits at the padded places are unspecified.  Only the tokens below the
+        count are marked in ``state.seen``.  ``state.position`` advances by ``m``, an upper bound; the capacity check
+        uses the largest count where the host knows the counts, ``m`` otherwise."""
         who = f"{type(self).__name__}.extend"
+        if counts is not None:
+            return torch.cat([self.output_head(h) for h in self._extend_ragged(who, tokens, prosody, state, use_memory,
+                                                                               counts)], dim=1)
         if tokens.dim() != 2 or tokens.shape[1] < 1:
             raise ValueError(f"{who}: tokens is [B, m] with m >= 1, got {tuple(tokens.shape)}")
         B, m = tokens.shape
@@ -171,12 +180,76 @@ class CachedDecodingMixin:
         state.seen.scatter_(1, tokens.to(torch.int64), 1)
         return logits[0] if len(logits) == 1 else torch.cat(logits, dim=1)
 
+    @staticmethod
+    def piece_counts(counts: torch.Tensor, t0: int) -> torch.Tensor:
+        """The counts of the piece that starts at token ``t0``: ``clamp(counts - t0, 0, ops.DECODE_EXTEND_MAX)``."""
+        return (counts - t0).clamp(0, ops.DECODE_EXTEND_MAX)
+
+    @staticmethod
+    def _mark_seen(seen: torch.Tensor, tokens: torch.Tensor, valid: torch.Tensor) -> None:
+        """``seen[b, tokens[b, j]] = 1`` where ``valid[b, j]``; the other places mark a column that is cut off."""
+        V = seen.shape[1]
+        marks = torch.zeros(seen.shape[0], V + 1, dtype=seen.dtype, device=seen.device)
+        marks.scatter_(1, torch.where(valid, tokens.to(torch.int64), V), 1)
+        seen.bitwise_or_(marks[:, :V])
+
+    @torch.no_grad()
+    def _extend_ragged(self, who: str, tokens, prosody, state, use_memory: bool, counts) -> List[torch.Tensor]:
+        """``extend`` with per-row counts up to the head: the last layer's hidden states, one [B, n, D] per piece."""
+        if tokens.dim() != 2 or tokens.shape[1] < 1:
+            raise ValueError(f"{who}: tokens is [B, m] with m >= 1, got {tuple(tokens.shape)}")
+        B, m = tokens.shape
+        self._check_state(who, state, B)
+        if prosody is not None and tuple(prosody.shape) != (B, m, 4):
+            raise ValueError(f"{who}: prosody is [B, m, 4] = ({B}, {m}, 4), got {tuple(prosody.shape)}")
+        dev = state.lengths.device
+        counts, known = row_counts(who, "counts", counts, B, 0, m, dev)
+        held = max(cache.max_length for cache in state.caches)
+        need = m if known is None else max(known, default=0)
+        if held + need > state.capacity:
+            raise RuntimeError(f"{who}: {need} more positions do not fit the caches ({held} of {state.capacity} may be "
+                               f"held); a sliding cache is not part of this module")
+        state.ragged = True                                                # the device lengths are every row's position
+        valid = torch.arange(m, dtype=torch.int32, device=dev)[None, :] < counts[:, None]
+        tokens = torch.where(valid, tokens.to(dev), 0)                     # a valid id where the padding may hold none
+        last = len(self.layers) - 1
+        hidden = []
+        for t0 in range(0, m, ops.DECODE_EXTEND_MAX):
+            piece = tokens[:, t0:t0 + ops.DECODE_EXTEND_MAX]
+            n = piece.shape[1]
+            part_counts = self.piece_counts(counts, t0)
+            bound = n if known is None else max((min(max(c - t0, 0), n) for c in known), default=0)
+            positions = state.lengths[:, None] + torch.arange(n, dtype=torch.int32, device=dev)
+            hidden_states, _ = embed_tokens(piece, self.semantic_encoder, self.pos_encoder, self.layer_norm,
+                                            dense=False, positions=positions)
+            hidden_states = self.dropout(hidden_states)
+            part = None if prosody is None else prosody[:, t0:t0 + n]
+            for i, (layer, cache) in enumerate(zip(self.layers, state.caches)):
+                hidden_states = layer.extend(hidden_states, prosody=part, use_memory=use_memory, cache=cache,
+                                             advance=i == last, counts=part_counts, count_bound=bound)
+            state.position += n
+            hidden.append(hidden_states)
+        self._mark_seen(state.seen, tokens, valid)
+        return hidden
+
+    @staticmethod
+    def _assemble(ids: torch.Tensor, lens: torch.Tensor, new: torch.Tensor, pad: int) -> torch.Tensor:
+        """[B, S + n]: row ``b`` holds its first ``lens[b]`` of ``ids`` [B, S], then ``new`` [B, n], then ``pad``."""
+        S, n = ids.shape[1], new.shape[1]
+        col = torch.arange(S + n, device=ids.device)[None, :]
+        lens = lens.to(torch.int64)[:, None]
+        src = torch.cat([ids.to(torch.int64), new], dim=1)
+        # column c of the result is column c of the prompt below the length, column S + (c - len) of the new tokens
+        # from there on, and padding past len + n
+        take = torch.where(col < lens, col, (col - lens + S).clamp(max=S + n - 1))
+        return torch.where(col < lens + n, src.gather(1, take), pad)
+
     def generate(self, input_ids: torch.Tensor, max_new_tokens: int = 50, temperature: float = 0.8, top_k: int = 50,
                  top_p: float = 0.9, use_memory: bool = True, repetition_penalty: float = 1.2, *,
                  repetition_rule: str = "divide", seed: Optional[int] = None, eos_token_id=_UNSET,
                  pad_token_id: Optional[int] = None, sync_every: int = 8, stream_ids=None,
                  fused_step: bool = False, state: Optional[DecodeState] = None, return_state: bool = False,
-                 capacity: Optional[int] = None):
+                 capacity: Optional[int] = None, prompt_lengths=None, new_lengths=None):
         """Generates up to ``max_new_tokens`` tokens after the prompts ``input_ids`` [B, S] (equal lengths, as in the
         reference) -> [B, S + n].  Runs under ``eval()`` and ``no_grad``: one ``prefill``, then per token one ``step``
         and one ``ops.sample_next`` that writes the token into its column of the preallocated result.
@@ -203,7 +276,14 @@ class CachedDecodingMixin:
         that token; ``finished`` is clear and ``ragged`` set.  ``generate(new_ids [B, S2], state=state, ..)`` feeds
         ``[pending, new_ids]`` through ``extend``, samples from the last position and decodes as above -> [B, S2 + n];
         ``state.step`` and ``state.seen`` carry on, the seed and the streams are the state's unless given.  It raises
-        on the host, without reading the device, when the turn may not fit the state's capacity."""
+        on the host, without reading the device, when the turn may not fit the state's capacity.
+
+        Ragged batches.  ``prompt_lengths`` [B] (first turn, ``1 <= prompt_lengths[b] <= S``) and ``new_lengths`` [B] (a
+        turn with ``state=``, ``0 <= new_lengths[b] <= S2``), ints on the host or the device: the rows of
+        ``input_ids`` are right-padded and what the padding holds is ignored.  Every row is prefilled or extended by
+        its own tokens only, its first logits are those at its own last token, and it generates what it generates
+        alone.  The result is [B, S + n]: row ``b`` holds its own ``len_b`` tokens, then its generated tokens, then
+        ``pad_token_id``.  Lengths the host knows are checked before any launch; no step syncs with the host."""
         who = f"{type(self).__name__}.generate"
         if input_ids.dim() != 2 or input_ids.shape[1] < 1:
             raise ValueError(f"{who}: input_ids is [B, S] with S >= 1, got {tuple(input_ids.shape)}")
@@ -239,6 +319,13 @@ class CachedDecodingMixin:
         dev = input_ids.device
         if stream_ids is not None and not isinstance(stream_ids, torch.Tensor):
             stream_ids = torch.as_tensor(list(stream_ids), dtype=torch.int64).to(dev)
+        if (prompt_lengths if state is not None else new_lengths) is not None:
+            raise ValueError(f"{who}: prompt_lengths goes with a first turn and new_lengths with a turn that has state=")
+        if prompt_lengths is not None or new_lengths is not None:
+            return self._generate_ragged(who, input_ids, max_new_tokens, prompt_lengths, new_lengths, state, capacity,
+                                         seed, stream_ids, eos, pad, sync_every, use_memory, bool(fused_step),
+                                         return_state, dict(penalty=repetition_penalty, penalty_rule=repetition_rule,
+                                                            temperature=temperature, top_k=top_k, top_p=top_p))
         self.eval()
         with torch.no_grad():
             generated = torch.empty(B, width, dtype=torch.int64, device=dev)
@@ -285,6 +372,65 @@ class CachedDecodingMixin:
             if return_state:
                 self._stand_at_history_end(state, base, generated[:, S:S + n], eos)
         return (generated[:, :S + n], state) if return_state else generated[:, :S + n]
+
+    def _generate_ragged(self, who, input_ids, max_new_tokens, prompt_lengths, new_lengths, state, capacity, seed,
+                         stream_ids, eos, pad, sync_every, use_memory, fused_step, return_state, sampling):
+        """``generate`` for right-padded rows (the arguments are checked and defaulted by ``generate``)."""
+        B, S = input_ids.shape
+        dev = input_ids.device
+        first = state is None
+        if first:
+            lens, _ = row_counts(who, "prompt_lengths", prompt_lengths, B, 1, S, dev, dtype=torch.int64)
+        else:
+            lens, known = row_counts(who, "new_lengths", new_lengths, B, 0, S, dev, dtype=torch.int64)
+            if seed is not None and (isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < (1 << 64)):
+                raise ValueError(f"{who}: seed must be an int in [0, 2^64), got {seed!r}")
+        self.eval()
+        with torch.no_grad():
+            if first:
+                state = self.new_state(B, capacity, seed=seed)
+                state.stream_ids = stream_ids
+                hidden = self._prefill_hidden(f"{type(self).__name__}.prefill", input_ids, None, state, use_memory, None,
+                                              lens)
+                fed = lens
+            else:
+                if seed is not None:
+                    state.seed = seed
+                if stream_ids is None:
+                    stream_ids = state.stream_ids
+                else:
+                    state.stream_ids = stream_ids
+                turn = torch.cat([state.pending.to(dev)[:, None], input_ids.to(torch.int64)], dim=1)
+                state.pending = None
+                fed = lens + 1                                              # the pending token is always fed
+                hidden = torch.cat(self._extend_ragged(who, turn, None, state, use_memory,
+                                                       fed if known is None else [c + 1 for c in known]), dim=1)
+            # every row's logits at its own last fed token: the rows are gathered before the head, [B, D] -> [B, V]
+            at = (fed - 1).clamp(min=0)[:, None, None].expand(B, 1, hidden.shape[2])
+            logits = self.output_head(hidden.gather(1, at)[:, 0])
+            base = state.lengths.clone() if return_state else None
+            new = torch.empty(B, max_new_tokens, dtype=torch.int64, device=dev)
+            n = 0
+            while True:
+                column = new[:, n]
+                ops.sample_next(logits, seen=state.seen, finished=state.finished, stream_ids=stream_ids,
+                                seed=state.seed, step=state.step, eos_id=eos, pad_id=pad, out=column, **sampling)
+                state.step += 1
+                n += 1
+                if n == max_new_tokens:
+                    break
+                if eos is not None:
+                    state.lengths.masked_fill_(state.finished.bool(), -1)
+                    if n % sync_every == 0 and bool(state.finished.all()):
+                        break
+                logits = self.step(column, state=state, use_memory=use_memory, fused=fused_step)
+            if eos is not None:
+                done_before = ((new[:, :n] == eos).cumsum(1) - (new[:, :n] == eos).to(torch.int64)) > 0
+                n = int((~done_before.all(0)).sum().item())
+            if return_state:
+                self._stand_at_history_end(state, base, new[:, :n], eos)
+            generated = self._assemble(input_ids, lens, new[:, :n], pad)
+        return (generated, state) if return_state else generated
 
     @staticmethod
     def _stand_at_history_end(state: DecodeState, base: torch.Tensor, new: torch.Tensor, eos) -> None:
@@ -347,19 +493,34 @@ class HippocampalTransformer(CachedDecodingMixin, nn.Module):
 
     # ------------------------------------------------------------------------------------------------ cached decoding
     def prefill(self, input_ids: torch.Tensor, prosody: Optional[torch.Tensor] = None,
-                state: Optional[DecodeState] = None, use_memory: bool = True) -> torch.Tensor:
+                state: Optional[DecodeState] = None, use_memory: bool = True, lengths=None) -> torch.Tensor:
         """``forward`` over a prompt [B, S] that also fills every layer's cache and marks the prompt's tokens in
-        ``state.seen``.  Returns the logits [B, S, V]."""
-        who = "HippocampalTransformer.prefill"
+        ``state.seen``.  Returns the logits [B, S, V].  ``lengths`` [B] (ints, ``1 <= lengths[b] <= S``, on the host or
+        the device): the rows are right-padded; the caches hold each row's own positions, only its own tokens are
+        marked, the state becomes ``ragged`` and the logits at the padded places are unspecified."""
+        return self.output_head(self._prefill_hidden("HippocampalTransformer.prefill", input_ids, prosody, state,
+                                                     use_memory, None, lengths))
+
+    def _prefill_hidden(self, who, input_ids, prosody, state, use_memory, memory, lengths) -> torch.Tensor:
+        """``prefill`` up to the head: the last layer's hidden states [B, S, D]."""
         if input_ids.dim() != 2:
             raise ValueError(f"{who}: input_ids is [B, S], got {tuple(input_ids.shape)}")
         B, S = input_ids.shape
         self._check_state(who, state, B)
+        if lengths is not None:
+            lengths, _ = row_counts(who, "lengths", lengths, B, 1, S, input_ids.device, dtype=torch.int64)
+            valid = torch.arange(S, device=input_ids.device)[None, :] < lengths[:, None]
+            input_ids = torch.where(valid, input_ids, 0)                   # a valid id where the padding may hold none
         hidden_states, _ = embed_tokens(input_ids, self.semantic_encoder, self.pos_encoder, self.layer_norm)
         hidden_states = self.dropout(hidden_states)
+        ragged = {} if lengths is None else dict(lengths=lengths)
         for layer, cache in zip(self.layers, state.caches):
-            hidden_states = layer.prefill(hidden_states, prosody=prosody, use_memory=use_memory, cache=cache)
+            hidden_states = layer.prefill(hidden_states, prosody=prosody, use_memory=use_memory, cache=cache, **ragged)
         with torch.no_grad():
-            state.seen.scatter_(1, input_ids.to(torch.int64), 1)
+            if lengths is None:
+                state.seen.scatter_(1, input_ids.to(torch.int64), 1)
+            else:
+                self._mark_seen(state.seen, input_ids, valid)
+                state.ragged = True
         state.position = S
-        return self.output_head(hidden_states)
+        return hidden_states

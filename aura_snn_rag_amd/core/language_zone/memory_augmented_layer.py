@@ -127,11 +127,15 @@ class MemoryAugmentedLayer(BatchedMemoryMixin, nn.Module):
             return inject_concat(hidden_states, memory_features, memory_scores)
         return inject_gate(hidden_states, memory_features, memory_scores, self.memory_proj, self.memory_gate)
 
-    def retrieve_context(self, hidden_states: torch.Tensor, **retrieve_kw) -> Optional[MemoryContext]:
+    def retrieve_context(self, hidden_states: torch.Tensor, lengths=None, **retrieve_kw) -> Optional[MemoryContext]:
         """The memories ``forward`` would retrieve for ``hidden_states`` [B, S, D] (the states after the attention
-        sublayer), as a ``MemoryContext`` to hold; ``None`` without a bank or with an empty one."""
+        sublayer), as a ``MemoryContext`` to hold; ``None`` without a bank or with an empty one.  ``lengths`` [B]
+        (a tensor, ``1 <= lengths[b] <= S``): the rows are right-padded and a row's query is the mean over its own
+        ``lengths[b]`` positions (``memory_ops.masked_mean``), so that it pins what the row alone pins."""
         if not self._bank_holds_memories():
             return None
+        if lengths is not None:
+            retrieve_kw["lengths"] = lengths
         features, scores = self.retrieve_memories(hidden_states, k=self.num_retrieved, **retrieve_kw)
         return MemoryContext(features, scores, None)
 
@@ -193,21 +197,25 @@ class MemoryAugmentedLayer(BatchedMemoryMixin, nn.Module):
         cache.c = context.contiguous()
 
     def prefill(self, hidden_states: torch.Tensor, prosody: Optional[torch.Tensor] = None, use_memory: bool = True,
-                cache: Optional[MemoryLayerCache] = None, memory: Optional[MemoryContext] = None) -> torch.Tensor:
+                cache: Optional[MemoryLayerCache] = None, memory: Optional[MemoryContext] = None,
+                lengths=None) -> torch.Tensor:
         """``forward`` over a prompt [B, S, D] that also fills the attention cache and pins the memory context for the
         steps that follow: ``memory`` if given, else what ``retrieve_context`` finds for the prompt; nothing with
-        ``use_memory=False``.  Returns what ``forward(.., memory=<the pinned context>)`` returns."""
+        ``use_memory=False``.  Returns what ``forward(.., memory=<the pinned context>)`` returns.  ``lengths`` [B]:
+        right-padded rows; the cache takes them as the attention's ``prefill`` does and the retrieval query is each
+        row's mean over its own positions."""
         who = "MemoryAugmentedLayer.prefill"
         self._check_cache(who, cache)
         if memory is not None:
             self._check_context(who, memory, hidden_states.shape[0])
+        ragged = {} if lengths is None else dict(lengths=torch.as_tensor(lengths))
         attn_output, _ = self.attention.prefill(self.attention_norm(hidden_states), prosody=prosody,
-                                                use_memory=use_memory, cache=cache.attention)
+                                                use_memory=use_memory, cache=cache.attention, **ragged)
         hidden_states = hidden_states + self.dropout(attn_output)
         if not use_memory:
             memory = None
         elif memory is None:
-            memory = self.retrieve_context(hidden_states)
+            memory = self.retrieve_context(hidden_states, **ragged)
         self._pin(cache, memory)
         return self._after_attention(hidden_states, memory is not None, memory)
 
@@ -238,14 +246,17 @@ class MemoryAugmentedLayer(BatchedMemoryMixin, nn.Module):
 
     @torch.no_grad()
     def extend(self, hidden_states: torch.Tensor, prosody: Optional[torch.Tensor] = None, use_memory: bool = True,
-               cache: Optional[MemoryLayerCache] = None, advance: bool = True) -> torch.Tensor:
+               cache: Optional[MemoryLayerCache] = None, advance: bool = True, counts=None,
+               count_bound: Optional[int] = None) -> torch.Tensor:
         """``m`` new tokens through the layer: hidden [B, m, D] -> [B, m, D], the layer's formula around the
         attention's ``extend``, with the memories ``prefill`` pinned injected at every new position
-        (``use_memory=False`` injects nothing)."""
+        (``use_memory=False`` injects nothing).  ``counts`` [B]: right-padded rows (see the attention's ``extend``);
+        what the padded places return is unspecified."""
         self._check_cache("MemoryAugmentedLayer.extend", cache)
         memory = cache.memory if use_memory else None
+        ragged = {} if counts is None and count_bound is None else dict(counts=counts, count_bound=count_bound)
         attn_output = self.attention.extend(self.attention_norm(hidden_states), prosody=prosody,
-                                            use_memory=use_memory, cache=cache.attention, advance=advance)
+                                            use_memory=use_memory, cache=cache.attention, advance=advance, **ragged)
         return self._after_attention(hidden_states + self.dropout(attn_output), memory is not None, memory)
 
     def _mlp(self):

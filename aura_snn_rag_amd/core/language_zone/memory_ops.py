@@ -182,6 +182,16 @@ class MemoryInjection(nn.Module):
         return hidden_states
 
 
+def masked_mean(hidden_states: torch.Tensor, lengths: torch.Tensor) -> torch.Tensor:
+    """The mean of every row of ``hidden_states`` [B, S, D] over its first ``lengths[b]`` positions: the valid
+    positions summed in fp32 (the padded ones selected out, so that nothing they hold, NaN included, counts) and
+    divided by the row's length.  Device ops only; ``lengths[b] >= 1`` is the caller's to ensure."""
+    lengths = lengths.to(hidden_states.device)
+    valid = torch.arange(hidden_states.shape[1], device=hidden_states.device)[None, :] < lengths[:, None]
+    total = torch.where(valid[..., None], hidden_states.float(), 0.0).sum(dim=1)
+    return (total / lengths.to(torch.float32)[:, None]).to(hidden_states.dtype)
+
+
 class BatchedMemoryMixin:
     """Overrides ``retrieve_memories`` / ``store_memory`` of the reference layer with the batched
     HIP path; ``inject_memories`` and everything else stay the layer's own."""
@@ -190,8 +200,10 @@ class BatchedMemoryMixin:
                           reinforce_cap: float = 1.0, *, diversity: Optional[float] = None,
                           max_similarity: Optional[float] = None, fetch_k: Optional[int] = None, tags=None,
                           newer_than: Optional[float] = None, older_than: Optional[float] = None,
-                          min_strength: Optional[float] = None):
-        query = self.query_proj(hidden_states.mean(dim=1))
+                          min_strength: Optional[float] = None, lengths=None):
+        """``lengths`` [B]: right-padded rows; the query is each row's mean over its own positions."""
+        pooled = hidden_states.mean(dim=1) if lengths is None else masked_mean(hidden_states, lengths)
+        query = self.query_proj(pooled)
         return retrieve_memories(self.hippocampus, query, k=k, dtype=hidden_states.dtype, reinforce=reinforce,
                                  reinforce_cap=reinforce_cap, diversity=diversity, max_similarity=max_similarity,
                                  fetch_k=fetch_k, tags=tags, newer_than=newer_than, older_than=older_than,

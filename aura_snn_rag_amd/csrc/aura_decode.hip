@@ -281,10 +281,26 @@ struct ExtendArgs {
     int m;
 };
 
-template <int GP>
-__global__ __launch_bounds__(64 * DEC_WAVES) void attn_extend_chunk_kernel(const ExtendArgs e) {
+// per-row counts ("a restriction of the rule"): row b takes its first counts[b] of the m padded query rows.  The kernels
+// below are one text for both argument types; with ExtendArgs the row's count is m itself, a compile-time identity, so
+// those instantiations are the code they were (register report: profiles/ragged_extend_kernels.json).
+struct RaggedExtendArgs {
+    DecodeArgs d;
+    int m;
+    const int32_t* counts;              // [B]
+};
+
+template <class Args> struct ext_ragged { static constexpr bool value = false; };
+template <> struct ext_ragged<RaggedExtendArgs> { static constexpr bool value = true; };
+
+__device__ __forceinline__ int ext_count(const ExtendArgs& e, int64_t) { return e.m; }
+__device__ __forceinline__ int ext_count(const RaggedExtendArgs& e, int64_t b) { return e.counts[b]; }
+
+template <int GP, class Args>
+__global__ __launch_bounds__(64 * DEC_WAVES) void attn_extend_chunk_kernel(const Args e) {
     constexpr int R = 64 / GP;
     constexpr int PER_SLOT = DEC_CHUNK / R;
+    constexpr bool RAGGED = ext_ragged<Args>::value;
     const DecodeArgs& a = e.d;
     const int m = e.m;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -300,7 +316,11 @@ __global__ __launch_bounds__(64 * DEC_WAVES) void attn_extend_chunk_kernel(const
     const int L = a.lengths[b];
     const int lim = a.cap < DEC_CHUNK * a.n_chunks ? a.cap : DEC_CHUNK * a.n_chunks;
     const int64_t stride = dec_stride(a);
-    if (L < 0 || L + m > lim) {                                         // inactive: the merge writes the zeros
+    const int mb = ext_count(e, b);                                     // the row's own count; m without counts
+    // with counts the four tests are joined without short circuit, so that the count's load does not wait behind the
+    // branch on the length: both loads are in flight together
+    const bool inactive = RAGGED ? bool((L < 0) | (mb < 0) | (mb > m) | (L + mb > lim)) : (L < 0 || L + m > lim);
+    if (inactive) {                                                     // the merge writes the zeros
         if (c == 0 && g0 == 0) {
             for (int q = lane; q < m; q += 64) {
                 const int64_t rh = (row0 + q) * a.H + h;
@@ -310,8 +330,18 @@ __global__ __launch_bounds__(64 * DEC_WAVES) void attn_extend_chunk_kernel(const
         }
         return;
     }
+    if (RAGGED) {
+        if (c == 0 && g0 == 0) {                                        // the padded queries: a header the merge can read
+            for (int q = mb + lane; q < m; q += 64) {
+                const int64_t rh = (row0 + q) * a.H + h;
+                reinterpret_cast<int32_t*>(a.ws + rh * stride)[0] = 0;
+                if (a.scale) a.scale[rh] = 0.0f;
+            }
+        }
+        if (g0 >= mb) return;                                           // no query of the row in this group; the whole
+    }                                                                   // wave, before any shuffle
     const int t0 = c * DEC_CHUNK;
-    const int glast = (g0 + EXT_GROUP < m ? g0 + EXT_GROUP : m) - 1;
+    const int glast = (g0 + EXT_GROUP < mb ? g0 + EXT_GROUP : mb) - 1;
     if (t0 > L + glast) return;                                         // no query of the group reaches this chunk; the
                                                                         // whole wave: no shuffle is skipped
 
@@ -340,7 +370,7 @@ __global__ __launch_bounds__(64 * DEC_WAVES) void attn_extend_chunk_kernel(const
             mx[g] = -INFINITY;
             l[g] = 0.0f;
             end[g] = t0;
-            if (q < m && t0 <= L + q) {                                 // uniform
+            if (q < mb && t0 <= L + q) {                                // uniform
                 end[g] = t0 + DEC_CHUNK < L + q + 1 ? t0 + DEC_CHUNK : L + q + 1;
                 const float s = dec_scale(a, row0 + q, h, lane);
                 if (col) {
@@ -452,7 +482,8 @@ __global__ __launch_bounds__(64 * DEC_WAVES) void attn_extend_chunk_kernel(const
     }
 }
 
-__global__ __launch_bounds__(64 * DEC_WAVES) void attn_extend_merge_kernel(const ExtendArgs e) {
+template <class Args>
+__global__ __launch_bounds__(64 * DEC_WAVES) void attn_extend_merge_kernel(const Args e) {
     const DecodeArgs& a = e.d;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t rh = (int64_t)blockIdx.x * DEC_WAVES + wave;          // (b m + j) H + h
@@ -487,7 +518,7 @@ __global__ __launch_bounds__(64 * DEC_WAVES) void attn_extend_merge_kernel(const
     }
     if (a.advance && h == 0 && row % e.m == 0 && lane == 0 && nv > 0) {
         const int64_t b = row / e.m;
-        a.lengths[b] = a.lengths[b] + e.m;
+        a.lengths[b] = a.lengths[b] + ext_count(e, b);                  // nv > 0 at j = 0: active, count >= 1
     }
 }
 
@@ -502,6 +533,53 @@ inline bool dec_shape_ok(int64_t B, int64_t H, int64_t dh, int64_t n_chunks) {
 
 inline int64_t dec_workspace_floats(int64_t B, int64_t H, int64_t dh, int64_t n_chunks) {
     return B * H * (DEC_HDR + n_chunks * (DEC_PART + dh));
+}
+
+inline void ext_set_counts(ExtendArgs&, const int32_t*) {}
+inline void ext_set_counts(RaggedExtendArgs& e, const int32_t* counts) { e.counts = counts; }
+
+// the extend's validation and its two launches, for either argument type
+template <class Args>
+int ext_launch(const float* q, const float* k_new, const float* v_new, const float* x, const float* prosody_or_null,
+               const float* Wp, const float* bp, const float* wm_or_null, const float* bm_or_null, int32_t* lengths,
+               const int32_t* counts, float* Kc, float* Vc, int64_t B, int64_t m, int64_t H, int64_t dh, int64_t cap,
+               int64_t n_chunks, int advance, float* workspace, int64_t workspace_bytes, float* ctx,
+               float* scale_or_null, void* stream) {
+    if (!dec_shape_ok(B, H, dh, n_chunks) || m < 1 || m > EXT_MAX_M) return AURA_E_INVAL;
+    if (B * m * H * n_chunks > 0x7fffffff) return AURA_E_INVAL;         // < 2^31 * 2^5 * 2^9 * 2^8: no overflow
+    if (cap < 1 || cap > DEC_MAX_CAP || n_chunks * DEC_CHUNK > cap + DEC_CHUNK - 1) return AURA_E_INVAL;
+    if (!q || !k_new || !v_new || !lengths || !Kc || !Vc || !workspace || !ctx) return AURA_E_INVAL;
+    if (prosody_or_null && (!Wp || !bp)) return AURA_E_INVAL;
+    if ((wm_or_null == nullptr) != (bm_or_null == nullptr) || (wm_or_null && !x)) return AURA_E_INVAL;
+    if (workspace_bytes < dec_workspace_floats(B * m, H, dh, n_chunks) * 4) return AURA_E_INVAL;
+    if (misaligned(q, 16) || misaligned(k_new, 16) || misaligned(v_new, 16) || misaligned(x, 16) ||
+        misaligned(wm_or_null, 16) || misaligned(Kc, 16) || misaligned(Vc, 16) || misaligned(workspace, 16) ||
+        misaligned(ctx, 16) || misaligned(prosody_or_null, 4) || misaligned(Wp, 4) || misaligned(bp, 4) ||
+        misaligned(bm_or_null, 4) || misaligned(lengths, 4) || misaligned(scale_or_null, 4))
+        return AURA_E_ALIGN;
+    if (B == 0) return AURA_OK;
+    Args e;
+    DecodeArgs& a = e.d;
+    a.q = q; a.k_new = k_new; a.v_new = v_new; a.x = x; a.prosody = prosody_or_null; a.Wp = Wp; a.bp = bp;
+    a.wm = wm_or_null; a.bm = bm_or_null; a.lengths = lengths; a.Kc = Kc; a.Vc = Vc; a.ws = workspace; a.ctx = ctx;
+    a.scale = scale_or_null;
+    a.B = B; a.H = (int)H; a.dh = (int)dh; a.D = (int)(H * dh); a.cap = (int)cap; a.n_chunks = (int)n_chunks;
+    a.advance = advance != 0;
+    a.isq = 1.0f / sqrtf((float)dh);
+    e.m = (int)m;
+    ext_set_counts(e, counts);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const dim3 block(64 * DEC_WAVES);
+    const int64_t n_groups = (m + EXT_GROUP - 1) / EXT_GROUP;           // B H n_chunks n_groups <= B m H n_chunks
+    const dim3 grid((unsigned)((B * H * n_chunks * n_groups + DEC_WAVES - 1) / DEC_WAVES));
+    const int G = (int)dh / 4;
+#define EXT_CHUNK_LAUNCH(GP) hipLaunchKernelGGL((attn_extend_chunk_kernel<GP, Args>), grid, block, 0, s, e)
+    if (G <= 1) EXT_CHUNK_LAUNCH(1); else if (G <= 2) EXT_CHUNK_LAUNCH(2); else if (G <= 4) EXT_CHUNK_LAUNCH(4);
+    else if (G <= 8) EXT_CHUNK_LAUNCH(8); else if (G <= 16) EXT_CHUNK_LAUNCH(16); else EXT_CHUNK_LAUNCH(32);
+#undef EXT_CHUNK_LAUNCH
+    hipLaunchKernelGGL((attn_extend_merge_kernel<Args>), dim3((unsigned)((B * m * H + DEC_WAVES - 1) / DEC_WAVES)), block,
+                       0, s, e);
+    return aura_check_launch();
 }
 
 }  // namespace
@@ -561,40 +639,22 @@ int aura_attn_decode_extend(const float* q, const float* k_new, const float* v_n
                             const float* bm_or_null, int32_t* lengths, float* Kc, float* Vc, int64_t B, int64_t m,
                             int64_t H, int64_t dh, int64_t cap, int64_t n_chunks, int advance, float* workspace,
                             int64_t workspace_bytes, float* ctx, float* scale_or_null, void* stream) {
-    if (!dec_shape_ok(B, H, dh, n_chunks) || m < 1 || m > EXT_MAX_M) return AURA_E_INVAL;
-    if (B * m * H * n_chunks > 0x7fffffff) return AURA_E_INVAL;         // < 2^31 * 2^5 * 2^9 * 2^8: no overflow
-    if (cap < 1 || cap > DEC_MAX_CAP || n_chunks * DEC_CHUNK > cap + DEC_CHUNK - 1) return AURA_E_INVAL;
-    if (!q || !k_new || !v_new || !lengths || !Kc || !Vc || !workspace || !ctx) return AURA_E_INVAL;
-    if (prosody_or_null && (!Wp || !bp)) return AURA_E_INVAL;
-    if ((wm_or_null == nullptr) != (bm_or_null == nullptr) || (wm_or_null && !x)) return AURA_E_INVAL;
-    if (workspace_bytes < dec_workspace_floats(B * m, H, dh, n_chunks) * 4) return AURA_E_INVAL;
-    if (misaligned(q, 16) || misaligned(k_new, 16) || misaligned(v_new, 16) || misaligned(x, 16) ||
-        misaligned(wm_or_null, 16) || misaligned(Kc, 16) || misaligned(Vc, 16) || misaligned(workspace, 16) ||
-        misaligned(ctx, 16) || misaligned(prosody_or_null, 4) || misaligned(Wp, 4) || misaligned(bp, 4) ||
-        misaligned(bm_or_null, 4) || misaligned(lengths, 4) || misaligned(scale_or_null, 4))
-        return AURA_E_ALIGN;
-    if (B == 0) return AURA_OK;
-    ExtendArgs e;
-    DecodeArgs& a = e.d;
-    a.q = q; a.k_new = k_new; a.v_new = v_new; a.x = x; a.prosody = prosody_or_null; a.Wp = Wp; a.bp = bp;
-    a.wm = wm_or_null; a.bm = bm_or_null; a.lengths = lengths; a.Kc = Kc; a.Vc = Vc; a.ws = workspace; a.ctx = ctx;
-    a.scale = scale_or_null;
-    a.B = B; a.H = (int)H; a.dh = (int)dh; a.D = (int)(H * dh); a.cap = (int)cap; a.n_chunks = (int)n_chunks;
-    a.advance = advance != 0;
-    a.isq = 1.0f / sqrtf((float)dh);
-    e.m = (int)m;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const dim3 block(64 * DEC_WAVES);
-    const int64_t n_groups = (m + EXT_GROUP - 1) / EXT_GROUP;           // B H n_chunks n_groups <= B m H n_chunks
-    const dim3 grid((unsigned)((B * H * n_chunks * n_groups + DEC_WAVES - 1) / DEC_WAVES));
-    const int G = (int)dh / 4;
-#define EXT_CHUNK_LAUNCH(GP) hipLaunchKernelGGL((attn_extend_chunk_kernel<GP>), grid, block, 0, s, e)
-    if (G <= 1) EXT_CHUNK_LAUNCH(1); else if (G <= 2) EXT_CHUNK_LAUNCH(2); else if (G <= 4) EXT_CHUNK_LAUNCH(4);
-    else if (G <= 8) EXT_CHUNK_LAUNCH(8); else if (G <= 16) EXT_CHUNK_LAUNCH(16); else EXT_CHUNK_LAUNCH(32);
-#undef EXT_CHUNK_LAUNCH
-    hipLaunchKernelGGL(attn_extend_merge_kernel, dim3((unsigned)((B * m * H + DEC_WAVES - 1) / DEC_WAVES)), block, 0, s,
-                       e);
-    return aura_check_launch();
+    return ext_launch<ExtendArgs>(q, k_new, v_new, x, prosody_or_null, Wp, bp, wm_or_null, bm_or_null, lengths, nullptr,
+                                  Kc, Vc, B, m, H, dh, cap, n_chunks, advance, workspace, workspace_bytes, ctx,
+                                  scale_or_null, stream);
+}
+
+int aura_attn_decode_extend_counts(const float* q, const float* k_new, const float* v_new, const float* x,
+                                   const float* prosody_or_null, const float* Wp, const float* bp,
+                                   const float* wm_or_null, const float* bm_or_null, int32_t* lengths,
+                                   const int32_t* counts, float* Kc, float* Vc, int64_t B, int64_t m, int64_t H,
+                                   int64_t dh, int64_t cap, int64_t n_chunks, int advance, float* workspace,
+                                   int64_t workspace_bytes, float* ctx, float* scale_or_null, void* stream) {
+    if (!counts) return AURA_E_INVAL;
+    if (misaligned(counts, 4)) return AURA_E_ALIGN;
+    return ext_launch<RaggedExtendArgs>(q, k_new, v_new, x, prosody_or_null, Wp, bp, wm_or_null, bm_or_null, lengths,
+                                        counts, Kc, Vc, B, m, H, dh, cap, n_chunks, advance, workspace, workspace_bytes,
+                                        ctx, scale_or_null, stream);
 }
 
 }  // extern "C"

@@ -938,8 +938,24 @@ def _attn_decode_extend_shapes(q, k_new, v_new, x, prosody, Wp, bp, wm, bm, leng
     return B, m, H, dh, cap, n_chunks
 
 
+def _attn_decode_extend_counts(counts, lengths) -> None:
+    """Type and shape checks of ``attn_decode_extend``'s ``counts``.  Touches no device; the values are never read."""
+    who = "attn_decode_extend"
+    if not isinstance(counts, torch.Tensor):
+        raise TypeError(f"{who}: counts must be a torch.Tensor, got {type(counts)}")
+    if counts.dtype != torch.int32:
+        raise TypeError(f"{who}: counts is {counts.dtype}; the kernel reads int32 counts")
+    if tuple(counts.shape) != tuple(lengths.shape):
+        raise ValueError(f"{who}: counts is [B] = {tuple(lengths.shape)}, got {tuple(counts.shape)}")
+    if not counts.is_contiguous():
+        raise ValueError(f"{who}: counts must be contiguous")
+    if counts.device != lengths.device:
+        raise ValueError(f"{who}: counts is on {counts.device}, the other tensors on {lengths.device}")
+
+
 def attn_decode_extend(q, k_new, v_new, x, prosody, Wp, bp, wm, bm, lengths, k_cache, v_cache, workspace,
-                       n_chunks: Optional[int] = None, advance: bool = True, return_scale: bool = False):
+                       n_chunks: Optional[int] = None, advance: bool = True, return_scale: bool = False,
+                       counts: Optional[torch.Tensor] = None):
     """``m`` new tokens per row appended to a cache that holds a context, in two launches and one pass over K and V (the
     rule: ``include/aura_hip.h``, "Decode attention: extend"): ``q``, ``k_new``, ``v_new``, ``x`` [B, m, D] and
     ``prosody`` [B, m, 4] are ``attn_decode_step``'s arguments for ``m`` successive steps, ``1 <= m <=
@@ -947,9 +963,17 @@ def attn_decode_extend(q, k_new, v_new, x, prosody, Wp, bp, wm, bm, lengths, k_c
     positions ``lengths[b] ..``.  Returns ``ctx`` [B, m, D].  A row with a negative length, or that does not fit whole
     (``lengths[b] + m > cap``), is inactive: zeros, nothing written.  ``advance`` adds ``m`` to the active rows'
     lengths.  ``workspace``: ``attn_decode_extend_workspace_floats`` fp32.  ``return_scale`` also returns ``s``
-    [B, m, H].  Every bit of the results, the caches and the lengths is what the ``m`` steps leave.  No host sync."""
+    [B, m, H].  Every bit of the results, the caches and the lengths is what the ``m`` steps leave.  No host sync.
+
+    ``counts`` (int32 [B] on the tensors' device, never read on the host): row ``b`` takes only its first
+    ``counts[b]`` of the ``m`` padded rows, which is what ``counts[b]`` steps leave; the rows from ``counts[b]`` on are
+    read by nobody and their ``ctx`` and scales are zero.  A row fits by its own count (``lengths[b] + counts[b] <=
+    cap``); a count outside ``[0, m]`` makes the row inactive, a count of 0 leaves it as it is.  ``advance`` adds
+    ``counts[b]``.  ``None`` is the call without counts."""
     B, m, H, dh, cap, n_chunks = _attn_decode_extend_shapes(q, k_new, v_new, x, prosody, Wp, bp, wm, bm, lengths,
                                                             k_cache, v_cache, workspace, n_chunks)
+    if counts is not None:
+        _attn_decode_extend_counts(counts, lengths)
     if prosody is None:
         Wp = bp = None
     if wm is None:
@@ -961,6 +985,14 @@ def attn_decode_extend(q, k_new, v_new, x, prosody, Wp, bp, wm, bm, lengths, k_c
                         wide=("q", "k_new", "v_new", "x", "wm", "k_cache", "v_cache", "workspace"))
     ctx = torch.empty(B, m, H * dh, dtype=torch.float32, device=dev)
     scale = torch.empty(B, m, H, dtype=torch.float32, device=dev) if return_scale else None
+    if counts is not None:
+        _need(counts, "attn_decode_extend: counts")
+        check(lib().aura_attn_decode_extend_counts(_p(q), _p(k_new), _p(v_new), _p(x), _p(prosody), _p(Wp), _p(bp),
+                                                   _p(wm), _p(bm), _p(lengths), _p(counts), _p(k_cache), _p(v_cache), B,
+                                                   m, H, dh, cap, n_chunks, int(bool(advance)), _p(workspace),
+                                                   workspace.numel() * 4, _p(ctx), _p(scale), _stream()),
+              "aura_attn_decode_extend_counts")
+        return (ctx, scale) if return_scale else ctx
     check(lib().aura_attn_decode_extend(_p(q), _p(k_new), _p(v_new), _p(x), _p(prosody), _p(Wp), _p(bp), _p(wm), _p(bm),
                                         _p(lengths), _p(k_cache), _p(v_cache), B, m, H, dh, cap, n_chunks,
                                         int(bool(advance)), _p(workspace), workspace.numel() * 4, _p(ctx), _p(scale),

@@ -1174,6 +1174,37 @@ int aura_attn_decode_extend(const float* q, const float* k_new, const float* v_n
                             int64_t H, int64_t dh, int64_t cap, int64_t n_chunks, int advance, float* workspace,
                             int64_t workspace_bytes, float* ctx, float* scale_or_null, void* stream);
 
+/* Decode attention: extend with per-row counts.  A restriction of the rule above to right-padded rows: row b brings only
+ * its first counts[b] of the m query rows.  The arrays keep their padded shapes [B][m][..] and strides; counts int32 [B].
+ * With m_b = counts[b] and L = lengths[b]:
+ *   inactive  L < 0, or m_b < 0, or m_b > m, or L + m_b > min(cap, 256 n_chunks).  Nothing is written to either cache,
+ *             lengths[b] stays, ctx[b][j] = 0 and scale[b][j][h] = 0 for every j < m.  The row fits by its own count:
+ *             L + m_b, not L + m, so a row is active even where the padded m would not fit.
+ *   m_b == 0  active but empty: nothing is written to the caches, lengths[b] stays, ctx and scale are 0.
+ *   active    the queries j < m_b are the extend's rule verbatim, L_j = L + j; the positions >= L are read from the
+ *             rows < m_b of k_new / v_new only.  The rows j >= m_b of q, k_new, v_new, x and prosody influence
+ *             nothing (they are never loaded, so they may hold NaN) and are not appended; their ctx[b][j] and
+ *             scale[b][j][h] are 0.
+ *   lengths   with `advance`, lengths[b] += m_b, by the second launch only.
+ * Hence, on the same inputs, row b after the call is bit for bit what m_b successive calls of aura_attn_decode_step
+ * leave: ctx, the scales, both caches and the length, whatever the other rows' counts are; counts all equal to m give
+ * the bits of aura_attn_decode_extend.
+ * The same two kernels, compiled with the row's count in the places where m bounds the row; the instantiations behind
+ * aura_attn_decode_extend are not touched.  A wave whose group of 8 queries starts at or past m_b exits at once, whole
+ * and before any shuffle, so the work follows sum_b m_b, not B m.  The first launch writes a chunk count of 0 into the
+ * workspace header of every query j >= m_b, and the second writes the zeros from it: it never reads a partial that
+ * nobody wrote.  No atomics, no LDS, no host sync.
+ *
+ * workspace: aura_attn_decode_extend_workspace_bytes(B, m, H, dh, n_chunks), as above.
+ * AURA_E_INVAL / AURA_E_ALIGN: the extend's conditions; counts NULL is AURA_E_INVAL, counts not 4-byte aligned
+ * AURA_E_ALIGN.  B == 0 launches nothing.  Two launches on `stream`. */
+int aura_attn_decode_extend_counts(const float* q, const float* k_new, const float* v_new, const float* x,
+                                   const float* prosody_or_null, const float* Wp, const float* bp,
+                                   const float* wm_or_null, const float* bm_or_null, int32_t* lengths,
+                                   const int32_t* counts, float* Kc, float* Vc, int64_t B, int64_t m, int64_t H,
+                                   int64_t dh, int64_t cap, int64_t n_chunks, int advance, float* workspace,
+                                   int64_t workspace_bytes, float* ctx, float* scale_or_null, void* stream);
+
 /* ---------------------------------------------------------------------------------------
  * Next token
  * ------------------------------------------------------------------------------------- */
