@@ -143,7 +143,7 @@ extern "C" int aura_addition_linear_backward(const float* x, const float* weight
                                              float* g_x, float* g_w, int64_t B, int64_t in_features,
                                              int64_t out_features, void* stream) {
     if (B < 0 || in_features <= 0 || out_features <= 0) return AURA_E_INVAL;
-    if (!x || !weight_patterns || (B > 0 && !g_out)) return AURA_E_INVAL;
+    if (!weight_patterns || (B > 0 && (!x || !g_out))) return AURA_E_INVAL;   // an empty batch has no x to point at
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int64_t gk = (in_features + BK - 1) / BK;
     if (g_x && B > 0) {
