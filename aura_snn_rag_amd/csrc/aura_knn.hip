@@ -413,17 +413,17 @@ __global__ __launch_bounds__(1024) void online_assign_kernel(float* meta, float*
     if (tid < eff_k) counts[tid] = s_counts[tid];
 }
 
-// ---- phase B, pipelined form (D <= 1024: one centroid element per thread) ----
+// ---- phase B, pipelined and decoupled form (D <= 1024: one centroid element per thread) ----
 // The simple form above spends ~2 us per row on three global round trips inside the serial chain: the row's d0
 // line, the winning centroid's row, the acknowledgement of its store.  Here nothing in the chain leaves the CU
 // when a row's decision is clear (the usual case):
 //   * d0[i], x_i and the centroid row of row i's PREDICTED winner (argmin of d0[i], computed by
 //     online_pred_kernel) are loaded three rows ahead into registers; the prediction is right whenever the bound
 //     decides the row, and a predicted row that an update of the last two iterations has overtaken is replaced
-//     by that update's own result, kept in registers (a thread only ever writes element `tid` of a centroid row,
+//     by that update's own result, kept in registers (a thread only ever writes its own element of a centroid row,
 //     so its own loads see its own stores: single-thread coherence; cross-thread reads happen only in the
 //     re-scoring branch, behind a fence and a barrier);
-//   * wave 0 decides from registers and LDS and publishes (winner, eta) in a two-slot mailbox: ONE barrier per row;
+//   * wave 0 decides from registers and LDS and publishes (winner, eta) in a mailbox (see below);
 //   * centroid ids go to a dense array (scattered into the metadata by a parallel launch afterwards).
 struct OnlSlot { float x, cpre; int cid; float d[4]; };
 
@@ -453,176 +453,13 @@ __global__ __launch_bounds__(256) void online_cid_scatter_kernel(float* meta, co
     if (i < n) meta[slots[i] * 4 + 2] = (float)cid[i];
 }
 
-__global__ __launch_bounds__(1024) void online_assign_fast_kernel(float* centroids, float* counts, int eff_k,
-                                                                  const float* __restrict__ feats,
-                                                                  const float* __restrict__ d0,
-                                                                  const float* __restrict__ xnorm,
-                                                                  const int32_t* __restrict__ pred,
-                                                                  int32_t* __restrict__ cid_out, int64_t n, int64_t D,
-                                                                  int vec4, float rel) {
-    extern __shared__ __attribute__((aligned(16))) float s_row[];   // [D] (re-scoring only)
-    __shared__ float s_delta[256], s_counts[256], s_fresh[256], s_xn[ONL_CHUNK];
-    __shared__ int s_cand[256], s_pred[ONL_CHUNK];
-    __shared__ int s_pub_best[2], s_pub_ncand[2];
-    __shared__ float s_pub_eta[2];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const bool owner = tid < D;                              // this thread owns element `tid` of every centroid row
-    if (tid < 256) {
-        s_delta[tid] = 0.0f;
-        s_counts[tid] = tid < eff_k ? counts[tid] : 0.0f;
-    }
-    for (int64_t i = tid; i < n; i += 1024) { s_pred[i] = pred[i]; s_xn[i] = xnorm[i]; }
-    __syncthreads();
-    auto prefetch = [&](OnlSlot& sl, int64_t row) {
-        if (row >= n) return;
-        const int p = s_pred[row];
-        sl.cid = p;
-        if (owner) {
-            sl.x = feats[row * D + tid];
-            sl.cpre = centroids[(int64_t)p * D + tid];
-        }
-        if (wave == 0) {
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int c = lane + 64 * u;
-                sl.d[u] = c < eff_k ? d0[row * 256 + c] : INFINITY;
-            }
-        }
-    };
-    auto commit = [&](int64_t i, int best, float dwin_up) {   // (one lane of wave 0)
-        const float cn = s_counts[best] + 1.0f;
-        s_counts[best] = cn;
-        const float eta = 1.0f / fmaxf(cn, 1.0f);
-        s_delta[best] += 1.0001f * (eta * dwin_up) + 3e-7f * (2.0f * s_xn[i] + dwin_up);
-        cid_out[i] = best;
-        s_pub_best[i & 1] = best;
-        s_pub_eta[i & 1] = eta;
-    };
-    int last1_id = -1, last2_id = -1;                         // centroids written in the previous two iterations ...
-    float last1_v = 0.0f, last2_v = 0.0f;                     // ... and this thread's element of what was written
-    auto step = [&](int64_t i, OnlSlot& sl) {
-        if (wave == 0) {
-            float lo[4], hi[4], dl[4];
-            float hmin = INFINITY;
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int c = lane + 64 * u;
-                const bool valid = c < eff_k;
-                dl[u] = s_delta[c];
-                const float m = dl[u] == 0.0f ? 0.0f : sl.d[u] * rel + dl[u] * 1.0001f;
-                lo[u] = valid ? sl.d[u] - m : INFINITY;
-                hi[u] = valid ? sl.d[u] + m : INFINITY;
-                hmin = fminf(hmin, hi[u]);
-            }
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) hmin = fminf(hmin, __shfl_xor(hmin, off));
-            unsigned long long cm[4];
-            int total = 0;
-            bool moved = false;
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const bool cnd = lo[u] <= hmin;
-                cm[u] = __ballot(cnd);
-                total += (int)__popcll(cm[u]);
-                moved = moved || (cnd && dl[u] != 0.0f);
-            }
-            const bool any_moved = __ballot(moved) != 0ull;
-            if (total == 0) {
-                if (lane == 0) { s_pub_ncand[i & 1] = 1; commit(i, 0, 0.0f); }
-            } else if (total == 1) {
-#pragma unroll
-                for (int u = 0; u < 4; ++u)
-                    if (lo[u] <= hmin) { s_pub_ncand[i & 1] = 1; commit(i, lane + 64 * u, hi[u]); }
-            } else if (!any_moved) {
-                float bd = INFINITY;
-                int best = 0x7fffffff;
-#pragma unroll
-                for (int u = 0; u < 4; ++u)
-                    if (lo[u] <= hmin && sl.d[u] < bd) { bd = sl.d[u]; best = lane + 64 * u; }
-#pragma unroll
-                for (int off = 32; off > 0; off >>= 1) {
-                    const float od = __shfl_xor(bd, off);
-                    const int ob = __shfl_xor(best, off);
-                    if (od < bd || (od == bd && ob < best)) { bd = od; best = ob; }
-                }
-                if (lane == 0) { s_pub_ncand[i & 1] = 1; commit(i, best, bd); }
-            } else {
-                int base = 0;
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    if (lo[u] <= hmin) {
-                        const int p = base + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(cm[u] >> 32),
-                                                  __builtin_amdgcn_mbcnt_lo((unsigned)cm[u], 0u));
-                        s_cand[p] = lane + 64 * u;
-                    }
-                    base += (int)__popcll(cm[u]);
-                }
-                if (lane == 0) s_pub_ncand[i & 1] = total;
-            }
-        }
-        __syncthreads();
-        const int ncand = s_pub_ncand[i & 1];
-        if (ncand > 1) {                                    // (workgroup-uniform) re-score the candidates
-            if (owner) s_row[tid] = sl.x;
-            __threadfence_block();                          // every thread's centroid stores are done ...
-            __syncthreads();                                // ... before any wave reads whole rows
-            for (int ci = wave; ci < ncand; ci += 16) {
-                const float d = centroid_dist_wave(s_row, centroids + (int64_t)s_cand[ci] * D, D, lane, vec4 != 0);
-                if (lane == 0) s_fresh[ci] = d;
-            }
-            __syncthreads();
-            if (wave == 0) {
-                float bd = INFINITY;
-                int bi = 0x7fffffff;
-                for (int ci = lane; ci < ncand; ci += 64) {
-                    const float d = s_fresh[ci];
-                    if (d < bd) { bd = d; bi = ci; }
-                }
-#pragma unroll
-                for (int off = 32; off > 0; off >>= 1) {
-                    const float od = __shfl_xor(bd, off);
-                    const int ob = __shfl_xor(bi, off);
-                    if (od < bd || (od == bd && ob < bi)) { bd = od; bi = ob; }
-                }
-                if (lane == 0) commit(i, s_cand[bi == 0x7fffffff ? 0 : bi], bd * (1.0f + rel));
-            }
-            __syncthreads();
-        }
-        const int best = s_pub_best[i & 1];
-        const float eta = s_pub_eta[i & 1];
-        const float one_m = 1.0f - eta;
-        if (owner) {
-            float c_old;
-            if (best == last1_id) c_old = last1_v;           // the newest value of that row is still in a register
-            else if (best == last2_id) c_old = last2_v;
-            else if (best == sl.cid) c_old = sl.cpre;        // prefetched behind every older store of this thread
-            else c_old = centroids[(int64_t)best * D + tid]; // prediction missed: one L2 round trip
-            const float c_new = one_m * c_old + eta * sl.x;
-            centroids[(int64_t)best * D + tid] = c_new;
-            last2_v = last1_v; last1_v = c_new;
-        }
-        last2_id = last1_id; last1_id = best;
-        prefetch(sl, i + 3);                                 // (issued behind this iteration's store)
-    };
-    OnlSlot a, b, c;
-    a.cid = b.cid = c.cid = -1;
-    prefetch(a, 0); prefetch(b, 1); prefetch(c, 2);
-    for (int64_t i = 0; i < n; i += 3) {
-        step(i, a);
-        if (i + 1 < n) step(i + 1, b);
-        if (i + 2 < n) step(i + 2, c);
-    }
-    __syncthreads();
-    if (tid < eff_k) counts[tid] = s_counts[tid];
-}
-
-// ---- phase B, decoupled form (round 3, second pass) ----
-// As the pipelined form above, without its barrier on the clear rows: wave 0 decides row i, publishes (winner, eta)
-// in a mailbox of ONL_WIN entries and a sequence number, applies its own 64 elements of the update and goes on to
-// row i + 1; the other fifteen waves wait for the sequence number (an LDS poll), apply theirs and prefetch.  A row
-// then costs max(decision, update) instead of decision + barrier + update.  Rows that need re-scoring meet at the
-// same barriers as before (every wave reads the same mailbox entry, so all of them take that branch), and one
-// barrier per ONL_WIN rows keeps the mailbox from being lapped.
+// ---- The decoupled part: no barrier on the clear rows.  Wave 0 decides row i, publishes (winner, eta) in a mailbox
+// of ONL_WIN entries and a sequence number, applies its own 64 elements of the update and goes on to row i + 1; the
+// other fifteen waves wait for the sequence number (an LDS poll), apply theirs and prefetch.  A row then costs
+// max(decision, update) instead of decision + barrier + update (the form with a two-slot mailbox and one barrier per
+// row was measured against this one and removed: DESIGN.md, online update).  Rows that need re-scoring meet at
+// barriers (every wave reads the same mailbox entry, so all of them take that branch), and one barrier per ONL_WIN
+// rows keeps the mailbox from being lapped.
 constexpr int ONL_WIN = 8;
 #ifndef AURA_ONL_POLL_SLEEP
 #define AURA_ONL_POLL_SLEEP 2
@@ -2438,29 +2275,21 @@ inline int launch_refine_for(const RefineArgs& r_in, int nqb, int64_t D, int cus
     const int64_t Dpad = (D + 31) / 32 * 32;
     RefineArgs r = r_in;
     // Passes of many queries: one WAVE per query first (coarse_refine_wave_kernel); the workgroup-per-query kernel
-    // then only works on the queries that one marked heavy.  AURA_RF_WAVE=0 / 1: never / always (A/B runs).
-    static const int wave_mode = getenv("AURA_RF_WAVE") ? atoi(getenv("AURA_RF_WAVE")) : -1;
+    // then only works on the queries that one marked heavy.
     // (At 8 queries per CU the workgroup-per-query kernel is the faster one: 125 us against 136 + list walk for the
     //  2048-query headline; beyond, its two queries per CU are the limit: 16384 queries 0.9 ms against 0.7.)
     // Beyond 8 queries per CU the one-wave form pays where most queries keep at most 512 candidates -- the shards of a
     // row-sharded bank (125 000 rows x 16 384 queries: 1.59 against 1.75 ms per recall); on a 1 M-row bank a query
     // keeps ~560, half of them overflow to the list and both kernels run (16 384 queries: 3.9 against 3.1 ms).
-    const bool use_wave = heavy && !r.dbg_out && (wave_mode == 1 || (wave_mode != 0 && nqb > 8 * cus && r.N <= 300000));
+    const bool use_wave = heavy && !r.dbg_out && nqb > 8 * cus && r.N <= 300000;
     if (use_wave) {
-        const bool big = nqb <= 8 * cus;                      // every query gets a wave at one workgroup per CU
-        const int rows_w = big ? 16 : 6;
-        const size_t region = (size_t)Dpad * 4 + (size_t)rows_w * (RW_KC + 4) * 4 + (size_t)RW_SURV * 12;
+        const size_t region = (size_t)Dpad * 4 + (size_t)RW_ROWS * (RW_KC + 4) * 4 + (size_t)RW_SURV * 12;
         const size_t lds_w = 8 * region;
         if (lds_w <= 150 * 1024) {
             r.heavy = heavy;
             if (hipMemsetAsync(heavy, 0, 4, s) != hipSuccess) return AURA_E_LAUNCH;
-            if (big) {
-                if (aura_ensure_lds_attr(reinterpret_cast<const void*>(coarse_refine_wave16_kernel), 150 * 1024)) return AURA_E_LAUNCH;
-                hipLaunchKernelGGL(coarse_refine_wave16_kernel, dim3((unsigned)((nqb + 7) / 8)), dim3(RF_THREADS), lds_w, s, r, nqb);
-            } else {
-                if (aura_ensure_lds_attr(reinterpret_cast<const void*>(coarse_refine_wave6_kernel), 150 * 1024)) return AURA_E_LAUNCH;
-                hipLaunchKernelGGL(coarse_refine_wave6_kernel, dim3((unsigned)((nqb + 7) / 8)), dim3(RF_THREADS), lds_w, s, r, nqb);
-            }
+            if (aura_ensure_lds_attr(reinterpret_cast<const void*>(coarse_refine_wave6_kernel), 150 * 1024)) return AURA_E_LAUNCH;
+            hipLaunchKernelGGL(coarse_refine_wave6_kernel, dim3((unsigned)((nqb + 7) / 8)), dim3(RF_THREADS), lds_w, s, r, nqb);
             if (aura_check_launch()) return AURA_E_LAUNCH;
         }
     }
@@ -2483,10 +2312,6 @@ inline int launch_refine_for(const RefineArgs& r_in, int nqb, int64_t D, int cus
         hipLaunchKernelGGL((coarse_refine_kernel<ROWS, KC, WHOLE>), dim3((unsigned)grid_q), dim3(RF_THREADS), lds, s, r);
         return aura_check_launch();
     };
-    static const int geom = getenv("AURA_RF_GEOM") ? atoi(getenv("AURA_RF_GEOM")) : 0;   // A/B runs
-    if (geom == 1) return launch_refine(std::integral_constant<int, 8>{}, std::integral_constant<int, 128>{}, std::false_type{});
-    if (geom == 2) return launch_refine(std::integral_constant<int, 6>{}, std::integral_constant<int, 128>{}, std::false_type{});
-    if (geom == 3) return launch_refine(std::integral_constant<int, 16>{}, std::integral_constant<int, 256>{}, std::false_type{});
     // more queries than CUs: whole rows in flight, 6 survivors per wave and round (48 per round), 53 KB of LDS
     if (nqb > cus) return launch_refine(std::integral_constant<int, 6>{}, std::integral_constant<int, 256>{}, std::true_type{});
     return launch_refine(std::integral_constant<int, 16>{}, std::integral_constant<int, 256>{}, std::false_type{});
@@ -2565,8 +2390,8 @@ inline int run_coarse_pass(const float* bank, const uint16_t* bank16, const floa
     int rc;
     // sample: strided 128-row logical tiles (8 coarse tiles each), sized as for the fp32 path
     int64_t sample_rows = (int64_t)k * N / 512;
-    static const int64_t sample_cap = getenv("AURA_CS_SAMPLE_ROWS") ? atoll(getenv("AURA_CS_SAMPLE_ROWS")) : 8192;
-    int64_t floor_rows = N / 8 < sample_cap ? N / 8 : sample_cap;
+    constexpr int64_t SAMPLE_ROWS_CAP = 8192;                // cap of the sample pass's floor
+    int64_t floor_rows = N / 8 < SAMPLE_ROWS_CAP ? N / 8 : SAMPLE_ROWS_CAP;
     if (floor_rows < (int64_t)k * 48) floor_rows = (int64_t)k * 48;
     if (sample_rows < floor_rows) sample_rows = floor_rows;
     const int64_t ntiles128 = N / 128;                       // whole logical tiles only
@@ -2740,11 +2565,8 @@ int aura_bank_write_online(float* bank, float* loc, float* meta, float* inv_norm
     float* const xnorm = reinterpret_cast<float*>(static_cast<char*>(workspace) + align_up(ch * 256 * 4, 256));
     int32_t* const pred = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(xnorm) + align_up(ch * 4, 256));
     int32_t* const cid = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(pred) + align_up(ch * 4, 256));
-    static const bool simple = getenv("AURA_ONLINE_SIMPLE") != nullptr;   // A/B runs: the unpipelined phase B
-    static const bool v1 = getenv("AURA_ONLINE_V1") != nullptr;         // A/B runs: one barrier per row (the pipelined form)
-    const bool fast = D <= 1024 && !simple;
-    if (fast && (aura_ensure_lds_attr(reinterpret_cast<const void*>(online_assign_fast_kernel), 8 * 1024) ||
-                 aura_ensure_lds_attr(reinterpret_cast<const void*>(online_assign_fast2_kernel), 8 * 1024))) return AURA_E_LAUNCH;
+    const bool fast = D <= 1024;                             // the decoupled phase B: one centroid element per thread
+    if (fast && aura_ensure_lds_attr(reinterpret_cast<const void*>(online_assign_fast2_kernel), 8 * 1024)) return AURA_E_LAUNCH;
     // fp slack of a computed distance against the exact one, both ways: 2 x (chain of D/64 fmaf + 6 butterfly
     // adds + subtraction, square root) x 2^-24, with a factor 2 in hand
     const float rel = 4.0f * ((float)((D + 63) / 64) + 10.0f) * 5.9604645e-8f;
@@ -2757,10 +2579,8 @@ int aura_bank_write_online(float* bank, float* loc, float* meta, float* inv_norm
         if (fast) {
             hipLaunchKernelGGL(online_pred_kernel, dim3((unsigned)((nr + 3) / 4)), dim3(256), 0, s, d0, eff_k, nr, pred);
             if ((rc = aura_check_launch())) return rc;
-            if (v1) hipLaunchKernelGGL(online_assign_fast_kernel, dim3(1), dim3(1024), lds, s, centroids, centroid_counts,
-                                       eff_k, feats + r0 * D, d0, xnorm, pred, cid, nr, D, vec4, rel);
-            else hipLaunchKernelGGL(online_assign_fast2_kernel, dim3(1), dim3(1024), lds, s, centroids, centroid_counts,
-                                    eff_k, feats + r0 * D, d0, xnorm, pred, cid, nr, D, vec4, rel);
+            hipLaunchKernelGGL(online_assign_fast2_kernel, dim3(1), dim3(1024), lds, s, centroids, centroid_counts,
+                               eff_k, feats + r0 * D, d0, xnorm, pred, cid, nr, D, vec4, rel);
             if ((rc = aura_check_launch())) return rc;
             hipLaunchKernelGGL(online_cid_scatter_kernel, dim3((unsigned)((nr + 255) / 256)), dim3(256), 0, s, meta,
                                slots + r0, cid, nr);
@@ -2929,8 +2749,7 @@ static int knn_search_impl(const float* bank, const uint16_t* bank_bf16, const f
                 g_prof.nq = nqb;   // all query blocks of the pass are scored by this one launch
                 g_prof.kind = 0;
             }
-            static const bool force_v1 = getenv("AURA_SCAN_V1") != nullptr;
-            if (nqb > 128 && !force_v1) {
+            if (nqb > 128) {
                 a.n_items = (N + 31) / 32 - 4 * n_sample_tiles;
                 if ((rc = launch_filter_v2(a, s))) return rc;
             } else {
@@ -3069,20 +2888,9 @@ int aura_knn_search_ivf2(const aura_ivf2_lists* lists, const float* queries, flo
         }
     };
     const int stiles = ivf2_stiles(n_sorted, k, stg != 0);   // sample tiles per list (fewer when a bound from outside follows)
-    static const bool w4 = getenv("AURA_CS_WAVES4") != nullptr;   // A/B runs: one wave per SIMD
-    // AURA_IVF_WG4: TWO independent four-wave workgroups per CU, 128 query slots per block (round-3 experiment)
-    static const bool wg4 = !w4 && getenv("AURA_IVF_WG4") != nullptr;
-    const int bsh = wg4 ? 7 : 8;
     // Relative time of a filter tile in a block of <= 128 queries and in a fuller one (the one- and the
     // two-column-block form of the tile loop): the plan splits tiles x weight evenly over the workgroups.
-    // AURA_IVF_W=s,d overrides (tuning runs); the one-wave-per-SIMD form has a single tile loop.
-    static int w_sparse = 0, w_dense = 0;
-    if (w_sparse == 0) {
-        int ws = 5, wd = 7;
-        if (const char* e = getenv("AURA_IVF_W")) { if (sscanf(e, "%d,%d", &ws, &wd) != 2 || ws < 1 || wd < 1 || ws > 64 || wd > 64) { ws = 5; wd = 7; } }
-        if (w4 || wg4) ws = wd = 1;
-        w_dense = wd; w_sparse = ws;
-    }
+    constexpr int w_sparse = 5, w_dense = 7;
     // The sorted rows' score constants depend on `now` and the bank only: the caller may keep them across
     // calls (rowc_cached, aura_ivf2_row_constants; 31 us per call at 1 M rows otherwise), else one launch per
     // call, not per pass.  (Measured dead end: the same launch on a side stream, forked and joined with events
@@ -3123,13 +2931,13 @@ int aura_knn_search_ivf2(const aura_ivf2_lists* lists, const float* queries, flo
         stage("probe");
         hipLaunchKernelGGL(ivf2_plan_kernel, dim3(1), dim3(256), 0, s, w.lq_cnt, pad_off, list_len, w.blk_off,
                            w.blk_list, w.blk_row0, w.blk_stride, w.blk_nq, w.item_off, w.sitem_off, w.nblk,
-                           stiles, w_sparse, w_dense, bsh);
+                           stiles, w_sparse, w_dense, IVF2_BSH);
         if ((rc = aura_check_launch())) return rc;
         stage("plan");
-        const int nslot_blocks = (int)((((int64_t)ivf2_maxblk(w.qp, bsh) << bsh) + 255) / 256);   // 256 slots per launch block
+        const int nslot_blocks = ivf2_maxblk(w.qp);           // one launch block of 256 threads per block of 256 slots
         hipLaunchKernelGGL(ivf2_slots_kernel, dim3((unsigned)nslot_blocks), dim3(256), 0, s,
                            w.lq_cnt, w.lq_list, w.blk_off, w.blk_list, w.nblk, w.eq_q, w.slotq, w.qslot, w.thr,
-                           w.eq_slot, bsh);
+                           w.eq_slot, IVF2_BSH);
         if ((rc = aura_check_launch())) return rc;
         stage("slots");
         }
@@ -3137,7 +2945,7 @@ int aura_knn_search_ivf2(const aura_ivf2_lists* lists, const float* queries, flo
         CoarseArgs c{};
         c.bank = bank; c.bank16 = sorted_bf16; c.rowc = rowc; c.qhat = w.qhat; c.inv_q = w.inv_q;
         c.eq = w.eq_slot; c.qzero = nqb;
-        c.N = n_sorted; c.D = D; c.nq = ivf2_maxblk(w.qp, bsh) << bsh;
+        c.N = n_sorted; c.D = D; c.nq = ivf2_maxblk(w.qp) << IVF2_BSH;
         c.thr = w.thr; c.cnt = w.cnt; c.cand_scores = w.cand_scores; c.cand_idx = w.cand_idx; c.cap = w.cap;
         c.blk_row0 = w.blk_row0; c.blk_stride = w.blk_stride; c.nblk = w.nblk; c.slotq = w.slotq;
         c.blk_nq = w.blk_nq; c.w_sparse = w_sparse; c.w_dense = w_dense;
@@ -3146,19 +2954,9 @@ int aura_knn_search_ivf2(const aura_ivf2_lists* lists, const float* queries, flo
         c.dbg = cs_dbg;
         auto launch_fmt = [&](int mode, auto F) -> int {
             constexpr bool F16 = decltype(F)::value;
-            if (wg4) {
-                if (KS == 8) return launch_coarse_ivf<8, 4, 2, F16>(c, mode, 2 * cus, s);
-                if (KS == 16) return launch_coarse_ivf<16, 4, 2, F16>(c, mode, 2 * cus, s);
-                return launch_coarse_ivf<24, 4, 2, F16>(c, mode, 2 * cus, s);
-            }
-            if (w4) {
-                if (KS == 8) return launch_coarse_ivf<8, 4, 4, F16>(c, mode, cus, s);
-                if (KS == 16) return launch_coarse_ivf<16, 4, 4, F16>(c, mode, cus, s);
-                return launch_coarse_ivf<24, 4, 4, F16>(c, mode, cus, s);
-            }
-            if (KS == 8) return launch_coarse_ivf<8, 8, 2, F16>(c, mode, cus, s);
-            if (KS == 16) return launch_coarse_ivf<16, 8, 2, F16>(c, mode, cus, s);
-            return launch_coarse_ivf<24, 8, 2, F16>(c, mode, cus, s);
+            if (KS == 8) return launch_coarse_ivf<8, F16>(c, mode, cus, s);
+            if (KS == 16) return launch_coarse_ivf<16, F16>(c, mode, cus, s);
+            return launch_coarse_ivf<24, F16>(c, mode, cus, s);
         };
         auto launch = [&](int mode) -> int {
             return f16 ? launch_fmt(mode, std::true_type{}) : launch_fmt(mode, std::false_type{});
@@ -3169,7 +2967,7 @@ int aura_knn_search_ivf2(const aura_ivf2_lists* lists, const float* queries, flo
         {
             const dim3 tg((unsigned)((nqb + 3) / 4)), tb(256);
 #define AURA_THR2(PER) hipLaunchKernelGGL((ivf2_threshold_kernel<PER>), tg, tb, 0, s, w.gmax, w.qslot, w.blk_list, list_len, \
-                                          nprobe, k, nqb, w.thr, w.cnt, stg == 1 ? k2 : 0, stg == 1 ? bounds : nullptr, bsh)
+                                          nprobe, k, nqb, w.thr, w.cnt, stg == 1 ? k2 : 0, stg == 1 ? bounds : nullptr, IVF2_BSH)
             if (stiles == 8) AURA_THR2(2);
             else if (stiles == 16) AURA_THR2(4);
             else if (stiles == 32) AURA_THR2(8);
@@ -3183,8 +2981,8 @@ int aura_knn_search_ivf2(const aura_ivf2_lists* lists, const float* queries, flo
         if (stg == 1) return AURA_OK;
         } else if (stg != 3) {
             // the caller's bound (e.g. combined over the shards of a row-sharded bank) tightens the thresholds
-            hipLaunchKernelGGL(ivf2_raise_thr_kernel, dim3((unsigned)((((int64_t)ivf2_maxblk(w.qp, bsh) << bsh) + 255) / 256)), dim3(256), 0, s,
-                               w.slotq, w.nblk, bounds, w.thr, bsh);
+            hipLaunchKernelGGL(ivf2_raise_thr_kernel, dim3((unsigned)ivf2_maxblk(w.qp)), dim3(256), 0, s,
+                               w.slotq, w.nblk, bounds, w.thr, IVF2_BSH);
             if ((rc = aura_check_launch())) return rc;
             stage("raise thresholds");
         }

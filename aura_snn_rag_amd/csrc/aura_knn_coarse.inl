@@ -133,10 +133,6 @@ __device__ __forceinline__ void glds4(const float* g, char* lds_wave_base) {
 // the 384 registers of query fragments are pinned by hand: the first CS_QA fragments live in
 // AGPRs (the hardware reads srcB from either file), the rest in VGPRs.  Hazards the compiler
 // would cover for its own MFMAs are covered by the s_nop statements around the groups.
-#ifndef AURA_CS_PF16
-#define AURA_CS_PF16 4
-#endif
-constexpr int CS_PF16 = AURA_CS_PF16;       // bf16-row kernels: fragment reads run this many k-steps ahead
 constexpr int CS_QA8 = 30;  // 8-wave kernels (48 fragments, 8 accumulators per wave)
 #ifndef AURA_CS_WFLUSH_DIV
 #define AURA_CS_WFLUSH_DIV 2
@@ -225,21 +221,12 @@ __device__ __forceinline__ void lds_write3(uint32_t addr, uint32_t a0, uint32_t 
 // and rows 4-11 of the next, and all 16 lanes must land in different 16-byte bank quads.
 //   bf16 image, 4 chunks per row : swz = (4 - row/4) & 3          = 0,3,2,1 for rows 0-3,4-7,8-11,12-15
 //   fp32 image, 8 chunks per row : swz = (m & 1) | (m & 4 ? 6 : 0), m = row/2   = 0,1,0,1,6,7,6,7
-// (AURA_CS_EXP_OLDSWZ: the first version's row/4 and row/2, conflict-free only for consecutive lanes.)
 __device__ __forceinline__ uint32_t cs_swz16(uint32_t row) {
-#ifdef AURA_CS_EXP_OLDSWZ
-    return (row >> 2) & 3;
-#else
     return (4u - (row >> 2)) & 3u;
-#endif
 }
 __device__ __forceinline__ uint32_t cs_swz32(uint32_t row) {
-#ifdef AURA_CS_EXP_OLDSWZ
-    return (row >> 1) & 7;
-#else
     const uint32_t m = row >> 1;
     return (m & 1u) | ((m & 4u) ? 6u : 0u);
-#endif
 }
 
 // mfma_bf16_q / mfma_f16_q: one body, two mnemonics (aura_mfma_q.inl).  The fragments are passed as 128-bit register
@@ -364,11 +351,9 @@ __global__ __launch_bounds__(256) void coarse_threshold_kernel(const float* __re
 // MASKED = centroid-candidate mode: the 256 queries' probe masks (8 KB) sit in LDS behind the candidate
 // buffer (only the bf16-row variant has the room) and gate every (query, row) pair in the epilogue.
 // IVF = inverted-list mode (see CoarseArgs): same scan, the work items are (block, tile) pairs.
-// NW = waves per workgroup: 4 (one per SIMD, 64 queries and 512 registers each) or, bf16 rows only,
-// 8 (two per SIMD, 32 queries and 256 registers each: the second wave fills the first one's stalls).
-// QBT = 16-query column blocks per wave.  NW = 4 with QBT = 2 (round 3, inverted lists only): a workgroup of four
-// waves holds 128 query slots in 256 registers per wave and half the LDS -- TWO independent workgroups per CU, so
-// that one's MFMA phase overlaps the other's wait / issue / epilogue without a barrier between them.
+// NW = waves per workgroup: 4 for fp32 rows (one per SIMD, 64 queries and 512 registers each), 8 for bf16 rows
+// (two per SIMD, 32 queries and 256 registers each: the second wave fills the first one's stalls).
+// QBT = 16-query column blocks per wave = 16 / NW: a block is always 256 query slots.
 // Per-wave phase timers of the filter launch (AURA_CS_DBG bit 64) exist only in builds with -DAURA_CS_TIMERS=1
 // (tools/build_variant.sh): s_memrealtime is a scalar-memory instruction, and with it in the tile loop hipcc puts
 // "s_waitcnt lgkmcnt(0)" wherever its destination registers are reused -- which also waits for the loop's
@@ -379,22 +364,20 @@ __global__ __launch_bounds__(256) void coarse_threshold_kernel(const float* __re
 #endif
 constexpr bool CS_TIMERS = AURA_CS_TIMERS != 0;
 
-template <int NW, int QBT> constexpr int cs_min_waves() { return (NW == 4 && QBT == 2) ? 2 : 1; }
-template <int NW, int QBT> constexpr int cs_cand_buf() { return (NW == 4 && QBT == 2) ? 512 : CS_BUF; }
 // F16 (inverted lists only): the sorted image and the query fragments are IEEE half, the MFMA is the f16 one -- same
 // bytes, same LDS image, same tile loop; only the mnemonic changes (mfma_f16_q).
 template <int KS, int MODE, bool SRC16, bool MASKED, bool IVF = false, int NW = 4, int QBT = 16 / NW, bool F16 = false>
-__global__ __launch_bounds__(64 * NW, (cs_min_waves<NW, QBT>())) void coarse_scan_kernel(const CoarseArgs a) {
+__global__ __launch_bounds__(64 * NW, 1) void coarse_scan_kernel(const CoarseArgs a) {
     static_assert(!F16 || IVF, "only the list-sorted image of the inverted lists is kept in half");
     static_assert(!MASKED || SRC16, "the probe masks need the LDS the bf16 rows leave free");
     static_assert(!IVF || (SRC16 && !MASKED), "inverted lists run over the sorted bf16 shadow");
-    static_assert(NW == 4 || (NW == 8 && SRC16), "8 waves: bf16 rows only");
+    static_assert(NW == (SRC16 ? 8 : 4), "8 waves for bf16 rows, 4 for fp32 rows");
     static_assert(KS % NW == 0, "pieces are dealt over the waves");
     constexpr int THREADS = 64 * NW;
     constexpr int QB = QBT;                                // 16-query MFMA column blocks per wave
-    constexpr int BLKQ = NW * 16 * QB;                     // query slots per block (256; 128 in the two-workgroup form)
-    static_assert(BLKQ == 256 || (IVF && BLKQ == 128), "a query block is 256 slots (128: inverted lists, NW = 4, QBT = 2)");
-    constexpr int CBUF = cs_cand_buf<NW, QBT>();           // candidate entries buffered per workgroup
+    constexpr int BLKQ = NW * 16 * QB;                     // query slots per block
+    static_assert(BLKQ == 256, "a query block is 256 slots");
+    constexpr int CBUF = CS_BUF;                           // candidate entries buffered per workgroup
     constexpr int QA = QB == 4 ? CS_QA : CS_QA8;           // fragments pinned in AGPRs
     constexpr int STEP_BYTES = SRC16 ? 1024 : 2048;        // one k-step (32 k) of 16 rows
     constexpr int TILE_BYTES = KS * STEP_BYTES;
@@ -497,7 +480,7 @@ __global__ __launch_bounds__(64 * NW, (cs_min_waves<NW, QBT>())) void coarse_sca
     // the halves' fill counts in scalar registers -- no LDS atomics, no shared counters, no cross-wave
     // ordering.  Tile t appends to half t&1; the other half is stable during tile t and is written out
     // (by its own wave) once it holds WFLUSH entries; entries beyond WCAP go straight to the lists.
-    constexpr int WCAP = CBUF / (2 * NW);                  // 64 (8 waves; 4 waves x 32 queries) or 128 (4 waves x 64 queries)
+    constexpr int WCAP = CBUF / (2 * NW);                  // 64 (8 waves) or 128 (4 waves)
     constexpr int EPL = WCAP / 64;                         // entries per lane and half in a write-out
     constexpr int WFLUSH = WCAP / CS_WFLUSH_DIV;
     const uint32_t cs_base = lds_addr(csmem);
@@ -777,10 +760,8 @@ __global__ __launch_bounds__(64 * NW, (cs_min_waves<NW, QBT>())) void coarse_sca
             for (int b = 0; b < NBc; ++b)
 #pragma unroll
                 for (int e = 0; e < 4; ++e) acc[b][e] = SRC16 ? __uint_as_float(eqr[b]) : 0.0f;
-            // fragment reads run two k-steps ahead of the MFMAs (one wave per SIMD: nothing else
-            // hides the LDS latency)
-            // k-steps the reads run ahead (8 waves: registers are short, the other wave hides the latency)
-            constexpr int PF = (SRC16 && NW == 4 && QB == 4) ? CS_PF16 : 2;
+            // fragment reads run two k-steps ahead of the MFMAs
+            constexpr int PF = 2;
             f32x4v xr[PF + 1][2];
             constexpr int RP = SRC16 ? 1 : 2;                // LDS reads per k-step
             constexpr int S_RC = KS >= 3 ? KS - 3 : 0;       // the row constants are fetched behind this step
@@ -856,7 +837,8 @@ __global__ __launch_bounds__(64 * NW, (cs_min_waves<NW, QBT>())) void coarse_sca
             for (int b = 0; b < NBc; ++b) gm[b] = -INFINITY;
             unsigned allow = 0xffffu;                        // bit 4 b + e: pair passes the probe mask
             if (MASKED) {
-                // 16 mask words (4 rows x 4 query blocks) by inline-asm LDS reads, one wait
+                // 8 mask words (4 rows x 2 query blocks: bf16 rows, 8 waves) by inline-asm LDS reads, one wait
+                static_assert(!MASKED || QB == 2, "the wait below names 8 mask words");
                 uint32_t mw[4 * QB];
                 int cidv[4];
 #pragma unroll
@@ -869,15 +851,9 @@ __global__ __launch_bounds__(64 * NW, (cs_min_waves<NW, QBT>())) void coarse_sca
                                      : "v"(mask_addr + (uint32_t)((qg * (16 * QB) + 16 * b + lr) * 32 + ((cidv[e] < 0 ? 0 : cidv[e]) >> 5) * 4))
                                      : "memory");
                 }
-                if constexpr (QB == 4)
-                    asm volatile("s_waitcnt lgkmcnt(0)"
-                                 : "+v"(mw[0]), "+v"(mw[1]), "+v"(mw[2]), "+v"(mw[3]), "+v"(mw[4]), "+v"(mw[5]),
-                                   "+v"(mw[6]), "+v"(mw[7]), "+v"(mw[8]), "+v"(mw[9]), "+v"(mw[10]), "+v"(mw[11]),
-                                   "+v"(mw[12]), "+v"(mw[13]), "+v"(mw[14]), "+v"(mw[15])::"memory");
-                else
-                    asm volatile("s_waitcnt lgkmcnt(0)"
-                                 : "+v"(mw[0]), "+v"(mw[1]), "+v"(mw[2]), "+v"(mw[3]), "+v"(mw[4]), "+v"(mw[5]),
-                                   "+v"(mw[6]), "+v"(mw[7])::"memory");
+                asm volatile("s_waitcnt lgkmcnt(0)"
+                             : "+v"(mw[0]), "+v"(mw[1]), "+v"(mw[2]), "+v"(mw[3]), "+v"(mw[4]), "+v"(mw[5]),
+                               "+v"(mw[6]), "+v"(mw[7])::"memory");
                 allow = 0u;
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
@@ -1075,11 +1051,12 @@ struct RefineArgs {
 // to the kernel below, launched right after with a small grid that walks that list (usually empty).
 // ------------------------------------------------------------------------------------------
 constexpr int RW_SURV = 128;             // survivors per query
-constexpr int RW_KC = 192;               // k-chunk of the private stage; RW_ROWS survivors per round: 16 (one workgroup
-                                         // = 8 queries per CU: a pass of at most 8 queries per CU, where a query's
-                                         // ~60 survivors should take few rounds) or 6 (two workgroups per CU)
+constexpr int RW_KC = 192;               // k-chunk of the private stage
+constexpr int RW_ROWS = 6;               // survivors per round: two workgroups (16 queries) per CU, so at most 128 registers
+constexpr int RW_CAND = 8;               // candidates per lane (512 per query at most)
+// (16 survivors per round and up to 1024 candidates at one workgroup per CU -- for passes of at most 8 queries per CU --
+//  was measured and removed: there the workgroup-per-query kernel is the faster one, see launch_refine_for.)
 
-template <int RW_ROWS, int RW_CAND>      // RW_CAND: candidates per lane (64 RW_CAND per query at most)
 __device__ __forceinline__ void refine_wave_body(const RefineArgs& a, int nq) {
     extern __shared__ __attribute__((aligned(16))) char rwmem[];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -1244,13 +1221,9 @@ __device__ __forceinline__ void refine_wave_body(const RefineArgs& a, int nq) {
     }
 }
 
-// 16 survivors per round, up to 1024 candidates: one workgroup (8 queries) per CU, up to 256 registers per lane;
-// 6 per round, up to 512 candidates: two workgroups per CU, so at most 128 registers
-__global__ __launch_bounds__(RF_THREADS) void coarse_refine_wave16_kernel(const RefineArgs a, int nq) {
-    refine_wave_body<16, 16>(a, nq);
-}
+// (the body stays a device function: written into the kernel itself it compiles to other code)
 __global__ __launch_bounds__(RF_THREADS, 4) void coarse_refine_wave6_kernel(const RefineArgs a, int nq) {
-    refine_wave_body<6, 8>(a, nq);
+    refine_wave_body(a, nq);
 }
 
 // ---- the candidates' own bounds, for a row-sharded bank (round 3): per query T_k and T_k2, the k-th and the
@@ -1259,11 +1232,10 @@ __global__ __launch_bounds__(RF_THREADS, 4) void coarse_refine_wave6_kernel(cons
 //      -- into a lower bound of the GLOBAL k-th best score, far tighter than the sampled one of stage 1 (it comes
 //      from the filtered candidates, i.e. from exact bounds of the best rows), and the refine launches re-score
 //      only candidates whose U reaches it (RefineArgs::t2_ext): ~k / S + gap survivors per shard instead of k + gap.
-//      One wave per query, candidates in registers as in refine_wave_body; a list too long for that (more than
+//      One wave per query, candidates in registers as in coarse_refine_wave6_kernel; a list too long for that (more than
 //      512 candidates) reports -inf, the neutral element of both reductions.  out [nq][2]. ----
 __global__ __launch_bounds__(RF_THREADS) void coarse_refine_bounds_kernel(const RefineArgs a, int nq, int k2,
                                                                           float* __restrict__ out) {
-    constexpr int RW_CAND = 8;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int q = blockIdx.x * (RF_THREADS / 64) + wave;
     if (q >= nq) return;
@@ -1636,28 +1608,17 @@ inline int launch_coarse(const CoarseArgs& a, int mode, int grid, hipStream_t s)
 
 inline int dispatch_coarse(const CoarseArgs& a, int mode, int grid, hipStream_t s) {
     const int64_t ks = (a.D + 31) / 32;
-    // bf16-row kernels run 8 waves per workgroup (two per SIMD) unless AURA_CS_WAVES4 is set (A/B runs)
-    static const bool w4 = getenv("AURA_CS_WAVES4") != nullptr;
+    // bf16-row kernels run 8 waves per workgroup (two per SIMD), fp32-row kernels 4
     if (a.bank16 && a.probe_mask) {
-        if (!w4) {
-            if (ks <= 8) return launch_coarse<8, true, true, 8>(a, mode, grid, s);
-            if (ks <= 16) return launch_coarse<16, true, true, 8>(a, mode, grid, s);
-            return launch_coarse<24, true, true, 8>(a, mode, grid, s);
-        }
-        if (ks <= 8) return launch_coarse<8, true, true>(a, mode, grid, s);
-        if (ks <= 16) return launch_coarse<16, true, true>(a, mode, grid, s);
-        return launch_coarse<24, true, true>(a, mode, grid, s);
+        if (ks <= 8) return launch_coarse<8, true, true, 8>(a, mode, grid, s);
+        if (ks <= 16) return launch_coarse<16, true, true, 8>(a, mode, grid, s);
+        return launch_coarse<24, true, true, 8>(a, mode, grid, s);
     }
     if (a.probe_mask) return AURA_E_INVAL;                   // masked mode needs the bf16 rows
     if (a.bank16) {
-        if (!w4) {
-            if (ks <= 8) return launch_coarse<8, true, false, 8>(a, mode, grid, s);
-            if (ks <= 16) return launch_coarse<16, true, false, 8>(a, mode, grid, s);
-            return launch_coarse<24, true, false, 8>(a, mode, grid, s);
-        }
-        if (ks <= 8) return launch_coarse<8, true, false>(a, mode, grid, s);
-        if (ks <= 16) return launch_coarse<16, true, false>(a, mode, grid, s);
-        return launch_coarse<24, true, false>(a, mode, grid, s);
+        if (ks <= 8) return launch_coarse<8, true, false, 8>(a, mode, grid, s);
+        if (ks <= 16) return launch_coarse<16, true, false, 8>(a, mode, grid, s);
+        return launch_coarse<24, true, false, 8>(a, mode, grid, s);
     }
     if (ks <= 8) return launch_coarse<8, false, false>(a, mode, grid, s);
     if (ks <= 16) return launch_coarse<16, false, false>(a, mode, grid, s);

@@ -36,10 +36,8 @@ constexpr int IVF2_STILES_MAX = 256;       // ... and at most
 //     bank on its own pays for the looser threshold in the refine, 1.53 -> 2.05 ms at 125 000 rows x 16 384 queries,
 //     and keeps the floor of 32.)
 static inline int ivf2_stiles(int64_t n_sorted, int k, bool exchanged = false) {
-    static const int forced = getenv("AURA_IVF_STILES") ? atoi(getenv("AURA_IVF_STILES")) : 0;   // tuning runs: 8 .. 256
     int st = exchanged ? IVF2_STILES : 32;
     while (st < IVF2_STILES_MAX && 8 * st < k) st *= 2;
-    if (forced == 8 || forced == 16 || forced == 32 || forced == 64 || forced == 128 || forced == 256) return forced > st ? forced : st;
     const int64_t avg_tiles = n_sorted / 16 / 256;
     while (st < IVF2_STILES_MAX && (int64_t)st * 12 < avg_tiles) st *= 2;
     return st;
@@ -48,9 +46,10 @@ constexpr int IVF2_MAXQ = 8192;            // queries per pass: every probed lis
                                            // queries that probe it, so large batches (bulk recall, the all-gathered
                                            // query blocks of a sharded bank) want long passes; workspace grows with
                                            // min(nq, IVF2_MAXQ) (2048 queries: as in r01)
-// A block holds 1 << bsh query slots: 256, or 128 in the two-workgroups-per-CU form of the scan (AURA_IVF_WG4).
-// Blocks of a pass of qp queries at most: sum over the lists of ceil(count / B) <= 256 + 8 qp / B.
-static inline int ivf2_maxblk(int64_t qp, int bsh = 8) { return 256 + (int)((qp * 8 + (1 << bsh) - 1) >> bsh); }
+// A block holds 1 << IVF2_BSH = 256 query slots (the plan, slot and threshold kernels take the shift as an argument).
+// Blocks of a pass of qp queries at most: sum over the lists of ceil(count / 256) <= 256 + 8 qp / 256.
+constexpr int IVF2_BSH = 8;
+static inline int ivf2_maxblk(int64_t qp) { return 256 + (int)((qp * 8 + 255) >> IVF2_BSH); }
 constexpr int IVF2_MAXBLK = 256 + IVF2_MAXQ * 8 / 128;
 static_assert(IVF2_MAXBLK <= IVF2_MAXBLK_C, "coarse_scan_kernel's block search covers IVF2_MAXBLK_C prefixes");
 
@@ -75,7 +74,7 @@ __global__ __launch_bounds__(256) void ivf2_plan_kernel(const int32_t* __restric
                                                         int32_t* nblk,
                                                         int stiles,          // sample tiles per list (ivf2_stiles)
                                                         int w_sparse, int w_dense,     // cost of a tile of a block of <= 128 / more queries
-                                                        int bsh) {           // log2 of the query slots per block (8 or 7)
+                                                        int bsh) {           // log2 of the query slots per block (IVF2_BSH)
     __shared__ int s_nb[257];
     const int tid = threadIdx.x;
     const int my_cnt = ivf2_list_queries(lq_cnt, tid);
@@ -395,8 +394,9 @@ static Ivf2Workspace carve_ivf2(void* base, int64_t Npad, int64_t nq, int k) {
     };
     int64_t qp = nq < IVF2_MAXQ ? (nq > 0 ? nq : 1) : IVF2_MAXQ;
     w.qp = (int)qp;
-    const int64_t mb = ivf2_maxblk(qp, 8);                 // mb * 256 query slots (the most either block size needs)
-    const int64_t mbb = ivf2_maxblk(qp, 7);                // blocks (the most either block size needs)
+    const int64_t mb = ivf2_maxblk(qp);                    // mb * 256 query slots
+    const int64_t mbb = 256 + (qp * 8 + 127) / 128;        // entries of the block tables: IVF2_MAXBLK's formula for qp
+                                                           // queries (>= mb; part of the workspace layout)
     w.cap = RF_CAP;                                         // refine holds at most this many per query
     w.inv_q = reinterpret_cast<float*>(take(qp * 4));
     w.probe = reinterpret_cast<uint32_t*>(take(qp * 32));
@@ -431,10 +431,11 @@ static Ivf2Workspace carve_ivf2(void* base, int64_t Npad, int64_t nq, int k) {
     return w;
 }
 
-template <int KS, int NW, int QBT = 16 / NW, bool F16 = false>
+// inverted lists: bf16 / half rows, eight waves of two column blocks each
+template <int KS, bool F16>
 inline int launch_coarse_ivf(const CoarseArgs& a, int mode, int grid, hipStream_t s) {
-    constexpr int BLKQ = NW * 16 * QBT;
-    const size_t lds = (size_t)cs_lds_slots<true, false, NW>() * (KS * 1024 + CS_AUX_BYTES) + (size_t)cs_cand_buf<NW, QBT>() * 12 +
+    constexpr int NW = 8, QBT = 2, BLKQ = 1 << IVF2_BSH;
+    const size_t lds = (size_t)cs_lds_slots<true, false, NW>() * (KS * 1024 + CS_AUX_BYTES) + (size_t)CS_BUF * 12 +
                        BLKQ * 4 + BLKQ * 4;
     if (aura_ensure_lds_attr(reinterpret_cast<const void*>(coarse_scan_kernel<KS, CS_MODE_SAMPLE, true, false, true, NW, QBT, F16>), (int)lds) ||
         aura_ensure_lds_attr(reinterpret_cast<const void*>(coarse_scan_kernel<KS, CS_MODE_FILTER, true, false, true, NW, QBT, F16>), (int)lds))

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Builds aura_snn_rag_amd/lib/variants/libaura_<name>.so with extra -D flags for ONE translation unit:
-#   tools/build_variant.sh pf6 aura_knn.hip -DAURA_CS_PF16=6
+#   tools/build_variant.sh wflush4 aura_knn.hip -DAURA_CS_WFLUSH_DIV=4
 #   tools/build_variant.sh u8 aura_neuron.hip -DAURA_RTC_UNROLL=8
 #   tools/build_variant.sh timers aura_knn.hip -DAURA_CS_TIMERS=1
 # Run a benchmark against it with AURA_HIP_LIB=<path of the .so>.
