@@ -37,7 +37,7 @@ SIGNATURES = {
     "aura_izh_run_btd": (I, [P, P, P, P, F, F, F, F, F, I64, I64, I64, P]),
     "aura_adex_run_nt": (I, [P, P, P, P, P, I64, I64, P]),
     "aura_adex_run_btd": (I, [P, P, P, P, P, I64, I64, I64, P]),
-    "aura_lif_run": (I, [P, P, P, P, P, I64, I64, I64, P]),
+    "aura_lif_run": (I, [P, P, P, P, P, I64, I64, I64, I, P]),
     "aura_gif_run": (I, [P, P, P, P, F, I, F, F, I64, I64, I64, I, I, P]),
     "aura_bank_row_norms": (I, [P, P, I64, I64, I64, P]),
     "aura_bank_write": (I, [P, P, P, P, P, P, I, P, P, P, I, F, I64, I64, P]),
@@ -84,21 +84,14 @@ SIGNATURES = {
     "aura_kmeans_commit": (I, [P, P, P, P, I64, I, P]),
     "aura_addition_linear": (I, [P, P, P, P, I64, I64, I64, P]),
     "aura_addition_linear_backward": (I, [P, P, P, P, P, I64, I64, I64, P]),
-    "aura_gif_train_forward": (I, [P, P, P, P, P, P, F, I, F, F, I64, I64, I64, P]),
-    "aura_gif_backward": (I, [P, P, P, P, P, P, F, I, F, F, I64, I64, I64, P]),
-    "aura_gif_train_forward_bf16": (I, [P, P, P, P, P, P, F, I, F, F, I64, I64, I64, P]),
-    "aura_gif_backward_bf16": (I, [P, P, P, P, P, P, F, I, F, F, I64, I64, I64, P]),
-    "aura_lif_train_forward": (I, [P, P, P, P, P, P, P, I64, I64, P]),
-    "aura_lif_backward": (I, [P, P, P, P, P, P, P, P, P, I64, I64, P]),
-    "aura_gif_prosody_run": (I, [P, P, P, P, P, F, I, F, F, F, I64, I64, I64, P]),
-    "aura_gif_prosody_train_forward": (I, [P, P, P, P, P, P, P, F, I, F, F, F, I64, I64, I64, P]),
-    "aura_gif_prosody_backward": (I, [P, P, P, P, P, P, P, P, P, F, I, F, F, F, I64, I64, I64, P]),
-    "aura_lif_run_bf16": (I, [P, P, P, P, P, I64, I64, I64, P]),
-    "aura_lif_train_forward_bf16": (I, [P, P, P, P, P, P, P, I64, I64, P]),
-    "aura_lif_backward_bf16": (I, [P, P, P, P, P, P, P, P, P, I64, I64, P]),
-    "aura_gif_prosody_run_bf16": (I, [P, P, P, P, P, F, I, F, F, F, I64, I64, I64, P]),
-    "aura_gif_prosody_train_forward_bf16": (I, [P, P, P, P, P, P, P, F, I, F, F, F, I64, I64, I64, P]),
-    "aura_gif_prosody_backward_bf16": (I, [P, P, P, P, P, P, P, P, P, F, I, F, F, F, I64, I64, I64, P]),
+    # the training neuron ops: the tensors' dtype (DTYPE_F32 / DTYPE_BF16) is the argument before the stream
+    "aura_gif_train_forward": (I, [P, P, P, P, P, P, F, I, F, F, I64, I64, I64, I, P]),
+    "aura_gif_backward": (I, [P, P, P, P, P, P, F, I, F, F, I64, I64, I64, I, P]),
+    "aura_lif_train_forward": (I, [P, P, P, P, P, P, P, I64, I64, I, P]),
+    "aura_lif_backward": (I, [P, P, P, P, P, P, P, P, P, I64, I64, I, P]),
+    "aura_gif_prosody_run": (I, [P, P, P, P, P, F, I, F, F, F, I64, I64, I64, I, P]),
+    "aura_gif_prosody_train_forward": (I, [P, P, P, P, P, P, P, F, I, F, F, F, I64, I64, I64, I, P]),
+    "aura_gif_prosody_backward": (I, [P, P, P, P, P, P, P, P, P, F, I, F, F, F, I64, I64, I64, I, P]),
     "aura_bank_shadow_update": (I, [P, P, P, P, P, I64, I64, I64, P]),
     "aura_knn_search_shadow": (I, [P, P, P, P, P, P, F, I64, I64, I64, I, I32, P, P, P, I64, I, P, P, I, P]),
     "aura_knn_ivf2_workspace_bytes": (I64, [I64, I64, I]),

@@ -11,8 +11,8 @@ registers.  The dense ``nn.Linear`` stays a library GEMM on the matrix cores.  f
 bf16 each op rounds to bf16 exactly as the reference's bf16 tensors do.
 
 Training: when autograd is recording (grad mode on and the input, a parameter or the state
-requires grad) the loop runs as ``aura_gif_train_forward[_bf16]`` and its gradient as
-``aura_gif_backward[_bf16]`` -- BPTT through the T steps with the triangular surrogate of
+requires grad) the loop runs as ``aura_gif_train_forward`` and its gradient as
+``aura_gif_backward`` -- BPTT through the T steps with the triangular surrogate of
 ``MultiBitSurrogate`` -- wrapped in ``GifLoopFunction``; the ``nn.Linear`` around it is ordinary
 autograd.  In bf16 the recording forward is the per-op-rounded inference loop bit for bit and the backward is the
 fp32 chain evaluated on the forward's bf16-rounded intermediates (``csrc/aura_train.hip``).
@@ -66,7 +66,7 @@ def wants_grad(module: nn.Module, x: torch.Tensor, state=None) -> bool:
 
 
 def _need_fp32_training(x: torch.Tensor, who: str) -> None:
-    """The GIF loop trains in fp32 and bf16 (``aura_gif_train_forward[_bf16]``); anything else is refused."""
+    """The GIF loop trains in fp32 and bf16 (``aura_gif_train_forward``); anything else is refused."""
     if x.dtype not in (torch.float32, torch.bfloat16):
         raise NotImplementedError(f"{who}: the surrogate-gradient kernels are fp32 / bf16; run {x.dtype} "
                                   f"under torch.no_grad() or train in fp32")

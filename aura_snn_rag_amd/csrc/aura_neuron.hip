@@ -123,80 +123,7 @@ __device__ __forceinline__ void step_vec(const Model& m, typename Model::Lane (&
     }
 }
 
-// ------------------------------------------------------------------------------------------
-// 16-byte vector I/O
-// ------------------------------------------------------------------------------------------
-template <typename T, int VEC>
-struct Io;
-
-template <>
-struct Io<float, 4> {
-    __device__ __forceinline__ static void load(const float* p, float (&x)[4]) {
-        float4 t = *reinterpret_cast<const float4*>(p);
-        x[0] = t.x; x[1] = t.y; x[2] = t.z; x[3] = t.w;
-    }
-    __device__ __forceinline__ static void store(float* p, const float (&x)[4]) {
-        *reinterpret_cast<float4*>(p) = make_float4(x[0], x[1], x[2], x[3]);
-    }
-    // streaming (touched once) tensors: non-temporal, so they do not evict each other from L2
-    typedef float v4f __attribute__((ext_vector_type(4)));
-    __device__ __forceinline__ static void load_nt(const float* p, float (&x)[4]) {
-        const v4f t = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(p));
-        x[0] = t[0]; x[1] = t[1]; x[2] = t[2]; x[3] = t[3];
-    }
-    __device__ __forceinline__ static void store_nt(float* p, const float (&x)[4]) {
-        const v4f t = {x[0], x[1], x[2], x[3]};
-        __builtin_nontemporal_store(t, reinterpret_cast<v4f*>(p));
-    }
-};
-template <>
-struct Io<float, 1> {
-    __device__ __forceinline__ static void load(const float* p, float (&x)[1]) { x[0] = *p; }
-    __device__ __forceinline__ static void store(float* p, const float (&x)[1]) { *p = x[0]; }
-    __device__ __forceinline__ static void load_nt(const float* p, float (&x)[1]) { x[0] = __builtin_nontemporal_load(p); }
-    __device__ __forceinline__ static void store_nt(float* p, const float (&x)[1]) { __builtin_nontemporal_store(x[0], p); }
-};
-
-__device__ __forceinline__ float bf16_bits_to_float(uint32_t b) { return __uint_as_float(b << 16); }
-__device__ __forceinline__ uint32_t float_to_bf16_bits(float x) {
-    return __float_as_uint(round_bf16(x)) >> 16;
-}
-
-template <>
-struct Io<uint16_t, 8> {
-    __device__ __forceinline__ static void load(const uint16_t* p, float (&x)[8]) {
-        uint4 t = *reinterpret_cast<const uint4*>(p);
-        uint32_t w[4] = {t.x, t.y, t.z, t.w};
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            x[2 * i] = __uint_as_float(w[i] << 16);
-            x[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
-        }
-    }
-    __device__ __forceinline__ static void store(uint16_t* p, const float (&x)[8]) {
-        uint32_t w[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-            w[i] = float_to_bf16_bits(x[2 * i]) | (float_to_bf16_bits(x[2 * i + 1]) << 16);
-        *reinterpret_cast<uint4*>(p) = make_uint4(w[0], w[1], w[2], w[3]);
-    }
-    // bf16 streams keep the default cache policy: non-temporal measured slower here (the bf16 GIF
-    // loop is VALU-bound: 0.67 vs 0.54 ms at 8192 x 16 x 3072), while it took the fp32 GIF loop from
-    // 5.5 to 6.4 TB/s
-    __device__ __forceinline__ static void load_nt(const uint16_t* p, float (&x)[8]) { load(p, x); }
-    __device__ __forceinline__ static void store_nt(uint16_t* p, const float (&x)[8]) { store(p, x); }
-};
-template <>
-struct Io<uint16_t, 1> {
-    __device__ __forceinline__ static void load_nt(const uint16_t* p, float (&x)[1]) { load(p, x); }
-    __device__ __forceinline__ static void store_nt(uint16_t* p, const float (&x)[1]) { store(p, x); }
-    __device__ __forceinline__ static void load(const uint16_t* p, float (&x)[1]) {
-        x[0] = bf16_bits_to_float(*p);
-    }
-    __device__ __forceinline__ static void store(uint16_t* p, const float (&x)[1]) {
-        *p = static_cast<uint16_t>(float_to_bf16_bits(x[0]));
-    }
-};
+#include "aura_io.inl"                   // Io<T, VEC>, aligned16, rtc_grid (shared with aura_train.hip)
 
 // ------------------------------------------------------------------------------------------
 // Channel-contiguous kernel: x[R][T][C] (or [R][C] if TIME_INV) -> out[R][T][C] (or the T-mean
@@ -483,16 +410,6 @@ __global__ __launch_bounds__(64) void seq_ntw_kernel(Model m, const float* __res
 // ------------------------------------------------------------------------------------------
 // Host-side launch helpers
 // ------------------------------------------------------------------------------------------
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
-inline int rtc_grid(int64_t items) {
-    // memory-bound streaming: cap at 256 CUs x 8 blocks and grid-stride the rest
-    int64_t blocks = (items + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    if (blocks < 1) blocks = 1;
-    return (int)blocks;
-}
-
 template <class Model>
 int launch_nt(const Model& m, const float* I, float* S, float* st0, float* st1, int64_t N,
               int64_t T, hipStream_t s) {
@@ -566,6 +483,12 @@ int launch_gif(const GifModel<BF16, POW2L>& m, const void* h, void* out, void* v
 
 }  // namespace
 
+// The bf16 LIF loop is the per-op-rounded forward kernel of aura_train.hip (its sizes and pointers are checked there);
+// internal to the library.
+__attribute__((visibility("hidden"))) int aura_lif_seq_bf16(const uint16_t* x, uint16_t* spikes, uint16_t* mem,
+                                                            const uint16_t* beta, const uint16_t* threshold, int64_t B,
+                                                            int64_t T, int64_t size, hipStream_t stream);
+
 // ------------------------------------------------------------------------------------------
 // C ABI
 // ------------------------------------------------------------------------------------------
@@ -610,13 +533,19 @@ int aura_adex_run_btd(const float* I, float* spikes, float* V, float* w, const f
                           static_cast<hipStream_t>(stream));
 }
 
-int aura_lif_run(const float* x, float* spikes, float* mem, const float* beta,
-                 const float* threshold, int64_t B, int64_t T, int64_t size, void* stream) {
+int aura_lif_run(const void* x, void* spikes, void* mem, const void* beta, const void* threshold,
+                 int64_t B, int64_t T, int64_t size, int dtype, void* stream) {
     if (B < 0 || T < 0 || size < 0) return AURA_E_INVAL;
+    if (dtype == AURA_DTYPE_BF16)
+        return aura_lif_seq_bf16(static_cast<const uint16_t*>(x), static_cast<uint16_t*>(spikes),
+                                 static_cast<uint16_t*>(mem), static_cast<const uint16_t*>(beta),
+                                 static_cast<const uint16_t*>(threshold), B, T, size,
+                                 static_cast<hipStream_t>(stream));
+    if (dtype != AURA_DTYPE_F32) return AURA_E_INVAL;
     if (B && size && (!mem || !beta || !threshold || (T && (!x || !spikes)))) return AURA_E_INVAL;
-    LifModel m{beta, threshold};
-    return launch_rtc_f32(m, x, spikes, mem, static_cast<float*>(nullptr), B, T, size,
-                          static_cast<hipStream_t>(stream));
+    LifModel m{static_cast<const float*>(beta), static_cast<const float*>(threshold)};
+    return launch_rtc_f32(m, static_cast<const float*>(x), static_cast<float*>(spikes), static_cast<float*>(mem),
+                          static_cast<float*>(nullptr), B, T, size, static_cast<hipStream_t>(stream));
 }
 
 int aura_gif_run(const void* h, void* out, void* v, void* theta, float decay, int L, float alpha,

@@ -49,6 +49,16 @@ def _need_image(t: torch.Tensor, name: str) -> int:
     return _lib.IMAGE_F16 if t.dtype == torch.float16 else _lib.IMAGE_BF16
 
 
+def _fp32_or_bf16(t: torch.Tensor, who: Optional[str]):
+    """``(dtype, the C ABI's dtype code)`` of an fp32 or bf16 tensor.  Any other dtype is a ``TypeError`` in the name of
+    ``who``; with ``who`` None it passes as fp32, for the per-tensor checks that follow to refuse by the tensor's name."""
+    if t.dtype == torch.bfloat16:
+        return torch.bfloat16, _lib.DTYPE_BF16
+    if t.dtype != torch.float32 and who is not None:
+        raise TypeError(f"{who} supports fp32 and bf16, got {t.dtype}")
+    return torch.float32, _lib.DTYPE_F32
+
+
 def half_image_rho_bound(rho: torch.Tensor, D: int) -> torch.Tensor:
     """A rigorous (loose) residual bound of the HALF image from the bf16 residual norms ``rho``, for one-shot callers that
     hold a half image without its ``rho16``: every element that stays normal is rounded to a grid that contains the
@@ -122,26 +132,22 @@ def adex_run_btd(I, spikes, V, w, params: Sequence[float]) -> None:
 def lif_run(x, spikes, mem, beta, threshold) -> None:
     """x, spikes: [B, T, size]; mem: [B, size] in/out; beta, threshold: [size].  fp32, or all five bf16 (a
     module moved to bf16: every op rounds to bf16)."""
-    dt = x.dtype
-    if dt not in (torch.float32, torch.bfloat16):
-        raise TypeError(f"lif_run supports fp32 and bf16, got {dt}")
+    dt, code = _fp32_or_bf16(x, "lif_run")
     for t, n in ((x, "x"), (spikes, "spikes"), (mem, "mem"), (beta, "beta"), (threshold, "threshold")):
         _need(t, n, dt)
     B, T, size = x.shape
     if spikes.shape != x.shape or mem.shape != (B, size) or beta.numel() != size or \
             threshold.numel() != size:
         raise ValueError("lif_run: shape mismatch")
-    fn = lib().aura_lif_run if dt == torch.float32 else lib().aura_lif_run_bf16
-    check(fn(_p(x), _p(spikes), _p(mem), _p(beta), _p(threshold), B, T, size, _stream()), "aura_lif_run")
+    check(lib().aura_lif_run(_p(x), _p(spikes), _p(mem), _p(beta), _p(threshold), B, T, size, code, _stream()),
+          "aura_lif_run")
 
 
 def gif_run(h, out, v, theta, decay: float, L: int, alpha: float, threshold: float, T: int,
             time_invariant: bool = False, mean_out: bool = False) -> None:
     """h: [rows, T, H] (or [rows, H] if time_invariant); out: [rows, T, H] (or [rows, H] if
     mean_out); v, theta: [rows, H] in/out.  fp32 or bf16 (all four the same dtype)."""
-    dt = h.dtype
-    if dt not in (torch.float32, torch.bfloat16):
-        raise TypeError(f"gif_run supports fp32 and bf16, got {dt}")
+    dt, code = _fp32_or_bf16(h, "gif_run")
     for t, n in ((h, "h"), (out, "out"), (v, "v"), (theta, "theta")):
         _need(t, n, dt)
     rows, H = v.shape
@@ -153,8 +159,7 @@ def gif_run(h, out, v, theta, decay: float, L: int, alpha: float, threshold: flo
         raise ValueError(f"gif_run: out has shape {tuple(out.shape)}")
     flags = (_lib.GIF_TIME_INVARIANT if time_invariant else 0) | (_lib.GIF_MEAN_OUT if mean_out else 0)
     check(lib().aura_gif_run(_p(h), _p(out), _p(v), _p(theta), decay, int(L), alpha, threshold,
-                             rows, T, H, _lib.DTYPE_F32 if dt == torch.float32 else _lib.DTYPE_BF16,
-                             flags, _stream()), "aura_gif_run")
+                             rows, T, H, code, flags, _stream()), "aura_gif_run")
 
 
 # ---------------------------------------------------------------------------------------
@@ -1449,13 +1454,6 @@ def sample_next(logits, *, seen=None, finished=None, stream_ids=None, penalty: f
 # surrogate-gradient training path + prosody-modulated GIF (fp32 and bf16)
 # ---------------------------------------------------------------------------------------
 
-def _same_f32(shape, *named) -> None:
-    for t, n in named:
-        _need(t, n, torch.float32)
-        if tuple(t.shape) != tuple(shape):
-            raise ValueError(f"{n}: expected shape {tuple(shape)}, got {tuple(t.shape)}")
-
-
 def _same_dtype(dtype, shape, *named) -> None:
     for t, n in named:
         _need(t, n, dtype)
@@ -1467,17 +1465,11 @@ def gif_train_forward(h, spikes, v, theta, save_a, save_theta, decay: float, L: 
                       threshold: float) -> None:
     """h [rows, T, H] -> spikes, save_a, save_theta [rows, T, H]; v, theta [rows, H] in/out (fp32 or bf16)."""
     rows, T, H = h.shape
-    if h.dtype == torch.bfloat16:
-        _same_dtype(torch.bfloat16, (rows, T, H), (h, "h"), (spikes, "spikes"), (save_a, "save_a"), (save_theta, "save_theta"))
-        _same_dtype(torch.bfloat16, (rows, H), (v, "v"), (theta, "theta"))
-        check(lib().aura_gif_train_forward_bf16(_p(h), _p(spikes), _p(v), _p(theta), _p(save_a), _p(save_theta),
-                                                decay, int(L), alpha, threshold, rows, T, H, _stream()),
-              "aura_gif_train_forward_bf16")
-        return
-    _same_f32((rows, T, H), (h, "h"), (spikes, "spikes"), (save_a, "save_a"), (save_theta, "save_theta"))
-    _same_f32((rows, H), (v, "v"), (theta, "theta"))
+    dt, code = _fp32_or_bf16(h, None)
+    _same_dtype(dt, (rows, T, H), (h, "h"), (spikes, "spikes"), (save_a, "save_a"), (save_theta, "save_theta"))
+    _same_dtype(dt, (rows, H), (v, "v"), (theta, "theta"))
     check(lib().aura_gif_train_forward(_p(h), _p(spikes), _p(v), _p(theta), _p(save_a), _p(save_theta),
-                                       decay, int(L), alpha, threshold, rows, T, H, _stream()),
+                                       decay, int(L), alpha, threshold, rows, T, H, code, _stream()),
           "aura_gif_train_forward")
 
 
@@ -1485,54 +1477,35 @@ def gif_backward(save_a, save_theta, g_spikes, g_h, g_v, g_theta, decay: float, 
                  threshold: float) -> None:
     """g_v, g_theta [rows, H]: gradients of the final state in, of the initial state out (fp32 or bf16)."""
     rows, T, H = save_a.shape
-    if save_a.dtype == torch.bfloat16:
-        _same_dtype(torch.bfloat16, (rows, T, H), (save_a, "save_a"), (save_theta, "save_theta"),
-                    (g_spikes, "g_spikes"), (g_h, "g_h"))
-        _same_dtype(torch.bfloat16, (rows, H), (g_v, "g_v"), (g_theta, "g_theta"))
-        check(lib().aura_gif_backward_bf16(_p(save_a), _p(save_theta), _p(g_spikes), _p(g_h), _p(g_v), _p(g_theta),
-                                           decay, int(L), alpha, threshold, rows, T, H, _stream()),
-              "aura_gif_backward_bf16")
-        return
-    _same_f32((rows, T, H), (save_a, "save_a"), (save_theta, "save_theta"), (g_spikes, "g_spikes"),
-              (g_h, "g_h"))
-    _same_f32((rows, H), (g_v, "g_v"), (g_theta, "g_theta"))
+    dt, code = _fp32_or_bf16(save_a, None)
+    _same_dtype(dt, (rows, T, H), (save_a, "save_a"), (save_theta, "save_theta"), (g_spikes, "g_spikes"),
+                (g_h, "g_h"))
+    _same_dtype(dt, (rows, H), (g_v, "g_v"), (g_theta, "g_theta"))
     check(lib().aura_gif_backward(_p(save_a), _p(save_theta), _p(g_spikes), _p(g_h), _p(g_v), _p(g_theta),
-                                  decay, int(L), alpha, threshold, rows, T, H, _stream()),
+                                  decay, int(L), alpha, threshold, rows, T, H, code, _stream()),
           "aura_gif_backward")
 
 
 def lif_train_forward(x, mem_in, beta, threshold, spikes, mem_out, pre) -> None:
     """One recording LIF step, [B, size]; fp32 or all bf16."""
     B, size = x.shape
-    dt = x.dtype
-    if dt not in (torch.float32, torch.bfloat16):
-        raise TypeError(f"lif_train_forward supports fp32 and bf16, got {dt}")
+    dt, code = _fp32_or_bf16(x, "lif_train_forward")
     _same_dtype(dt, (B, size), (x, "x"), (mem_in, "mem_in"), (spikes, "spikes"), (mem_out, "mem_out"), (pre, "pre"))
     _same_dtype(dt, (size,), (beta, "beta"), (threshold, "threshold"))
-    fn = lib().aura_lif_train_forward if dt == torch.float32 else lib().aura_lif_train_forward_bf16
-    check(fn(_p(x), _p(mem_in), _p(beta), _p(threshold), _p(spikes), _p(mem_out), _p(pre), B, size, _stream()),
-          "aura_lif_train_forward")
+    check(lib().aura_lif_train_forward(_p(x), _p(mem_in), _p(beta), _p(threshold), _p(spikes), _p(mem_out), _p(pre),
+                                       B, size, code, _stream()), "aura_lif_train_forward")
 
 
 def lif_backward(pre, g_spikes, g_mem, beta, threshold, slope, g_x, g_mem_prev, raw_slope) -> None:
     """raw_slope [B, size] is fp32 in both forms (sum it over the batch for d/d slope)."""
     B, size = pre.shape
-    dt = pre.dtype
-    if dt not in (torch.float32, torch.bfloat16):
-        raise TypeError(f"lif_backward supports fp32 and bf16, got {dt}")
+    dt, code = _fp32_or_bf16(pre, "lif_backward")
     _same_dtype(dt, (B, size), (pre, "pre"), (g_spikes, "g_spikes"), (g_mem, "g_mem"), (g_x, "g_x"),
                 (g_mem_prev, "g_mem_prev"))
-    _same_f32((B, size), (raw_slope, "raw_slope"))
+    _same_dtype(torch.float32, (B, size), (raw_slope, "raw_slope"))
     _same_dtype(dt, (size,), (beta, "beta"), (threshold, "threshold"), (slope, "slope"))
-    fn = lib().aura_lif_backward if dt == torch.float32 else lib().aura_lif_backward_bf16
-    check(fn(_p(pre), _p(g_spikes), _p(g_mem), _p(beta), _p(threshold), _p(slope), _p(g_x), _p(g_mem_prev),
-             _p(raw_slope), B, size, _stream()), "aura_lif_backward")
-
-
-def _prosody_dtype(h, who: str):
-    if h.dtype not in (torch.float32, torch.bfloat16):
-        raise TypeError(f"{who} supports fp32 and bf16, got {h.dtype}")
-    return h.dtype
+    check(lib().aura_lif_backward(_p(pre), _p(g_spikes), _p(g_mem), _p(beta), _p(threshold), _p(slope), _p(g_x),
+                                  _p(g_mem_prev), _p(raw_slope), B, size, code, _stream()), "aura_lif_backward")
 
 
 def gif_prosody_run(h, gains, spikes, v, theta, decay: float, L: int, alpha: float, threshold: float,
@@ -1540,43 +1513,42 @@ def gif_prosody_run(h, gains, spikes, v, theta, decay: float, L: int, alpha: flo
     """h, spikes [rows, T, H]; gains [rows, T] or None; v, theta [rows, H] in/out.  fp32, or everything
     (gains included) bf16."""
     rows, T, H = h.shape
-    dt = _prosody_dtype(h, "gif_prosody_run")
+    dt, code = _fp32_or_bf16(h, "gif_prosody_run")
     _same_dtype(dt, (rows, T, H), (h, "h"), (spikes, "spikes"))
     _same_dtype(dt, (rows, H), (v, "v"), (theta, "theta"))
     if gains is not None:
         _same_dtype(dt, (rows, T), (gains, "gains"))
-    fn = lib().aura_gif_prosody_run if dt == torch.float32 else lib().aura_gif_prosody_run_bf16
-    check(fn(_p(h), _p(gains), _p(spikes), _p(v), _p(theta), decay, int(L), alpha, threshold, strength, rows, T, H,
-             _stream()), "aura_gif_prosody_run")
+    check(lib().aura_gif_prosody_run(_p(h), _p(gains), _p(spikes), _p(v), _p(theta), decay, int(L), alpha, threshold,
+                                     strength, rows, T, H, code, _stream()), "aura_gif_prosody_run")
 
 
 def gif_prosody_train_forward(h, gains, spikes, v, theta, save_a, save_theta, decay: float, L: int, alpha: float,
                               threshold: float, strength: float) -> None:
     rows, T, H = h.shape
-    dt = _prosody_dtype(h, "gif_prosody_train_forward")
+    dt, code = _fp32_or_bf16(h, "gif_prosody_train_forward")
     _same_dtype(dt, (rows, T, H), (h, "h"), (spikes, "spikes"), (save_a, "save_a"), (save_theta, "save_theta"))
     _same_dtype(dt, (rows, H), (v, "v"), (theta, "theta"))
     if gains is not None:
         _same_dtype(dt, (rows, T), (gains, "gains"))
-    fn = lib().aura_gif_prosody_train_forward if dt == torch.float32 else lib().aura_gif_prosody_train_forward_bf16
-    check(fn(_p(h), _p(gains), _p(spikes), _p(v), _p(theta), _p(save_a), _p(save_theta), decay, int(L), alpha,
-             threshold, strength, rows, T, H, _stream()), "aura_gif_prosody_train_forward")
+    check(lib().aura_gif_prosody_train_forward(_p(h), _p(gains), _p(spikes), _p(v), _p(theta), _p(save_a),
+                                               _p(save_theta), decay, int(L), alpha, threshold, strength, rows, T, H,
+                                               code, _stream()), "aura_gif_prosody_train_forward")
 
 
 def gif_prosody_backward(save_a, save_theta, h, gains, g_spikes, g_h, g_gains, g_v, g_theta, decay: float, L: int,
                          alpha: float, threshold: float, strength: float) -> None:
     """g_gains [rows, T], fp32 in both forms, must be zero on entry (channels are accumulated into it)."""
     rows, T, H = save_a.shape
-    dt = _prosody_dtype(save_a, "gif_prosody_backward")
+    dt, code = _fp32_or_bf16(save_a, "gif_prosody_backward")
     _same_dtype(dt, (rows, T, H), (save_a, "save_a"), (save_theta, "save_theta"), (h, "h"), (g_spikes, "g_spikes"),
                 (g_h, "g_h"))
     _same_dtype(dt, (rows, H), (g_v, "g_v"), (g_theta, "g_theta"))
     if gains is not None:
         _same_dtype(dt, (rows, T), (gains, "gains"))
-        _same_f32((rows, T), (g_gains, "g_gains"))
-    fn = lib().aura_gif_prosody_backward if dt == torch.float32 else lib().aura_gif_prosody_backward_bf16
-    check(fn(_p(save_a), _p(save_theta), _p(h), _p(gains), _p(g_spikes), _p(g_h), _p(g_gains), _p(g_v), _p(g_theta),
-             decay, int(L), alpha, threshold, strength, rows, T, H, _stream()), "aura_gif_prosody_backward")
+        _same_dtype(torch.float32, (rows, T), (g_gains, "g_gains"))
+    check(lib().aura_gif_prosody_backward(_p(save_a), _p(save_theta), _p(h), _p(gains), _p(g_spikes), _p(g_h),
+                                          _p(g_gains), _p(g_v), _p(g_theta), decay, int(L), alpha, threshold, strength,
+                                          rows, T, H, code, _stream()), "aura_gif_prosody_backward")
 
 
 # ---------------------------------------------------------------------------------------

@@ -73,9 +73,11 @@ int aura_adex_run_btd(const float* I, float* spikes, float* V, float* w, const f
 
 /* Vectorised LIF over x[B][T][size] (T = 1 is the single step of VectorizedLIFNeuron.forward,
  * src/base/neuron.py:131-139; T > 1 is the per-t loop of EnhancedSpikingNeuron.forward,
- * src/base/snn_brain_zones.py:73-79).  beta, threshold: [size]; mem: [B][size] in/out. */
-int aura_lif_run(const float* x, float* spikes, float* mem, const float* beta,
-                 const float* threshold, int64_t B, int64_t T, int64_t size, void* stream);
+ * src/base/snn_brain_zones.py:73-79).  beta, threshold: [size]; mem: [B][size] in/out; dtype of all five =
+ * AURA_DTYPE_*.  In bf16 (a module moved to bf16: buffers, parameters, input and state) every op rounds its fp32
+ * result to bf16, as the reference does. */
+int aura_lif_run(const void* x, void* spikes, void* mem, const void* beta, const void* threshold,
+                 int64_t B, int64_t T, int64_t size, int dtype, void* stream);
 
 /* GIF membrane loop (decay, clamp, divide, floor-spike, soft reset, threshold adaptation).
  * h: currents after the neuron's nn.Linear, [rows][T][H] (or [rows][H] with
@@ -757,97 +759,67 @@ int aura_host_word_free(void* host_word);
 int aura_signal_flag(const int32_t* flag_dev, uint32_t* host_word, uint32_t host_seq, void* stream);
 
 /* ---------------------------------------------------------------------------------------
- * Surrogate-gradient training path and the prosody-modulated GIF (fp32, [rows][T][H] layout)
+ * Surrogate-gradient training path and the prosody-modulated GIF ([rows][T][H] layout)
+ *
+ * One entry point per operation; `dtype` = AURA_DTYPE_F32 or AURA_DTYPE_BF16 is the element type of every tensor
+ * argument declared void* (bf16: bit patterns), any other value is AURA_E_INVAL.  g_gains and raw_slope are fp32
+ * in both forms.  The bf16 form is the module moved to bf16 with .bfloat16() / .to(torch.bfloat16): buffers,
+ * parameters, input, state AND gains are bf16 and every forward op rounds its fp32 result to bf16 (Python scalars
+ * enter as fp32), which the forward kernels reproduce bit for bit (spikes and state are aura_gif_run's; save_a /
+ * save_theta / pre are the bf16 values the reference's graph holds).  The backward kernels evaluate the fp32 chains
+ * on the saved values with the forward's roundings re-applied to the recomputed intermediates, carry state
+ * gradients in fp32 over the T steps and round once on the way out (the reference's bf16 autograd rounds every
+ * intermediate gradient instead).  The GIF loops take L <= 256 in bf16 (spike counts up to 256 are exact there).
+ * (A bf16 input to an fp32 module, or fp32 gains with a bf16 input, promote to fp32 in the reference: the host
+ * runs those in fp32.)
  * ------------------------------------------------------------------------------------- */
 
-/* GIF loop for training: as aura_gif_run (fp32, no flags) and additionally saves, per step, the
+/* GIF loop for training: as aura_gif_run (no flags) and additionally saves, per step, the
  * pre-clamp membrane potential (save_a) and the threshold the step started from (save_theta),
  * both [rows][T][H].  Forward of GIFNeuron.forward when autograd is recording,
  * src/core/language_zone/gif_neuron.py:54-69. */
-int aura_gif_train_forward(const float* h, float* spikes, float* v, float* theta, float* save_a,
-                           float* save_theta, float decay, int L, float alpha, float threshold,
-                           int64_t rows, int64_t T, int64_t H, void* stream);
+int aura_gif_train_forward(const void* h, void* spikes, void* v, void* theta, void* save_a, void* save_theta,
+                           float decay, int L, float alpha, float threshold, int64_t rows, int64_t T, int64_t H,
+                           int dtype, void* stream);
 
 /* Backward of that loop (BPTT over T): g_spikes [rows][T][H] in; g_h [rows][T][H] out; g_v,
  * g_theta [rows][H]: in = gradients of the final state, out = gradients of the initial state.
  * Spike gradient = MultiBitSurrogate.backward (triangular window, gif_neuron.py:16-22); the
  * clamp with tensor bounds routes the gradient of clamped values to theta, as autograd does. */
-int aura_gif_backward(const float* save_a, const float* save_theta, const float* g_spikes, float* g_h,
-                      float* g_v, float* g_theta, float decay, int L, float alpha, float threshold,
-                      int64_t rows, int64_t T, int64_t H, void* stream);
-
-/* The same pair for bf16 tensors (bit patterns, uint16_t): forward = aura_gif_run's per-op-rounded bf16
- * loop (bit-identical spikes and state; save_a / save_theta are the bf16 values the reference's graph
- * holds); backward = the fp32 BPTT evaluated from them with the forward's roundings re-applied to
- * b, d, n, s, gradients carried in fp32 over the T steps and rounded to bf16 on the way out (the
- * reference's bf16 autograd rounds every intermediate gradient instead).  L <= 256. */
-int aura_gif_train_forward_bf16(const uint16_t* h, uint16_t* spikes, uint16_t* v, uint16_t* theta,
-                                uint16_t* save_a, uint16_t* save_theta, float decay, int L, float alpha,
-                                float threshold, int64_t rows, int64_t T, int64_t H, void* stream);
-int aura_gif_backward_bf16(const uint16_t* save_a, const uint16_t* save_theta, const uint16_t* g_spikes,
-                           uint16_t* g_h, uint16_t* g_v, uint16_t* g_theta, float decay, int L, float alpha,
-                           float threshold, int64_t rows, int64_t T, int64_t H, void* stream);
+int aura_gif_backward(const void* save_a, const void* save_theta, const void* g_spikes, void* g_h, void* g_v,
+                      void* g_theta, float decay, int L, float alpha, float threshold, int64_t rows, int64_t T,
+                      int64_t H, int dtype, void* stream);
 
 /* LIF step for training: spikes, mem_out as aura_lif_run (T = 1) plus pre = beta*mem + x - thr
  * (the surrogate's input), all [B][size]; mem_in is not modified. */
-int aura_lif_train_forward(const float* x, const float* mem_in, const float* beta,
-                           const float* threshold, float* spikes, float* mem_out, float* pre,
-                           int64_t B, int64_t size, void* stream);
+int aura_lif_train_forward(const void* x, const void* mem_in, const void* beta, const void* threshold, void* spikes,
+                           void* mem_out, void* pre, int64_t B, int64_t size, int dtype, void* stream);
 
 /* Backward of the LIF step with LearnableSurrogateGradient.backward (src/base/neuron.py:80-108):
- * g_x, g_mem_prev [B][size] and raw_slope [B][size] (sum it over the batch to get d/d slope). */
-int aura_lif_backward(const float* pre, const float* g_spikes, const float* g_mem, const float* beta,
-                      const float* threshold, const float* slope, float* g_x, float* g_mem_prev,
-                      float* raw_slope, int64_t B, int64_t size, void* stream);
+ * g_x, g_mem_prev [B][size] and raw_slope [B][size], fp32 in both forms (sum it over the batch to get d/d slope). */
+int aura_lif_backward(const void* pre, const void* g_spikes, const void* g_mem, const void* beta,
+                      const void* threshold, const void* slope, void* g_x, void* g_mem_prev, float* raw_slope,
+                      int64_t B, int64_t size, int dtype, void* stream);
 
 /* ProsodyModulatedGIF.forward loop, src/core/language_zone/prosody_gif.py:69-106: gains [rows][T]
  * (NULL = no modulation) scale the input, the effective threshold (x clamp(1 - strength*(g-1),
  * 0.5, 1.5)) and the adaptation rate; no 1e-6 in the division (unlike GIFNeuron). */
-int aura_gif_prosody_run(const float* h, const float* gains, float* spikes, float* v, float* theta,
-                         float decay, int L, float alpha, float threshold, float strength,
-                         int64_t rows, int64_t T, int64_t H, void* stream);
+int aura_gif_prosody_run(const void* h, const void* gains, void* spikes, void* v, void* theta, float decay, int L,
+                         float alpha, float threshold, float strength, int64_t rows, int64_t T, int64_t H, int dtype,
+                         void* stream);
 
 /* Training forward / backward of that loop: as aura_gif_train_forward / aura_gif_backward with the
- * gains; additionally g_gains [rows][T] receives dL/d gains (ZEROED by the caller; channels are summed
- * with float atomics): through the input gain, the threshold scale (where its clamp is inactive) and the
- * adaptation rate.  h = the currents of the forward pass.  Backward of prosody_gif.py:69-106 with
- * MultiBitSurrogate (gif_neuron.py:16-22). */
-int aura_gif_prosody_train_forward(const float* h, const float* gains, float* spikes, float* v, float* theta,
-                                   float* save_a, float* save_theta, float decay, int L, float alpha,
-                                   float threshold, float strength, int64_t rows, int64_t T, int64_t H,
-                                   void* stream);
-int aura_gif_prosody_backward(const float* save_a, const float* save_theta, const float* h, const float* gains,
-                              const float* g_spikes, float* g_h, float* g_gains, float* g_v, float* g_theta,
-                              float decay, int L, float alpha, float threshold, float strength, int64_t rows,
-                              int64_t T, int64_t H, void* stream);
-
-/* bf16 forms of the LIF step and of the prosody GIF (bit patterns, uint16_t) for modules moved to bf16 with
- * .bfloat16() / .to(torch.bfloat16): buffers, parameters, input, state AND gains are bf16 and every op of
- * src/base/neuron.py:135-139 / src/core/language_zone/prosody_gif.py:64-101 rounds its fp32 result to bf16
- * (Python scalars enter as fp32), which the forward kernels reproduce bit for bit.  The backward kernels
- * evaluate the fp32 chains of aura_lif_backward / aura_gif_prosody_backward on the saved bf16 values with the
- * forward's roundings re-applied, carry state gradients in fp32 and round once on the way out; raw_slope and
- * g_gains stay fp32 (the caller reduces / rounds them).  L <= 256.  (A bf16 input to an fp32 module, or fp32
- * gains with a bf16 input, promote to fp32 in the reference: the host runs those on the fp32 entry points.) */
-int aura_lif_run_bf16(const uint16_t* x, uint16_t* spikes, uint16_t* mem, const uint16_t* beta,
-                      const uint16_t* threshold, int64_t B, int64_t T, int64_t size, void* stream);
-int aura_lif_train_forward_bf16(const uint16_t* x, const uint16_t* mem_in, const uint16_t* beta,
-                                const uint16_t* threshold, uint16_t* spikes, uint16_t* mem_out, uint16_t* pre,
-                                int64_t B, int64_t size, void* stream);
-int aura_lif_backward_bf16(const uint16_t* pre, const uint16_t* g_spikes, const uint16_t* g_mem, const uint16_t* beta,
-                           const uint16_t* threshold, const uint16_t* slope, uint16_t* g_x, uint16_t* g_mem_prev,
-                           float* raw_slope, int64_t B, int64_t size, void* stream);
-int aura_gif_prosody_run_bf16(const uint16_t* h, const uint16_t* gains, uint16_t* spikes, uint16_t* v, uint16_t* theta,
-                              float decay, int L, float alpha, float threshold, float strength, int64_t rows,
-                              int64_t T, int64_t H, void* stream);
-int aura_gif_prosody_train_forward_bf16(const uint16_t* h, const uint16_t* gains, uint16_t* spikes, uint16_t* v,
-                                        uint16_t* theta, uint16_t* save_a, uint16_t* save_theta, float decay, int L,
-                                        float alpha, float threshold, float strength, int64_t rows, int64_t T,
-                                        int64_t H, void* stream);
-int aura_gif_prosody_backward_bf16(const uint16_t* save_a, const uint16_t* save_theta, const uint16_t* h,
-                                   const uint16_t* gains, const uint16_t* g_spikes, uint16_t* g_h, float* g_gains,
-                                   uint16_t* g_v, uint16_t* g_theta, float decay, int L, float alpha, float threshold,
-                                   float strength, int64_t rows, int64_t T, int64_t H, void* stream);
+ * gains; additionally g_gains [rows][T], fp32 in both forms, receives dL/d gains (ZEROED by the caller; channels
+ * are summed with float atomics; the caller rounds it): through the input gain, the threshold scale (where its
+ * clamp is inactive) and the adaptation rate.  h = the currents of the forward pass.  Backward of
+ * prosody_gif.py:69-106 with MultiBitSurrogate (gif_neuron.py:16-22). */
+int aura_gif_prosody_train_forward(const void* h, const void* gains, void* spikes, void* v, void* theta, void* save_a,
+                                   void* save_theta, float decay, int L, float alpha, float threshold, float strength,
+                                   int64_t rows, int64_t T, int64_t H, int dtype, void* stream);
+int aura_gif_prosody_backward(const void* save_a, const void* save_theta, const void* h, const void* gains,
+                              const void* g_spikes, void* g_h, float* g_gains, void* g_v, void* g_theta, float decay,
+                              int L, float alpha, float threshold, float strength, int64_t rows, int64_t T, int64_t H,
+                              int dtype, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * Brain-zone projection

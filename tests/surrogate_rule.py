@@ -24,7 +24,7 @@ GIF step   (``gif_bwd_kernel``; k = roundings already on gv / gth)
            gth'   = ... + (-gn b / (d d)) + gcl 2L    product, square, quotient, sum, then the
                                                       clamp term's sum after it                    k + 10
            gh = ga = gb;  gv' = ga decay                                                           k + 8
-prosody    (``gif_prosody_bwd_kernel``) gathers the three theta terms in gte first and adds ``gte scale``:
+prosody    (``prosody_bwd_kernel``) gathers the three theta terms in gte first and adds ``gte scale``:
            one product and one sum more                                                 gth'       k + 12
            gh = ga g                                                                               k + 8
 autograd   (the oracle) performs the same operations node by node and accumulates the five uses of theta

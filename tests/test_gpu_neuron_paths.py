@@ -247,7 +247,7 @@ def test_second_grid_pass_izhikevich_btd(dev):
 
 
 def test_second_grid_pass_gif_training(dev):
-    """``gif_train_fwd_kernel<1>`` and ``gif_bwd_kernel<1>`` past one grid pass; gradients held to the bound of
+    """``gif_fwd_kernel<F32, 1>`` and ``gif_bwd_kernel<F32, 1>`` past one grid pass; gradients held to the bound of
     ``test_gif_bptt_matches_oracle`` (its ``_close``)."""
     from aura_snn_rag_amd.core.language_zone.gif_neuron import run_gif_loop_grad
     rows, T, H, L, alpha = 4099, 2, 129, 8, 0.01

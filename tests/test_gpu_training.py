@@ -261,7 +261,7 @@ def _rb(x):
 
 
 def _gif_bf16_bptt_fp32_math(h, v0, t0, ws, wv, wt, decay, L, alpha, thr0):
-    """What aura_gif_backward_bf16 is meant to compute, in torch on the CPU: the bf16 forward (per-op rounding),
+    """What aura_gif_backward in bf16 is meant to compute, in torch on the CPU: the bf16 forward (per-op rounding),
     then BPTT in fp32 from the saved bf16 (a_t, theta_{t-1}) with the forward's roundings re-applied."""
     rows, T, H = h.shape
     f = lambda x: x.to(torch.float32)

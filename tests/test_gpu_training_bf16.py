@@ -104,7 +104,7 @@ def test_prosody_gif_mixed_dtypes_promote_like_the_reference(dev):
 
 
 def _prosody_bf16_bptt_fp32_math(h, gains, v0, t0, ws, wv, wt, decay, L, alpha, thr0, strength):
-    """What aura_gif_prosody_backward_bf16 is meant to compute, in torch on the CPU."""
+    """What aura_gif_prosody_backward in bf16 is meant to compute, in torch on the CPU."""
     rows, T, H = h.shape
     mod = gains is not None
     v, th = _f(v0), _f(t0)

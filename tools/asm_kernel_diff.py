@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
 """Per-kernel diff of two trees' device assembly (`hipcc --cuda-device-only -S` of each .hip, one .s per file).
 
-    asm_kernel_diff.py BEFORE_DIR AFTER_DIR [-o table.json]
+    asm_kernel_diff.py BEFORE_DIR AFTER_DIR [-o table.json] [--rename table.json]
 
 For every kernel symbol: identical / changed instruction text (comments, directives and local label numbers aside)
-and the resource figures of both sides.  Exit status 1 if the symbol sets or any resource figure differ.
+and the resource figures of both sides.  Exit status 1 if the symbol sets or any resource figure differ.  --rename: a
+JSON object {symbol before: symbol after} for kernels that changed their name in between.
 """
 import argparse
 import json
@@ -49,13 +50,19 @@ def main():
     ap.add_argument("before")
     ap.add_argument("after")
     ap.add_argument("-o", "--out")
+    ap.add_argument("--rename")
     a = ap.parse_args()
+    rename = json.load(open(a.rename)) if a.rename else {}
+    was = {new: old for old, new in rename.items()}
     table, bad = [], 0
     for f in sorted(x for x in os.listdir(a.before) if x.endswith(".s")):
         kb, ka = kernels(os.path.join(a.before, f)), kernels(os.path.join(a.after, f))
+        kb = {rename.get(sym, sym): k for sym, k in kb.items()}
         for sym in sorted(set(kb) | set(ka)):
             b, c = kb.get(sym), ka.get(sym)
             e = {"file": f[:-2] + ".hip", "kernel": sym}
+            if sym in was:
+                e["kernel_before"] = was[sym]
             if b is None or c is None:
                 e["status"] = "only before" if c is None else "only after"
                 bad += 1
