@@ -35,6 +35,7 @@ _LAZY = {"PlaceCellSemanticEncoder": "core.language_zone.place_cell_encoder",
          "MemoryAugmentedLayer": "core.language_zone.memory_augmented_layer",
          "MemoryContext": "core.language_zone.memory_augmented_layer",
          "MemoryLayerCache": "core.language_zone.memory_augmented_layer",
+         "FoldedMemory": "core.language_zone.memory_augmented_layer",
          "SNNRAGTransformer": "core.language_zone.snn_rag_transformer"}
 
 

@@ -100,6 +100,10 @@ class CachedDecodingMixin:
             raise ValueError(f"{who}: the state holds {state.batch} rows and {len(state.caches)} caches, this call "
                              f"needs {B} rows and {len(self.layers)} caches")
 
+    def _before_fused_steps(self, state: DecodeState) -> None:
+        """What ``generate(fused_step=True)`` runs once between the prefill (or a turn's extend) and the first step: a
+        model whose fused step needs per-generation constants beyond the caches builds them here.  Nothing here."""
+
     @torch.no_grad()
     def step(self, tokens: torch.Tensor, prosody: Optional[torch.Tensor] = None, state: Optional[DecodeState] = None,
              use_memory: bool = True, *, fused: bool = False) -> torch.Tensor:
@@ -346,6 +350,8 @@ class CachedDecodingMixin:
                 turn = torch.cat([state.pending.to(dev)[:, None], input_ids.to(torch.int64)], dim=1)
                 state.pending = None
                 logits = self.extend(turn, state=state, use_memory=use_memory)[:, -1]
+            if fused_step:
+                self._before_fused_steps(state)
             # every row's length with the prompt consumed, before the first retirement: what the returned state counts from
             base = state.lengths.clone() if return_state else None
             n = 0
@@ -408,6 +414,8 @@ class CachedDecodingMixin:
             # every row's logits at its own last fed token: the rows are gathered before the head, [B, D] -> [B, V]
             at = (fed - 1).clamp(min=0)[:, None, None].expand(B, 1, hidden.shape[2])
             logits = self.output_head(hidden.gather(1, at)[:, 0])
+            if fused_step:
+                self._before_fused_steps(state)
             base = state.lengths.clone() if return_state else None
             new = torch.empty(B, max_new_tokens, dtype=torch.int64, device=dev)
             n = 0

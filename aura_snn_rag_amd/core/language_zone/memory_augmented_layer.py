@@ -20,6 +20,9 @@ the whole sequence computes.  Re-retrieval during a generation is not part of th
     ``extend`` several at once (``ops.attn_decode_extend``).  ``step(fused=True)`` replaces the strings of small torch
     launches by ``ops.row_linear``, for the ``gate`` injection ``ops.row_linear_gate`` and for the spiking FFN
     ``ops.row_linear_gif`` (``csrc/aura_rowlin.hip``); it raises where it does not apply and never falls back.
+  * ``fold_memory(cache)`` -> ``FoldedMemory`` or ``None``: the pinned memories of a ``cross_attention`` layer folded
+    through both projections of ``memory_attention``, once per generation; the fused step's injection is then one
+    launch (``ops.memory_attend``, ``csrc/aura_memattend.hip``).
 """
 from __future__ import annotations
 
@@ -45,19 +48,30 @@ class MemoryContext(NamedTuple):
     rows: Optional[torch.Tensor] = None
 
 
+class FoldedMemory(NamedTuple):
+    """The pinned memories of a ``cross_attention`` layer folded through ``memory_attention``'s projections (the rule:
+    ``include/aura_hip.h``, "Memory attend"): ``G`` [B, H, k, D] and ``s0`` [B, H, k], the keys met with the query
+    projection and the softmax scale, and ``U`` [B, H, k, D], the values carried through ``out_proj``'s weight."""
+    G: torch.Tensor
+    s0: torch.Tensor
+    U: torch.Tensor
+
+
 class MemoryLayerCache:
     """What one ``MemoryAugmentedLayer`` carries through a generation: the ``attention`` cache, the pinned ``memory``
     (a ``MemoryContext`` or ``None``: nothing is injected) and the per-row constants the pinned memories make of the
     injection: ``c`` [B, D], the score-weighted context (``gate``: projected by ``memory_proj``), and for ``gate``
     ``u = W_g[:, D:] c + b_g`` [B, D], the half of the gate's pre-activation that does not depend on the token.
+    ``fold`` (``cross_attention``): the ``FoldedMemory`` tables, built by ``fold_memory`` on demand, ``None`` until then.
     ``lengths``, ``capacity``, ``max_length`` and ``retire`` are the attention cache's."""
-    __slots__ = ("attention", "memory", "c", "u")
+    __slots__ = ("attention", "memory", "c", "u", "fold")
 
     def __init__(self, attention: AttentionCache):
         self.attention = attention
         self.memory = None
         self.c = None
         self.u = None
+        self.fold = None
 
     @property
     def lengths(self):
@@ -184,7 +198,7 @@ class MemoryAugmentedLayer(BatchedMemoryMixin, nn.Module):
     @torch.no_grad()
     def _pin(self, cache: MemoryLayerCache, memory: Optional[MemoryContext]) -> None:
         """Holds ``memory`` in the cache with the constants it makes of the injection (see ``MemoryLayerCache``)."""
-        cache.memory, cache.c, cache.u = memory, None, None
+        cache.memory, cache.c, cache.u, cache.fold = memory, None, None, None
         if memory is None or self.memory_injection == "cross_attention":
             return
         weights = F.softmax(memory.scores, dim=-1).unsqueeze(-1)
@@ -195,6 +209,54 @@ class MemoryAugmentedLayer(BatchedMemoryMixin, nn.Module):
             context = self.memory_proj(context)
             cache.u = F.linear(context, gate.weight[:, D:], gate.bias).contiguous()
         cache.c = context.contiguous()
+
+    def _check_foldable(self, who: str) -> None:
+        """What the fold assumes of ``memory_attention``: one packed ``in_proj_weight`` and nothing appended to the keys
+        and values."""
+        att = self.memory_attention
+        if not att._qkv_same_embed_dim:
+            raise ValueError(f"{who}: memory_attention must hold one packed in_proj_weight (kdim = vdim = embed_dim)")
+        if att.bias_k is not None or att.bias_v is not None or att.add_zero_attn:
+            raise ValueError(f"{who}: memory_attention with bias_k, bias_v or add_zero_attn attends rows that are not "
+                             f"memories; the fold does not cover them")
+
+    @torch.no_grad()
+    def fold_memory(self, cache: MemoryLayerCache) -> Optional[FoldedMemory]:
+        """Folds the pinned memories of a ``cross_attention`` layer through ``memory_attention``'s projections into the
+        tables ``ops.memory_attend`` reads (``FoldedMemory``; the rule: ``include/aura_hip.h``, "Memory attend") and
+        holds them in ``cache.fold``: what ``step(fused=True)`` needs.  Once per generation: computed in fp64 from the
+        fp32 parameters and rounded once, so every table element carries a single rounding; torch ops only, on the
+        device the memories are on.  A second call returns the tables it holds.  ``None``, and nothing done, for the
+        other injections and when nothing is pinned.  The zero rows of empty slots are folded like any memory."""
+        who = "MemoryAugmentedLayer.fold_memory"
+        self._check_cache(who, cache)
+        if self.memory_injection != "cross_attention" or cache.memory is None:
+            return None
+        if cache.fold is not None:
+            return cache.fold
+        self._check_foldable(who)
+        att = self.memory_attention
+        features = cache.memory.features
+        B, M, D = features.shape
+        H = att.num_heads
+        dh = D // H
+        if D % 4 != 0 or not 4 <= D <= ops.MEMORY_ATTEND_MAX_D or not 1 <= M <= ops.MEMORY_ATTEND_MAX_M \
+                or H * M > ops.MEMORY_ATTEND_MAX_HM:
+            raise ValueError(f"{who}: D={D}, H={H} and k={M} are outside ops.memory_attend's limits (D % 4 == 0, D <= "
+                             f"{ops.MEMORY_ATTEND_MAX_D}, k <= {ops.MEMORY_ATTEND_MAX_M}, H k <= "
+                             f"{ops.MEMORY_ATTEND_MAX_HM}); use fused=False")
+        W = att.in_proj_weight.double()
+        b = torch.zeros(3 * D, dtype=torch.float64, device=W.device) if att.in_proj_bias is None \
+            else att.in_proj_bias.double()
+        mem = features.double()
+        keys = (mem @ W[D:2 * D].T + b[D:2 * D]).view(B, M, H, dh)
+        values = (mem @ W[2 * D:].T + b[2 * D:]).view(B, M, H, dh)
+        root = float(dh) ** 0.5
+        G = torch.einsum("bmhj,hjd->bhmd", keys, W[:D].view(H, dh, D)) / root
+        s0 = torch.einsum("bmhj,hj->bhm", keys, b[:D].view(H, dh)) / root
+        U = torch.einsum("bmhj,dhj->bhmd", values, att.out_proj.weight.double().view(D, H, dh))
+        cache.fold = FoldedMemory(G.float().contiguous(), s0.float().contiguous(), U.float().contiguous())
+        return cache.fold
 
     def prefill(self, hidden_states: torch.Tensor, prosody: Optional[torch.Tensor] = None, use_memory: bool = True,
                 cache: Optional[MemoryLayerCache] = None, memory: Optional[MemoryContext] = None,
@@ -226,9 +288,10 @@ class MemoryAugmentedLayer(BatchedMemoryMixin, nn.Module):
         (``use_memory=False`` injects nothing).  ``advance=False`` leaves the cache's lengths alone.
 
         ``fused=False`` is the layer's formula from torch ops around ``attention.step``.  ``fused=True`` (B <= 32, eval
-        mode or no dropout, the exact GELU, ``gate`` or ``concat`` injection) makes an MLP layer seven launches: four of
-        the attention's fused step, ``ops.row_linear_gate`` for the injection (``concat``: one torch add), LayerNorm +
-        ``ffn.0`` + GELU, ``ffn.2`` + residual.  A HybridFFN layer is eleven: the MLP branch without its residual, then
+        mode or no dropout, the exact GELU) makes an MLP layer seven launches: four of the attention's fused step, one
+        for the injection (``gate``: ``ops.row_linear_gate``; ``cross_attention``: ``ops.memory_attend`` over the tables
+        ``fold_memory(cache)`` made, which must have been called: the step never folds; ``concat``: one torch add),
+        LayerNorm + ``ffn.0`` + GELU, ``ffn.2`` + residual.  A HybridFFN layer is eleven: the MLP branch without its residual, then
         the four of the spiking branch (``_snn_branch``: ``ops.row_linear`` and ``ops.row_linear_gif``, the ``B * T``
         rows of ``syn2`` and ``neuron2.linear`` in groups of whole tokens of at most 32 rows), the last of which mixes
         the branches and adds the residual.  It raises where it does not apply; it never falls back."""
@@ -264,10 +327,11 @@ class MemoryAugmentedLayer(BatchedMemoryMixin, nn.Module):
 
     def _fused_step(self, hidden_states, prosody, use_memory, cache, advance, memory) -> torch.Tensor:
         who = "MemoryAugmentedLayer.step(fused=True)"
-        if self.memory_injection == "cross_attention":
-            raise ValueError(f"{who}: the cross_attention injection has no fused step; use fused=False")
+        cross = self.memory_injection == "cross_attention"
         mlp = self._mlp()
         drops = [self.dropout.p, mlp[3].p] + ([self.ffn.snn.dropout.p] if self.use_snn_ffn else [])
+        if cross:
+            drops.append(self.memory_attention.dropout)
         if self.training and any(p > 0 for p in drops):
             raise RuntimeError(f"{who}: the fused step has no dropout; call eval() first (dropout={max(drops)})")
         if not isinstance(mlp[1], nn.GELU) or getattr(mlp[1], "approximate", "none") != "none":
@@ -277,10 +341,21 @@ class MemoryAugmentedLayer(BatchedMemoryMixin, nn.Module):
                              f"fused=False")
         if self.ffn_norm.weight is None or self.ffn_norm.bias is None:
             raise ValueError(f"{who}: the fused prologue needs a LayerNorm with weight and bias")
+        if cross and memory is not None:
+            if self.memory_norm.weight is None or self.memory_norm.bias is None:
+                raise ValueError(f"{who}: the fused cross_attention injection needs a memory_norm with weight and bias")
+            self._check_foldable(who)
+            if cache.fold is None:
+                raise ValueError(f"{who}: the cross_attention injection steps fused from the folded tables of the "
+                                 f"pinned memories: call fold_memory(cache) once after prefill, or use fused=False")
         hidden = self.attention.step(hidden_states, prosody=prosody, use_memory=use_memory, cache=cache.attention,
                                      advance=advance, fused=True, residual=hidden_states, norm=self.attention_norm)
         if memory is not None:
-            if self.memory_injection == "gate":
+            if cross:
+                fold, mn = cache.fold, self.memory_norm
+                hidden = ops.memory_attend(hidden, (mn.weight, mn.bias), fold.G, fold.s0, fold.U,
+                                           self.memory_attention.out_proj.bias, eps=mn.eps)
+            elif self.memory_injection == "gate":
                 D = self.config.embedding_dim
                 hidden = ops.row_linear_gate(hidden, self.memory_gate[0].weight[:, :D], None, cache.u, cache.c, hidden)
             else:

@@ -130,3 +130,13 @@ class SNNRAGTransformer(CachedDecodingMixin, nn.Module):
     def pinned_memory(state: DecodeState) -> List[Optional[MemoryContext]]:
         """The contexts the layers hold in ``state`` after ``prefill``: what ``forward(.., memory=)`` takes."""
         return [cache.memory for cache in state.caches]
+
+    def fold_memory(self, state: DecodeState) -> list:
+        """Folds every layer's pinned memories into the tables its fused ``cross_attention`` step reads
+        (``MemoryAugmentedLayer.fold_memory``): one ``FoldedMemory`` or ``None`` per layer.  Idempotent; nothing to do
+        for ``gate`` and ``concat``."""
+        self._check_state("SNNRAGTransformer.fold_memory", state, state.batch)
+        return [layer.fold_memory(cache) for layer, cache in zip(self.layers, state.caches)]
+
+    def _before_fused_steps(self, state: DecodeState) -> None:
+        self.fold_memory(state)

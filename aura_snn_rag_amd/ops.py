@@ -1305,6 +1305,100 @@ def row_linear_gif(x, weight, bias=None, *, T: int, decay: float, L: int, alpha:
 
 
 # ---------------------------------------------------------------------------------------
+# memory attend (the rule: include/aura_hip.h, "Memory attend")
+# ---------------------------------------------------------------------------------------
+
+MEMORY_ATTEND_MAX_ROWS = 32
+MEMORY_ATTEND_MAX_D = 2048
+MEMORY_ATTEND_MAX_M = 32
+MEMORY_ATTEND_MAX_HM = 1024
+
+
+def _ma_f32(name: str, t, shape, what: str) -> None:
+    """One tensor of ``memory_attend``: fp32, contiguous and of the given shape."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"memory_attend: {name} must be a torch.Tensor, got {type(t)}")
+    if t.dtype != torch.float32:
+        raise TypeError(f"memory_attend: {name} is {t.dtype}; the kernel runs in fp32 only (bf16 and fp16 tables are "
+                        f"not supported)")
+    if tuple(t.shape) != shape:
+        raise ValueError(f"memory_attend: {name} is {what} = {shape}, got {tuple(t.shape)}")
+    if not t.is_contiguous():
+        raise ValueError(f"memory_attend: {name} must be contiguous")
+
+
+def _memory_attend_args(x, norm, G, s0, U, bias, eps, out):
+    """Type, shape and limit checks of ``memory_attend``: ``(R, D, H, M, gamma, beta)``.  Touches no device."""
+    who = "memory_attend"
+    for name, t in (("x", x), ("G", G), ("s0", s0), ("U", U)):
+        if t is None:
+            raise ValueError(f"{who}: {name} is required")
+    if not isinstance(x, torch.Tensor):
+        raise TypeError(f"{who}: x must be a torch.Tensor, got {type(x)}")
+    if x.dim() != 2:
+        raise ValueError(f"{who}: x is [R, D], got {tuple(x.shape)}")
+    R, D = x.shape
+    _ma_f32("x", x, (R, D), "[R, D]")
+    if not 1 <= R <= MEMORY_ATTEND_MAX_ROWS:
+        raise ValueError(f"{who}: R={R} rows must be in [1, {MEMORY_ATTEND_MAX_ROWS}]")
+    if D % 4 != 0 or not 4 <= D <= MEMORY_ATTEND_MAX_D:
+        raise ValueError(f"{who}: D={D} must be a multiple of 4 in [4, {MEMORY_ATTEND_MAX_D}] (the row lives in "
+                         f"registers)")
+    if not isinstance(norm, (tuple, list)) or len(norm) != 2 or norm[0] is None or norm[1] is None:
+        raise ValueError(f"{who}: norm is (gamma, beta), the LayerNorm's weight and bias")
+    gamma, beta = norm
+    _ma_f32("gamma", gamma, (D,), "[D]")
+    _ma_f32("beta", beta, (D,), "[D]")
+    if isinstance(eps, bool) or not isinstance(eps, (int, float)) or not eps >= 0.0:
+        raise ValueError(f"{who}: eps={eps!r} must be a number that is not negative")
+    if not isinstance(G, torch.Tensor):
+        raise TypeError(f"{who}: G must be a torch.Tensor, got {type(G)}")
+    if G.dim() != 4 or G.shape[0] != R or G.shape[3] != D:
+        raise ValueError(f"{who}: G is [R, H, M, D] = ({R}, H, M, {D}), got {tuple(G.shape)}")
+    H, M = G.shape[1], G.shape[2]
+    if not 1 <= M <= MEMORY_ATTEND_MAX_M:
+        raise ValueError(f"{who}: M={M} memories must be in [1, {MEMORY_ATTEND_MAX_M}]")
+    if not 1 <= H * M <= MEMORY_ATTEND_MAX_HM:
+        raise ValueError(f"{who}: H M = {H} x {M} must be in [1, {MEMORY_ATTEND_MAX_HM}]")
+    _ma_f32("G", G, (R, H, M, D), "[R, H, M, D]")
+    _ma_f32("s0", s0, (R, H, M), "[R, H, M]")
+    _ma_f32("U", U, (R, H, M, D), "[R, H, M, D]")
+    if bias is not None:
+        _ma_f32("bias", bias, (D,), "[D]")
+    if out is not None:
+        _ma_f32("out", out, (R, D), "[R, D]")
+    return R, D, H, M, gamma, beta
+
+
+def memory_attend(x, norm, G, s0, U, bias=None, *, eps: float = 1e-5, out=None):
+    """The cross-attention injection of a decoding step over folded memories in one launch (the rule:
+    ``include/aura_hip.h``, "Memory attend"): ``y = x + bias + sum_h sum_m p[h, m] U[:, h, m]`` with ``p[h] =
+    softmax_m(G[:, h, m] . LayerNorm(x) + s0[:, h, m])``.  ``x`` [R, D] with R <= 32, ``norm=(gamma, beta)`` the
+    LayerNorm's weight and bias, ``G`` and ``U`` [R, H, M, D], ``s0`` [R, H, M] (``MemoryAugmentedLayer.fold_memory``
+    builds the three), ``bias`` [D] or ``None``.  Returns ``y`` [R, D] (``out`` receives it; it may alias no input).  fp32
+    only.  A row's bits are the same alone or in any batch.  No host sync."""
+    R, D, H, M, gamma, beta = _memory_attend_args(x, norm, G, s0, U, bias, eps, out)
+    dev = None
+    for name, t in (("x", x), ("gamma", gamma), ("beta", beta), ("G", G), ("s0", s0), ("U", U), ("bias", bias),
+                    ("out", out)):
+        if t is None:
+            continue
+        if not t.is_cuda:
+            raise AuraDeviceError(f"memory_attend: {name} is on {t.device}: aura_snn_rag_amd runs the hot path only as "
+                                  f"HIP kernels on an AMD GPU (no CPU/PyTorch fallback).")
+        if dev is not None and t.device != dev:
+            raise ValueError("memory_attend: tensors are on different devices")
+        if name != "s0" and t.data_ptr() % 16:
+            raise ValueError(f"memory_attend: {name} is not 16-byte aligned (a view into the middle of a buffer?)")
+        dev = t.device
+    y = out if out is not None else torch.empty((R, D), dtype=torch.float32, device=dev)
+    check(lib().aura_memory_attend(x.data_ptr(), R, D, gamma.data_ptr(), beta.data_ptr(), float(eps), G.data_ptr(),
+                                   s0.data_ptr(), U.data_ptr(), H, M, _p(bias), _p(y), _stream()),
+          "aura_memory_attend")
+    return y
+
+
+# ---------------------------------------------------------------------------------------
 # next token (the rule: include/aura_hip.h, "Next token")
 # ---------------------------------------------------------------------------------------
 

@@ -1338,6 +1338,49 @@ int aura_row_linear_gif(const float* x, int64_t R, int64_t K, const float* W, co
                         const float* res_or_null, const float* m_or_null, const float* gate_or_null, int nontemporal,
                         void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Memory attend
+ * ------------------------------------------------------------------------------------- */
+
+/* The cross-attention memory injection of a decoding step, h + out_proj(softmax(q K^T / sqrt(dh)) V) with q the query
+ * projection of LayerNorm(h) and K, V the projections of M memories, in one launch, csrc/aura_memattend.hip.  The
+ * memories are pinned for the generation, so both D x D projections are folded, once per generation, into two tables
+ * per row (the caller builds them): G[r][h][m][:] = Wq_h^T k_h[m] / sqrt(dh), s0[r][h][m] = bq_h . k_h[m] / sqrt(dh) and
+ * U[r][h][m][:] = Wo[:, h] v_h[m].  All fp32, fl() = round to nearest even; `/` and sqrtf are correctly rounded, expf
+ * is the device function (1 ulp).
+ *
+ * x [R][D], gamma, beta [D], G [R][H][M][D], s0 [R][H][M], U [R][H][M][D], bo [D] or NULL, y [R][D] (y aliases no
+ * input).  1 <= R <= 32; D % 4 == 0, 4 <= D <= 2048; 1 <= M <= 32; 1 <= H M <= 1024.  Per row r:
+ *   xh      the LayerNorm of "Row linear"'s prologue, bit for bit: the same row sum sum_D, mu, var (two passes), rstd and
+ *           xh[k] = fl(fl(fl(d rstd) gamma[k]) + beta[k]).
+ *   scores  dot(h, m): lane l of one wave chains t = fmaf(xh[k], G[r][h][m][k], t) over the k with (k / 4) mod 64 == l
+ *           in ascending k, from t = 0; the 64 lane values are added by the xor butterfly 32, 16, 8, 4, 2, 1 ("Row
+ *           linear"'s dot with K = D).  s[h][m] = fl(s0[r][h][m] + dot(h, m)).
+ *   softmax per head: mx = max_m s[h][m] (fmaxf), e[m] = expf(fl(s[h][m] - mx)), sum = e[0] + e[1] + .. in ascending m
+ *           from 0, one rounding per add, p[h][m] = fl(e[m] / sum).
+ *   sum     acc[d] = 0, then acc[d] = fl(acc[d] + fl(p[h][m] U[r][h][m][d])) over (h, m) in ascending h, then ascending
+ *           m: every product is rounded on its own.
+ *   y[r][d] = fl(x[r][d] + fl(bo[d] + acc[d]))  (without bo: fl(x[r][d] + acc[d])).
+ * The order of every sum is a function of D, H and M alone: not of R, the other rows or the launch geometry.  So a
+ * row's bits are the same alone or in any batch and over repeated calls, and a NaN or inf row leaves the others alone.
+ * One workgroup per row; no atomics, no flags, no host sync; one launch is one pass.
+ * Against fp64 on the same fp32 inputs (tests/memory_attend_rule.py derives it), e = 2^-24, every rounding behind the dot
+ * entered at a whole ulp (2e), ds the bound of "Row linear" for the score (its bias is s0), p64 the fp64 softmax:
+ *     eta_m = ds_m + 2e (mx64 - s64_m + ds_m + max_k ds_k),     A_m = expm1(eta_m) + 2e exp(eta_m),
+ *     B = sum_k p64_k A_k + 2e (M - 1) (1 + max_k A_k),
+ *     dp_m <= p64_m (A_m (1 - p64_m) + sum_{k != m} p64_k A_k + 2e (M - 1) (1 + max_k A_k)) / (1 - B) + 2e p64_m + tiny,
+ *     |y - y64| <= sum_j |U_j| dp_j + 2e H M sum_j (p64_j + dp_j) |U_j| + 2e |bo + acc64| + 2e |y64|.
+ *
+ * AURA_E_INVAL: R, D, H or M outside the limits above; a null x, gamma, beta, G, s0, U or y; eps < 0 or NaN.
+ * AURA_E_ALIGN: x, gamma, beta, G, U, bo or y not 16-byte aligned, s0 not 4-byte aligned.  One launch on `stream`. */
+#define AURA_MEMORY_ATTEND_MAX_ROWS 32
+#define AURA_MEMORY_ATTEND_MAX_D 2048
+#define AURA_MEMORY_ATTEND_MAX_M 32
+#define AURA_MEMORY_ATTEND_MAX_HM 1024
+int aura_memory_attend(const float* x, int64_t R, int64_t D, const float* gamma, const float* beta, float eps,
+                       const float* G, const float* s0, const float* U, int64_t H, int64_t M,
+                       const float* bo_or_null, float* y, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
