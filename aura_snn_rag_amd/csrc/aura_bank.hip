@@ -456,7 +456,13 @@ int aura_kmeans_segment_means(const float* bank, const int32_t* order, const int
                               void* workspace, int64_t workspace_bytes, int64_t N, int64_t D, int k,
                               int sums_only, void* stream) {
     if (N < 0 || N > 0x7ffffff0LL || D <= 0 || (D & 3) || k <= 0 || k > 256) return AURA_E_INVAL;
-    if (N == 0) return AURA_OK;
+    if (N == 0) {                                           // every cluster is empty: zero sums, means keep their rows
+        if (!sums_only) return AURA_OK;                     // (seg_off is not read: an empty call may pass none)
+        if (!centroids) return AURA_E_INVAL;                // the caller vouches for k rows of D floats, as on the
+                                                            // path below (ops.kmeans_segment_means checks the shape)
+        return hipMemsetAsync(centroids, 0, (size_t)k * (size_t)D * sizeof(float), static_cast<hipStream_t>(stream)) ==
+                       hipSuccess ? AURA_OK : AURA_E_LAUNCH;
+    }
     if (!bank || !order || !seg_off || !centroids || !workspace) return AURA_E_INVAL;
     if ((reinterpret_cast<uintptr_t>(bank) & 15) || (reinterpret_cast<uintptr_t>(centroids) & 15) ||
         (reinterpret_cast<uintptr_t>(workspace) & 15))
@@ -479,7 +485,7 @@ int aura_kmeans_segment_means(const float* bank, const int32_t* order, const int
 int aura_kmeans_commit(const int32_t* assign, const int32_t* seg_off, float* meta, float* counts, int64_t N,
                        int k, void* stream) {
     if (N < 0 || k <= 0 || k > 256) return AURA_E_INVAL;
-    if (!assign || !seg_off || !meta) return AURA_E_INVAL;
+    if ((N > 0 && (!assign || !meta)) || !seg_off) return AURA_E_INVAL;   // (an empty assignment has no address)
     const int64_t blocks = N > 0 ? (N + 255) / 256 : 1;
     hipLaunchKernelGGL(kmeans_commit_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream),
                        assign, seg_off, meta, counts, N, k);

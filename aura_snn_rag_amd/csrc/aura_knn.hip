@@ -1275,7 +1275,11 @@ __global__ __launch_bounds__(SCAN_THREADS) void knn_scan_filter_v2(const ScanArg
 //   j-th group's m-th MFMA (any k permutation is fine as long as A and B use the same one).  ||c||^2
 //   falls out of the same loads (the lane's partial over its k, summed over the four h lanes).
 //   Keys go to LDS; then 16 lanes per query hold 16 keys each and run `nprobe` rounds of
-//   (local argmin, 4-step butterfly), ties to the lower centroid; the winner leaves through an alive mask.
+//   (local argmin, 4-step butterfly), equal keys to the lower centroid; the winner leaves through an alive mask.
+//   (Equal KEYS: two copies of a row have equal keys when one wave sums both, i.e. inside a 32-row group, or when
+//   every wave walks k alike -- D <= 64, one stage, and D > PR_QLDS_MAX_D.  In between wave w starts at stage w % nst:
+//   copies in different groups are summed in different orders and either may come first, within the rounding bound.
+//   All-zero rows have the key 0 in any order.)
 //   The per-list query lists of the inverted-list recall (lq_cnt / lq_list, optional) are filled here:
 //   one returning atomic per probe on the list's counter (zeroed by the caller); the order inside a
 //   list is whatever the atomics make it (results do not depend on it).

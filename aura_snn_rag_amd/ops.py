@@ -1650,6 +1650,7 @@ def gif_prosody_backward(save_a, save_theta, h, gains, g_spikes, g_h, g_gains, g
 # ---------------------------------------------------------------------------------------
 
 def bank_row_norms(bank, inv_norm, row0: int, n: int) -> None:
+    """inv_norm[r] = 1 / max(||bank[r]||, 1e-12) for r in [row0, row0 + n): a zero row gets 1 / 1e-12f, no inf."""
     _need(bank, "bank", torch.float32); _need(inv_norm, "inv_norm", torch.float32)
     M, D = bank.shape
     if row0 < 0 or n < 0 or row0 + n > M or inv_norm.numel() != M:
@@ -2753,8 +2754,11 @@ def ivf2_row_constants(meta, rho, sorted_rows, n_sorted: int, D: int, now: float
 
 def centroid_probe(queries, centroids, nprobe: int = 8) -> torch.Tensor:
     """ids [nq, 8] int32: column p < nprobe = the p-th nearest of the 256 centroid rows to each query (L2 on the
-    unnormalised query, ties to the lower row, ``hippocampal.py:261-262``) -- the probes ``knn_search_ivf2``
-    computes for itself, for callers that want them once per query (``sharded.ShardedHippocampus``)."""
+    unnormalised query, ``hippocampal.py:261-262``) -- the probes ``knn_search_ivf2`` computes for itself, for callers
+    that want them once per query (``sharded.ShardedHippocampus``).  Equal KEYS go to the lower row.  Rows with the
+    same bits have equal keys when they sit in one 32-row group (rows [32 w, 32 w + 32) are summed in one order), and
+    all-zero rows have everywhere; copies of a row in different groups are summed in different orders once
+    64 < D <= 1024 and may then come out in either order, inside the key's rounding bound (tests/index_rule.py)."""
     _need(queries, "queries", torch.float32); _need(centroids, "centroids", torch.float32)
     nq, D = queries.shape
     if centroids.shape != (256, D) or not (0 < nprobe <= 8):
@@ -3087,7 +3091,8 @@ def group_by_cluster(assign, k: int = 256) -> Tuple[torch.Tensor, torch.Tensor]:
 
 def kmeans_segment_means(bank, order, seg_off, centroids, k: int, sums_only: bool = False) -> None:
     """centroids[c] = mean of bank[order[seg_off[c]:seg_off[c+1]]] for c < k (empty clusters keep theirs);
-    ``sums_only``: the sums instead (zeros for empty clusters) -- a shard's partial result."""
+    ``sums_only``: the sums instead (zeros for empty clusters, also when ``order`` is empty) -- a shard's partial result.
+    The summation order is fixed (``aura_hip.h``): the same segment gives the same bits under any id, beside any others."""
     _need(bank, "bank", torch.float32); _need(centroids, "centroids", torch.float32)
     _need(order, "order", torch.int32); _need(seg_off, "seg_off", torch.int32)
     M, D = bank.shape

@@ -586,6 +586,10 @@ int aura_topk_merge(const float* in_scores, const int32_t* in_idx, int S, int64_
  *   in a fixed order (reproducible); empty clusters keep their centroid (:362-363).  With sums_only
  *   the per-cluster SUMS are written instead (zeros for empty clusters): a rank's partial result
  *   of a row-sharded bank, all-reduced with the counts.  Reads the bank once.
+ *   N == 0: every cluster is empty -- with sums_only the first k rows become zeros, else nothing is written.
+ *   The order is a tested contract (tests/index_rule.py segment_sum32): per chunk of 64 rows of the segment four
+ *   accumulators take rows r, r+1, r+2, r+3 while four remain, the rest go to the first, s = (a0 + a1) + (a2 + a3);
+ *   the chunks are added in order from zero; the mean is that sum divided by float(len), rounded once.
  *   D % 4 == 0; workspace: aura_kmeans_means_workspace_bytes(N, D, k) bytes, 16-byte aligned.
  * commit: meta[i][2] = assign[i] for i < N and counts[c] = seg_off[c+1] - seg_off[c] (counts may be
  *   NULL) -- the recount / metadata write of :370-376. */

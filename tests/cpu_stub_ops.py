@@ -38,7 +38,7 @@ def bank_write(bank, loc, meta, inv_norm, feats, slots, cur_loc, now, centroids=
 
 
 def bank_decay(meta, rate, count):
-    meta[:count, 0] *= (1.0 - rate)
+    meta[:count, 0] *= (torch.tensor(1.0) - torch.tensor(rate, dtype=torch.float32))   # the kernel's 1.0f - rate, in fp32
 
 
 def knn_search(bank, inv_norm, meta, queries, k, now, count=None, loc=None, q_loc=None, idx_base=0,
@@ -80,7 +80,7 @@ def topk_merge(scores, idx, k):
 
 def bank_gather(bank, idx):
     out = torch.zeros(*idx.shape, bank.shape[1])
-    ok = idx >= 0
+    ok = (idx >= 0) & (idx < bank.shape[0])                   # anything else gathers zeros, as the kernel does
     out[ok] = bank[idx[ok].long()]
     return out
 
