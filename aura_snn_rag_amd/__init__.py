@@ -11,6 +11,7 @@ episodic-retrieval hot path, behind the reference's own module API.
     from aura_snn_rag_amd import HippocampalProsodyAttention, HippocampalTransformerLayer, AttentionCache
     from aura_snn_rag_amd import HippocampalTransformer, DecodeState      # forward, prefill / step, generate
     from aura_snn_rag_amd import SNNRAGTransformer, MemoryAugmentedLayer, MemoryContext     # generation with memory
+    from aura_snn_rag_amd import MoELanguageZone, LiquidMoERouter, SNNExpert                # fused routing and experts
 
 All arithmetic on the path runs in ``lib/libaura_hip.so`` (hand-written HIP, C ABI in
 ``include/aura_hip.h``); there is no CPU or eager-PyTorch fallback.
@@ -36,7 +37,11 @@ _LAZY = {"PlaceCellSemanticEncoder": "core.language_zone.place_cell_encoder",
          "MemoryContext": "core.language_zone.memory_augmented_layer",
          "MemoryLayerCache": "core.language_zone.memory_augmented_layer",
          "FoldedMemory": "core.language_zone.memory_augmented_layer",
-         "SNNRAGTransformer": "core.language_zone.snn_rag_transformer"}
+         "SNNRAGTransformer": "core.language_zone.snn_rag_transformer",
+         "MoELanguageZone": "core.language_zone.moe_language_zone",
+         "MoEOutput": "core.language_zone.moe_language_zone",
+         "SNNExpert": "core.language_zone.snn_expert",
+         "LiquidMoERouter": "core.liquid_moe"}
 
 
 def __getattr__(name):

@@ -128,6 +128,9 @@ SIGNATURES = {
     "aura_row_linear_gate": (I, [P, I64, I64, P, I64, P, P, P, P, P, I64, I, P]),
     "aura_row_linear_gif": (I, [P, I64, I64, P, P, P, I64, I64, F, I, F, F, I, P, P, P, I, P]),
     "aura_memory_attend": (I, [P, I64, I64, P, P, F, P, P, P, I64, I64, P, P, P]),
+    "aura_moe_workspace_bytes": (I64, [I64, I64, I64]),
+    "aura_moe_route": (I, [P, I64, I64, P, P, P, I64, F, P, P, I64, I64, F, P, P, P, P, P, I64, P]),
+    "aura_moe_experts": (I, [P, I64, I64, I64, I64, I64, I64, P, P, P, P, P, P, P, P, I64, P]),
     "aura_profile_begin": (I, [I]),
     "aura_debug_cs_flags": (I, [I]),
     "aura_debug_clock_mhz": (I, [P, I, P]),

@@ -1399,6 +1399,233 @@ def memory_attend(x, norm, G, s0, U, bias=None, *, eps: float = 1e-5, out=None):
 
 
 # ---------------------------------------------------------------------------------------
+# MoE zone (the rule: include/aura_hip.h, "MoE zone")
+# ---------------------------------------------------------------------------------------
+
+MOE_MAX_N = 1 << 24
+MOE_MAX_DM = 256
+MOE_MAX_HH = 512
+MOE_MAX_HR = 256
+MOE_MAX_E = 64
+MOE_MAX_K = 8
+MOE_MAX_LAYERS = 4
+MOE_MAX_L = 64
+MOE_TILE = 32
+
+
+def _moe_f32(who: str, name: str, t, shape=None) -> None:
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{who}: {name} must be a torch.Tensor, got {type(t)}")
+    if t.dtype != torch.float32:
+        raise TypeError(f"{who}: {name} is {t.dtype}; the MoE kernels run in fp32 only")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{who}: {name} has shape {tuple(t.shape)}, expected {tuple(shape)}")
+    if not t.is_contiguous():
+        raise ValueError(f"{who}: {name} must be contiguous")
+
+
+def _moe_x(who: str, x) -> Tuple[int, int]:
+    _moe_f32(who, "x", x)
+    if x.dim() != 2:
+        raise ValueError(f"{who}: x is [N, Dm], got {tuple(x.shape)}")
+    N, Dm = x.shape
+    if N > MOE_MAX_N:
+        raise ValueError(f"{who}: N={N} rows exceed {MOE_MAX_N}")
+    if Dm % 4 or not 4 <= Dm <= MOE_MAX_DM:
+        raise ValueError(f"{who}: Dm={Dm} must be a multiple of 4 in [4, {MOE_MAX_DM}]")
+    return N, Dm
+
+
+def _moe_device(who: str, named) -> torch.device:
+    dev = None
+    for name, t in named:
+        if t is None:
+            continue
+        if not t.is_cuda:
+            raise AuraDeviceError(f"{who}: {name} is on {t.device}: aura_snn_rag_amd runs the hot path only as HIP "
+                                  f"kernels on an AMD GPU (no CPU/PyTorch fallback).")
+        if dev is not None and t.device != dev:
+            raise ValueError(f"{who}: tensors are on different devices")
+        dev = t.device
+    return dev
+
+
+def moe_workspace_bytes(N: int, E: int, k: int) -> int:
+    """Bytes of the plan ``moe_route`` leaves for ``moe_experts`` (host arithmetic, the C entry point's own layout)."""
+    a256 = lambda n: (n + 255) // 256 * 256
+    G = (N + MOE_TILE - 1) // MOE_TILE
+    tiles = (N * k + MOE_TILE - 1) // MOE_TILE + E
+    return 2 * a256(G * E * 4) + a256((E + 1) * 4) + a256(tiles * 12) + a256(N * k * 4)
+
+
+def _moe_route_args(x, U, bU, bW, gate_w, gate_b, dt, k, temperature, attn_gain):
+    """Type, shape and limit checks of ``moe_route``: ``(N, Dm, Hr, E, k)``.  Touches no device."""
+    who = "moe_route"
+    N, Dm = _moe_x(who, x)
+    _moe_f32(who, "U", U)
+    if U.dim() != 2 or U.shape[1] != Dm:
+        raise ValueError(f"{who}: U is [Hr, Dm={Dm}], got {tuple(U.shape)}")
+    Hr = U.shape[0]
+    if not 1 <= Hr <= MOE_MAX_HR:
+        raise ValueError(f"{who}: Hr={Hr} must be in [1, {MOE_MAX_HR}]")
+    _moe_f32(who, "bU", bU, (Hr,))
+    _moe_f32(who, "bW", bW, (Hr,))
+    _moe_f32(who, "gate_w", gate_w)
+    if gate_w.dim() != 2 or gate_w.shape[1] != Hr:
+        raise ValueError(f"{who}: gate_w is [E, Hr={Hr}], got {tuple(gate_w.shape)}")
+    E = gate_w.shape[0]
+    if not 1 <= E <= MOE_MAX_E:
+        raise ValueError(f"{who}: E={E} experts must be in [1, {MOE_MAX_E}]")
+    _moe_f32(who, "gate_b", gate_b, (E,))
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= min(E, MOE_MAX_K):
+        raise ValueError(f"{who}: k={k!r} must be an integer in [1, min(E, {MOE_MAX_K})] (pass min(top_k, E))")
+    for name, v in (("dt", dt), ("temperature", temperature)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)):
+            raise TypeError(f"{who}: {name}={v!r} must be a number")
+    if attn_gain is not None:
+        _moe_f32(who, "attn_gain", attn_gain, (N,))
+    return N, Dm, Hr, E, k
+
+
+class MoeRouting:
+    """What ``moe_route`` leaves: ``indices`` int32 [N, k], ``weights`` [N, k], ``probs`` [N, E] and ``plan``, the
+    device-side grouping of the (token, slot) pairs by expert that ``moe_experts`` reads (a byte tensor; opaque)."""
+    __slots__ = ("indices", "weights", "probs", "plan", "E", "k")
+
+    def __init__(self, indices, weights, probs, plan, E, k):
+        self.indices, self.weights, self.probs, self.plan, self.E, self.k = indices, weights, probs, plan, E, k
+
+
+def moe_route(x, U, bU, bW, gate_w, gate_b, *, dt: float, k: int, temperature: float = 1.0, attn_gain=None) -> MoeRouting:
+    """The liquid router in one launch and the plan of the expert launch in two more (the rule: ``include/aura_hip.h``,
+    "MoE zone"): ``x`` [N, Dm]; ``U`` [Hr, Dm], ``bU``, ``bW`` [Hr] the cell's ``U.weight``, ``U.bias`` and ``W.bias``;
+    ``gate_w`` [E, Hr], ``gate_b`` [E]; ``k = min(top_k, E)``; ``attn_gain`` [N] or ``None``.  fp32.  No host sync."""
+    N, Dm, Hr, E, k = _moe_route_args(x, U, bU, bW, gate_w, gate_b, dt, k, temperature, attn_gain)
+    dev = _moe_device("moe_route", (("x", x), ("U", U), ("bU", bU), ("bW", bW), ("gate_w", gate_w), ("gate_b", gate_b),
+                                    ("attn_gain", attn_gain)))
+    for name, t in (("x", x), ("U", U)):
+        if t.data_ptr() % 16:
+            raise ValueError(f"moe_route: {name} is not 16-byte aligned (a view into the middle of a buffer?)")
+    indices = torch.empty((N, k), dtype=torch.int32, device=dev)
+    weights = torch.empty((N, k), dtype=torch.float32, device=dev)
+    probs = torch.empty((N, E), dtype=torch.float32, device=dev)
+    nbytes = moe_workspace_bytes(N, E, k)
+    plan = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    check(lib().aura_moe_route(x.data_ptr(), N, Dm, U.data_ptr(), bU.data_ptr(), bW.data_ptr(), Hr, float(dt),
+                               gate_w.data_ptr(), gate_b.data_ptr(), E, k, float(temperature), _p(attn_gain),
+                               indices.data_ptr(), weights.data_ptr(), probs.data_ptr(), plan.data_ptr(), nbytes,
+                               _stream()), "aura_moe_route")
+    return MoeRouting(indices, weights, probs, plan, E, k)
+
+
+def _moe_expert_params(experts, gif):
+    """Checks of ``moe_expert_table``: ``(E, layers, Dm, Hh)``.  ``experts[e]`` is the flat list ``[W_s, b_s, W_g, b_g] *
+    layers + [W_r, b_r]`` of expert ``e``, ``gif[e][l] = (decay, L, alpha, threshold)``.  Touches no device."""
+    who = "moe_expert_table"
+    E = len(experts)
+    if not 1 <= E <= MOE_MAX_E or len(gif) != E:
+        raise ValueError(f"{who}: {E} experts (and {len(gif)} neuron settings) must be equal and in [1, {MOE_MAX_E}]")
+    n = len(experts[0])
+    if n < 6 or (n - 2) % 4:
+        raise ValueError(f"{who}: an expert is 4 tensors per layer and 2 of the readout, got {n}")
+    layers = (n - 2) // 4
+    if layers > MOE_MAX_LAYERS:
+        raise ValueError(f"{who}: num_layers={layers} exceeds {MOE_MAX_LAYERS}")
+    _moe_f32(who, "experts[0] W_s", experts[0][0])
+    if experts[0][0].dim() != 2:
+        raise ValueError(f"{who}: a weight is a matrix, got {tuple(experts[0][0].shape)}")
+    Hh, Dm = experts[0][0].shape
+    if Dm % 4 or not 4 <= Dm <= MOE_MAX_DM:
+        raise ValueError(f"{who}: Dm={Dm} must be a multiple of 4 in [4, {MOE_MAX_DM}]")
+    if Hh % 4 or not 4 <= Hh <= MOE_MAX_HH:
+        raise ValueError(f"{who}: Hh={Hh} must be a multiple of 4 in [4, {MOE_MAX_HH}]")
+    for e, (ts, gs) in enumerate(zip(experts, gif)):
+        if len(ts) != n or len(gs) != layers:
+            raise ValueError(f"{who}: expert {e} has another number of layers")
+        for l in range(layers):
+            shapes = ((Hh, Dm if l == 0 else Hh), (Hh,), (Hh, Hh), (Hh,))
+            for j, shp in enumerate(shapes):
+                if ts[4 * l + j] is None:
+                    raise ValueError(f"{who}: expert {e} layer {l}: a bias is required (bias=False is not supported)")
+                _moe_f32(who, f"expert {e} layer {l} tensor {j}", ts[4 * l + j], shp)
+            decay, L, alpha, thr = gs[l]
+            if not 1 <= int(L) <= MOE_MAX_L or int(L) != L:
+                raise ValueError(f"{who}: expert {e} layer {l}: L={L} must be an integer in [1, {MOE_MAX_L}]")
+        _moe_f32(who, f"expert {e} readout.weight", ts[-2], (Dm, Hh))
+        _moe_f32(who, f"expert {e} readout.bias", ts[-1], (Dm,))
+    return E, layers, Dm, Hh
+
+
+class MoeExpertTable:
+    """The device table of per-expert parameter pointers and neuron settings ``moe_experts`` reads.  It holds the
+    tensors it points to; nothing is copied or concatenated."""
+    __slots__ = ("ptrs", "gif", "E", "layers", "Dm", "Hh", "held")
+
+    def __init__(self, ptrs, gif, E, layers, Dm, Hh, held):
+        self.ptrs, self.gif, self.E, self.layers, self.Dm, self.Hh, self.held = ptrs, gif, E, layers, Dm, Hh, held
+
+
+def moe_expert_table(experts, gif) -> MoeExpertTable:
+    """Build the pointer table of ``moe_experts`` (one small host-to-device copy; build it once and keep it while the
+    parameters' storages stay).  See ``_moe_expert_params`` for the arguments."""
+    E, layers, Dm, Hh = _moe_expert_params(experts, gif)
+    flat = [t for ts in experts for t in ts]
+    dev = _moe_device("moe_expert_table", ((f"tensor {i}", t) for i, t in enumerate(flat)))
+    for i, t in enumerate(flat):
+        if t.data_ptr() % 16:
+            raise ValueError(f"moe_expert_table: tensor {i} is not 16-byte aligned")
+    ptrs = torch.tensor([t.data_ptr() for t in flat], dtype=torch.int64).reshape(E, 4 * layers + 2).to(dev)
+    g = torch.tensor([[[float(v) for v in gl] for gl in gs] for gs in gif], dtype=torch.float32).reshape(E, layers, 4)
+    return MoeExpertTable(ptrs, g.to(dev), E, layers, Dm, Hh, flat)
+
+
+def _moe_experts_args(x, routing, table, out, return_trace):
+    """Checks of ``moe_experts``: ``(N, Dm, P)``.  Touches no device."""
+    who = "moe_experts"
+    N, Dm = _moe_x(who, x)
+    if not isinstance(routing, MoeRouting):
+        raise TypeError(f"{who}: routing is what moe_route returned, got {type(routing)}")
+    if not isinstance(table, MoeExpertTable):
+        raise TypeError(f"{who}: table is what moe_expert_table returned, got {type(table)}")
+    if table.Dm != Dm:
+        raise ValueError(f"{who}: the experts take Dm={table.Dm}, x has {Dm}")
+    if table.E != routing.E:
+        raise ValueError(f"{who}: routed over {routing.E} experts, the table holds {table.E}")
+    if tuple(routing.indices.shape) != (N, routing.k):
+        raise ValueError(f"{who}: the routing is of {routing.indices.shape[0]} rows, x has {N}")
+    if out is not None:
+        _moe_f32(who, "out", out, (N, Dm))
+    return N, Dm, N * routing.k
+
+
+def moe_experts(x, routing: MoeRouting, table: MoeExpertTable, *, out=None, return_trace: bool = False):
+    """Every selected expert's ``SNNExpert.predict`` on its own tokens and the weighted sum, in two launches (the rule:
+    ``include/aura_hip.h``, "MoE zone").  ``x`` is the tensor ``moe_route`` was given.  Returns ``(out [N, Dm], y [N, k,
+    Dm], trace)``: ``y`` every pair's expert output, ``trace`` [N, k, layers, Hh] every layer's spikes or ``None``."""
+    N, Dm, P = _moe_experts_args(x, routing, table, out, return_trace)
+    dev = _moe_device("moe_experts", (("x", x), ("indices", routing.indices), ("table", table.ptrs), ("out", out)))
+    if x.data_ptr() % 16 or (out is not None and out.data_ptr() % 16):
+        raise ValueError("moe_experts: x or out is not 16-byte aligned")
+    k = routing.k
+    y = torch.empty((N, k, Dm), dtype=torch.float32, device=dev)
+    res = out if out is not None else torch.empty((N, Dm), dtype=torch.float32, device=dev)
+    trace = torch.empty((N, k, table.layers, table.Hh), dtype=torch.float32, device=dev) if return_trace else None
+    check(lib().aura_moe_experts(x.data_ptr(), N, Dm, table.Hh, table.layers, table.E, k, table.ptrs.data_ptr(),
+                                 table.gif.data_ptr(), routing.indices.data_ptr(), routing.weights.data_ptr(),
+                                 y.data_ptr(), res.data_ptr(), _p(trace), routing.plan.data_ptr(),
+                                 routing.plan.numel(), _stream()), "aura_moe_experts")
+    return res, y, trace
+
+
+def moe_forward(x, U, bU, bW, gate_w, gate_b, table: MoeExpertTable, *, dt: float, k: int, temperature: float = 1.0,
+                attn_gain=None, out=None, return_trace: bool = False):
+    """``moe_route`` then ``moe_experts``: five launches, no host sync.  Returns ``(out, routing, y, trace)``."""
+    routing = moe_route(x, U, bU, bW, gate_w, gate_b, dt=dt, k=k, temperature=temperature, attn_gain=attn_gain)
+    res, y, trace = moe_experts(x, routing, table, out=out, return_trace=return_trace)
+    return res, routing, y, trace
+
+
+# ---------------------------------------------------------------------------------------
 # next token (the rule: include/aura_hip.h, "Next token")
 # ---------------------------------------------------------------------------------------
 

@@ -1385,6 +1385,78 @@ int aura_memory_attend(const float* x, int64_t R, int64_t D, const float* gamma,
                        const float* G, const float* s0, const float* U, int64_t H, int64_t M,
                        const float* bo_or_null, float* y, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * MoE zone
+ * ------------------------------------------------------------------------------------- */
+
+/* The sparse mixture of spiking experts of MoELanguageZone (src/core/language_zone/moe_language_zone.py): the liquid
+ * router's top-k of E experts per token, every selected expert's SNNExpert.predict on its own tokens only, and the
+ * weighted sum, in five launches, csrc/aura_moe.hip.  All fp32, unfused (-ffp-contract=off) except where fmaf is
+ * written; fl() = round to nearest even; `/` is IEEE division; tanhf and expf are the device functions.  chain_K(a, w)
+ * below is t = 0, then t = fmaf(a[k], w[k], t) over k in the stated order.
+ *
+ * Route (aura_moe_route).  x [N][Dm]; U [Hr][Dm], bU, bW [Hr] (LiquidCell.U.weight, U.bias, W.bias); gate_w [E][Hr],
+ * gate_b [E]; attn_gain [N] or NULL; k = the caller's min(top_k, E).  Per row:
+ *   1  g[j]  = tanhf(fl(bW[j] + fl(chain_Dm(x, U[j]) + bU[j]))), k ascending
+ *   2  h[j]  = fl(dt g[j])
+ *   3  z[e]  = fl(chain_Hr(h, gate_w[e]) + gate_b[e]), j ascending
+ *   4  temp  = temperature, or with attn_gain fminf(fmaxf(temperature / fl(attn_gain[row] + 1e-6f), 0.1f), 5.0f);
+ *      z[e]  = z[e] / temp
+ *   5  mx = max_e z[e] (fmaxf), ex[e] = expf(fl(z[e] - mx)), sum = the xor butterfly 32, 16, 8, 4, 2, 1 over 64 values
+ *      (ex[e] for e < E, +0 above): its order is a function of E alone.  p[e] = ex[e] / sum.
+ *   6  the top k of p by (value descending, expert id ascending); NaN ranks first (then by id).  torch.topk leaves ties
+ *      open; here the lower id wins.
+ *   7  s = p[e_0], then s = fl(s + p[e_r]) in rank order; w[r] = p[e_r] / fl(s + 1e-8f).
+ * The state of the reference's cell starts at zero, so -h_prev / (tau + 1e-6) is -0 for every finite tau > -1e-6 and
+ * W.weight meets a zero vector: V and W.weight are not read.  The one case that differs from the reference's op
+ * sequence: a row whose V(x) is not finite (NaN, or -inf, which makes tau NaN through softplus) beside a finite U(x)
+ * gives NaN there and the finite result here.
+ * Writes indices int32 [N][k], weights [N][k], probs [N][E], and into the workspace the plan: the P = N k (token, slot)
+ * pairs grouped by expert, within an expert in ascending token order, cut into tiles of at most 32 pairs of one expert.
+ * Places come from counts and prefix sums, never from an atomic.  Three launches.
+ *
+ * Experts and combine (aura_moe_experts), after aura_moe_route on the same workspace, x, indices and weights.
+ * ptr_table: device array [E][4 layers + 2] of device pointers: per layer Synapsis.weight [Hh][in], Synapsis.bias [Hh],
+ * GIFNeuron.linear.weight [Hh][Hh], linear.bias [Hh] (in = Dm for layer 0, Hh after), then readout.weight [Dm][Hh],
+ * readout.bias [Dm]; every pointer non-null, matrices 16-byte aligned.  gif_table: device [E][layers][4] = decay, L,
+ * alpha, threshold of each GIFNeuron.  Per pair (token, slot) with expert e, a = x[token]:
+ *   per layer   c[n] = fl(dot_in(a, W_s[n]) + b_s[n]);  i[n] = fl(dot_Hh(c, W_g[n]) + b_g[n]);
+ *               s[n] = GifModel<false>::step from v = 0, theta = threshold on i[n] (csrc/aura_gif_model.inl: the spikes
+ *               of aura_gif_run at T = 1 for equal currents);  the next layer's a is s
+ *   y[n] = fl(dot_Hh(s_last, W_r[n]) + b_r[n])
+ *   dot_K = chain_K in this order: for each block of eight k from 0, the k's b, b + 4, b + 1, b + 5, b + 2, b + 6,
+ *   b + 3, b + 7 (those below K; K % 4 == 0): a function of K alone.  It is computed as a chain of
+ *   v_mfma_f32_32x32x2_f32, which is this fmaf chain bit for bit.
+ * y [P][Dm] at place token k + slot; trace (or NULL: nothing written) [P][layers][Hh] receives every layer's spikes.
+ *   out[token][d] = sum over the token's slots in ascending expert id of fl(w[slot] y[slot][d]), from the first
+ *   product (0 + p is p): the order of the reference's loop over the experts.
+ * Two launches; the expert launch is sized by the bound ceil(P / 32) + E and reads the tile count on the device.
+ *
+ * Properties: no global atomics, no host read; a token's indices, weights, probs, y and out are bit for bit the same
+ * alone or in any batch, for any N and over repeated calls; a NaN row leaves the other rows alone.
+ * Limits: 0 <= N <= AURA_MOE_MAX_N; Dm % 4 == 0, 4 <= Dm <= 256; Hh % 4 == 0, 4 <= Hh <= 512; 1 <= Hr <= 256;
+ * 1 <= k <= min(E, 8); E <= 64; 1 <= layers <= 4.  GIFNeuron's L, 1 <= L <= 64, is device data in gif_table: the caller checks it.
+ * AURA_E_INVAL: a size outside the limits, a null pointer other than attn_gain / trace, a workspace smaller than
+ *   aura_moe_workspace_bytes(N, E, k) (which is -1 for sizes outside the limits).  AURA_E_ALIGN: x, U, y or out not
+ *   16-byte aligned, the workspace not 256-byte, ptr_table not 8-byte, any other pointer not 4-byte aligned.
+ *   N == 0 launches nothing. */
+#define AURA_MOE_MAX_N 16777216
+#define AURA_MOE_MAX_DM 256
+#define AURA_MOE_MAX_HH 512
+#define AURA_MOE_MAX_HR 256
+#define AURA_MOE_MAX_E 64
+#define AURA_MOE_MAX_K 8
+#define AURA_MOE_MAX_LAYERS 4
+int64_t aura_moe_workspace_bytes(int64_t N, int64_t E, int64_t k);
+int aura_moe_route(const float* x, int64_t N, int64_t Dm, const float* U, const float* bU, const float* bW, int64_t Hr,
+                   float dt, const float* gate_w, const float* gate_b, int64_t E, int64_t k, float temperature,
+                   const float* attn_gain_or_null, int32_t* indices, float* weights, float* probs, void* workspace,
+                   int64_t workspace_bytes, void* stream);
+int aura_moe_experts(const float* x, int64_t N, int64_t Dm, int64_t Hh, int64_t layers, int64_t E, int64_t k,
+                     const void* ptr_table, const float* gif_table, const int32_t* indices, const float* weights,
+                     float* y, float* out, float* trace_or_null, const void* workspace, int64_t workspace_bytes,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif
