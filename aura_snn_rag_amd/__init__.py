@@ -12,6 +12,7 @@ episodic-retrieval hot path, behind the reference's own module API.
     from aura_snn_rag_amd import HippocampalTransformer, DecodeState      # forward, prefill / step, generate
     from aura_snn_rag_amd import SNNRAGTransformer, MemoryAugmentedLayer, MemoryContext     # generation with memory
     from aura_snn_rag_amd import MoELanguageZone, LiquidMoERouter, SNNExpert                # fused routing and experts
+    from aura_snn_rag_amd import ZoneState                                 # MoELanguageZone's prefill / step / generate
 
 All arithmetic on the path runs in ``lib/libaura_hip.so`` (hand-written HIP, C ABI in
 ``include/aura_hip.h``); there is no CPU or eager-PyTorch fallback.
@@ -40,6 +41,7 @@ _LAZY = {"PlaceCellSemanticEncoder": "core.language_zone.place_cell_encoder",
          "SNNRAGTransformer": "core.language_zone.snn_rag_transformer",
          "MoELanguageZone": "core.language_zone.moe_language_zone",
          "MoEOutput": "core.language_zone.moe_language_zone",
+         "ZoneState": "core.language_zone.moe_language_zone",
          "SNNExpert": "core.language_zone.snn_expert",
          "LiquidMoERouter": "core.liquid_moe"}
 

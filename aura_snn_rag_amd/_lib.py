@@ -131,6 +131,7 @@ SIGNATURES = {
     "aura_moe_workspace_bytes": (I64, [I64, I64, I64]),
     "aura_moe_route": (I, [P, I64, I64, P, P, P, I64, F, P, P, I64, I64, F, P, P, P, P, P, I64, P]),
     "aura_moe_experts": (I, [P, I64, I64, I64, I64, I64, I64, P, P, P, P, P, P, P, P, I64, P]),
+    "aura_poisson_rate": (I, [P, I64, I64, P, P, I64, I64, U64, P, I64, I64, P, P, P, P, P]),
     "aura_profile_begin": (I, [I]),
     "aura_debug_cs_flags": (I, [I]),
     "aura_debug_clock_mhz": (I, [P, I, P]),

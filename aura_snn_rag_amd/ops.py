@@ -1626,6 +1626,125 @@ def moe_forward(x, U, bU, bW, gate_w, gate_b, table: MoeExpertTable, *, dt: floa
 
 
 # ---------------------------------------------------------------------------------------
+# Poisson bridge (the rule: include/aura_hip.h, "Poisson bridge")
+# ---------------------------------------------------------------------------------------
+
+BRIDGE_MAX_N, BRIDGE_MAX_K, BRIDGE_MAX_H, BRIDGE_MAX_T = 1 << 24, MOE_MAX_DM, 4096, 64
+
+
+def _bridge_f32(name: str, t, shape=None) -> None:
+    who = "poisson_rate"
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{who}: {name} must be a torch.Tensor, got {type(t)}")
+    if t.dtype != torch.float32:
+        raise TypeError(f"{who}: {name} is {t.dtype}; the Poisson bridge runs in fp32 only (bf16 is not supported)")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{who}: {name} has shape {tuple(t.shape)}, expected {tuple(shape)}")
+    if not t.is_contiguous():
+        raise ValueError(f"{who}: {name} must be contiguous")
+
+
+def _poisson_rate_args(x, weight, bias, T, seed, streams, rows_per_stream, start, return_probs, return_spikes, out):
+    """Type, shape and limit checks of ``poisson_rate``: ``(N, K, H, T, seed, B, S, start)`` with ``start`` the host's
+    int (0 beside a device ``start``).  Touches no device and loads nothing."""
+    who = "poisson_rate"
+    _bridge_f32("x", x)
+    if x.dim() != 2:
+        raise ValueError(f"{who}: x is [N, K], got {tuple(x.shape)}")
+    N, K = x.shape
+    if N > BRIDGE_MAX_N:
+        raise ValueError(f"{who}: N={N} rows exceed {BRIDGE_MAX_N}")
+    if K % 4 or not 4 <= K <= BRIDGE_MAX_K:
+        raise ValueError(f"{who}: K={K} must be a multiple of 4 in [4, {BRIDGE_MAX_K}]")
+    _bridge_f32("weight", weight)
+    if weight.dim() != 2 or weight.shape[1] != K:
+        raise ValueError(f"{who}: weight is [H, K={K}] (nn.Linear's layout), got {tuple(weight.shape)}")
+    H = weight.shape[0]
+    if not 1 <= H <= BRIDGE_MAX_H:
+        raise ValueError(f"{who}: H={H} channels must be in [1, {BRIDGE_MAX_H}]")
+    if bias is not None:
+        _bridge_f32("bias", bias, (H,))
+    T = _sample_int(who, "T", T, 1, BRIDGE_MAX_T + 1)
+    seed = _sample_int(who, "seed", seed, 0, 1 << 64)
+    if (streams is None) != (rows_per_stream is None):
+        raise ValueError(f"{who}: streams and rows_per_stream come together (default: every row its own stream, the "
+                         f"row number)")
+    if streams is None:
+        B, S = N, 1
+    else:
+        S = _sample_int(who, "rows_per_stream", rows_per_stream, 1, max(N, 1) + 1)
+        if N % S:
+            raise ValueError(f"{who}: N={N} rows are not a multiple of rows_per_stream={S}")
+        B = N // S
+        if isinstance(streams, torch.Tensor):
+            if streams.dtype not in (torch.int32, torch.int64) or tuple(streams.shape) != (B,) \
+                    or not streams.is_contiguous():
+                raise ValueError(f"{who}: streams is a contiguous int32 (the bits of a uint32) or int64 [B] = ({B},), "
+                                 f"got {streams.dtype} {tuple(streams.shape)}")
+        else:
+            ids = np.asarray(streams)
+            if ids.dtype.kind not in "iu" or ids.shape != (B,) or (ids.astype(np.int64) < 0).any() \
+                    or (ids.astype(np.int64) >= (1 << 32)).any():
+                raise ValueError(f"{who}: streams is [B] = ({B},) integers in [0, 2^32), got {streams!r}")
+    if isinstance(start, torch.Tensor):
+        if start.dtype != torch.int32 or tuple(start.shape) != (B,) or not start.is_contiguous():
+            raise ValueError(f"{who}: a device start is a contiguous int32 [B] = ({B},), got {start.dtype} "
+                             f"{tuple(start.shape)}")
+        start0 = 0
+    else:
+        start0 = _sample_int(who, "start", start, 0, (1 << 31) - S + 1)
+    if out is not None:
+        _bridge_f32("out", out, (N, H))
+    for name, t in (("x", x), ("weight", weight)):
+        if t.data_ptr() % 16:
+            raise ValueError(f"{who}: {name} is not 16-byte aligned (a view into the middle of a buffer?)")
+    return N, K, H, T, seed, B, S, start0
+
+
+def poisson_rate(x, weight, bias=None, *, T: int, seed: int, streams=None, rows_per_stream: Optional[int] = None,
+                 start=0, return_probs: bool = False, return_spikes: bool = False, out=None):
+    """``ContinuousToSpikeBridge`` ('poisson') and the mean over its timesteps in one launch (the rule:
+    ``include/aura_hip.h``, "Poisson bridge"): ``x`` [N, K], ``weight`` [H, K], ``bias`` [H] or ``None`` ->
+    ``rate`` [N, H], the mean over ``T`` steps of ``spike = u < sigmoid(x W^T + b)``.  The uniforms are Philox4x32-10 under
+    ``seed``, keyed by (channel, timestep group, position, stream): row ``n = b S + i`` of stream ``streams[b]`` (int32
+    holding the bits of a uint32, int64 taken modulo 2^32, or ints in [0, 2^32)) stands at position ``start[b] + i``,
+    ``S = rows_per_stream``; ``start`` is an int or an int32 [B] device tensor the host never reads.  Default: row ``n``
+    is stream ``n``, one row each.  A row's bits depend only on its own ``x`` row, stream, position and seed.
+
+    Returns ``rate``, written into ``out`` [N, H] if given; with ``return_probs`` and / or ``return_spikes`` a tuple
+    ``(rate, probs [N, H], spikes [N, T, H])`` of those asked for, in this order.  fp32 only.  No host sync."""
+    N, K, H, T, seed, B, S, start0 = _poisson_rate_args(x, weight, bias, T, seed, streams, rows_per_stream, start,
+                                                       return_probs, return_spikes, out)
+    who = "poisson_rate"
+    dev = None
+    for name, t in (("x", x), ("weight", weight), ("bias", bias), ("out", out), ("streams", streams), ("start", start)):
+        if not isinstance(t, torch.Tensor):
+            continue
+        if not t.is_cuda:
+            raise AuraDeviceError(f"{who}: {name} is on {t.device}: aura_snn_rag_amd runs the hot path only as HIP "
+                                  f"kernels on an AMD GPU (no CPU/PyTorch fallback).")
+        if dev is not None and t.device != dev:
+            raise ValueError(f"{who}: tensors are on different devices")
+        dev = t.device
+    if streams is None:
+        streams = torch.arange(N, dtype=torch.int32, device=dev)
+    elif not isinstance(streams, torch.Tensor):
+        streams = torch.as_tensor(np.asarray(streams, dtype=np.int64).astype(np.uint32).view(np.int32), device=dev)
+    elif streams.dtype == torch.int64:
+        streams = streams.to(torch.int32)                           # modulo 2^32: the low word's bits
+    rate = out if out is not None else torch.empty((N, H), dtype=torch.float32, device=dev)
+    probs = torch.empty((N, H), dtype=torch.float32, device=dev) if return_probs else None
+    spikes = torch.empty((N, T, H), dtype=torch.float32, device=dev) if return_spikes else None
+    if N > 0:                                                       # (no rows: nothing to launch, nothing to point at)
+        check(lib().aura_poisson_rate(x.data_ptr(), N, K, weight.data_ptr(), _p(bias), H, T, seed, streams.data_ptr(),
+                                      S, start0, _p(start) if isinstance(start, torch.Tensor) else None,
+                                      rate.data_ptr(), _p(probs), _p(spikes), _stream()), "aura_poisson_rate")
+    if not (return_probs or return_spikes):
+        return rate
+    return (rate,) + tuple(t for t in (probs, spikes) if t is not None)
+
+
+# ---------------------------------------------------------------------------------------
 # next token (the rule: include/aura_hip.h, "Next token")
 # ---------------------------------------------------------------------------------------
 

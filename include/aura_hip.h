@@ -1457,6 +1457,58 @@ int aura_moe_experts(const float* x, int64_t N, int64_t Dm, int64_t Hh, int64_t 
                      float* y, float* out, float* trace_or_null, const void* workspace, int64_t workspace_bytes,
                      void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Poisson bridge
+ * ------------------------------------------------------------------------------------- */
+
+/* ContinuousToSpikeBridge with encoding 'poisson' (src/core/language_zone/spike_bridge.py), its projection, sigmoid,
+ * draw, comparison and the mean over the timesteps that follows it in MoELanguageZone, in one launch,
+ * csrc/aura_bridge.hip.  The reference draws torch.rand(rows, T, dim), which depends on the call's shape and on the
+ * generator's history; here a draw is a function of what it belongs to, so a token's spikes are the same in a forward
+ * over the sequence and in a one-token step.  All fp32, unfused (-ffp-contract=off) except where fmaf is written;
+ * fl() = round to nearest even; `/` is IEEE division; expf is the accurate device function.
+ *
+ * THE RULE.  x [N][K]; W [H][K] (nn.Linear's layout), b [H] or NULL; T timesteps; seed; streams uint32 [B], S =
+ * rows_per_stream, N = B S; start.  Row n = b S + i has stream s = streams[b] and position p = start[b] + i (start_dev,
+ * int32 [B] read on the device) or start + i (the host's `start`; start_dev NULL).  For row n and channel c:
+ *   1. pre-activation  z = fl(dot_K(x[n], W[c]) + b[c]), without a bias z = dot_K(x[n], W[c]); dot_K is "MoE zone"'s:
+ *                      t = 0, then t = fmaf(x[k], W[k], t) over each block of eight k from 0 in the order b, b + 4,
+ *                      b + 1, b + 5, b + 2, b + 6, b + 3, b + 7: a function of K alone.
+ *   2. probability     q = fl(1 / fl(1 + expf(-z))).  z = +inf: q = 1; z = -inf: q = 0; NaN: NaN.
+ *   3. random words    for j = 0 .. ceil(T / 4) - 1, the FOUR words w_0 .. w_3 of Philox4x32-10 with counter (c, j, p, s)
+ *                      and key (seed & 0xffffffff, seed >> 32), the constants of "Replay"; word w_i serves timestep
+ *                      t = 4 j + i, words with t >= T are discarded.
+ *   4. uniform         u_t = ((w >> 9) + 0.5) * 2^-23, "Replay"'s: exact in fp32, never 0 or 1.
+ *   5. spike           spike[n][t][c] = u_t < q ? 1 : 0.  A NaN q never spikes, q = 1 always, q = 0 never.
+ *   6. rate            rate[n][c] = fl(float(count) fl(1 / float(T))), count the number of spikes over t: the sum times
+ *                      the rounded reciprocal, which is how torch's device mean divides, so these are the bits of
+ *                      spikes.mean(dim=1) on the GPU.  (A true division differs from it in the last bit for some
+ *                      (count, T), 9 of 10 among them; torch's CPU mean is the true division.)
+ * The same seed may drive "Next token": there the counter is (token id, stream, step lo, step hi) and the word decides
+ * a token; here it is (channel, word group, position, stream) and the words decide spikes.  Two counters of the two
+ * rules may coincide as numbers; they feed different decisions, and neither rule reads the other's words.
+ *
+ * Outputs: rate [N][H] always; q_or_null [N][H] the probability of step 2; spikes_or_null [N][T][H] the train.
+ * Properties: no atomics, no host read, no scratch; a row's bits depend only on its own x row, stream, position and
+ * seed: the same alone or in any batch, at any (S, start) split that gives the same (s, p), over repeated calls and
+ * with or without the optional outputs; a NaN or inf row leaves the other rows alone.
+ * Against fp64 on the same fp32 inputs (tests/poisson_bridge_rule.py derives it): with e = 2^-24,
+ *     dz = |z - z64| <= (K + 8) e (sum_k |x_k W_k| + |b|),    |q - q64| <= dz / 4 + the sigmoid's own roundings.
+ * Limits: 0 <= N <= AURA_BRIDGE_MAX_N; K % 4 == 0, 4 <= K <= AURA_MOE_MAX_DM; 1 <= H <= AURA_BRIDGE_MAX_H; 1 <= T <=
+ * AURA_BRIDGE_MAX_T; S >= 1, N % S == 0; 0 <= start and start + S <= 2^31 (positions below 2^31); with start_dev the
+ * host's start is 0 and the device positions are the caller's to keep below 2^31 (they are taken modulo 2^32 and index
+ * nothing).
+ * AURA_E_INVAL, nothing launched: a size outside the limits, a null x, W, streams or rate, start != 0 beside
+ *   start_dev.  AURA_E_ALIGN: x or W not 16-byte aligned, any other pointer not 4-byte aligned.  N == 0 launches
+ *   nothing.  One launch on `stream`: a workgroup per 32 rows and 128 channels. */
+#define AURA_BRIDGE_MAX_N 16777216
+#define AURA_BRIDGE_MAX_H 4096
+#define AURA_BRIDGE_MAX_T 64
+int aura_poisson_rate(const float* x, int64_t N, int64_t K, const float* W, const float* b_or_null, int64_t H, int64_t T,
+                      uint64_t seed, const uint32_t* streams, int64_t rows_per_stream, int64_t start,
+                      const int32_t* start_dev_or_null, float* rate, float* q_or_null, float* spikes_or_null,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif
