@@ -26,19 +26,18 @@ Decoding is fp32, runs under ``no_grad`` and has no CPU fallback: CPU tensors ra
 from __future__ import annotations
 
 import time
-from typing import List, Optional, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 import torch
 import torch.nn as nn
 from torch.utils.checkpoint import checkpoint
 
 from ... import ops
+from .decoding import _UNSET, check_seed, decode_loop, start_turn, trim_to_last_finish
 from .hippocampal_attention import AttentionCache, row_counts
 from .hippocampal_layer import HippocampalTransformerLayer
 from .place_cell_encoder import PlaceCellSemanticEncoder
 from .theta_gamma_encoding import ThetaGammaPositionalEncoding, embed_tokens
-
-_UNSET = object()
 
 
 class DecodeState:
@@ -76,15 +75,15 @@ class DecodeState:
 
 
 class CachedDecodingMixin:
-    """``new_state`` / ``step`` / ``extend`` / ``generate`` of a model that has ``config``, ``layers`` (each with ``new_cache`` and
-    ``step`` and ``extend``), ``semantic_encoder``, ``pos_encoder``, ``layer_norm``, ``dropout``, ``output_head`` and its own
-    ``prefill(input_ids, prosody=None, state=None, use_memory=True)``: the decode loop ``HippocampalTransformer`` and
-    ``SNNRAGTransformer`` share.  Messages name the class that raises."""
+    """``new_state`` / ``step`` / ``extend`` / ``generate`` of a model that has ``config``, ``layers`` (each with ``new_cache``,
+    ``prefill``, ``step`` and ``extend``), ``semantic_encoder``, ``pos_encoder``, ``layer_norm``, ``dropout``, ``output_head``
+    and its own ``prefill(input_ids, prosody=None, state=None, use_memory=True)``: the cached decoding
+    ``HippocampalTransformer`` and ``SNNRAGTransformer`` share, on the loop of ``decoding.py``.  Messages name the class
+    that raises."""
 
     def new_state(self, batch: int, capacity: int, seed: int = 0) -> DecodeState:
         """An empty decoding state for ``batch`` sequences of at most ``capacity`` positions, on the model's device."""
-        if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < (1 << 64):
-            raise ValueError(f"{type(self).__name__}.new_state: seed must be an int in [0, 2^64), got {seed!r}")
+        seed = check_seed(f"{type(self).__name__}.new_state", seed)
         if len(self.layers) < 1:
             raise ValueError(f"{type(self).__name__}.new_state: a model without layers has nothing to cache")
         caches = [layer.new_cache(batch, capacity) for layer in self.layers]
@@ -103,6 +102,37 @@ class CachedDecodingMixin:
     def _before_fused_steps(self, state: DecodeState) -> None:
         """What ``generate(fused_step=True)`` runs once between the prefill (or a turn's extend) and the first step: a
         model whose fused step needs per-generation constants beyond the caches builds them here.  Nothing here."""
+
+    def _prefill_layer_kwargs(self, who: str, memory) -> Sequence[dict]:
+        """What ``_prefill_hidden`` passes to every layer's ``prefill`` beyond the hidden states, the prosody,
+        ``use_memory``, the cache and the lengths: one dict per layer.  Nothing here."""
+        return [{}] * len(self.layers)
+
+    def _prefill_hidden(self, who, input_ids, prosody, state, use_memory, lengths, memory=None) -> torch.Tensor:
+        """``prefill`` up to the head: the last layer's hidden states [B, S, D]."""
+        if input_ids.dim() != 2:
+            raise ValueError(f"{who}: input_ids is [B, S], got {tuple(input_ids.shape)}")
+        B, S = input_ids.shape
+        self._check_state(who, state, B)
+        extras = self._prefill_layer_kwargs(who, memory)
+        if lengths is not None:
+            lengths, _ = row_counts(who, "lengths", lengths, B, 1, S, input_ids.device, dtype=torch.int64)
+            valid = torch.arange(S, device=input_ids.device)[None, :] < lengths[:, None]
+            input_ids = torch.where(valid, input_ids, 0)                   # a valid id where the padding may hold none
+        hidden_states, _ = embed_tokens(input_ids, self.semantic_encoder, self.pos_encoder, self.layer_norm)
+        hidden_states = self.dropout(hidden_states)
+        ragged = {} if lengths is None else dict(lengths=lengths)
+        for layer, cache, extra in zip(self.layers, state.caches, extras):
+            hidden_states = layer.prefill(hidden_states, prosody=prosody, use_memory=use_memory, cache=cache, **extra,
+                                          **ragged)
+        with torch.no_grad():
+            if lengths is None:
+                state.seen.scatter_(1, input_ids.to(torch.int64), 1)
+            else:
+                self._mark_seen(state.seen, input_ids, valid)
+                state.ragged = True
+        state.position = S
+        return hidden_states
 
     @torch.no_grad()
     def step(self, tokens: torch.Tensor, prosody: Optional[torch.Tensor] = None, state: Optional[DecodeState] = None,
@@ -148,41 +178,10 @@ class CachedDecodingMixin:
         the padding holds is ignored and the logits at the padded places are unspecified.  Only the tokens below the
         count are marked in ``state.seen``.  ``state.position`` advances by ``m``, an upper bound; the capacity check
         uses the largest count where the host knows the counts, ``m`` otherwise."""
-        who = f"{type(self).__name__}.extend"
-        if counts is not None:
-            return torch.cat([self.output_head(h) for h in self._extend_ragged(who, tokens, prosody, state, use_memory,
-                                                                               counts)], dim=1)
-        if tokens.dim() != 2 or tokens.shape[1] < 1:
-            raise ValueError(f"{who}: tokens is [B, m] with m >= 1, got {tuple(tokens.shape)}")
-        B, m = tokens.shape
-        self._check_state(who, state, B)
-        if prosody is not None and tuple(prosody.shape) != (B, m, 4):
-            raise ValueError(f"{who}: prosody is [B, m, 4] = ({B}, {m}, 4), got {tuple(prosody.shape)}")
-        held = max(cache.max_length for cache in state.caches)
-        if held + m > state.capacity:
-            raise RuntimeError(f"{who}: {m} more positions do not fit the caches ({held} of {state.capacity} may be "
-                               f"held); a sliding cache is not part of this module")
-        last = len(self.layers) - 1
-        logits = []
-        for t0 in range(0, m, ops.DECODE_EXTEND_MAX):
-            piece = tokens[:, t0:t0 + ops.DECODE_EXTEND_MAX]
-            n = piece.shape[1]
-            if state.ragged:
-                positions = state.lengths[:, None] + torch.arange(n, dtype=torch.int32, device=state.lengths.device)
-                hidden_states, _ = embed_tokens(piece, self.semantic_encoder, self.pos_encoder, self.layer_norm,
-                                                dense=False, positions=positions)
-            else:
-                hidden_states, _ = embed_tokens(piece, self.semantic_encoder, self.pos_encoder, self.layer_norm,
-                                                start=state.position, dense=False)
-            hidden_states = self.dropout(hidden_states)
-            part = None if prosody is None else prosody[:, t0:t0 + n]
-            for i, (layer, cache) in enumerate(zip(self.layers, state.caches)):
-                hidden_states = layer.extend(hidden_states, prosody=part, use_memory=use_memory, cache=cache,
-                                             advance=i == last)
-            state.position += n
-            logits.append(self.output_head(hidden_states))
-        state.seen.scatter_(1, tokens.to(torch.int64), 1)
-        return logits[0] if len(logits) == 1 else torch.cat(logits, dim=1)
+        logits = [self.output_head(h) for h in self._extend_hidden(f"{type(self).__name__}.extend", tokens, prosody,
+                                                                   state, use_memory, counts)]
+        # (one piece without counts is returned as it is; with counts the result has always been a copy)
+        return logits[0] if counts is None and len(logits) == 1 else torch.cat(logits, dim=1)
 
     @staticmethod
     def piece_counts(counts: torch.Tensor, t0: int) -> torch.Tensor:
@@ -198,8 +197,10 @@ class CachedDecodingMixin:
         seen.bitwise_or_(marks[:, :V])
 
     @torch.no_grad()
-    def _extend_ragged(self, who: str, tokens, prosody, state, use_memory: bool, counts) -> List[torch.Tensor]:
-        """``extend`` with per-row counts up to the head: the last layer's hidden states, one [B, n, D] per piece."""
+    def _extend_hidden(self, who: str, tokens, prosody, state, use_memory: bool, counts) -> List[torch.Tensor]:
+        """``extend`` up to the head: the last layer's hidden states, one [B, n, D] per piece.  Without ``counts`` the
+        layers are called without ``counts`` and ``count_bound`` and a state that is not ragged keeps its scalar
+        position."""
         if tokens.dim() != 2 or tokens.shape[1] < 1:
             raise ValueError(f"{who}: tokens is [B, m] with m >= 1, got {tuple(tokens.shape)}")
         B, m = tokens.shape
@@ -207,33 +208,43 @@ class CachedDecodingMixin:
         if prosody is not None and tuple(prosody.shape) != (B, m, 4):
             raise ValueError(f"{who}: prosody is [B, m, 4] = ({B}, {m}, 4), got {tuple(prosody.shape)}")
         dev = state.lengths.device
-        counts, known = row_counts(who, "counts", counts, B, 0, m, dev)
+        known = None
+        if counts is not None:
+            counts, known = row_counts(who, "counts", counts, B, 0, m, dev)
         held = max(cache.max_length for cache in state.caches)
         need = m if known is None else max(known, default=0)
         if held + need > state.capacity:
             raise RuntimeError(f"{who}: {need} more positions do not fit the caches ({held} of {state.capacity} may be "
                                f"held); a sliding cache is not part of this module")
-        state.ragged = True                                                # the device lengths are every row's position
-        valid = torch.arange(m, dtype=torch.int32, device=dev)[None, :] < counts[:, None]
-        tokens = torch.where(valid, tokens.to(dev), 0)                     # a valid id where the padding may hold none
+        if counts is not None:
+            state.ragged = True                                            # the device lengths are every row's position
+            valid = torch.arange(m, dtype=torch.int32, device=dev)[None, :] < counts[:, None]
+            tokens = torch.where(valid, tokens.to(dev), 0)                 # a valid id where the padding may hold none
         last = len(self.layers) - 1
         hidden = []
         for t0 in range(0, m, ops.DECODE_EXTEND_MAX):
             piece = tokens[:, t0:t0 + ops.DECODE_EXTEND_MAX]
             n = piece.shape[1]
-            part_counts = self.piece_counts(counts, t0)
-            bound = n if known is None else max((min(max(c - t0, 0), n) for c in known), default=0)
-            positions = state.lengths[:, None] + torch.arange(n, dtype=torch.int32, device=dev)
+            at = dict(start=state.position)
+            if state.ragged:
+                at = dict(positions=state.lengths[:, None] + torch.arange(n, dtype=torch.int32, device=dev))
             hidden_states, _ = embed_tokens(piece, self.semantic_encoder, self.pos_encoder, self.layer_norm,
-                                            dense=False, positions=positions)
+                                            dense=False, **at)
             hidden_states = self.dropout(hidden_states)
             part = None if prosody is None else prosody[:, t0:t0 + n]
+            rows = {}
+            if counts is not None:
+                bound = n if known is None else max((min(max(c - t0, 0), n) for c in known), default=0)
+                rows = dict(counts=self.piece_counts(counts, t0), count_bound=bound)
             for i, (layer, cache) in enumerate(zip(self.layers, state.caches)):
                 hidden_states = layer.extend(hidden_states, prosody=part, use_memory=use_memory, cache=cache,
-                                             advance=i == last, counts=part_counts, count_bound=bound)
+                                             advance=i == last, **rows)
             state.position += n
             hidden.append(hidden_states)
-        self._mark_seen(state.seen, tokens, valid)
+        if counts is None:
+            state.seen.scatter_(1, tokens.to(torch.int64), 1)
+        else:
+            self._mark_seen(state.seen, tokens, valid)
         return hidden
 
     @staticmethod
@@ -325,119 +336,54 @@ class CachedDecodingMixin:
             stream_ids = torch.as_tensor(list(stream_ids), dtype=torch.int64).to(dev)
         if (prompt_lengths if state is not None else new_lengths) is not None:
             raise ValueError(f"{who}: prompt_lengths goes with a first turn and new_lengths with a turn that has state=")
-        if prompt_lengths is not None or new_lengths is not None:
-            return self._generate_ragged(who, input_ids, max_new_tokens, prompt_lengths, new_lengths, state, capacity,
-                                         seed, stream_ids, eos, pad, sync_every, use_memory, bool(fused_step),
-                                         return_state, dict(penalty=repetition_penalty, penalty_rule=repetition_rule,
-                                                            temperature=temperature, top_k=top_k, top_p=top_p))
+        first, lens = state is None, None
+        if prompt_lengths is not None:
+            lens, _ = row_counts(who, "prompt_lengths", prompt_lengths, B, 1, S, dev, dtype=torch.int64)
+        elif new_lengths is not None:
+            lens, known = row_counts(who, "new_lengths", new_lengths, B, 0, S, dev, dtype=torch.int64)
+        if not first and seed is not None:
+            seed = check_seed(who, seed)
+        sampling = dict(penalty=repetition_penalty, penalty_rule=repetition_rule, temperature=temperature, top_k=top_k,
+                        top_p=top_p)
         self.eval()
         with torch.no_grad():
-            generated = torch.empty(B, width, dtype=torch.int64, device=dev)
-            generated[:, :S] = input_ids
-            if state is None:
+            if lens is None:
+                generated = torch.empty(B, width, dtype=torch.int64, device=dev)
+                generated[:, :S] = input_ids
+                new = generated[:, S:]
+            else:
+                new = torch.empty(B, max_new_tokens, dtype=torch.int64, device=dev)
+            if first:
                 state = self.new_state(B, capacity, seed=seed)
                 state.stream_ids = stream_ids
-                logits = self.prefill(input_ids, state=state, use_memory=use_memory)[:, -1]
             else:
-                if seed is not None:
-                    if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < (1 << 64):
-                        raise ValueError(f"{who}: seed must be an int in [0, 2^64), got {seed!r}")
-                    state.seed = seed
-                if stream_ids is None:
-                    stream_ids = state.stream_ids
+                turn = start_turn(state, input_ids, seed, stream_ids)
+            if lens is None:
+                logits = (self.prefill(input_ids, state=state, use_memory=use_memory) if first else
+                          self.extend(turn, state=state, use_memory=use_memory))[:, -1]
+            else:
+                if first:
+                    fed = lens
+                    hidden = self._prefill_hidden(f"{type(self).__name__}.prefill", input_ids, None, state, use_memory,
+                                                  lens)
                 else:
-                    state.stream_ids = stream_ids
-                turn = torch.cat([state.pending.to(dev)[:, None], input_ids.to(torch.int64)], dim=1)
-                state.pending = None
-                logits = self.extend(turn, state=state, use_memory=use_memory)[:, -1]
+                    fed = lens + 1                                          # the pending token is always fed
+                    hidden = torch.cat(self._extend_hidden(who, turn, None, state, use_memory,
+                                                           fed if known is None else [c + 1 for c in known]), dim=1)
+                # every row's logits at its own last fed token: the rows are gathered before the head, [B, D] -> [B, V]
+                at = (fed - 1).clamp(min=0)[:, None, None].expand(B, 1, hidden.shape[2])
+                logits = self.output_head(hidden.gather(1, at)[:, 0])
             if fused_step:
                 self._before_fused_steps(state)
             # every row's length with the prompt consumed, before the first retirement: what the returned state counts from
             base = state.lengths.clone() if return_state else None
-            n = 0
-            while True:
-                column = generated[:, S + n]
-                ops.sample_next(logits, seen=state.seen, finished=state.finished, stream_ids=stream_ids,
-                                penalty=repetition_penalty, penalty_rule=repetition_rule, temperature=temperature,
-                                top_k=top_k, top_p=top_p, seed=state.seed, step=state.step, eos_id=eos, pad_id=pad,
-                                out=column)
-                state.step += 1
-                n += 1
-                if n == max_new_tokens:
-                    break
-                if eos is not None:
-                    state.lengths.masked_fill_(state.finished.bool(), -1)
-                    if n % sync_every == 0 and bool(state.finished.all()):
-                        break
-                logits = self.step(column, state=state, use_memory=use_memory, fused=bool(fused_step))
-            if eos is not None:
-                # the step at which the last row finished: a column is padding when every row had finished before it
-                new = generated[:, S:S + n]
-                done_before = ((new == eos).cumsum(1) - (new == eos).to(torch.int64)) > 0
-                n = int((~done_before.all(0)).sum().item())
-            if return_state:
-                self._stand_at_history_end(state, base, generated[:, S:S + n], eos)
-        return (generated[:, :S + n], state) if return_state else generated[:, :S + n]
-
-    def _generate_ragged(self, who, input_ids, max_new_tokens, prompt_lengths, new_lengths, state, capacity, seed,
-                         stream_ids, eos, pad, sync_every, use_memory, fused_step, return_state, sampling):
-        """``generate`` for right-padded rows (the arguments are checked and defaulted by ``generate``)."""
-        B, S = input_ids.shape
-        dev = input_ids.device
-        first = state is None
-        if first:
-            lens, _ = row_counts(who, "prompt_lengths", prompt_lengths, B, 1, S, dev, dtype=torch.int64)
-        else:
-            lens, known = row_counts(who, "new_lengths", new_lengths, B, 0, S, dev, dtype=torch.int64)
-            if seed is not None and (isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < (1 << 64)):
-                raise ValueError(f"{who}: seed must be an int in [0, 2^64), got {seed!r}")
-        self.eval()
-        with torch.no_grad():
-            if first:
-                state = self.new_state(B, capacity, seed=seed)
-                state.stream_ids = stream_ids
-                hidden = self._prefill_hidden(f"{type(self).__name__}.prefill", input_ids, None, state, use_memory, None,
-                                              lens)
-                fed = lens
-            else:
-                if seed is not None:
-                    state.seed = seed
-                if stream_ids is None:
-                    stream_ids = state.stream_ids
-                else:
-                    state.stream_ids = stream_ids
-                turn = torch.cat([state.pending.to(dev)[:, None], input_ids.to(torch.int64)], dim=1)
-                state.pending = None
-                fed = lens + 1                                              # the pending token is always fed
-                hidden = torch.cat(self._extend_ragged(who, turn, None, state, use_memory,
-                                                       fed if known is None else [c + 1 for c in known]), dim=1)
-            # every row's logits at its own last fed token: the rows are gathered before the head, [B, D] -> [B, V]
-            at = (fed - 1).clamp(min=0)[:, None, None].expand(B, 1, hidden.shape[2])
-            logits = self.output_head(hidden.gather(1, at)[:, 0])
-            if fused_step:
-                self._before_fused_steps(state)
-            base = state.lengths.clone() if return_state else None
-            new = torch.empty(B, max_new_tokens, dtype=torch.int64, device=dev)
-            n = 0
-            while True:
-                column = new[:, n]
-                ops.sample_next(logits, seen=state.seen, finished=state.finished, stream_ids=stream_ids,
-                                seed=state.seed, step=state.step, eos_id=eos, pad_id=pad, out=column, **sampling)
-                state.step += 1
-                n += 1
-                if n == max_new_tokens:
-                    break
-                if eos is not None:
-                    state.lengths.masked_fill_(state.finished.bool(), -1)
-                    if n % sync_every == 0 and bool(state.finished.all()):
-                        break
-                logits = self.step(column, state=state, use_memory=use_memory, fused=fused_step)
-            if eos is not None:
-                done_before = ((new[:, :n] == eos).cumsum(1) - (new[:, :n] == eos).to(torch.int64)) > 0
-                n = int((~done_before.all(0)).sum().item())
+            n = decode_loop(logits, state, new, sampling, eos, pad, sync_every,
+                            lambda column: self.step(column, state=state, use_memory=use_memory, fused=bool(fused_step)),
+                            retire=True)
+            n = trim_to_last_finish(new[:, :n], eos)
             if return_state:
                 self._stand_at_history_end(state, base, new[:, :n], eos)
-            generated = self._assemble(input_ids, lens, new[:, :n], pad)
+            generated = generated[:, :S + n] if lens is None else self._assemble(input_ids, lens, new[:, :n], pad)
         return (generated, state) if return_state else generated
 
     @staticmethod
@@ -507,28 +453,4 @@ class HippocampalTransformer(CachedDecodingMixin, nn.Module):
         the device): the rows are right-padded; the caches hold each row's own positions, only its own tokens are
         marked, the state becomes ``ragged`` and the logits at the padded places are unspecified."""
         return self.output_head(self._prefill_hidden("HippocampalTransformer.prefill", input_ids, prosody, state,
-                                                     use_memory, None, lengths))
-
-    def _prefill_hidden(self, who, input_ids, prosody, state, use_memory, memory, lengths) -> torch.Tensor:
-        """``prefill`` up to the head: the last layer's hidden states [B, S, D]."""
-        if input_ids.dim() != 2:
-            raise ValueError(f"{who}: input_ids is [B, S], got {tuple(input_ids.shape)}")
-        B, S = input_ids.shape
-        self._check_state(who, state, B)
-        if lengths is not None:
-            lengths, _ = row_counts(who, "lengths", lengths, B, 1, S, input_ids.device, dtype=torch.int64)
-            valid = torch.arange(S, device=input_ids.device)[None, :] < lengths[:, None]
-            input_ids = torch.where(valid, input_ids, 0)                   # a valid id where the padding may hold none
-        hidden_states, _ = embed_tokens(input_ids, self.semantic_encoder, self.pos_encoder, self.layer_norm)
-        hidden_states = self.dropout(hidden_states)
-        ragged = {} if lengths is None else dict(lengths=lengths)
-        for layer, cache in zip(self.layers, state.caches):
-            hidden_states = layer.prefill(hidden_states, prosody=prosody, use_memory=use_memory, cache=cache, **ragged)
-        with torch.no_grad():
-            if lengths is None:
-                state.seen.scatter_(1, input_ids.to(torch.int64), 1)
-            else:
-                self._mark_seen(state.seen, input_ids, valid)
-                state.ragged = True
-        state.position = S
-        return hidden_states
+                                                     use_memory, lengths))

@@ -16,8 +16,8 @@ O(1) time and O(hidden) state, with no K/V cache and no capacity.  What stood in
 ``ContinuousToSpikeBridge.rate_code`` launch (``ops.poisson_rate``; the rule: ``include/aura_hip.h``, "Poisson
 bridge") whose draw is keyed by (channel, timestep, position, stream) under the seed, so position ``p`` draws the same
 in a forward over the sequence and in a one-token ``step``.  ``new_state`` / ``prefill`` / ``step`` / ``generate`` build
-on it; ``generate`` has the meanings and defaults of ``CachedDecodingMixin.generate`` and a loop of its own (the
-mixin's is about attention caches).  One seed drives the sampler and the bridge: the sampler's Philox counter is
+on it; ``generate`` has the meanings and defaults of ``CachedDecodingMixin.generate`` and runs the same loop
+(``decoding.py``), without the retirement of finished rows: there is no cache to take a row out of.  One seed drives the sampler and the bridge: the sampler's Philox counter is
 (token id, stream, step lo, step hi), the bridge's (channel, timestep group, position, stream); the words feed
 different decisions.  ``forward(.., seed=None)`` is what it was, launch for launch.
 
@@ -39,8 +39,8 @@ import torch.nn as nn
 
 from ... import ops
 from ..liquid_moe import LiquidMoERouter, _recording
+from .decoding import _UNSET, check_seed, decode_loop, start_turn, trim_to_last_finish
 from .gif_neuron import GIFNeuron
-from .hippocampal_transformer import _UNSET
 from .snn_expert import SNNExpert
 from .spike_bridge import ContinuousToSpikeBridge, SpikeToContinuousBridge
 
@@ -67,12 +67,6 @@ class ZoneState:
     @property
     def batch(self) -> int:
         return self.seen.shape[0]
-
-
-def _check_seed(who: str, seed) -> int:
-    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < (1 << 64):
-        raise ValueError(f"{who}: seed must be an int in [0, 2^64), got {seed!r}")
-    return int(seed)
 
 
 def _zone_streams(who: str, stream_ids, B: int, dev):
@@ -191,7 +185,7 @@ class MoELanguageZone(nn.Module):
                 raise ValueError("MoELanguageZone.forward: stream_ids, start and state go with a seed")
             return self._forward_unseeded(input_ids, keep_on_device)
         who = "MoELanguageZone.forward"
-        seed = _check_seed(who, seed)
+        seed = check_seed(who, seed)
         B, S = input_ids.shape
         if state is not None and (not isinstance(state, ZoneState) or state.batch != B):
             raise ValueError(f"{who}: state must be a ZoneState (new_state) of {B} rows")
@@ -224,7 +218,7 @@ class MoELanguageZone(nn.Module):
         """A fresh state for ``batch`` sequences on the model's device: ``v = 0``, ``theta = threshold``, position 0.
         ``stream_ids`` [B] number the rows' random streams (default: the row numbers)."""
         who = "MoELanguageZone.new_state"
-        seed = _check_seed(who, seed)
+        seed = check_seed(who, seed)
         if isinstance(batch, bool) or not isinstance(batch, int) or batch < 1:
             raise ValueError(f"{who}: batch must be an int >= 1, got {batch!r}")
         dev = self.output_proj.weight.device
@@ -354,7 +348,7 @@ class MoELanguageZone(nn.Module):
             if state.pending is None:
                 raise ValueError(f"{who}: state must be one that generate(.., return_state=True) returned")
         if seed is not None:
-            seed = _check_seed(who, seed)
+            seed = check_seed(who, seed)
         eos = getattr(self, "eos_token_id", None) if eos_token_id is _UNSET else eos_token_id
         pad = pad_token_id if pad_token_id is not None else (eos if eos is not None else 0)
         if isinstance(pad, bool) or not isinstance(pad, int) or not 0 <= pad < self.vocab_size:
@@ -370,39 +364,21 @@ class MoELanguageZone(nn.Module):
                 state = self.new_state(B, seed=seed, stream_ids=stream_ids)
                 turn = input_ids
             else:
-                if seed is not None:
-                    state.seed = seed
                 if stream_ids is not None:
-                    state.stream_ids, state.streams = _zone_streams(who, stream_ids, B, dev)
-                turn = torch.cat([state.pending.to(dev)[:, None], input_ids.to(torch.int64)], dim=1)
-                state.pending = None
-            width = S + max_new_tokens
-            generated = torch.empty(B, width, dtype=torch.int64, device=dev)
+                    stream_ids, state.streams = _zone_streams(who, stream_ids, B, dev)
+                turn = start_turn(state, input_ids, seed, stream_ids)
+            generated = torch.empty(B, S + max_new_tokens, dtype=torch.int64, device=dev)
             generated[:, :S] = input_ids
-            logits = self.prefill(turn, state)[:, -1]
-            n = 0
-            while True:
-                column = generated[:, S + n]
-                ops.sample_next(logits, seen=state.seen, finished=state.finished, stream_ids=state.stream_ids,
-                                penalty=repetition_penalty, penalty_rule=repetition_rule, temperature=temperature,
-                                top_k=top_k, top_p=top_p, seed=state.seed, step=state.step, eos_id=eos, pad_id=pad,
-                                out=column)
-                state.step += 1
-                n += 1
-                if n == max_new_tokens:
-                    break
-                if eos is not None and n % sync_every == 0 and bool(state.finished.all()):
-                    break
-                logits = self.step(column, state)
+            new = generated[:, S:]
+            sampling = dict(penalty=repetition_penalty, penalty_rule=repetition_rule, temperature=temperature,
+                            top_k=top_k, top_p=top_p)
+            n = decode_loop(self.prefill(turn, state)[:, -1], state, new, sampling, eos, pad, sync_every,
+                            lambda column: self.step(column, state), retire=False)
             if return_state:
-                state.pending = generated[:, S + n - 1].clone()
+                state.pending = new[:, n - 1].clone()
                 state.finished.zero_()
-            elif eos is not None:
-                # the step at which the last row finished: a column is padding when every row had finished before it
-                new = generated[:, S:S + n]
-                done_before = ((new == eos).cumsum(1) - (new == eos).to(torch.int64)) > 0
-                n = int((~done_before.all(0)).sum().item())
-        return (generated[:, :S + n], state) if return_state else generated[:, :S + n]
+                return generated[:, :S + n], state
+            return generated[:, :S + trim_to_last_finish(new[:, :n], eos)]
 
     def setup_moe_router(self, *args, **kwargs):
         pass

@@ -25,7 +25,6 @@ import torch
 import torch.nn as nn
 from torch.utils.checkpoint import checkpoint
 
-from .hippocampal_attention import row_counts
 from .hippocampal_transformer import CachedDecodingMixin, DecodeState
 from .memory_augmented_layer import MemoryAugmentedLayer, MemoryContext
 from .place_cell_encoder import PlaceCellSemanticEncoder
@@ -98,33 +97,10 @@ class SNNRAGTransformer(CachedDecodingMixin, nn.Module):
         the mean over a row's own positions, only its own tokens are marked, the state becomes ``ragged`` and the
         logits at the padded places are unspecified."""
         return self.output_head(self._prefill_hidden("SNNRAGTransformer.prefill", input_ids, prosody, state,
-                                                     use_memory, memory, lengths))
+                                                     use_memory, lengths, memory))
 
-    def _prefill_hidden(self, who, input_ids, prosody, state, use_memory, memory, lengths) -> torch.Tensor:
-        """``prefill`` up to the head: the last layer's hidden states [B, S, D]."""
-        if input_ids.dim() != 2:
-            raise ValueError(f"{who}: input_ids is [B, S], got {tuple(input_ids.shape)}")
-        B, S = input_ids.shape
-        self._check_state(who, state, B)
-        contexts = self._layer_contexts(who, memory)
-        if lengths is not None:
-            lengths, _ = row_counts(who, "lengths", lengths, B, 1, S, input_ids.device, dtype=torch.int64)
-            valid = torch.arange(S, device=input_ids.device)[None, :] < lengths[:, None]
-            input_ids = torch.where(valid, input_ids, 0)                   # a valid id where the padding may hold none
-        hidden_states, _ = embed_tokens(input_ids, self.semantic_encoder, self.pos_encoder, self.layer_norm)
-        hidden_states = self.dropout(hidden_states)
-        ragged = {} if lengths is None else dict(lengths=lengths)
-        for layer, cache, context in zip(self.layers, state.caches, contexts):
-            hidden_states = layer.prefill(hidden_states, prosody=prosody, use_memory=use_memory, cache=cache,
-                                          memory=context, **ragged)
-        with torch.no_grad():
-            if lengths is None:
-                state.seen.scatter_(1, input_ids.to(torch.int64), 1)
-            else:
-                self._mark_seen(state.seen, input_ids, valid)
-                state.ragged = True
-        state.position = S
-        return hidden_states
+    def _prefill_layer_kwargs(self, who: str, memory) -> Sequence[dict]:
+        return [dict(memory=context) for context in self._layer_contexts(who, memory)]
 
     @staticmethod
     def pinned_memory(state: DecodeState) -> List[Optional[MemoryContext]]:
